@@ -13,10 +13,14 @@ and is NOT counted as steps.  The matrix has a U-shaped family-frequency spectru
 the three well-separated latent classes of SURVEY.md 8(d) NEM is at its fixed point after ONE iteration, which
 would time the cheapest path (--spectrum latent3 selects that generator).
 
-Timing: W warm-up steps, then `--repeats` (25) blocks of EXACTLY K steps, each bracketed by a barrier and a device
-synchronisation on both sides, maximum over ranks per block; `ms_per_step` / `value` come from the MEDIAN block,
-`ms_per_step_min` / `_max` give the spread (a block of 20 steps lasts under a millisecond: one scheduler hiccup
-would otherwise move the headline by double digits).
+Timing: W warm-up steps, then the timed steps.  N = 1: EXACTLY K timed steps (`timed_steps`), the restarts they take
+grouped into up to `--repeats` (25) blocks of whole restarts, each synchronised on both sides; `ms_per_step` (the
+milliseconds of one timed step) and `value` come from the MEDIAN block's rate, `ms_per_step_min` / `_max` give the
+spread (one scheduler hiccup would otherwise move the headline by double digits).  N > 1: `--repeats` blocks of K steps
+each, bracketed by a barrier, maximum over ranks per block, the median block reported the same way.
+--dump-outputs DIR (N = 1) then writes what the last timed step computed as DIR/<name>.npy; with the same arguments
+the inputs are the same from run to run (seeded generators), so two builds can be compared output for output.  Inside
+the tree, bench_outputs/ is the place for them (git ignores it): --dump-outputs bench_outputs/<build>.
 
 N = 1 (default): BASELINE configs[1], 20 000 families x 500 organisms, K=3, beta=0.5, contiguity graph,
 ncem / sk_ / pk exactly as ppanggolin.py:1769-1826 calls nem().  The JSON line also carries `north_star_target`:
@@ -65,7 +69,8 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--repeats", type=int, default=25, help="timed blocks of --steps steps each (median reported)")
+    ap.add_argument("--repeats", type=int, default=25,
+                    help="1 GPU: blocks the --steps timed steps are grouped into; N > 1: blocks of --steps steps each (median reported)")
     ap.add_argument("--families", type=int, default=None,
                     help="families: of the problem (1 GPU, strong scaling) or per GPU (weak scaling, replicas)")
     ap.add_argument("--organisms", type=int, default=None)
@@ -94,6 +99,9 @@ def parse_args(argv=None):
     ap.add_argument("--phase-timeout", type=float, default=300.0,
                     help="N > 1: seconds a phase (a mode's measurement) may take before the job's watchdog ends it and rank 0 "
                          "prints the record it has")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="1 GPU: after the timed steps write what the last one computed (posteriors, parameters, criteria) "
+                         "as DIR/<name>.npy (in the tree: bench_outputs/<name of the build>)")
     ap.add_argument("--watchdog-selftest", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
 
@@ -184,12 +192,15 @@ class EngineRun:
         eng.configure(algo=algo, beta=beta, disper=disper, propor="pk", cvtest="none", it_max=100, tie=tie, seed=1)
         eng.set_graph_policy(True)
 
-    def run_steps(self, count):
-        done, rounds = 0, 0
-        while done < count:
-            m = min(self.cycle, count - done)
-            rounds += self.eng.restart_iterate(m)["sweep_rounds"]      # reset + initial sweeps + m iterations
-            done += m
+    def restarts(self, count):
+        """the iterations of each restart that `count` steps take: whole cycles, then what is left"""
+        return [self.cycle] * (count // self.cycle) + ([count % self.cycle] if count % self.cycle else [])
+
+    def run_steps(self, count, restarts=None):
+        rounds = 0
+        for m in (self.restarts(count) if restarts is None else restarts):
+            self.last = self.eng.restart_iterate(m)                    # reset + initial sweeps + m iterations
+            rounds += self.last["sweep_rounds"]
         return rounds
 
     def prime(self, steps, warmup):
@@ -205,28 +216,39 @@ class EngineRun:
             if (c1["plain"], c1["captured"]) == (c0["plain"], c0["captured"]):
                 break
 
-    def block(self, steps):
+    def block(self, restarts):
         """one timed block: restart_iterate() synchronises the stream before returning"""
         t0 = time.perf_counter()
-        rounds = self.run_steps(steps)
+        rounds = self.run_steps(None, restarts)
         return time.perf_counter() - t0, rounds
 
-    def timed(self, steps, warmup, repeats, sync=None):
-        """sync(seconds) -> seconds: barrier + maximum over ranks around a block (multi-rank callers)"""
+    def timed(self, steps, warmup, repeats, sync=None, split=False):
+        """`repeats` blocks of `steps` steps each; split: `steps` steps in all, the restarts run_steps(steps) makes
+        grouped into up to `repeats` blocks.  A block's entry is the seconds `steps` steps take at its rate.
+        sync(seconds) -> seconds: barrier + maximum over ranks around a block (multi-rank callers)"""
         eng = self.eng
         self.prime(steps, warmup)
         c0 = eng.graph_counters()
-        blocks, rounds = [], 0
-        for _ in range(max(1, repeats)):
+        if split:
+            whole = self.restarts(steps)
+            nb = min(max(1, repeats), len(whole))
+            plan = [whole[i * len(whole) // nb:(i + 1) * len(whole) // nb] for i in range(nb)]
+        else:
+            plan = [self.restarts(steps)] * max(1, repeats)
+        blocks, rounds, region = [], 0, 0.0
+        for part in plan:
             if sync is not None:
                 sync(None)
-            dt, r = self.block(steps)
-            blocks.append(sync(dt) if sync is not None else dt)
+            dt, r = self.block(part)
+            dt = sync(dt) if sync is not None else dt
+            blocks.append(dt * steps / sum(part))
+            region += dt
             rounds += r
         c1 = eng.graph_counters()
-        total = steps * len(blocks)
-        restarts = len(blocks) * ((steps + self.cycle - 1) // self.cycle)
+        total = sum(map(sum, plan))
+        restarts = sum(map(len, plan))
         info = dict(
+            timed_steps=total, timed_region_s=region,
             graphs_primed=(c1["captured"] == c0["captured"] and c1["plain"] == c0["plain"]),
             graph_replays_timed=c1["replayed"] - c0["replayed"],
             host_finished_sweeps_timed=c1["host_finished_sweeps"] - c0["host_finished_sweeps"],
@@ -235,6 +257,28 @@ class EngineRun:
             sweep_rounds_per_iteration=(rounds - 2 * restarts) / max(total, 1) if rounds else None,
         )
         return blocks, info
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, run):
+    """What the timed path's last step returns to its caller -- the posteriors c [n, K], the parameters, the class sizes,
+    the six criteria, its iteration count -- as out_dir/<name>.npy (float32; the count float64).  Posteriors beyond
+    half of DUMP_BYTES are a fixed, seeded sample of rows: c_rows holds their indices."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    res = run.eng.results()
+    arrays = {name: np.asarray(res[name], np.float32) for name in ("c", "prop", "center", "disp", "nbobs_k")}
+    arrays["crit"] = np.asarray(run.last["crit"], np.float32)
+    arrays["iters"] = np.asarray([run.last["iters"]], np.float64)
+    c = arrays["c"]
+    if c.nbytes > DUMP_BYTES // 2:
+        rows = np.sort(np.random.default_rng(0).choice(c.shape[0], (DUMP_BYTES // 2) // c[0].nbytes, replace=False))
+        arrays["c"] = c[rows]
+        arrays["c_rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def host_facts():
@@ -846,6 +890,10 @@ def main():
         args.disper = "skd" if ksweep else "sk_"
     if multi and ksweep:
         raise SystemExit("the multi-GPU modes benchmark K = 3")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if multi and args.dump_outputs:
+        raise SystemExit("--dump-outputs writes the single-GPU path's outputs (--gpus 1 without --dist)")
     extra, also = {}, None
     x = nei = prop = center = disp = run = None
     wd = Watchdog(json_fd, rank, enabled=multi and world > 1)
@@ -858,7 +906,9 @@ def main():
         x, nei, prop, center, disp, _, what = make_workload(n_tot, d, k, args.spectrum, 3 if (n_tot, d) == (50000, 1000) else 2, ksweep,
                                                             weights=args.weights)
         run = EngineRun(x, nei, k, prop, center, disp, args.algo, beta, args.disper)
-        blocks, extra = run.timed(args.steps, args.warmup, args.repeats)
+        blocks, extra = run.timed(args.steps, args.warmup, args.repeats, split=True)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, run)
         # kernel durations: HIP events on the engine's stream around strings of launches, on the state the timed region
         # just left (the timed region itself replays captured graphs, which carry no events)
         kernels = kernel_probe(run.eng)

@@ -20,13 +20,14 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def reference():
-    from oracle import pyoracle
-    if not pyoracle.have_reference():
-        if os.path.isdir(pyoracle.REF_SRC):
-            pyoracle.build(ref=True)
-        else:
-            pytest.skip("compiled reference (oracle/_ref) not available here")
-    return pyoracle.Reference()
+    """The compiled reference's answers as recorded under tests/golden/refcalls (tests/refcalls.py).
+    NEM_REFERENCE_RECORD=1 calls the compiled reference instead and records what it returns
+    (tests/golden/make_refcalls.py)."""
+    from tests.refcalls import RecordedReference
+    if os.environ.get("NEM_REFERENCE_RECORD") == "1":
+        from oracle import pyoracle
+        return RecordedReference(live=pyoracle.Reference())
+    return RecordedReference()
 
 
 @pytest.fixture(scope="session")

@@ -144,14 +144,23 @@ def test_random_starts_match_oracle(gpu_lib, oracle, n, d, k, algo, disper, star
     eng.close()
 
 
-@pytest.mark.parametrize("n,d,k,starts,seed", [(600, 6, 3, 6, 21), (1500, 4, 4, 5, 8)])
+TIE_STREAM_CASES = [(600, 6, 3, 6, 21), (1500, 4, 4, 5, 8)]
+
+
+def tie_stream_inputs(n, d, seed):
+    """(x, nei) of test_random_starts_with_the_reference_tie_stream (tests/golden/make_refcalls.py gives the reference
+    the same)"""
+    x, _ = synth.bernoulli_pa_matrix(n, d, seed, p=(0.9, 0.5, 0.1))
+    return x, synth.contiguity_graph(n, seed)
+
+
+@pytest.mark.parametrize("n,d,k,starts,seed", TIE_STREAM_CASES)
 def test_random_starts_with_the_reference_tie_stream(gpu_lib, oracle, reference, n, d, k, starts, seed):
     """INIT_RANDOM with TieRule = TIE_RANDOM as in the reference: the starts' centre draws and the C-steps' tie draws
     are ONE random() stream (few organisms => many identical families => many ties), so every start's draws depend
     on how many ties the starts before it met.  Engine == oracle == the compiled reference, draw for draw."""
     from pangenomenem_amd.engine import NemEngine
-    x, _ = synth.bernoulli_pa_matrix(n, d, seed, p=(0.9, 0.5, 0.1))
-    nei = synth.contiguity_graph(n, seed)
+    x, nei = tie_stream_inputs(n, d, seed)
     eng = NemEngine(n, d, k)
     eng.set_matrix(x)
     eng.set_graph(nei)

@@ -144,53 +144,64 @@ def test_dropin_argument_errors(gpu_lib, tmp_path):
     assert call(algo=b"typo") == 0                            # quirk: unknown algo runs as "nem" (nem_exe.c:371-376, 472)
 
 
-@pytest.mark.parametrize("algo,disper,n,d", [("ncem", "sk_", 2048, 15), ("nem", "skd", 900, 21), ("ncem", "s__", 1500, 9)])
-def test_dropin_log_file_equals_the_reference(gpu_lib, tmp_path, algo, disper, n, d):
-    """<Fname>.log (dolog=1): header, criteria before and after every E-step sweep, all parameters per iteration --
-    the text of the reference's own log except its date line."""
-    import shutil
-    from oracle import pyoracle
-    if not pyoracle.have_reference():
-        pytest.skip("compiled reference (oracle/_ref) not present")
+LOG_CASES = [("ncem", "sk_", 2048, 15), ("nem", "skd", 900, 21), ("ncem", "s__", 1500, 9)]
+
+
+def log_case(path, algo, disper, n, d):
+    """the input files and nem() arguments of test_dropin_log_file_equals_the_reference (tests/golden/make_refcalls.py
+    gives the reference the same)"""
     from pangenomenem_amd import nemfiles, synth
-    import nem as nem_module
     x, _ = synth.bernoulli_pa_matrix(n, d, n + d)
     nei = synth.contiguity_graph(n, n + d)
     prop, center, disp = synth.default_init(d)
+    base = nemfiles.write_nem_inputs(path, x, nei, prop, center, disp)
+    return base, (3, algo.encode(), 0.5, b"clas", 1e-8, b"fuzzy", 20, True, b"bern", b"pk", disper.encode(), 2)
+
+
+@pytest.mark.parametrize("algo,disper,n,d", LOG_CASES)
+def test_dropin_log_file_equals_the_reference(gpu_lib, reference, tmp_path, algo, disper, n, d):
+    """<Fname>.log (dolog=1): header, criteria before and after every E-step sweep, all parameters per iteration --
+    the text of the reference's own log except its date line."""
+    import shutil
+    import nem as nem_module
     ours, ref = str(tmp_path / "ours"), str(tmp_path / "ref")
-    base = nemfiles.write_nem_inputs(ours, x, nei, prop, center, disp)
+    base, args = log_case(ours, algo, disper, n, d)
     shutil.copytree(ours, ref)
     ref_base = os.path.join(ref, "nem_file")
-    args = (3, algo.encode(), 0.5, b"clas", 1e-8, b"fuzzy", 20, True, b"bern", b"pk", disper.encode(), 2)
     assert nem_module.nem(base.encode(), *args) == 0
-    assert pyoracle.Reference().nem(ref_base, *args) == 0
+    assert reference.nem(ref_base, *args) == 0
     from tests.util import assert_same_nem_log
     assert_same_nem_log(open(base + ".log").read(), open(ref_base + ".log").read())
 
 
-@pytest.mark.parametrize("algo,disper,thres,dolog", [("ncem", "sk_", 1e-4, True), ("nem", "skd", 1e-4, True),
-                                                     ("ncem", "sk_", 0.05, True), ("nem", "sk_", 1e-3, True)])
-def test_dropin_crit_convergence_equals_the_reference(gpu_lib, tmp_path, algo, disper, thres, dolog):
-    """nem(..., convergence="crit", ...) as a logging run (dolog, what PPanGGOLiN passes): the reference compares the
-    first iteration's criterion with the initial partition's (WriteLogCrit, nem_alg.c:1980, 2398).  Same iteration
-    count, same .uf byte for byte, same parameter lines of .mf as the reference's own nem() on the same files."""
-    import shutil
-    from oracle import pyoracle
-    if not pyoracle.have_reference():
-        pytest.skip("compiled reference (oracle/_ref) not present")
+CRIT_CASES = [("ncem", "sk_", 1e-4, True), ("nem", "skd", 1e-4, True), ("ncem", "sk_", 0.05, True), ("nem", "sk_", 1e-3, True)]
+
+
+def crit_case(path, algo, disper, thres, dolog):
+    """the input files and nem() arguments of test_dropin_crit_convergence_equals_the_reference
+    (tests/golden/make_refcalls.py gives the reference the same)"""
     from pangenomenem_amd import nemfiles, synth
-    import nem as nem_module
     n, d = 2048, 15
     x, _ = synth.ushaped_pa_matrix(n, d, 4)
     nei = synth.contiguity_graph(n, 4)
     prop, center, disp = synth.default_init(d)
+    base = nemfiles.write_nem_inputs(path, x, nei, prop, center, disp)
+    return base, (3, algo.encode(), 0.5, b"crit", thres, b"fuzzy", 60, dolog, b"bern", b"pk", disper.encode(), 2)
+
+
+@pytest.mark.parametrize("algo,disper,thres,dolog", CRIT_CASES)
+def test_dropin_crit_convergence_equals_the_reference(gpu_lib, reference, tmp_path, algo, disper, thres, dolog):
+    """nem(..., convergence="crit", ...) as a logging run (dolog, what PPanGGOLiN passes): the reference compares the
+    first iteration's criterion with the initial partition's (WriteLogCrit, nem_alg.c:1980, 2398).  Same iteration
+    count, same .uf byte for byte, same parameter lines of .mf as the reference's own nem() on the same files."""
+    import shutil
+    import nem as nem_module
     ours, ref = str(tmp_path / "ours"), str(tmp_path / "ref")
-    base = nemfiles.write_nem_inputs(ours, x, nei, prop, center, disp)
+    base, args = crit_case(ours, algo, disper, thres, dolog)
     shutil.copytree(ours, ref)
     ref_base = os.path.join(ref, "nem_file")
-    args = (3, algo.encode(), 0.5, b"crit", thres, b"fuzzy", 60, dolog, b"bern", b"pk", disper.encode(), 2)
     assert nem_module.nem(base.encode(), *args) == 0
-    assert pyoracle.Reference().nem(ref_base, *args) == 0
+    assert reference.nem(ref_base, *args) == 0
     import re
     it_ours = re.search(r"NEM (converged|did not converge) after (\d+) iterations", open(base + ".stderr").read())
     it_ref = re.search(r"NEM (converged|did not converge) after (\d+) iterations", open(ref_base + ".stderr", errors="replace").read())

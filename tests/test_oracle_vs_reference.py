@@ -1,5 +1,5 @@
 """Pins the oracle to the compiled, unmodified reference (oracle/_ref) on inputs beyond the committed
-fixtures.  Runs where /root/reference (or a prebuilt oracle/_ref) exists; skipped elsewhere."""
+fixtures.  The reference's answers to these calls are recorded under tests/golden/refcalls (tests/refcalls.py)."""
 import numpy as np
 import pytest
 

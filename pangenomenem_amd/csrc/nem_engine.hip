@@ -52,9 +52,8 @@ void set_error(const std::string& msg) { g_last_error = msg; }
 
 namespace {
 constexpr int kRoundCap = 64;     // relaxation rounds per flag window
-// what is zeroed ahead of every sweep (by the density launch, or a fill): FLAG_MOVED, the round window, the meeting words
-constexpr int kMeetWords = 2 * kFusedMaxBlocks;
-constexpr int kSweepFlagWords = 1 + kRoundCap * FLAG_ROUND_STRIDE + kMeetWords;
+// what is zeroed ahead of every sweep (by the density launch, or a fill): FLAG_MOVED and the round window
+constexpr int kSweepFlagWords = 1 + kRoundCap * FLAG_ROUND_STRIDE;
 constexpr int kRoundBatchMax = 4;
 constexpr int kRoundsMax = 7;       // most rounds a sweep of the pipelined loop is given ahead (ctrl_logic reads 8 slots)
 constexpr int kFzPositions = 16;    // fuzzy NEM: leading iterations of a run whose round counts are learned
@@ -106,9 +105,8 @@ struct nemgpu_engine {
     float *nbobs_k = nullptr, *iner = nullptr;
     int *fz_lastz = nullptr, *fz_any1 = nullptr;
     float *fz_in0 = nullptr, *fz_in1 = nullptr, *fz_inh = nullptr;
-    float* fz_ct = nullptr;       // class-major copy of the memberships, [k][npad] (the wave-per-chain M-step)
-    float* fz_chk = nullptr;      // the zeros' chains every 64 families, [k][ceil(n/64) + 1][64 ceil(d/64)] (producer/consumer M-step)
-    int fuzzy_chains = 2;         // NEM_MI355X_FUZZY_CHAINS: 2 producer/consumer (lane per chain, adds only), 1 wave per chain, 0 lane per chain as in round 1
+    float* fz_ct = nullptr;       // class-major copy of the memberships, [k][npad] (the fuzzy M-step)
+    float* fz_chk = nullptr;      // the zeros' chains every 64 families, [k][ceil(n/64) + 1][64 ceil(d/64)] (the fuzzy M-step)
     double2* tabT = nullptr;
     double* tabL0 = nullptr;
     uint32_t *nz0 = nullptr, *nz1 = nullptr, *am0 = nullptr, *am1 = nullptr;
@@ -150,7 +148,7 @@ struct nemgpu_engine {
     int cur = 0;
     uint64_t* mask = nullptr;
     int* stats = nullptr;
-    int* flags_dev = nullptr;     // [C_WORDS loop control] [FLAG_ITER_STRIDE] [kRoundCap * FLAG_ROUND_STRIDE] [2 * kFusedMaxBlocks meeting words of the fused sweep]
+    int* flags_dev = nullptr;     // [C_WORDS loop control] [FLAG_ITER_STRIDE] [kRoundCap * FLAG_ROUND_STRIDE]
     int* flags_host = nullptr;    // pinned mirror
     const int* stop_ptr = nullptr;   // &ctrl[C_STOP] while the pipelined loop is being enqueued, else nullptr
 
@@ -180,18 +178,6 @@ struct nemgpu_engine {
     // then every later one gets round_batch.  (Labels are sticky: on the bench's pre-convergence data only the sweep
     // that starts from the blind partition needs a third round; an early-exit launch per iteration costs 2.5 us.)
     int rounds_iter = 2;
-    // k_sweep_fused (NEM_MI355X_FUSED_SWEEP=1 turns it on): the first rounds of a sweep in ONE launch, the blocks
-    // meeting between rounds (nem_sweep_dev.hpp).  OFF by default -- measured, round 4 (profiles/r04_fused_sweep_*.json):
-    // a meeting of 79-241 blocks costs 3-3.5 us on the in-kernel clock whichever way it is built (one counter: 79
-    // same-address atomics; one word per block + a wave-wide poll: a store's way to the other XCDs and two polls), a
-    // 2-round sweep needs two of them, and a launch boundary with its prologue is no dearer: 20 000 x 500 0.0391 vs
-    // 0.0370 ms per EM iteration, 50 000 x 1 000 0.0512 vs 0.0477, 200 000 x 5 000 0.1227 vs 0.1247.
-    // fused_rounds: rounds per such launch (NEM_MI355X_FUSED_ROUNDS, at most kFusedMaxRounds; the pipelined loop takes
-    // min(4, .): its loop control looks at four slots).  fused_sweep goes off for good when a launch's blocks did not all
-    // meet (kFusedFailed: the grid was not resident as a whole).
-    bool fused_sweep = false; int fused_rounds = 4; int n_fused_failed = 0, n_fused = 0;
-    double* exp_tab = nullptr; float exp_beta = 0.0f; bool exp_ready = false;   // SweepArgs::exp_tab for cfg.beta
-    int exp_need = kExpTabGlobal;        // entries a context of this graph can index: 1 + the largest row sum of |weights| (set_graph)
     // ... but not all iterations are alike: the first ones after a start move many labels and tend to need the
     // extra round, the later ones almost never do.  The first deep_iters iterations of a run get round_batch rounds;
     // an iteration further on whose sweep the host had to finish moves the mark (it is kept across restarts: the
@@ -272,10 +258,6 @@ struct nemgpu_engine {
     int* iter_flags() const { return flags_dev + C_WORDS; }
     int* round_flags(int r) const { return flags_dev + C_WORDS + FLAG_ITER_STRIDE + (r % kRoundCap) * FLAG_ROUND_STRIDE; }
     size_t flag_words() const { return C_WORDS + FLAG_ITER_STRIDE + (size_t)kRoundCap * FLAG_ROUND_STRIDE; }   // what the host mirrors
-    // k_sweep_fused: the words through which the blocks of a launch meet between rounds (behind the mirrored part;
-    // zeroed with the round flags ahead of every sweep)
-    size_t flag_alloc_words() const { return flag_words() + 2 * (size_t)kFusedMaxBlocks; }
-    unsigned* meet_words() const { return reinterpret_cast<unsigned*>(flags_dev + flag_words()); }
     const int* h_ctrl() const { return flags_host; }
     const int* h_iter() const { return flags_host + C_WORDS; }
     const int* h_round(int r) const { return flags_host + C_WORDS + FLAG_ITER_STRIDE + (r % kRoundCap) * FLAG_ROUND_STRIDE; }
@@ -587,7 +569,7 @@ int alloc_model_buffers(nemgpu_engine* e)
     A(dev_alloc(&e->pkfki, (size_t)k * e->npad)); A(dev_alloc(&e->logpkfki, (size_t)k * e->npad));
     A(dev_alloc(&e->mask, (size_t)k * e->nw64));
     A(dev_alloc(&e->stats, (size_t)k + kd));
-    A(dev_alloc(&e->flags_dev, e->flag_alloc_words()));
+    A(dev_alloc(&e->flags_dev, e->flag_words()));
     return r;
 }
 
@@ -776,73 +758,11 @@ int publish_draw_ctl(nemgpu_engine* e)
     return NEMGPU_OK;
 }
 
-// May the first rounds of a sweep go out as ONE launch whose blocks meet between rounds (k_sweep_fused)?  NCEM without
-// the libc tie stream, the whole problem on this engine, issued for real (a lock-step batch zips the classic rounds), a
-// kernel instance for K, and a grid that is resident as a whole: at most one block per CU.
-bool sweep_fused_ok(const nemgpu_engine* e, bool use_nei)
-{
-    return e->fused_sweep && use_nei && e->ncem() && !e->libc() && e->sh_world == 1 && e->sh_stride == 0 && e->lo == 0 &&
-           e->n == e->n_total && e->parent == nullptr && current_recorder() == nullptr && sweep_fused_has_instance(e->k) &&
-           sweep_grid_blocks(e->n, e->k) <= kFusedMaxBlocks;
-}
-// rounds of a sweep's first batch: what the caller wants, or the fused launch's rounds (inside the pipelined loop at
-// most the four slots its loop control reads)
-int sweep_first_rounds(const nemgpu_engine* e, float beta, int wanted, int pipelined = -1)
-{
-    if (!sweep_fused_ok(e, e->has_graph && beta != 0.0f)) return wanted;
-    if (pipelined < 0) pipelined = e->stop_ptr != nullptr ? 1 : 0;
-    return std::max(wanted, pipelined ? std::min(e->fused_rounds, 4) : e->fused_rounds);
-}
-// SweepArgs::exp_tab for the configured beta (outside any capture / recording: loop_begin, init_partition)
-int ensure_exp_table(nemgpu_engine* e)
-{
-    if (current_recorder() != nullptr || !e->ncem() || !e->has_graph || e->cfg.beta == 0.0f || e->parent != nullptr) return NEMGPU_OK;
-    if (e->exp_need <= 64) return NEMGPU_OK;              // (small weights: every block computes its 64 entries itself)
-    // (measured neutral, round 4 -- profiles/r04_exp_table_ab.json: adjacency weights, one engine 0.03450 vs 0.03469 ms per
-    //  iteration, 64 problems in lock step 5.02 vs 4.98 us per problem-iteration: the exponentials are not what bounds a
-    //  round, alone or in a batch -- so the table is opt-in, NEM_MI355X_EXP_TABLE=1; the fused sweep uses it when both are on)
-    static const bool on = getenv("NEM_MI355X_EXP_TABLE") && getenv("NEM_MI355X_EXP_TABLE")[0] == '1';
-    if (!on) return NEMGPU_OK;
-    if (e->exp_ready && e->exp_beta == e->cfg.beta) return NEMGPU_OK;
-    if (e->exp_tab == nullptr) { alloc_for(e); int r = dev_alloc(&e->exp_tab, (size_t)kExpTabGlobal); if (r) return r; }
-    launch_exp_table(e->cfg.beta, e->exp_tab, kExpTabGlobal, e->stream);
-    HIPCHK(hipGetLastError());
-    e->exp_beta = e->cfg.beta; e->exp_ready = true;
-    return NEMGPU_OK;
-}
-
 int sweep_launch_rounds(nemgpu_engine* e, SweepCtx& c, int count)
 {
     const bool ncem = e->ncem();
     const int P = e->cur, Q = (e->cur + 1) % 3, R = (e->cur + 2) % 3;
     const int r0 = c.r;
-    c.a.fused_rounds = 0;
-    if (r0 == 0 && count >= 2 && c.multi && sweep_fused_ok(e, c.use_nei) && c.slot_base + count <= kRoundCap) {
-        // the sweep's first `count` rounds in one launch: round t writes flag slot t and buffer Q (t even) / R (t odd),
-        // as `count` launches would -- whoever reads the flags afterwards goes on from there
-        count = std::min(count, kFusedMaxRounds);
-        SweepArgs& a = c.a;
-        a.lab_old = e->lab[P]; a.lab_guess = e->lab[P]; a.lab_out = e->lab[Q]; a.lab_out2 = e->lab[R];
-        a.tie_cnt_guess = e->tie_cnt[P]; a.tie_cnt_out = e->tie_cnt[Q];
-        a.flags = e->round_flags(c.slot_base);
-        a.bar = e->meet_words();
-        a.fused_rounds = count;
-        a.exp_tab = (e->exp_ready && e->exp_beta == a.beta) ? e->exp_tab : nullptr; a.exp_tab_len = e->exp_need;
-        a.fold_ticket = e->sweep_next + 32;
-        a.prev_changed = nullptr;
-        a.stop = e->stop_ptr;
-        a.post_on = 0;
-        if (c.post) {
-            a.post_on = 1; a.post_from_guess = 0; a.post_moved = c.post_moved ? 1 : 0; a.post_skip_guess = 0;
-            a.post_nw64 = e->nw64; a.post_mask = e->mask; a.post_flags = e->iter_flags(); a.post_ctrl = c.post_ctrl;
-        }
-        launch_sweep(a, true, e->stream);
-        HIPCHK(hipGetLastError());
-        e->n_fused++;
-        c.r += count;
-        a.fused_rounds = 0;
-        return NEMGPU_OK;
-    }
     for (int b = 0; b < count; b++, c.r++) {
         const int r = c.r;
         const int gb = (r == 0) ? P : ((r - 1) % 2 == 0 ? Q : R);
@@ -885,10 +805,6 @@ int sweep_setup(nemgpu_engine* e, float beta, SweepCtx& c, bool id_by_value)
         if (e->stop_ptr == nullptr) { int r = ensure_draw_window(e, e->draws, draw_need(e)); if (r) return r; }
         sweep_draw_args(e, a, e->stop_ptr == nullptr);
     }
-    // exp(beta * context) from the per-beta table where the graph's weights reach beyond the 64 entries a block computes
-    // itself (sweep_body); the table was made by ensure_exp_table, ahead of any capture or recording
-    a.exp_tab = (c.use_nei && e->ncem() && e->exp_ready && e->exp_beta == beta) ? e->exp_tab : nullptr;
-    a.exp_tab_len = e->exp_need;
     return NEMGPU_OK;
 }
 
@@ -901,25 +817,7 @@ int sweep_enqueue(nemgpu_engine* e, float beta, SweepCtx& c, bool id_by_value = 
     { int r = sweep_setup(e, beta, c, id_by_value); if (r) return r; }
     if (!e->flags_clean) { int r = clear_sweep_flags(e); if (r) return r; }
     e->flags_clean = false;
-    return sweep_launch_rounds(e, c, c.multi ? sweep_first_rounds(e, beta, rounds > 0 ? rounds : e->round_batch) : 1);
-}
-
-// Did a fused launch among the rounds [from, to) of this sweep fail to meet (kFusedFailed)?  Then its rounds are void.
-bool fused_failed_seen(const nemgpu_engine* e, int slot_base, int from, int to)
-{
-    for (int q = from; q < to; q++) if (e->h_round(slot_base + q)[FLAG_CHANGED] & kFusedFailed) return true;
-    return false;
-}
-// ... the sweep starts again from round 0, one launch per round from now on (the old partition and the densities are
-// untouched; the flag window is cleared)
-int fused_fallback(nemgpu_engine* e, SweepCtx& c)
-{
-    e->fused_sweep = false;
-    e->n_fused_failed++;
-    drop_graphs(e);                                      // (they hold fused launches)
-    HIPCHK(hipMemsetAsync(e->round_flags(0), 0, (kRoundCap * FLAG_ROUND_STRIDE + kMeetWords) * sizeof(int), e->stream));
-    c.r = 0; c.checked = 0;
-    return NEMGPU_OK;
+    return sweep_launch_rounds(e, c, c.multi ? (rounds > 0 ? rounds : e->round_batch) : 1);
 }
 
 // `extra` is set when rounds beyond the first batch were needed (work enqueued after the first
@@ -940,13 +838,6 @@ int sweep_complete(nemgpu_engine* e, SweepCtx& c, int* rounds_out, bool* extra, 
         { const int fr = check_fault(e); if (fr) return fr; }
         if (!c.multi) { done_at = 0; break; }
         bool tab_short = false;
-        if (fused_failed_seen(e, c.slot_base, c.checked, c.r)) {
-            int rr = fused_fallback(e, c);
-            if (rr) return rr;
-            if (extra) *extra = true;
-            if ((rr = sweep_launch_rounds(e, c, e->round_batch))) return rr;
-            continue;
-        }
         for (int q = c.checked; q < c.r; q++) {
             if (e->h_round(c.slot_base + q)[FLAG_CHANGED] == 0) { done_at = q; break; }
             if (e->h_round(c.slot_base + q)[FLAG_NTIES] & (1 << 30)) tab_short = true;
@@ -966,7 +857,7 @@ int sweep_complete(nemgpu_engine* e, SweepCtx& c, int* rounds_out, bool* extra, 
         if (c.r % kRoundCap == 0 || c.r % kRoundCap + more > kRoundCap) {
             // the flag window is about to wrap: every earlier round has been examined, start a clean window
             // (keeps the parity of r, which selects the ping-pong buffers)
-            HIPCHK(hipMemsetAsync(e->round_flags(0), 0, (kRoundCap * FLAG_ROUND_STRIDE + kMeetWords) * sizeof(int), e->stream));
+            HIPCHK(hipMemsetAsync(e->round_flags(0), 0, kRoundCap * FLAG_ROUND_STRIDE * sizeof(int), e->stream));
             while (c.r % kRoundCap != 0) c.r += 2;       // skip to the window start, same parity
             c.checked = c.r;
         }
@@ -1012,9 +903,9 @@ int do_mstep(nemgpu_engine* e, const CtrlArgs* prev_ctrl = nullptr)
         launch_finish(finish_args(e, 1, e->stats), e->stream);
     } else {
         launch_mstep_fuzzy(e->n, e->npad, e->k, e->d, e->xw, e->xt, e->nw64, e->cbuf[e->cur] + (size_t)e->lo * e->k,
-                           e->fuzzy_chains ? e->fz_ct : nullptr, e->nbobs_k,
+                           e->fz_ct, e->nbobs_k,
                            e->fz_in0, e->fz_in1, e->fz_inh, e->fz_lastz, e->fz_any1, e->center, e->iner, e->stop_ptr, e->stream,
-                           e->fuzzy_chains == 2 ? e->fz_chk : nullptr, e->iter_flags() + FLAG_FAULT, e->fault_inject);
+                           e->fz_chk, e->iter_flags() + FLAG_FAULT, e->fault_inject);
         launch_finish(finish_args(e, 2, nullptr), e->stream);
     }
     HIPCHK(hipGetLastError());
@@ -1045,7 +936,6 @@ int init_partition(nemgpu_engine* e)
     if (!e->have_matrix || !e->have_params) { set_error("matrix and parameters must be set first"); return NEMGPU_E_FUNCARG; }
     if ((r = flush_reset(e))) return r;
     if ((r = ensure_state_buffers(e))) return r;
-    if ((r = ensure_exp_table(e))) return r;
     if ((r = do_tables(e))) return r;
     if ((r = do_density(e))) return r;
     // ClassifM starts as zeros (calloc, nem_exe.c:524-526): the blind beta = 0 sweep never reads it
@@ -1095,8 +985,6 @@ int host_rounds_ctx(nemgpu_engine* e, SweepCtx& sc, uint32_t sweep_id, int launc
     a.n_local = e->n; a.lo = e->lo; a.n_total = e->n_total; a.K = e->k; a.npad = e->npad; a.use_nei = sc.use_nei ? 1 : 0;
     a.nei_ptr = e->nei_ptr; a.nei_idx = e->nei_idx; a.nei_w = e->nei_w; a.beta = e->cfg.beta; a.pkfki = e->pkfki;
     a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.sweep_id = sweep_id; a.sweep_id_ptr = nullptr;
-    a.exp_tab = (sc.use_nei && e->ncem() && e->exp_ready && e->exp_beta == a.beta) ? e->exp_tab : nullptr;
-    a.exp_tab_len = e->exp_need;
     sc.r = launched; sc.checked = launched;               // (the enqueued rounds all changed something)
     if (e->libc()) {
         for (int q = 0; q < launched; q++) if (e->h_round(q)[FLAG_NTIES] & (1 << 30)) e->tie_heavy = true;
@@ -1160,7 +1048,7 @@ int enqueue_iteration(nemgpu_engine* e, int cur, uint32_t sweep_id, bool defer_c
     CtrlArgs ca{};
     // (members of a lock-step batch all take the same number of rounds: a member with a sequence of its own would
     //  need launches of its own)
-    const int it_rounds = sweep_first_rounds(e, e->cfg.beta, iteration_rounds(e, pos, deep));
+    const int it_rounds = iteration_rounds(e, pos, deep);
     ca.ctrl = e->ctrl(); ca.iter_flags = e->iter_flags(); ca.round0 = e->round_flags(0); ca.n_rounds = it_rounds;
     ca.param_fix = e->cfg.param_fix; ca.use_nei = ((e->has_graph && e->cfg.beta != 0.0f) || e->libc()) ? 1 : 0; ca.cvtest = e->cfg.cvtest;
     ca.ncem = e->ncem() ? 1 : 0; ca.cvthres = e->cfg.cvthres; ca.sweep_next = e->sweep_next; ca.ticket = e->sweep_next + 32;
@@ -1189,11 +1077,11 @@ static bool libc_init_pipelined()
 }
 
 // relaxation rounds a pipelined start enqueues for its beta sweep (enqueue_init; batch_finish continues from there)
-static int init_beta_rounds(const nemgpu_engine* e, int pipelined = -1)
+static int init_beta_rounds(const nemgpu_engine* e)
 {
-    int n = sweep_first_rounds(e, e->cfg.beta, std::max<int>(e->round_batch, (!e->ncem() && current_recorder() == nullptr) ? e->fz_init_need : 0), pipelined);
-    if (e->libc()) n = sweep_first_rounds(e, e->cfg.beta, e->libc_rb, pipelined);      // (what 95 % of the starts so far needed: batch_plan)
-    else if (e->ncem() && current_recorder() == nullptr && e->init_rounds_ncem >= 2) n = sweep_first_rounds(e, e->cfg.beta, e->init_rounds_ncem, pipelined);
+    int n = std::max<int>(e->round_batch, (!e->ncem() && current_recorder() == nullptr) ? e->fz_init_need : 0);
+    if (e->libc()) n = e->libc_rb;                       // (what 95 % of the starts so far needed: batch_plan)
+    else if (e->ncem() && current_recorder() == nullptr && e->init_rounds_ncem >= 2) n = e->init_rounds_ncem;
     return n;
 }
 
@@ -1411,8 +1299,7 @@ int loop_begin(nemgpu_engine* e, LoopCursor& lc, int n_iters, bool with_init)
     if (with_init) {
         if (!e->have_matrix || !e->have_params) { set_error("matrix and parameters must be set first"); return NEMGPU_E_FUNCARG; }
         if ((r = ensure_state_buffers(e))) return r;
-        if ((r = ensure_exp_table(e))) return r;
-        if ((r = clear_fault(e))) return r;
+            if ((r = clear_fault(e))) return r;
         e->reset_pending = false;                          // (the head of the first batch is the device half of a reset)
         e->run_deep_used = 0; e->run_tracked = true;
         e->cur = 0; e->sweep_counter = 0;
@@ -1518,7 +1405,7 @@ int batch_finish(nemgpu_engine* e, LoopCursor& lc)
     e->flags_clean = false;
     e->tables_fresh = e->cfg.param_fix;                        // (the fused density kernel does not rebuild the table buffers)
     if (e->ncem()) e->masks_valid = true;
-    const int init_launched = first ? init_beta_rounds(e, 1) : 0;    // (before the count below is touched)
+    const int init_launched = first ? init_beta_rounds(e) : 0;    // (before the count below is touched)
     if (first && !e->libc() && e->ncem() && current_recorder() == nullptr && e->has_graph && e->cfg.beta != 0.0f) {
         if (c[C_NEED_ROUNDS] == 2) {
             if (e->init_rounds_ncem != 0) { e->init_rounds_ncem = 0; drop_graphs(e); }       // (back to round_batch)
@@ -1536,7 +1423,6 @@ int batch_finish(nemgpu_engine* e, LoopCursor& lc)
         SweepCtx sc;
         const int launched = init_launched;
         if ((r = host_rounds_ctx(e, sc, 1u, launched))) return r;
-        if (fused_failed_seen(e, 0, 0, launched)) { if ((r = fused_fallback(e, sc))) return r; }
         if ((r = sweep_launch_rounds(e, sc, e->round_batch))) return r;
         int init_rounds = 0;
         if ((r = sweep_complete(e, sc, &init_rounds, nullptr))) return r;
@@ -1578,9 +1464,8 @@ int batch_finish(nemgpu_engine* e, LoopCursor& lc)
         e->n_host_rounds++;
         SweepCtx sc;
         const int pos = lc.pos0 + done - 1;                          // the run-relative number of that iteration
-        const int launched = sweep_first_rounds(e, e->cfg.beta, iteration_rounds(e, pos, e->ncem() && done - 1 < lc.deep), 1);
+        const int launched = iteration_rounds(e, pos, e->ncem() && done - 1 < lc.deep);
         if ((r = host_rounds_ctx(e, sc, sweep0 + (uint32_t)(done - 1), launched))) return r;
-        if (fused_failed_seen(e, 0, 0, launched)) { if ((r = fused_fallback(e, sc))) return r; }
         e->deep_iters = std::max(e->deep_iters, e->iters);          // from now on: one round more up to this iteration of a run
         e->run_deep_used = std::max(e->run_deep_used, e->iters);
         if ((r = sweep_launch_rounds(e, sc, e->round_batch))) return r;
@@ -2457,9 +2342,6 @@ int nemgpu_create(nemgpu_engine** out, int n_total, int d, int k, int site_lo, i
     if (const char* g = getenv("NEM_MI355X_ROUNDS")) e->round_batch = std::max(2, std::min(kRoundBatchMax, atoi(g)));
     if (const char* g = getenv("NEM_MI355X_ROUNDS_ITER")) e->rounds_iter = std::max(2, std::min(e->round_batch, atoi(g)));
     e->rounds_iter = std::min(e->rounds_iter, e->round_batch);
-    if (const char* g = getenv("NEM_MI355X_FUSED_SWEEP")) e->fused_sweep = (g[0] == '1');   // 1: the first rounds of a sweep in one launch
-    if (const char* g = getenv("NEM_MI355X_FUSED_ROUNDS")) e->fused_rounds = std::max(2, std::min(kFusedMaxRounds, atoi(g)));
-    if (const char* g = getenv("NEM_MI355X_FUZZY_CHAINS")) e->fuzzy_chains = std::max(0, std::min(2, atoi(g)));
     if (const char* g = getenv("NEM_MI355X_FAULT_INJECT")) e->fault_inject = !strcmp(g, "fuzzy_pc") ? 1 : 0;
     if (const char* g = getenv("NEM_MI355X_FF")) e->ff_mode = (g[0] == '0') ? 0 : (g[0] == '1') ? 1 : -1;   // 0 plain chain, 1 always
     if (const char* g = getenv("NEM_MI355X_SORT")) e->use_sort = (g[0] != '0');       // 0: E1 lanes in family order
@@ -2790,16 +2672,6 @@ int nemgpu_set_graph(nemgpu_engine* e, const int32_t* ptr, const int32_t* idx, c
     }
     e->nnz = nnz;
     e->has_graph = nnz > 0;
-    {
-        // how far a class context can reach: the largest row sum (what the fused sweep copies of its exp table)
-        double top = 0.0;
-        for (int i = 0; i < e->n; i++) {
-            double sum = 0.0;
-            for (int t = ptr[i]; t < ptr[i + 1]; t++) sum += std::fabs((double)w[t]);
-            if (!(sum <= top)) top = sum;                          // (a NaN weight: the whole table)
-        }
-        e->exp_need = (top < (double)(kExpTabGlobal - 1)) ? std::max(1, (int)top + 2) : kExpTabGlobal;
-    }
     drop_graphs(e);
     return NEMGPU_OK;
 }
@@ -2838,7 +2710,6 @@ int nemgpu_configure(nemgpu_engine* e, const nemgpu_config* cfg)
     e->cfg = *cfg;
     HIPCHK(hipSetDevice(e->device));
     drop_graphs(e);                                                // kernel arguments are baked into captured batches
-    { const int xr = ensure_exp_table(e); if (xr) return xr; }     // (the graph is normally set by now; loop_begin looks again)
     return reset_state(e, true);
 }
 
@@ -3517,7 +3388,7 @@ static int adopt_chunk(nemgpu_engine* e, const nemgpu_master* M, const nemk::Chu
     nemk::ChunkFill f{e->n, e->d, e->wf, e->npad, e->xf_stage, e->perm, e->nei_ptr, e->nei_idx, e->nei_w};
     nemk::launch_chunk_fill(M->dev, plan, f, e->stream);
     HIPCHK(hipGetLastError());
-    e->nnz = nnz; e->has_graph = nnz > 0; e->exp_need = kExpTabGlobal;
+    e->nnz = nnz; e->has_graph = nnz > 0;
     e->host_bits = nullptr; e->host_bits_words = 0;              // (no host copy of the rows: random starts are not for chunk engines)
     if (e->defer_layout) e->layout_pending = true;               // (the group's first step carries the layouts, zipped)
     else { launch_layout(e->xf_stage, e->n, e->wf, e->W, e->npad, e->d, e->nw64, e->xw, e->xt, e->perm, e->xws, e->stream); HIPCHK(hipGetLastError()); }
@@ -3870,7 +3741,6 @@ static int make_clone(nemgpu_engine* p, nemgpu_engine** out, char* slab, size_t 
     c->xw = p->xw; c->xws = p->xws; c->perm = p->perm; c->xt = p->xt; c->use_sort = p->use_sort;
     c->nei_ptr = p->nei_ptr; c->nei_idx = p->nei_idx; c->nei_w = p->nei_w; c->nnz = p->nnz;
     c->use_graphs = p->use_graphs; c->ff_mode = p->ff_mode; c->round_batch = p->round_batch; c->rounds_iter = p->rounds_iter;
-    c->fuzzy_chains = p->fuzzy_chains;   // (graphs: the zipped sequences')
     c->parent = p; c->carve_all = true;
     c->chunks.push_back({slab, slab_bytes, 0, false});
     c->shared_chunk = 0;
@@ -4321,8 +4191,6 @@ void shard_sweep_args(nemgpu_engine* e, SweepArgs& a, float beta, int sweep_id)
     a.stop = e->stop_ptr;
     a.n_ranks = e->sh_world; a.slot_stride = e->sh_stride; a.slot_pad = e->sh_stride - e->sh_blk;
     a.fold_ticket = e->sweep_next + 32;
-    a.exp_tab = (a.use_nei && e->ncem() && e->exp_ready && e->exp_beta == beta) ? e->exp_tab : nullptr;
-    a.exp_tab_len = e->exp_need;
     if (e->libc()) { sweep_draw_args(e, a, e->stop_ptr == nullptr); a.rank_index = e->sh_rank; }
 }
 uint8_t* own_flag_byte(nemgpu_engine* e, uint8_t* labels) { return labels + (size_t)e->sh_rank * e->sh_stride + e->sh_blk; }
@@ -4591,9 +4459,9 @@ int nemgpu_shard_fuzzy_mstep_cols(nemgpu_engine* e, const float* c_dev, float* n
     int r;
     if ((r = ensure_state_buffers(e))) return r;
     launch_mstep_fuzzy(e->n, e->npad, e->k, e->d, e->xw, e->xt, e->nw64, c_dev + (size_t)e->lo * e->k,
-                       e->fuzzy_chains ? e->fz_ct : nullptr, e->nbobs_k,
+                       e->fz_ct, e->nbobs_k,
                        e->fz_in0, e->fz_in1, e->fz_inh, e->fz_lastz, e->fz_any1, e->center, e->iner, nullptr, e->stream,
-                       e->fuzzy_chains == 2 ? e->fz_chk : nullptr, e->iter_flags() + FLAG_FAULT, e->fault_inject);
+                       e->fz_chk, e->iter_flags() + FLAG_FAULT, e->fault_inject);
     HIPCHK(hipGetLastError());
     const size_t kd = (size_t)e->k * e->d;
     HIPCHK(hipMemcpyAsync(nbobs_out_dev, e->nbobs_k, sizeof(float) * e->k, hipMemcpyDeviceToDevice, e->stream));
@@ -5363,21 +5231,12 @@ int nemgpu_graph_counters(const nemgpu_engine* e, int out[4])
     return NEMGPU_OK;
 }
 
-int nemgpu_sweep_counters(const nemgpu_engine* e, int out[4])
-{
-    if (!e || !out) return NEMGPU_E_FUNCARG;
-    out[0] = e->n_fused; out[1] = e->n_fused_failed; out[2] = e->fused_sweep ? 1 : 0; out[3] = 0;
-    return NEMGPU_OK;
-}
-
 int nemgpu_random_start_counters(const nemgpu_engine* e, int out[4])
 {
     if (!e || !out) return NEMGPU_E_FUNCARG;
     out[0] = e->rs_rounds; out[1] = e->rs_lockstep; out[2] = e->rs_alone; out[3] = e->rs_redone;
     return NEMGPU_OK;
 }
-
-int nemgpu_sweep_phases(unsigned long long out64[64]) { return out64 && nemk::sweep_phases_read(out64) == 0 ? NEMGPU_OK : NEMGPU_E_FUNCARG; }
 
 int nemgpu_set_stream(nemgpu_engine* e, void* hip_stream)
 {

@@ -1414,19 +1414,13 @@ __device__ __forceinline__ void finish_body(const FinishArgs& a, const int nblk)
 
 // ------------------------------------------------------------------------------------------
 // Fuzzy NEM M-step.  The reference's sums are i-ordered float accumulators, so every (class, organism) chain
-// stays on one lane and the K*D chains run in parallel; a wave holds 64 organisms of one class.  With so few
-// waves (K*D/64) a wave is alone on its SIMD and the time is (instructions per family) x N, so:
-//   * the N families are walked 64 at a time: one strided vector load brings the 64 memberships c_ik, two more
-//     the 64 bit words of the wave's organisms, the next group's loads fly over this group's chain, and the
-//     inner loop takes everything from registers (v_readlane -> SGPRs: c_ik is wave-uniform, and the two bit
-//     words of a family ARE the wave's 64-bit lane mask "organism has the family");
-//   * every chain gets its own wave (roles along blockIdx.x), each step = 3 v_readlane + an add + a select:
-//       pass A  inertia for mu = 0 (sum of c_ik over the ones) / for mu = 1 (over the zeros) / the class total
-//               N_k / the inertia for mu = 0.5 (the same for every organism) / the two order-free facts
-//               ComputeMedian's tie rule needs (they do not depend on N_k, so they run here, beside the sums)
-//       pass B  ComputeMedian's prefix scan over the zeros against N_k/2 (needs pass A's N_k).
-//   (float)((double)a + (double)b) is the float sum a + b -- a double holds the exact sum of two floats' leading
-//   2*24+2 bits, so the double rounding is innocuous -- which is how the mu = 0 / mu = 1 chains are float adds.
+// stays on one lane and the K*D chains run in parallel; a wave holds 64 organisms of one class.  A wave that walks
+// the N families itself takes them 64 at a time (FuzzyWalk): one strided vector load brings the 64 memberships c_ik,
+// two more the 64 bit words of the wave's organisms, the next group's loads fly over this group's chain, and the
+// inner loop takes everything from registers (v_readlane -> SGPRs: c_ik is wave-uniform, and the two bit words of a
+// family ARE the wave's 64-bit lane mask "organism has the family").
+// (float)((double)a + (double)b) is the float sum a + b -- a double holds the exact sum of two floats' leading
+// 2*24+2 bits, so the double rounding is innocuous -- which is how the mu = 0 / mu = 1 chains are float adds.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ float lane_f32(float v, int j) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j)); }
 __device__ __forceinline__ uint64_t lane_mask(uint32_t lo, uint32_t hi, int j)
@@ -1480,379 +1474,7 @@ __device__ __forceinline__ FuzzyWalk fuzzy_walk(int n, int npad, int K, int D, i
     return w;
 }
 
-// The sums that take c_ik from the families where the lane's organism has a given bit -- the inertia candidates, the
-// median's prefix sum -- read that bit from the lane's OWN row of bits (`xt`, organism-major: one 64-bit word per 64
-// families) and the 64 memberships from LDS, four per broadcast read: a step is a sign-extended bit, an AND and an
-// add (the addend is c_ik or +0, and adding +0 leaves a sum that is >= +0 as it is), three instructions instead of
-// three readlanes, an add and a select.
-struct OwnWalk {
-    const float* c; const uint64_t* row; int n, K, k, nw64, lane; float* sC;
-    // group(i0, cnt, own): sC[0..cnt) holds the memberships of families i0 .. i0 + cnt - 1, bit j of `own` is the
-    // lane's organism's bit for family i0 + j
-    template <typename G> __device__ __forceinline__ void groups(G&& group)
-    {
-        // (two groups ahead: the bit words of a wave's 64 organisms are 64 different cache lines)
-        float cn = c[(size_t)min(lane, n - 1) * K + k], cn2 = c[(size_t)min(64 + lane, n - 1) * K + k];
-        uint64_t on = row[0], on2 = row[min(1, nw64 - 1)];
-        int g = 0;
-        for (int i0 = 0; i0 < n; i0 += 64, g++) {
-            const float cv = cn;
-            const uint64_t own = on;
-            cn = cn2; on = on2;
-            if (i0 + 128 < n) { cn2 = c[(size_t)min(i0 + 128 + lane, n - 1) * K + k]; on2 = row[g + 2]; }
-            __syncthreads();                             // (one wave per block: the previous group's reads are done)
-            sC[lane] = cv;
-            __syncthreads();
-            group(i0, min(64, n - i0), own);
-        }
-    }
-    // acc += c for the families whose bit in `sel` is set, in family order
-    __device__ __forceinline__ void masked_add(float& acc, int cnt, uint64_t sel) const
-    {
-        const uint32_t lo = (uint32_t)sel, hi = (uint32_t)(sel >> 32);
-        if (cnt == 64) {
-            const float4* s4 = reinterpret_cast<const float4*>(sC);
-#pragma unroll
-            for (int q = 0; q < 16; q++) {
-                const float4 v = s4[q];
-                const uint32_t w = q < 8 ? lo : hi;
-                const int b = (4 * q) & 31;
-                acc += __int_as_float(__float_as_int(v.x) & __builtin_amdgcn_sbfe((int)w, b, 1));
-                acc += __int_as_float(__float_as_int(v.y) & __builtin_amdgcn_sbfe((int)w, b + 1, 1));
-                acc += __int_as_float(__float_as_int(v.z) & __builtin_amdgcn_sbfe((int)w, b + 2, 1));
-                acc += __int_as_float(__float_as_int(v.w) & __builtin_amdgcn_sbfe((int)w, b + 3, 1));
-            }
-        } else {
-            for (int j = 0; j < cnt; j++)
-                acc += ((sel >> j) & 1ull) ? sC[j] : 0.0f;
-        }
-    }
-};
-
-// roles along blockIdx.x: [0,DB) in0, [DB,2DB) in1, [2DB,3DB) last zero of weight >= EPSILON,
-// [3DB,4DB) "some one has weight >= EPSILON", 4DB: N_k, 4DB+1: inertia for mu = 0.5
-__device__ __forceinline__ void mstep_fuzzy_a_body(int n, int npad, int K, int D, const uint32_t* __restrict__ xw,
-                                                      const uint64_t* __restrict__ xt, int nw64,
-                                                      const float* __restrict__ c, float* __restrict__ nbobs_k,
-                                                      float* __restrict__ in0_out, float* __restrict__ in1_out,
-                                                      float* __restrict__ inh_k, int* __restrict__ lastz_out,
-                                                      int* __restrict__ any1_out, const int* __restrict__ stop,
-                                                      const int flags_only)
-{
-    if (stop != nullptr && *stop) return;
-    const int DB = (D + 63) >> 6;
-    const int role = blockIdx.x < 4 * DB ? blockIdx.x / DB : 4 + (int)blockIdx.x - 4 * DB;
-    if (flags_only && role != 2 && role != 3) return;                    // (the sums are k_mstep_fuzzy_sums' then)
-    const int bx = role < 4 ? blockIdx.x - role * DB : 0;
-    const int k = blockIdx.y;
-    const int d = bx * 64 + threadIdx.x;
-    __shared__ float sC[64];
-    OwnWalk ow{c, xt + (size_t)min(d, D - 1) * nw64, n, K, k, nw64, (int)threadIdx.x, sC};
-    if (role == 4) {                                                     // N_k (nem_mod.c:1308): every membership
-        float nk = 0.0f;
-        ow.groups([&](int, int cnt, uint64_t) { ow.masked_add(nk, cnt, ~0ull); });
-        if (threadIdx.x == 0) nbobs_k[k] = nk;
-        return;
-    }
-    if (role == 5) {
-        // nem_mod.c:1683 with |x - 0.5| = 0.5: inh = (float)((double)inh + (double)c * 0.5).  When c/2 is a float
-        // (always, but for an odd subnormal) that is the float sum inh + c/2; groups holding such a c take the
-        // double form.
-        float inh = 0.0f;
-        ow.groups([&](int, int cnt, uint64_t) {
-            const float cv = sC[threadIdx.x];
-            const float hv = cv * 0.5f;
-            const bool halves = __ballot(threadIdx.x < (unsigned)cnt && hv * 2.0f != cv) == 0;
-            __syncthreads();
-            if (halves) {
-                sC[threadIdx.x] = hv;
-                __syncthreads();
-                ow.masked_add(inh, cnt, ~0ull);
-            } else {
-                for (int j = 0; j < cnt; j++) inh = (float)((double)inh + (double)sC[j] * 0.5);
-            }
-        });
-        if (threadIdx.x == 0) inh_k[k] = inh;
-        return;
-    }
-    if (role == 2 || role == 3) {
-        // The two facts ComputeMedian's tie rule needs (nem_mod.c:1470-1483) do not depend on the order of the
-        // families: the index of the last zero whose weight is >= EPSILON (pass B compares it with where its chain
-        // crossed) and whether some one has such a weight -- a ballot of the weights per 64 families against the
-        // lane's own word of bits.
-        int last = -1;
-        bool some = false;
-        ow.groups([&](int i0, int cnt, uint64_t own) {
-            const float cv = sC[threadIdx.x];
-            uint64_t big = __ballot(threadIdx.x < (unsigned)cnt && !((double)cv < kEpsilonD));
-            const uint64_t z = ~own & big, o = own & big;
-            if (z != 0) last = i0 + 63 - __clzll((long long)z);
-            some |= (o != 0);
-        });
-        if (d < D) {
-            if (role == 2) lastz_out[k * D + d] = last;
-            else any1_out[k * D + d] = some ? 1 : 0;
-        }
-        return;
-    }
-    const uint64_t flip = role == 1 ? ~0ull : 0ull;                      // role 1 sums over the zeros
-    float acc = 0.0f;
-    ow.groups([&](int, int cnt, uint64_t own) { ow.masked_add(acc, cnt, own ^ flip); });   // nem_mod.c:1683, |x - mu| = 1
-    if (d < D) (role == 0 ? in0_out : in1_out)[k * D + d] = acc;
-}
-
-__device__ __forceinline__ void mstep_fuzzy_b_body(int n, int npad, int K, int D, const uint32_t* __restrict__ xw,
-                                                      const uint64_t* __restrict__ xt, int nw64,
-                                                      const float* __restrict__ c, const float* __restrict__ nbobs_k,
-                                                      const float* __restrict__ in0, const float* __restrict__ in1,
-                                                      const float* __restrict__ inh_k, const int* __restrict__ lastz,
-                                                      const int* __restrict__ any1, float* __restrict__ center,
-                                                      float* __restrict__ iner, const int* __restrict__ stop)
-{
-    if (stop != nullptr && *stop) return;
-    const int k = blockIdx.y;
-    const int d = blockIdx.x * 64 + threadIdx.x;
-    const int t = k * D + min(d, D - 1);
-    FuzzyWalk w = fuzzy_walk(n, npad, K, D, k, blockIdx.x, xw, c);
-    const float nk = nbobs_k[k];
-    if (!((double)nk > kEpsilonD)) {
-        // "empty" class (nem_mod.c:1404-1408): the centre is kept, and EstimLaplaceIner (:1669-1686) still runs
-        // against that old centre -- the class may hold weights between 0 and EPSILON, which InerToDisp* then
-        // turns into a dispersion (they test N_K > 0, not > EPSILON)
-        const float mu = center[t];
-        const double a1 = fabs((double)(1.0f - mu)), a0 = fabs((double)(0.0f - mu));
-        float in = 0.0f;
-        w.run([&](float cv, uint32_t xl, uint32_t xh, int j) {
-            const float ci = lane_f32(cv, j);
-            const bool one = __builtin_amdgcn_inverse_ballot_w64(lane_mask(xl, xh, j));
-            in = (float)((double)in + (double)ci * (one ? a1 : a0));     // :1683
-        });
-        if (d < D) iner[t] = in;
-        return;
-    }
-    // Only the zeros' chain decides (nem_mod.c:1439-1497): once the cumulated weight of the zeros reaches N_k/2
-    // the median sits among them, otherwise it is a one (or midway between two ones) whatever the ones' chain
-    // does.  crossed = lane mask "the chain has reached N_k/2" (it is frozen from there on).
-    const float half = nk / 2;                           // nem_mod.c:1439
-    const double half_eps = (double)half + kEpsilonD;    // nem_mod.c:1464
-    // The weights are >= 0, so a chain that has reached N_k/2 stays there: the walk runs the bare chain (add, select
-    // on the family's lane mask) over 64 families, tests the crossing once per group, and only a group in which
-    // some lane crossed is walked again, from the saved start, to find that lane's family and value.
-    float run = 0.0f, cum = 0.0f;
-    int istar = n;                                       // family at which the chain crossed
-    uint64_t crossed = 0;
-    __shared__ float sC[64];
-    OwnWalk ow{c, xt + (size_t)min(d, D - 1) * nw64, n, K, k, nw64, (int)threadIdx.x, sC};
-    ow.groups([&](int i0, int cnt, uint64_t own) {
-        const float start = run;
-        ow.masked_add(run, cnt, ~own);                   // the zeros' memberships, in family order
-        const uint64_t newly = __ballot(!(run < half)) & ~crossed;
-        if (newly != 0) {
-            float cv; uint32_t xl, xh;                   // this group again, family by family (lane j = family i0 + j)
-            w.load(i0, cv, xl, xh);
-            float r2 = start;
-            int cj = -1;
-            uint64_t seen = ~newly;
-            FuzzyWalk::lanes(cnt, [&](int j) {
-                const uint64_t one = lane_mask(xl, xh, j);
-                const float nx = r2 + lane_f32(cv, j);
-                const uint64_t now = __ballot(!(nx < half)) & ~one & ~seen;
-                r2 = __builtin_amdgcn_inverse_ballot_w64(one) ? r2 : nx;
-                cum = __builtin_amdgcn_inverse_ballot_w64(now) ? nx : cum;
-                cj = __builtin_amdgcn_inverse_ballot_w64(now) ? j : cj;
-                seen |= now;
-            });
-            istar = cj >= 0 ? i0 + cj : istar;
-            crossed |= newly;
-        }
-    });
-    const bool ph0 = __builtin_amdgcn_inverse_ballot_w64(crossed);
-    const bool gt0 = (double)cum > half_eps;             // cum is the value at the crossing
-    float mu;
-    if (ph0) {                                           // median position among the zeros
-        const bool next0 = lastz[t] > istar;             // a zero of weight >= EPSILON follows the crossing
-        if (gt0 || next0) mu = 0.0f;                     // x_med = 0 (or midway to another 0)
-        else if (any1[t]) mu = 0.5f;                     // midway to the first one with weight
-        else mu = 0.0f;                                  // reference runs off the array here (UB)
-    } else {
-        mu = 1.0f;                                       // x_med = 1 (or midway to another 1)
-    }
-    if (d < D) {
-        center[t] = mu;
-        iner[t] = (mu == 0.0f) ? in0[t] : (mu == 1.0f ? in1[t] : inh_k[k]);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// The fuzzy M-step's sums, split along the families.  Each of the K*(2D+2) sums of pass A and the K*D prefix scans
-// of pass B is an i-ordered float accumulator over all N families (nem_mod.c:1303-1313, 1677-1686, 1448-1458) --
-// N dependent adds, whoever runs them.  But between two powers of two a float accumulator moves on a fixed grid
-// and the chain is a prefix sum of integers (nem_chain.hpp); the sum is then a matter of a scan.  Here ONE WAVE
-// owns a chain and takes it 256 families at a time: every lane turns its four memberships into grid increments,
-// a DPP scan places them, the first element the integer form cannot take (the next binade, an exact tie, a sum
-// that is not ready) is found with a ballot and stepped -- with a short burst behind it -- by the reference's own
-// float add.  Float inputs make this simpler than the criteria's chains: c * 2^s is exact, so "near a tie" is
-// "exactly a tie".  (float)((double)a + (double)b) is the float sum, so all four kinds of sums are float adds.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);   // row_shr:8: prefix inside each row of 16
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15 into rows 1 and 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31 into rows 2 and 3
-    return v;
-}
-
-// LDS written by some lanes of a wave and read by others of the SAME wave: the hardware keeps a wave's LDS
-// operations in order; this only stops the compiler from moving them across (no block barrier: the chains of a
-// block's waves advance independently)
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-constexpr int kEPL = 4;                                  // families per lane and window of the chain kernels
-constexpr int kWin = 64 * kEPL;                          // families per window
-
-struct WaveChain {
-    float* sx;                                           // LDS: the window's kWin addends, family order
-    float acc;                                           // the accumulator (the same value in every lane)
-    int burst;
-    // sequential float adds of sx[p .. p + count): the reference's own arithmetic, sixteen addends fetched ahead
-    __device__ __forceinline__ void steps(int p, int count)
-    {
-        int i = 0;
-        for (; i + 16 <= count; i += 16) {
-            float v[16];
-#pragma unroll
-            for (int t = 0; t < 16; t++) v[t] = sx[p + i + t];
-#pragma unroll
-            for (int t = 0; t < 16; t++) acc = acc + v[t];
-        }
-        for (; i < count; i++) acc = acc + sx[p + i];
-    }
-    // the window: wn (<= kWin) addends, lane l holds x[0 .. kEPL) = addends kEPL l .. (the same values are in sx).
-    // Branch-free per element: what an element adds and whether the integer form can take it are selects.
-    __device__ __forceinline__ void window(const float (&x)[kEPL], int wn)
-    {
-        const int e0 = kEPL * (int)(threadIdx.x & 63);
-        int pos = 0;
-        while (pos < wn) {
-            const uint32_t ab = __float_as_uint(acc);
-            const int E = (int)((ab >> 23) & 255u);
-            if ((ab >> 31) != 0u || E < 24 || E > 253) {      // negative, tiny, zero or not finite: step
-                const int cnt = min(burst, wn - pos);
-                steps(pos, cnt);
-                pos += cnt;
-                burst = nemchain::next_burst(burst, -1);
-                continue;
-            }
-            const float sc = __uint_as_float((uint32_t)(127 + 150 - E) << 23);    // 1 / ulp(acc): 2^(150 - E), a normal float
-            const uint32_t M0 = (ab & 0x7fffffu) | 0x800000u;
-            constexpr uint32_t top = 1u << 24;
-            if (pos == 0) {
-                // most windows hold nothing the integer form cannot take and end inside the binade they began in:
-                // then all that is needed is the sum of the increments (no scan, no search for the first stop)
-                uint32_t tot = 0; bool clean = true;
-#pragma unroll
-                for (int j = 0; j < kEPL; j++) {
-                    const float q = x[j] * sc;           // (addends behind wn are -0: increment 0)
-                    const float fl = floorf(q);
-                    const float fr = q - fl;
-                    clean = clean & (q >= 0.0f) & (q < 33554432.0f) & (fr != 0.5f);
-                    tot += (uint32_t)fl + (fr > 0.5f ? 1u : 0u);
-                }
-                const bool small = tot < (1u << 17);     // (64 lanes of less than 2^17 cannot wrap 32 bits)
-                if (__ballot(!(clean & small)) == 0ull) {
-                    const uint32_t Mt = M0 + (uint32_t)wave_reduce_add((int)tot);
-                    if (Mt <= top) {
-                        acc = __uint_as_float(Mt >= top ? ((uint32_t)(E + 1) << 23) : (((uint32_t)E << 23) | (Mt & 0x7fffffu)));
-                        burst = nemchain::next_burst(burst, wn);
-                        return;
-                    }
-                }
-            }
-            uint32_t inc[kEPL];
-            int stop = kEPL;                             // first of mine the integer form cannot take
-            uint32_t lsum = 0;
-#pragma unroll
-            for (int j = 0; j < kEPL; j++) {
-                const int e = e0 + j;
-                const bool act = (e >= pos) & (e < wn);
-                const float q = x[j] * sc;               // exact (a power-of-two scaling; an overflow gives inf)
-                const float fl = floorf(q);
-                const float fr = q - fl;                 // exact
-                // takeable: 0 <= q < 2^25 (a shrinking sum, NaN or inf fail the compares) and not a tie (its rounding
-                // depends on the parity of M)
-                const bool ok = (q >= 0.0f) & (q < 33554432.0f) & (fr != 0.5f);
-                const uint32_t v = (uint32_t)fl + (fr > 0.5f ? 1u : 0u);
-                const bool first_bad = act & !ok & (stop == kEPL);
-                stop = first_bad ? j : stop;
-                inc[j] = (act & ok & (stop == kEPL)) ? v : 0u;
-                lsum += inc[j];
-            }
-            const uint32_t incl = wave_scan_incl(lsum);
-            uint32_t M = M0 + incl - lsum;
-            int cand = INT_MAX; uint32_t candM = 0;
-#pragma unroll
-            for (int j = 0; j < kEPL; j++) {
-                const int e = e0 + j;
-                const bool act = (e >= pos) & (e < wn);
-                const bool hit = act & (cand == INT_MAX) & ((j == stop) | (M >= top) | (M + inc[j] > top));
-                candM = hit ? M : candM;
-                cand = hit ? e : cand;
-                M += inc[j];
-            }
-            const uint64_t who = __ballot(cand != INT_MAX);
-            if (who == 0ull) {                           // the rest of the window went through in integer form
-                const uint32_t Mt = (uint32_t)__builtin_amdgcn_readlane((int)(M0 + incl), 63);
-                acc = __uint_as_float(Mt >= top ? ((uint32_t)(E + 1) << 23) : (((uint32_t)E << 23) | (Mt & 0x7fffffu)));
-                burst = nemchain::next_burst(burst, wn - pos);
-                pos = wn;
-                break;
-            }
-            const int first = (int)__ffsll((long long)who) - 1;      // (a lane behind the first stop holds a wrong M: ignored)
-            const int p = __builtin_amdgcn_readlane(cand, first);
-            const uint32_t Mb = (uint32_t)__builtin_amdgcn_readlane((int)candM, first);
-            acc = __uint_as_float(Mb >= top ? ((uint32_t)(E + 1) << 23) : (((uint32_t)E << 23) | (Mb & 0x7fffffu)));
-            const int cnt = min(burst, wn - p);
-            steps(p, cnt);
-            burst = nemchain::next_burst(burst, p - pos);
-            pos = p + cnt;
-        }
-    }
-};
-
-// One window's inputs of a lane: its kEPL memberships of class k (class-major copy ct[K][npad]) for families
-// i0 + kEPL lane .. and the word of organism row `row` that holds their bits.  (The word is handed on as loaded:
-// shifting it here would make the fetch wait for its own load, and the fetch runs ahead of its use.)
-struct FuzzyIn { float4 c[kEPL / 4]; uint64_t word; };
-__device__ __forceinline__ void fuzzy_fetch(const float* __restrict__ ctk, const uint64_t* __restrict__ row, int i0, int lane,
-                                            int nw64, FuzzyIn& in)
-{
-    const float4* p = reinterpret_cast<const float4*>(ctk + i0 + kEPL * lane);
-#pragma unroll
-    for (int t = 0; t < kEPL / 4; t++) in.c[t] = p[t];
-    const int w = min((i0 >> 6) + ((kEPL * lane) >> 6), nw64 - 1);
-    in.word = row != nullptr ? row[w] : ~0ull;
-}
-__device__ __forceinline__ uint32_t fuzzy_bits(uint64_t word, int lane) { return (uint32_t)(word >> ((kEPL * lane) & 63)) & ((1u << kEPL) - 1u); }
-__device__ __forceinline__ void fuzzy_unpack(const FuzzyIn& in, float (&x)[kEPL])
-{
-#pragma unroll
-    for (int t = 0; t < kEPL / 4; t++) { x[4 * t] = in.c[t].x; x[4 * t + 1] = in.c[t].y; x[4 * t + 2] = in.c[t].z; x[4 * t + 3] = in.c[t].w; }
-}
-__device__ __forceinline__ void fuzzy_stage(float* sx, int lane, const float (&x)[kEPL])
-{
-    float4* d = reinterpret_cast<float4*>(sx + kEPL * lane);
-#pragma unroll
-    for (int t = 0; t < kEPL / 4; t++) d[t] = make_float4(x[4 * t], x[4 * t + 1], x[4 * t + 2], x[4 * t + 3]);
-}
-
+constexpr int kWin = 256;                                // families per window of ct (ctpad is a multiple of it)
 // c [n][K] -> ct [K][ctpad] (zeros behind n; ctpad: n rounded up to whole windows)
 __device__ __forceinline__ void transpose_c_body(int n, int ctpad, int K, const float* __restrict__ c, float* __restrict__ ct,
                                                  const int* __restrict__ stop)
@@ -2107,7 +1729,8 @@ __device__ __forceinline__ void mstep_fuzzy_med2_body(const FuzzyArgs& a)
     const float nk = a.nbobs_k[k];
     if (!((double)nk > kEpsilonD)) {
         // "empty" class (nem_mod.c:1404-1408): the centre is kept, and EstimLaplaceIner (:1669-1686) still runs
-        // against that old centre (see mstep_fuzzy_b_body)
+        // against that old centre -- the class may hold weights between 0 and EPSILON, which InerToDisp* then
+        // turns into a dispersion (they test N_K > 0, not > EPSILON)
         FuzzyWalk w = fuzzy_walk(n, a.npad, K, D, k, blockIdx.x, a.xw, a.c);
         const float mu = a.center[t];
         const double a1 = fabs((double)(1.0f - mu)), a0 = fabs((double)(0.0f - mu));
@@ -2174,175 +1797,6 @@ __device__ __forceinline__ void mstep_fuzzy_med2_body(const FuzzyArgs& a)
         a.center[t] = mu;
         a.iner[t] = (mu == 0.0f) ? a.in0[t] : (mu == 1.0f ? a.in1[t] : a.inh_k[k]);
     }
-}
-
-// pass A: chains [0, D) inertia for mu = 0 (the ones), [D, 2D) for mu = 1 (the zeros), 2D: N_k, 2D + 1: mu = 1/2
-__device__ __forceinline__ void mstep_fuzzy_sums_body(const FuzzyArgs& a)
-{
-    if (a.stop != nullptr && *a.stop) return;
-    __shared__ float sx_all[kFuzzyWaves][kWin];
-    const int k = blockIdx.y, D = a.D, lane = threadIdx.x & 63;
-    const int chain = blockIdx.x * kFuzzyWaves + (threadIdx.x >> 6);             // one chain per wave
-    if (chain >= 2 * D + 2) return;
-    float* sx = sx_all[threadIdx.x >> 6];
-    const int role = chain < D ? 0 : chain < 2 * D ? 1 : chain - 2 * D + 2;      // 0 ones, 1 zeros, 2 all, 3 halves
-    const int d = role == 0 ? chain : role == 1 ? chain - D : 0;
-    const uint64_t* row = role < 2 ? a.xt + (size_t)d * a.nw64 : nullptr;
-    const float* ctk = a.ct + (size_t)k * a.ctpad;
-    WaveChain wc{sx, 0.0f, nemchain::kBurst};
-    int fact = -1;                                       // this lane's last family of the sum with a weight >= EPSILON
-    // Four windows are in flight ahead of the one being summed (a window's arithmetic is shorter than a trip to
-    // memory): four register sets, each refilled right after use.  Every fetch is issued unconditionally (behind the
-    // last window it repeats the last one), so that the compiler counts outstanding loads exactly and waits for the
-    // oldest only.
-    const int nwin = (a.n + kWin - 1) / kWin;
-    int gi = 0;
-    auto fetch = [&](FuzzyIn& dst) { fuzzy_fetch(ctk, row, min(gi, nwin - 1) * kWin, lane, a.nw64, dst); gi++; };
-    auto take = [&](const FuzzyIn& cur, const int i0) {
-        uint32_t b = fuzzy_bits(cur.word, lane);
-        if (role == 1) b = ~b;
-        float x[kEPL];
-        fuzzy_unpack(cur, x);
-        const int wn = min(kWin, a.n - i0);
-        bool halves = true;
-        if (role < 2) {
-            // the two order-free facts ComputeMedian's tie rule needs (nem_mod.c:1470-1483), beside the sums: whether
-            // some ONE has a weight >= EPSILON (with the ones' sum), the last ZERO that has (with the zeros' sum)
-#pragma unroll
-            for (int j = 0; j < kEPL; j++) {
-                const bool in = ((b >> j) & 1u) != 0 && kEPL * lane + j < wn;
-                if (in && !((double)x[j] < kEpsilonD)) fact = i0 + kEPL * lane + j;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < kEPL; j++) {
-            if (role == 3) {                             // nem_mod.c:1683 with |x - 1/2| = 1/2: (float)((double)s + (double)c * 0.5)
-                const float h = x[j] * 0.5f;             //  = the float sum s + c/2 whenever c/2 is a float
-                halves = halves && (h * 2.0f == x[j]);
-                x[j] = h;
-            } else if (!((b >> j) & 1u) || kEPL * lane + j >= wn) x[j] = -0.0f;   // not in this sum: the additive identity
-        }
-        if (role == 3 && __ballot(!halves) != 0ull) {    // an odd subnormal membership: this window in the double form
-            float raw[kEPL];
-            fuzzy_unpack(cur, raw);
-            wave_lds_sync();
-            fuzzy_stage(sx, lane, raw);
-            wave_lds_sync();
-            for (int j = 0; j < wn; j++) wc.acc = (float)((double)wc.acc + (double)sx[j] * 0.5);
-            return;
-        }
-        wave_lds_sync();                                 // (the previous window's reads are done)
-        fuzzy_stage(sx, lane, x);
-        wave_lds_sync();
-        wc.window(x, wn);
-    };
-    FuzzyIn r0, r1, r2, r3;
-    fetch(r0); fetch(r1); fetch(r2); fetch(r3);
-    for (int w = 0; w < nwin; w += 4) {
-        take(r0, w * kWin); fetch(r0);
-        if (w + 1 < nwin) { take(r1, (w + 1) * kWin); fetch(r1); }
-        if (w + 2 < nwin) { take(r2, (w + 2) * kWin); fetch(r2); }
-        if (w + 3 < nwin) { take(r3, (w + 3) * kWin); fetch(r3); }
-    }
-    if (role < 2) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) fact = max(fact, __shfl_xor(fact, o));
-    }
-    if (lane == 0) {
-        if (role == 0) { a.in0[k * D + d] = wc.acc; a.any1[k * D + d] = fact >= 0 ? 1 : 0; }
-        else if (role == 1) { a.in1[k * D + d] = wc.acc; a.lastz[k * D + d] = fact; }
-        else if (role == 2) a.nbobs_k[k] = wc.acc;
-        else a.inh_k[k] = wc.acc;
-    }
-}
-
-// pass B: ComputeMedian's prefix scan over the zeros of organism d against N_k / 2 (nem_mod.c:1439-1497), then the
-// centre and its inertia; a class without weight keeps its centres and gets its inertia against them (:1404-1408, 1669-1686)
-__device__ __forceinline__ void mstep_fuzzy_median_body(const FuzzyArgs& a)
-{
-    if (a.stop != nullptr && *a.stop) return;
-    __shared__ float sx_all[kFuzzyWaves][kWin];
-    const int k = blockIdx.y, D = a.D, lane = threadIdx.x & 63, d = blockIdx.x * kFuzzyWaves + (threadIdx.x >> 6);
-    if (d >= D) return;
-    float* sx = sx_all[threadIdx.x >> 6];
-    const int t = k * D + d;
-    const uint64_t* row = a.xt + (size_t)d * a.nw64;
-    const float* ctk = a.ct + (size_t)k * a.ctpad;
-    const float nk = a.nbobs_k[k];
-    const bool empty = !((double)nk > kEpsilonD);
-    const float mu_old = a.center[t];
-    const float half = nk / 2;                           // nem_mod.c:1439
-    const double half_eps = (double)half + kEpsilonD;    // nem_mod.c:1464
-    WaveChain wc{sx, 0.0f, nemchain::kBurst};
-    int istar = a.n; float cum = 0.0f; bool crossed = false;
-    const int nwin = (a.n + kWin - 1) / kWin;            // (four windows in flight: see mstep_fuzzy_sums_body)
-    int gi = 0;
-    auto fetch = [&](FuzzyIn& dst) { fuzzy_fetch(ctk, row, min(gi, nwin - 1) * kWin, lane, a.nw64, dst); gi++; };
-    auto take = [&](const FuzzyIn& cur, const int i0) {
-        const uint32_t b = fuzzy_bits(cur.word, lane);
-        float x[kEPL];
-        fuzzy_unpack(cur, x);
-        const int wn = min(kWin, a.n - i0);
-        bool exact = true;
-#pragma unroll
-        for (int j = 0; j < kEPL; j++) {
-            const bool one = ((b >> j) & 1u) != 0;
-            if (kEPL * lane + j >= wn) x[j] = -0.0f;
-            else if (empty) {                            // c * |x - mu_old|, |.| in {0, 1/2, 1} for the centres the M-step makes
-                const float ad = fabsf((one ? 1.0f : 0.0f) - mu_old);
-                const float v = x[j] * ad;
-                exact = exact && (ad == 0.0f || ad == 1.0f || (ad == 0.5f && v * 2.0f == x[j]));
-                x[j] = ad == 0.0f ? -0.0f : v;
-            } else if (one) x[j] = -0.0f;                // the scan runs over the zeros
-        }
-        if (empty && __ballot(!exact) != 0ull) {         // a centre outside {0, 1/2, 1} (hand-made .m): the double form
-            float raw[kEPL];
-            fuzzy_unpack(cur, raw);
-            wave_lds_sync();
-            fuzzy_stage(sx, lane, raw);
-            wave_lds_sync();
-            for (int j = 0; j < wn; j++) {
-                const int i = i0 + j;
-                const bool one = ((row[i >> 6] >> (i & 63)) & 1ull) != 0;
-                wc.acc = (float)((double)wc.acc + (double)sx[j] * fabs((double)((one ? 1.0f : 0.0f) - mu_old)));   // :1683
-            }
-            return;
-        }
-        wave_lds_sync();
-        fuzzy_stage(sx, lane, x);
-        wave_lds_sync();
-        const float before = wc.acc;
-        wc.window(x, wn);
-        if (!empty && !(wc.acc < half)) {
-            // the weights are >= 0: the scan reached N_k / 2 inside this window -- walk it again for the family
-            float run = before;
-            for (int j = 0; j < wn; j++) {
-                run = run + sx[j];
-                if (!(run < half)) { istar = i0 + j; cum = run; break; }
-            }
-            crossed = true;
-        }
-    };
-    FuzzyIn r0, r1, r2, r3;
-    fetch(r0); fetch(r1); fetch(r2); fetch(r3);
-    for (int w = 0; w < nwin && !crossed; w += 4) {
-        take(r0, w * kWin); fetch(r0);
-        if (w + 1 < nwin && !crossed) { take(r1, (w + 1) * kWin); fetch(r1); }
-        if (w + 2 < nwin && !crossed) { take(r2, (w + 2) * kWin); fetch(r2); }
-        if (w + 3 < nwin && !crossed) { take(r3, (w + 3) * kWin); fetch(r3); }
-    }
-    if (lane != 0) return;
-    if (empty) { a.iner[t] = wc.acc; return; }
-    float mu;
-    if (crossed) {                                       // median position among the zeros
-        const bool gt0 = (double)cum > half_eps;         // cum is the value at the crossing
-        const bool next0 = a.lastz[t] > istar;           // a zero of weight >= EPSILON follows the crossing
-        if (gt0 || next0) mu = 0.0f;                     // x_med = 0 (or midway to another 0)
-        else if (a.any1[t]) mu = 0.5f;                   // midway to the first one with weight
-        else mu = 0.0f;                                  // reference runs off the array here (UB)
-    } else mu = 1.0f;                                    // x_med = 1 (or midway to another 1)
-    a.center[t] = mu;
-    a.iner[t] = (mu == 0.0f) ? a.in0[t] : (mu == 1.0f ? a.in1[t] : a.inh_k[k]);
 }
 
 // CVTEST_CLAS for float partitions (nem_alg.c:2077-2088): converged iff no |c - cold| >= thres
@@ -2690,38 +2144,12 @@ __global__ __launch_bounds__(256) void k_mstep_counts_b(const void* arr, int str
     NEM_B_HEAD(CountsArgs)
     mstep_counts_body<R>(a.K, a.D, a.nw64, a.xt, a.mask, a.stats, a.stop, a.prev_ctrl, blockIdx.x, nblk);
 }
-__global__ __launch_bounds__(64) void k_mstep_fuzzy_a(FuzzyArgs a)
-{
-    mstep_fuzzy_a_body(a.n, a.npad, a.K, a.D, a.xw, a.xt, a.nw64, a.c, a.nbobs_k, a.in0, a.in1, a.inh_k, a.lastz, a.any1, a.stop,
-                       a.ct != nullptr);
-}
-__global__ __launch_bounds__(64) void k_mstep_fuzzy_a_b(const void* arr, int stride, const int* gx)
-{
-    NEM_B_HEAD(FuzzyArgs)
-    mstep_fuzzy_a_body(a.n, a.npad, a.K, a.D, a.xw, a.xt, a.nw64, a.c, a.nbobs_k, a.in0, a.in1, a.inh_k, a.lastz, a.any1, a.stop,
-                       a.ct != nullptr);
-}
-__global__ __launch_bounds__(64) void k_mstep_fuzzy_b(FuzzyArgs a)
-{
-    mstep_fuzzy_b_body(a.n, a.npad, a.K, a.D, a.xw, a.xt, a.nw64, a.c, a.nbobs_k, a.in0, a.in1, a.inh_k, a.lastz, a.any1, a.center,
-                       a.iner, a.stop);
-}
-__global__ __launch_bounds__(64) void k_mstep_fuzzy_b_b(const void* arr, int stride, const int* gx)
-{
-    NEM_B_HEAD(FuzzyArgs)
-    mstep_fuzzy_b_body(a.n, a.npad, a.K, a.D, a.xw, a.xt, a.nw64, a.c, a.nbobs_k, a.in0, a.in1, a.inh_k, a.lastz, a.any1, a.center,
-                       a.iner, a.stop);
-}
 __global__ __launch_bounds__(64 * kPcWaves) void k_mstep_fuzzy_pc(FuzzyArgs a) { mstep_fuzzy_pc_body(a); }
 __global__ __launch_bounds__(64 * kPcWaves) void k_mstep_fuzzy_pc_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FuzzyArgs) mstep_fuzzy_pc_body(a); }
 __global__ __launch_bounds__(64) void k_mstep_fuzzy_med2(FuzzyArgs a) { mstep_fuzzy_med2_body(a); }
 __global__ __launch_bounds__(64) void k_mstep_fuzzy_med2_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FuzzyArgs) mstep_fuzzy_med2_body(a); }
 __global__ void k_transpose_c(FuzzyArgs a) { transpose_c_body(a.n, a.ctpad, a.K, a.c, a.ct, a.stop); }
 __global__ void k_transpose_c_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FuzzyArgs) transpose_c_body(a.n, a.ctpad, a.K, a.c, a.ct, a.stop); }
-__global__ __launch_bounds__(64 * kFuzzyWaves) void k_mstep_fuzzy_sums(FuzzyArgs a) { mstep_fuzzy_sums_body(a); }
-__global__ __launch_bounds__(64 * kFuzzyWaves) void k_mstep_fuzzy_sums_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FuzzyArgs) mstep_fuzzy_sums_body(a); }
-__global__ __launch_bounds__(64 * kFuzzyWaves) void k_mstep_fuzzy_median(FuzzyArgs a) { mstep_fuzzy_median_body(a); }
-__global__ __launch_bounds__(64 * kFuzzyWaves) void k_mstep_fuzzy_median_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FuzzyArgs) mstep_fuzzy_median_body(a); }
 __global__ void k_conv_fuzzy(ConvFuzzyArgs a) { conv_fuzzy_body(a.m, a.c, a.cold, a.thres, a.flags, a.stop, a.ca, gridDim.x); }
 __global__ void k_conv_fuzzy_b(const void* arr, int stride, const int* gx)
 {
@@ -2916,32 +2344,13 @@ void launch_mstep_fuzzy(int n, int npad, int K, int D, const uint32_t* xw, const
     const int DB = (D + 63) / 64;
     const int ctpad = (n + kWin - 1) / kWin * kWin;
     FuzzyArgs a{n, npad, K, D, xw, xt, nw64, c, nbobs_k, in0, in1, inh_k, lastz, any1, center, iner, stop, ct, ctpad, chk, fault, inject};
-    if (ct != nullptr && chk != nullptr) {
-        // one lane per chain at the chain's own speed: producer waves make the addends (see mstep_fuzzy_pc_body)
-        if (!record_op(OP_FUZZY_T, 0, dim3(ctpad / 256), 256, a))
-            hipLaunchKernelGGL(k_transpose_c, dim3(ctpad / 256), dim3(256), 0, s, a);
-        if (!record_op(OP_FUZZY_PC, 0, dim3(2 * DB + 2, K), 64 * kPcWaves, a))
-            hipLaunchKernelGGL(k_mstep_fuzzy_pc, dim3(2 * DB + 2, K), dim3(64 * kPcWaves), 0, s, a);
-        if (!record_op(OP_FUZZY_MED2, 0, dim3(DB, K), 64, a))
-            hipLaunchKernelGGL(k_mstep_fuzzy_med2, dim3(DB, K), dim3(64), 0, s, a);
-        return;
-    }
-    if (ct == nullptr) {                                 // one lane per chain (kept for comparison: NEM_MI355X_FUZZY_CHAINS=0)
-        if (!record_op(OP_FUZZY_A, 0, dim3(4 * DB + 2, K), 64, a))
-            hipLaunchKernelGGL(k_mstep_fuzzy_a, dim3(4 * DB + 2, K), dim3(64), 0, s, a);
-        if (!record_op(OP_FUZZY_B, 0, dim3(DB, K), 64, a))
-            hipLaunchKernelGGL(k_mstep_fuzzy_b, dim3(DB, K), dim3(64), 0, s, a);
-        return;
-    }
-    // one wave per chain, 256 families per step: class-major copy of the memberships, the sums (and with them the two
-    // order-free facts of ComputeMedian's tie rule), the medians
+    // one lane per chain at the chain's own speed: producer waves make the addends (see mstep_fuzzy_pc_body)
     if (!record_op(OP_FUZZY_T, 0, dim3(ctpad / 256), 256, a))
         hipLaunchKernelGGL(k_transpose_c, dim3(ctpad / 256), dim3(256), 0, s, a);
-    const dim3 gs((2 * D + 2 + kFuzzyWaves - 1) / kFuzzyWaves, K), gm((D + kFuzzyWaves - 1) / kFuzzyWaves, K);
-    if (!record_op(OP_FUZZY_SUMS, 0, gs, 64 * kFuzzyWaves, a))
-        hipLaunchKernelGGL(k_mstep_fuzzy_sums, gs, dim3(64 * kFuzzyWaves), 0, s, a);
-    if (!record_op(OP_FUZZY_MED, 0, gm, 64 * kFuzzyWaves, a))
-        hipLaunchKernelGGL(k_mstep_fuzzy_median, gm, dim3(64 * kFuzzyWaves), 0, s, a);
+    if (!record_op(OP_FUZZY_PC, 0, dim3(2 * DB + 2, K), 64 * kPcWaves, a))
+        hipLaunchKernelGGL(k_mstep_fuzzy_pc, dim3(2 * DB + 2, K), dim3(64 * kPcWaves), 0, s, a);
+    if (!record_op(OP_FUZZY_MED2, 0, dim3(DB, K), 64, a))
+        hipLaunchKernelGGL(k_mstep_fuzzy_med2, dim3(DB, K), dim3(64), 0, s, a);
 }
 
 void launch_conv_fuzzy(size_t m, const float* c, const float* cold, float thres, int* flags, const int* stop,
@@ -2991,11 +2400,7 @@ void launch_zipped(int kind, int variant, int B, const void* arr, int stride, co
         break;
     case OP_LABELS_POST: hipLaunchKernelGGL(k_labels_post_b, grid, blk, 0, s, arr, stride, gx); break;
     case OP_CTRL: hipLaunchKernelGGL(k_ctrl_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_FUZZY_A: hipLaunchKernelGGL(k_mstep_fuzzy_a_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_FUZZY_B: hipLaunchKernelGGL(k_mstep_fuzzy_b_b, grid, blk, 0, s, arr, stride, gx); break;
     case OP_FUZZY_T: hipLaunchKernelGGL(k_transpose_c_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_FUZZY_SUMS: hipLaunchKernelGGL(k_mstep_fuzzy_sums_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_FUZZY_MED: hipLaunchKernelGGL(k_mstep_fuzzy_median_b, grid, blk, 0, s, arr, stride, gx); break;
     case OP_FUZZY_PC: hipLaunchKernelGGL(k_mstep_fuzzy_pc_b, grid, blk, 0, s, arr, stride, gx); break;
     case OP_FUZZY_MED2: hipLaunchKernelGGL(k_mstep_fuzzy_med2_b, grid, blk, 0, s, arr, stride, gx); break;
     case OP_CONV_FUZZY: hipLaunchKernelGGL(k_conv_fuzzy_b, grid, blk, 0, s, arr, stride, gx); break;

@@ -97,37 +97,15 @@ struct SweepArgs {
     const uint8_t* rank_tot_in; int rank_index; uint8_t* rank_tot_out;
     // sites per block of the large-shard kernel instances (set by launch_sweep; 0: the kernel's block size)
     int spb;
-    // ---- k_sweep_fused: up to `fused_rounds` relaxation rounds in ONE launch (NCEM, one engine, every block resident).
-    // Round t of the launch (t = 0: this block's `flags`, `lab_guess`, `lab_out` as above) writes flag slot t
-    // (FLAG_ROUND_STRIDE ints further on each) and the label buffer lab_out (t even) / lab_out2 (t odd) -- exactly what
-    // `fused_rounds` separate launches would have written, so that the loop control and the host go on from there if the
-    // rounds were not enough.  Between two rounds the blocks meet through bar[2][kFusedMaxBlocks] (one word per block
-    // and round parity, see fused_meet; zero before the sweep) and re-read only the labels of their sites'
-    // lower-indexed neighbours in OTHER blocks; a site whose inputs did not change keeps its label without an evaluation.
-    int fused_rounds;
-    uint8_t* lab_out2;
-    unsigned* bar;
-    // exp((double)beta * (double)(float)m), m = 0 .. exp_tab_len - 1, made once per beta by k_exp_table with the device
-    // exp the sweep itself would call (nullptr: the block computes the first entries itself)
-    const double* exp_tab; int exp_tab_len;
-    // development probe (NEM_MI355X_SWEEP_PROF=1): the 100 MHz clock at the phase boundaries of a fused launch, first and
-    // last block (nemgpu_sweep_phases)
-    unsigned long long* prof;
 };
-// bits of a round's FLAG_CHANGED word besides bit 0
-constexpr int kFusedFailed = 1 << 28;   // k_sweep_fused: a block gave up waiting for the others (not every block resident?):
-                                        // the launch's rounds are void, the host redoes the sweep with one launch per round
-constexpr int kFusedMaxBlocks = 256;    // one block per CU at most: every block of a fused launch must be resident
-constexpr int kFusedMaxRounds = 16;     // (the pipelined loop uses 4: ctrl_logic's window)
-constexpr int kExpTabGlobal = 4096;     // entries of SweepArgs::exp_tab
 // argument blocks of the kernels whose launch wrappers take scalars (the batched launches need them as structs)
 struct LabelsPostArgs { int n_local, lo, K, nw64; const uint8_t* lab_new; const uint8_t* lab_old; uint64_t* mask; int* flags;
                         const int* stop; CtrlArgs ca; };
 struct CountsArgs { int K, D, nw64; const uint64_t* xt; const uint64_t* mask; int* stats; const int* stop; CtrlArgs prev_ctrl; };
 struct FuzzyArgs { int n, npad, K, D; const uint32_t* xw; const uint64_t* xt; int nw64; const float* c; float* nbobs_k;
                    float* in0; float* in1; float* inh_k; int* lastz; int* any1; float* center; float* iner; const int* stop;
-                   float* ct; int ctpad;      // ct: class-major copy of c, [K][ctpad] (nullptr: the one-lane-per-chain kernels)
-                   float* chk;                // producer/consumer kernels: the zeros' chains every 64 families, [K][nwin + 1][64 DB]
+                   float* ct; int ctpad;      // ct: class-major copy of c, [K][ctpad]
+                   float* chk;                // the zeros' chains every 64 families, [K][nwin + 1][64 DB]
                    int* fault;                // the iteration flags' FLAG_FAULT word (nullptr: faults go unreported)
                    int inject; };             // test hook (NEM_MI355X_FAULT_INJECT=fuzzy_pc): one producer skips a hand-over
 struct ConvFuzzyArgs { size_t m; const float* c; const float* cold; float thres; int* flags; const int* stop; CtrlArgs ca; };
@@ -147,8 +125,8 @@ struct LayoutArgs { const uint32_t* xf; const int* perm; int n, wf, W, npad, d, 
 // of it.  A host thread that sets a Recorder gets the launches of the code it then runs RECORDED instead of issued
 // (same argument blocks, same grids); the batch driver (nem_engine.hip) records one sequence per problem, checks that
 // the sequences agree launch for launch, and issues each position once for all problems with launch_zipped.
-enum OpKind { OP_FINISH = 1, OP_DENSITY, OP_DENSITY_FUSED, OP_SWEEP, OP_COUNTS, OP_LABELS_POST, OP_CTRL, OP_FUZZY_A, OP_FUZZY_B,
-              OP_CONV_FUZZY, OP_ONEHOT, OP_CRIT_TERMS, OP_CRIT_REDUCE, OP_CRIT_FINAL, OP_FILL, OP_COPY, OP_FUZZY_T, OP_FUZZY_SUMS, OP_FUZZY_MED,
+enum OpKind { OP_FINISH = 1, OP_DENSITY, OP_DENSITY_FUSED, OP_SWEEP, OP_COUNTS, OP_LABELS_POST, OP_CTRL,
+              OP_CONV_FUZZY, OP_ONEHOT, OP_CRIT_TERMS, OP_CRIT_REDUCE, OP_CRIT_FINAL, OP_FILL, OP_COPY, OP_FUZZY_T,
               OP_FUZZY_PC, OP_FUZZY_MED2, OP_LAYOUT_WORDS, OP_LAYOUT_BITS };
 constexpr int kOpArgBytes = 512;
 struct OpRecord {
@@ -197,11 +175,6 @@ constexpr int kFusedMaxD = 1024;   // beyond this the per-block parameter deriva
 void launch_density_fused(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
                           int* zero_flags, int n_zero_flags, hipStream_t s);
 void launch_sweep(const SweepArgs& a, bool ncem, hipStream_t s);
-// blocks a launch of launch_sweep would use for n_local sites (what decides whether the fused form may be used)
-int sweep_grid_blocks(int n_local, int K);
-bool sweep_fused_has_instance(int K);
-int sweep_phases_read(unsigned long long* out64);       // the probe's stamps of the last fused launch (64 words), or -1
-void launch_exp_table(float beta, double* tab, int len, hipStream_t s);   // SweepArgs::exp_tab (recordable)
 // one NCEM relaxation round and the M-step counts (of the partition whose class masks exist already) in ONE launch;
 // returns false when the shape has no such kernel (2 <= K <= 5, fewer than 65 536 families, not recordable)
 bool launch_sweep_counts(const SweepArgs& sw, int K, int D, int nw64, const uint64_t* xt, const uint64_t* mask, int* stats,
@@ -212,7 +185,7 @@ void launch_mstep_counts(int K, int D, int nw64, const uint64_t* xt, const uint6
                          const int* stop, const CtrlArgs* prev_ctrl, hipStream_t s);
 void launch_mstep_fuzzy(int n, int npad, int K, int D, const uint32_t* xw, const uint64_t* xt, int nw64, const float* c,
                         float* ct, float* nbobs_k, float* in0, float* in1, float* inh_k, int* lastz, int* any1, float* center,
-                        float* iner, const int* stop, hipStream_t s, float* chk = nullptr, int* fault = nullptr, int inject = 0);
+                        float* iner, const int* stop, hipStream_t s, float* chk, int* fault, int inject);
 void launch_conv_fuzzy(size_t m, const float* c, const float* cold, float thres, int* flags, const int* stop,
                        const CtrlArgs* ctrl, hipStream_t s);
 void launch_chain_debug(const double* x, long long n, float init, float* out, hipStream_t s);

@@ -284,7 +284,6 @@ __device__ __forceinline__ bool local_proba(const SweepArgs& a, int K, const dou
 // that a guess of the new partition carries the guess of who draws with it.
 constexpr int kLabMask = 0x7F, kLabDrew = 0x80;
 constexpr int kTabShort = 1 << 30;                       // in a round's FLAG_NTIES word: the draw table was too short
-constexpr int kFuzzyWaves = 4;                          // chains (waves) per block of the fuzzy M-step's chain kernels
 constexpr int kInnerCap = 64;                            // block-local iterations per round (any cap is exact)
 
 // sum over the 64 lanes, in every lane (data-parallel-primitive adds, no LDS)
@@ -299,66 +298,11 @@ __device__ __forceinline__ int wave_sum_i32(int v)
     return __builtin_amdgcn_readlane(v, 63);
 }
 
-// A label byte of another block as that block published it between two rounds of ONE launch (k_sweep_fused): the
-// aligned word it sits in, by an agent-scope load that no cache of this CU answers (MI355X_MICROARCH.md, inter-workgroup
-// visibility: the producers' stores are agent-scope word stores, drained before their block's arrival on the barrier)
-__device__ __forceinline__ int label_coherent(const uint8_t* buf, int j)
-{
-    const uint32_t w = __hip_atomic_load(reinterpret_cast<const uint32_t*>(buf + (j & ~3)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return (int)((w >> (8 * (j & 3))) & 0xFFu);
-}
-
-// The meeting of a fused launch's blocks between two relaxation rounds.  No counter: 79 arrivals on one word are 79
-// same-address atomics, served one after the other (~45 ns each: 3-4.5 us per meeting, measured with the in-kernel
-// clock) -- every block has a word of its own instead, words[parity of the round][block] = (round + 1) << 1 | "this
-// block changed a label", written by one agent-scope store once every wave of the block has waited for its label
-// stores (vmcnt(0)) and the block has met; the block's first wave then polls ALL blocks' words, one load instruction
-// per 64 blocks, until every word carries this round.  Two parities: a block can reach the next meeting while a slow
-// one is still reading this one's words, never the one after (it would need the slow block's arrival).  The words are
-// zero before the sweep.  Bounded (100 MHz clock): a block that waits longer than kFusedWaitTicks gives up and
-// reports it (-1), so that the grid always drains.  Returns the number of blocks that changed something, the same
-// value in every block.
-constexpr unsigned long long kFusedWaitTicks = 400000ull;      // 4 ms
-__device__ __forceinline__ int fused_meet(unsigned* words, int nblk, int rnd, bool blk_changed, int bx)
-{
-    __shared__ int s_meet;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        unsigned* w = words + (rnd & 1) * kFusedMaxBlocks;
-        const unsigned want = (unsigned)(rnd + 1);
-        if (threadIdx.x == 0) __hip_atomic_store(&w[bx], (want << 1) | (blk_changed ? 1u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long t0 = wall_clock64();
-        int total = 0;
-        for (;;) {
-            bool ok = true;
-            int chg = 0;
-            for (int b = threadIdx.x; b < nblk; b += 64) {
-                const unsigned v = __hip_atomic_load(&w[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ok = ok && (v >> 1) == want;
-                chg += (int)(v & 1u);
-            }
-            if (__all(ok)) { total = wave_sum_i32(chg); break; }
-            if (__any(wall_clock64() - t0 > kFusedWaitTicks)) { total = -1; break; }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        if (threadIdx.x == 0) s_meet = total;
-    }
-    __syncthreads();
-    return s_meet;
-}
-
 // LIBC: the reference's tie stream (TIE_LIBC) -- its bookkeeping (who drew, per wave and block, at every block-local
 // step) is compiled into the instances that need it only
-// FUSED: up to a.fused_rounds relaxation rounds in this one launch (see SweepArgs); NCEM, no tie stream, every block
-// of the grid resident
-template <int KT, bool NCEM, int BS, bool LIBC = false, bool FUSED = false>
+template <int KT, bool NCEM, int BS, bool LIBC = false>
 __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, const int nblk)
 {
-    static_assert(!FUSED || (NCEM && !LIBC), "the fused rounds exist for NCEM without the libc tie stream");
-#define NEM_SWEEP_STAMP(i_) do { if (FUSED && a.prof != nullptr && threadIdx.x == 0 && (bx == 0 || bx == nblk - 1) && (i_) < 32) \
-        a.prof[(bx == 0 ? 0 : 32) + (i_)] = wall_clock64(); } while (0)
-    NEM_SWEEP_STAMP(0);
     int fold_hint = 0;
     if (a.stop != nullptr) {
         static_assert(C_STOP == 0 && C_FOLD == 1, "one 8-byte load");
@@ -389,12 +333,10 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     // weights, small integers in PPanGGOLiN's graphs (numbers of organisms sharing an adjacency): the block fills a table
     // exp((double)beta * (double)(float)m), m = 0 .. kExpTab - 1, with the SAME device exp on the same argument the site
     // would pass (bit-identical by construction), one entry per thread, and a site whose context is such an integer
-    // reads it instead of running three double-precision exp (a third of the round's vector instructions)
-    // Graphs with PPanGGOLiN's own edge weights -- counts of organisms, up to D -- have contexts in the hundreds: there the
-    // table comes from SweepArgs::exp_tab (made once per beta by the same exp on the same arguments, k_exp_table) and is
-    // copied to LDS, as many entries as the graph's largest weight sum can index: up to 1024 in a round of its own, 4096
-    // in a fused launch.  (64 entries or fewer: the block computes them itself, no dependent load at its head.)
-    constexpr int kExpTab = FUSED ? kExpTabGlobal : 1024;
+    // reads it instead of running three double-precision exp (a third of the round's vector instructions).
+    // (A larger per-beta table for the contexts of PPanGGOLiN's own edge weights, which reach the hundreds, measured
+    // neutral: NOTES_negative_results.md section 10.)
+    constexpr int kExpTab = 64;
     __shared__ double s_exp[NCEM ? kExpTab : 1];
     __shared__ __attribute__((aligned(16))) uint8_t s_lab[NCEM ? BS : 1];   // the block's labels while it iterates
     __shared__ uint64_t s_drew[BS / 64];                 // TIE_LIBC: per wave, which of its sites drew
@@ -417,12 +359,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     __shared__ int s_anydrew;                            // TIE_LIBC: a site of the block drew at some local step of this launch
     if (threadIdx.x == 0) { s_nzero = 0; s_first = 0; s_chg = 0; s_mov = 0; s_anydrew = 0; }
     if (NCEM) s_lab[threadIdx.x] = (uint8_t)my_guess;
-    int exp_len = 64;                                    // usable entries of s_exp
-    if (NCEM && a.exp_tab != nullptr && (FUSED || a.exp_tab_len > 64)) {
-        exp_len = a.exp_tab_len < kExpTab ? a.exp_tab_len : kExpTab;
-        if (a.use_nei && !skip) for (int m = threadIdx.x; m < exp_len; m += BS) s_exp[m] = a.exp_tab[m];
-    } else if (NCEM && a.use_nei && !skip && threadIdx.x < 64) s_exp[threadIdx.x] = exp((double)a.beta * (double)(float)threadIdx.x);
-    int* rflags = a.flags;                               // this round's flag slot (a fused launch moves on slot by slot)
+    if (NCEM && a.use_nei && !skip && threadIdx.x < kExpTab) s_exp[threadIdx.x] = exp((double)a.beta * (double)(float)threadIdx.x);
     // TIE_LIBC: draws of the blocks below this one, as the guess has them -- summed once by the block's first wave (a
     // lane that ties used to add the counts up itself: up to 78 loads in a row per tying lane, 2-3 us of a round on
     // data that tie in every sweep, the initial sweeps of a random start)
@@ -442,7 +379,6 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     bool blk_drew = false;
     if (LIBC) blk_drew = __syncthreads_or((my_guess & kLabDrew) != 0) != 0;
     else __syncthreads();
-    NEM_SWEEP_STAMP(1);
 
     if (NCEM) {
     // ------------------------------------------------------------------------------------------
@@ -462,9 +398,8 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     // the first four neighbours live in registers: index, weight, and the label when it cannot change in here
     int nb = 0, ne = 0;
     int dyn[4]; float wn[4]; int fl[4];
-    int jlow[4];                                         // FUSED: label slot of a lower neighbour in another block (re-read between rounds), else -1
 #pragma unroll
-    for (int u = 0; u < 4; u++) { dyn[u] = -1; wn[u] = 0.0f; fl[u] = 255; jlow[u] = -1; }
+    for (int u = 0; u < 4; u++) { dyn[u] = -1; wn[u] = 0.0f; fl[u] = 255; }
     if (active && !skip && a.use_nei) {
         nb = a.nei_ptr[i]; ne = a.nei_ptr[i + 1];
         int jn[4];
@@ -478,10 +413,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
         for (int u = 0; u < 4; u++) {
             if (nb + u < ne) {
                 if (jn[u] < gi && jn[u] >= blk_lo) dyn[u] = jn[u] - blk_lo;
-                else {
-                    fl[u] = ((jn[u] < gi) ? a.lab_guess[jn[u]] : a.lab_old[jn[u]]) & kLabMask;
-                    if (FUSED && jn[u] < gi) jlow[u] = jn[u];
-                }
+                else fl[u] = ((jn[u] < gi) ? a.lab_guess[jn[u]] : a.lab_old[jn[u]]) & kLabMask;
             }
         }
     }
@@ -491,17 +423,6 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     int cur = my_guess;                                  // this site's byte in s_lab
     int seen[4] = {-1, -1, -1, -1};                      // labels the last evaluation used for the dyn neighbours
     uint64_t seen_drew = ~0ull; int seen_wave_draws = -1;
-    // FUSED: the rounds of this launch.  Round `rnd` reads the labels of other blocks from guess_buf -- the old
-    // partition in round 0 (a fused launch starts a sweep), the buffer every block published before the meeting
-    // afterwards -- and publishes this block's labels to out_buf.  `dirty`: this site must be evaluated at the round's
-    // first local step (round 0: every site; later: the sites one of whose inputs from outside the block changed).
-    const uint8_t* guess_buf = a.lab_guess;
-    uint8_t* out_buf = a.lab_out;
-    const int n_rounds = FUSED ? a.fused_rounds : 1;
-    bool dirty = true;
-    bool fused_failed = false;
-    int rnd = 0;
-    for (;;) {
     for (int it = 0; it < kInnerCap; it++) {
         int below_in_block = 0;
         uint64_t drew_lt = 0;
@@ -515,7 +436,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
         int nxt = cur;
         if (active && !skip) {
             int lab[4];
-            bool same = !(it == 0 && dirty) && !long_row;
+            bool same = it != 0 && !long_row;
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 lab[u] = dyn[u] >= 0 ? (s_lab[dyn[u]] & kLabMask) : fl[u];
@@ -541,14 +462,13 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
                     const float wt = a.nei_w[t];
                     int l;
                     if (j < gi && j >= blk_lo) l = s_lab[j - blk_lo] & kLabMask;
-                    else if (FUSED && rnd > 0 && j < gi) l = label_coherent(guess_buf, j) & kLabMask;
                     else l = ((j < gi) ? a.lab_guess[j] : a.lab_old[j]) & kLabMask;
 #pragma unroll
                     for (int k = 0; k < KA; k++)
                         if (k < K) ctx[k] = ctx[k] + ((l == k) ? wt : -0.0f);
                 }
                 float cf[KA];
-                zero_density = local_proba<KA>(a, K, pkf, ctx, cf, s_exp, exp_len);
+                zero_density = local_proba<KA>(a, K, pkf, ctx, cf, s_exp, kExpTab);
                 // ComputeMAP, nem_alg.c:603-640
                 int kmax = 0; float ukmax = cf[0];
 #pragma unroll
@@ -603,49 +523,8 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     if (active && !skip) {
         changed = (cur != my_guess) || tab_short;         // (a void round never passes for the fixed point)
         my_new = cur & kLabMask;
-        if (!FUSED) a.lab_out[gi] = (uint8_t)cur;
-        if (tab_short) atomicOr(&rflags[FLAG_NTIES], kTabShort);
-    }
-    if (!FUSED) break;
-    NEM_SWEEP_STAMP(2 + 4 * rnd);
-    // ---- fused launch: publish this round's labels, meet the other blocks, look at what they changed
-    // (the block's labels go out as whole words by agent-scope stores: what label_coherent reads on the other side)
-    if ((int)threadIdx.x < spb / 4 && bx * spb + 4 * (int)threadIdx.x < a.n_local)
-        __hip_atomic_store(reinterpret_cast<uint32_t*>(out_buf + blk_lo) + threadIdx.x,
-                           reinterpret_cast<const uint32_t*>(s_lab)[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (rnd == n_rounds - 1) break;                      // the launch's last round reports like a round of its own (below)
-    {
-        const int blk_changed = __syncthreads_or(changed ? 1 : 0);
-        NEM_SWEEP_STAMP(3 + 4 * rnd);
-        const int total = fused_meet(a.bar, nblk, rnd, blk_changed != 0, bx);
-        NEM_SWEEP_STAMP(4 + 4 * rnd);
-        if (total < 0) { fused_failed = true; break; }
-        if (total == 0) break;                           // nothing changed anywhere: this round's output is the fixed point
-        // the round changed something: its slot says so; the next one takes the next slot and the other buffer
-        if (bx == 0 && threadIdx.x == 0) __hip_atomic_store(&rflags[FLAG_CHANGED], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        rflags += FLAG_ROUND_STRIDE;
-        guess_buf = out_buf;
-        out_buf = (rnd & 1) ? a.lab_out : a.lab_out2;
-        rnd++;
-        my_guess = cur;
-        changed = false;
-        dirty = false;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            if (jlow[u] >= 0) {
-                const int nl = label_coherent(guess_buf, jlow[u]) & kLabMask;
-                if (nl != fl[u]) { fl[u] = nl; dirty = true; }
-            }
-        }
-        NEM_SWEEP_STAMP(1 + 4 * rnd);                    // (rnd has moved on: the slot behind the meeting's)
-    }
-    }
-    if (FUSED && fused_failed) {
-        // a block gave up waiting: every slot from this round on says "changed" and why -- the loop control stops the
-        // pipeline, the host redoes the sweep with one launch per round
-        changed = true;
-        if (threadIdx.x == 0)
-            for (int q = 0; q < n_rounds - rnd; q++) atomicOr(&rflags[q * FLAG_ROUND_STRIDE + FLAG_CHANGED], 1 | kFusedFailed);
+        a.lab_out[gi] = (uint8_t)cur;
+        if (tab_short) atomicOr(&a.flags[FLAG_NTIES], kTabShort);
     }
     if (libc && !skip) {
         // the block's draws of this round, next to the labels they belong to: a guess is (labels, counts)
@@ -659,7 +538,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
             if (blk_drew) for (int w = 0; w < (int)(blockDim.x >> 6); w++) cnt += (int)__popcll(s_drew[w]);
             if (cnt != blk_cnt_guess) changed = true;
             a.tie_cnt_out[bx] = cnt;
-            if (cnt > 0) atomicAdd(&rflags[FLAG_NTIES], cnt);
+            if (cnt > 0) atomicAdd(&a.flags[FLAG_NTIES], cnt);
         }
     }
     } else if (active && !skip) {
@@ -725,11 +604,11 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     // counters instead.
     const bool fold = fold_hint != 0 && a.fold_ticket != nullptr && nblk > 32;
     if (threadIdx.x == 0 && s_nzero > 0) {
-        if (!fold) atomicAdd(&rflags[FLAG_NZERO], s_nzero);
-        if (rflags[FLAG_FIRSTZERO] < s_first) atomicMax(&rflags[FLAG_FIRSTZERO], s_first);   // first site = n_total - max
+        if (!fold) atomicAdd(&a.flags[FLAG_NZERO], s_nzero);
+        if (a.flags[FLAG_FIRSTZERO] < s_first) atomicMax(&a.flags[FLAG_FIRSTZERO], s_first);   // first site = n_total - max
     }
     if (threadIdx.x == 0) {
-        if (s_chg && __hip_atomic_load(&rflags[FLAG_CHANGED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicOr(&rflags[FLAG_CHANGED], 1);
+        if (s_chg && __hip_atomic_load(&a.flags[FLAG_CHANGED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicOr(&a.flags[FLAG_CHANGED], 1);
         if (NCEM && a.post_on && s_mov && __hip_atomic_load(&a.post_flags[FLAG_MOVED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
             atomicOr(&a.post_flags[FLAG_MOVED], 1);
     }
@@ -745,20 +624,18 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     const bool post_ctrl = NCEM && a.post_on && a.post_ctrl.ctrl != nullptr;
     if (a.publish_byte != nullptr || post_ctrl || fold) {
         int* ticket = a.publish_byte != nullptr ? a.publish_ticket : (post_ctrl ? a.post_ctrl.ticket : a.fold_ticket);
-        if (last_block_ticket(ticket, nblk, fold ? s_nzero : 0, fold ? &rflags[FLAG_NZERO] : nullptr)) {
+        if (last_block_ticket(ticket, nblk, fold ? s_nzero : 0, fold ? &a.flags[FLAG_NZERO] : nullptr)) {
             if (a.publish_byte != nullptr) {
-                *a.publish_byte = (uint8_t)(__hip_atomic_load(&rflags[FLAG_CHANGED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0);
+                *a.publish_byte = (uint8_t)(__hip_atomic_load(&a.flags[FLAG_CHANGED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0);
                 if (NCEM && a.post_on && a.post_moved)          // (sharded: this rank's 'a label moved' byte rides next to it)
                     a.publish_byte[1] = (uint8_t)(__hip_atomic_load(&a.post_flags[FLAG_MOVED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0);
                 if (LIBC && a.rank_tot_out != nullptr)           // (... and its draws of this round)
                     *reinterpret_cast<int*>(a.rank_tot_out) =
-                        __hip_atomic_load(&rflags[FLAG_NTIES], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & (kTabShort - 1);
+                        __hip_atomic_load(&a.flags[FLAG_NTIES], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & (kTabShort - 1);
             }
             if (post_ctrl) ctrl_logic(a.post_ctrl);
         }
     }
-    NEM_SWEEP_STAMP(31);
-#undef NEM_SWEEP_STAMP
 }
 
 }  // namespace nemk

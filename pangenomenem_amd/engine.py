@@ -102,7 +102,6 @@ def load_library():
     lib.nemgpu_set_graph_policy.argtypes = [vp, C.c_int]
     lib.nemgpu_graph_counters.argtypes = [vp, ip]
     lib.nemgpu_profile_density_many.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    lib.nemgpu_sweep_counters.argtypes = [vp, ip]
     lib.nemgpu_random_start_counters.argtypes = [vp, ip]
     lib.nemgpu_rccl_ranks.argtypes = [vp]
     lib.nemgpu_rccl_selftest.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -432,11 +431,6 @@ class NemEngine:
         out = (C.c_int * 4)()
         self._chk(self.lib.nemgpu_graph_counters(self._h, out))
         return dict(plain=out[0], captured=out[1], replayed=out[2], host_finished_sweeps=out[3])
-
-    def sweep_counters(self):
-        out = (C.c_int * 4)()
-        self._chk(self.lib.nemgpu_sweep_counters(self._h, out))
-        return dict(fused_launches=out[0], fused_failed=out[1], fused_on=bool(out[2]))
 
     def random_start_counters(self):
         out = (C.c_int * 4)()

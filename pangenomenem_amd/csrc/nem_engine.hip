@@ -54,6 +54,7 @@ namespace {
 constexpr int kRoundCap = 64;     // relaxation rounds per flag window
 // what is zeroed ahead of every sweep (by the density launch, or a fill): FLAG_MOVED and the round window
 constexpr int kSweepFlagWords = 1 + kRoundCap * FLAG_ROUND_STRIDE;
+constexpr int kFlagSetWords = FLAG_ITER_STRIDE + kRoundCap * FLAG_ROUND_STRIDE;   // one iteration flag block + its round window
 constexpr int kRoundBatchMax = 4;
 constexpr int kRoundsMax = 7;       // most rounds a sweep of the pipelined loop is given ahead (ctrl_logic reads 8 slots)
 constexpr int kFzPositions = 16;    // fuzzy NEM: leading iterations of a run whose round counts are learned
@@ -148,7 +149,7 @@ struct nemgpu_engine {
     int cur = 0;
     uint64_t* mask = nullptr;
     int* stats = nullptr;
-    int* flags_dev = nullptr;     // [C_WORDS loop control] [FLAG_ITER_STRIDE] [kRoundCap * FLAG_ROUND_STRIDE]
+    int* flags_dev = nullptr;     // [C_WORDS loop control] then flag_sets x ([FLAG_ITER_STRIDE] [kRoundCap * FLAG_ROUND_STRIDE])
     int* flags_host = nullptr;    // pinned mirror
     const int* stop_ptr = nullptr;   // &ctrl[C_STOP] while the pipelined loop is being enqueued, else nullptr
 
@@ -171,6 +172,14 @@ struct nemgpu_engine {
     hipGraphExec_t graphs[2][3][8][8] = {};   // [with initial sweeps][current buffer][iterations][leading iterations with one round more]
     uint8_t graph_asked[2][3][8][8] = {};   // how often a batch shape was enqueued before it got a graph
     bool use_graphs = true;
+    // Shadow-verify schedule (NEM_MI355X_SHADOW_VERIFY, default on; see shadow_batch_enqueue): a sweep's verifying round
+    // runs in the next iteration's density launch, so an iteration's parameters, densities and flag block are written
+    // before the loop control has accepted the one before.  Three copies of each, one per label buffer; prop, center,
+    // disp, nbobs_k, pkfki, logpkfki and the flag accessors show copy `fset`, which outside a batch's enqueue is the
+    // copy of the last accepted iteration.  (flag_sets: 3 when the copies exist, else 1.)
+    bool shadow_verify = true;
+    int flag_sets = 1, fset = 0;
+    float* par_copy[3] = {}; double* pkfki_copy[3] = {}; float* logpkfki_copy[3] = {};
     // relaxation rounds enqueued per sweep before anybody looks (round 0, its verification, and one more that costs
     // an early-exit launch when it is not needed and a host round trip when it is missing); NEM_MI355X_ROUNDS=2..4
     int round_batch = 3;
@@ -255,12 +264,12 @@ struct nemgpu_engine {
 
     bool ncem() const { return cfg.algo == NEMGPU_ALGO_NCEM; }
     int* ctrl() const { return flags_dev; }
-    int* iter_flags() const { return flags_dev + C_WORDS; }
-    int* round_flags(int r) const { return flags_dev + C_WORDS + FLAG_ITER_STRIDE + (r % kRoundCap) * FLAG_ROUND_STRIDE; }
-    size_t flag_words() const { return C_WORDS + FLAG_ITER_STRIDE + (size_t)kRoundCap * FLAG_ROUND_STRIDE; }   // what the host mirrors
+    int* iter_flags() const { return flags_dev + C_WORDS + (size_t)fset * kFlagSetWords; }
+    int* round_flags(int r) const { return iter_flags() + FLAG_ITER_STRIDE + (r % kRoundCap) * FLAG_ROUND_STRIDE; }
+    size_t flag_words() const { return C_WORDS + (size_t)flag_sets * kFlagSetWords; }   // what the host mirrors
     const int* h_ctrl() const { return flags_host; }
-    const int* h_iter() const { return flags_host + C_WORDS; }
-    const int* h_round(int r) const { return flags_host + C_WORDS + FLAG_ITER_STRIDE + (r % kRoundCap) * FLAG_ROUND_STRIDE; }
+    const int* h_iter() const { return flags_host + C_WORDS + (size_t)fset * kFlagSetWords; }
+    const int* h_round(int r) const { return h_iter() + FLAG_ITER_STRIDE + (r % kRoundCap) * FLAG_ROUND_STRIDE; }
 };
 
 // A master pangenome on the device (nemgpu_master_create): what the chunks of PPanGGOLiN's voting loop are formed from
@@ -567,6 +576,11 @@ int alloc_model_buffers(nemgpu_engine* e)
     A(dev_alloc(&e->uni, (size_t)k)); A(dev_alloc(&e->nonuni, (size_t)k)); A(dev_alloc(&e->sweep_next, (size_t)32 + kTicketWords));   // [0] sweep number, [32..] last-block ticket counters
     A(dev_alloc(&e->pk, (size_t)k)); A(dev_alloc(&e->logpk, (size_t)k));
     A(dev_alloc(&e->pkfki, (size_t)k * e->npad)); A(dev_alloc(&e->logpkfki, (size_t)k * e->npad));
+    e->par_copy[0] = e->prop; e->pkfki_copy[0] = e->pkfki; e->logpkfki_copy[0] = e->logpkfki;
+    for (int c = 1; c < e->flag_sets; c++) {
+        A(dev_alloc(&e->par_copy[c], e->par_words));
+        A(dev_alloc(&e->pkfki_copy[c], (size_t)k * e->npad)); A(dev_alloc(&e->logpkfki_copy[c], (size_t)k * e->npad));
+    }
     A(dev_alloc(&e->mask, (size_t)k * e->nw64));
     A(dev_alloc(&e->stats, (size_t)k + kd));
     A(dev_alloc(&e->flags_dev, e->flag_words()));
@@ -637,6 +651,7 @@ FinishArgs finish_args(nemgpu_engine* e, int mode, const int* stats)
     t.stop = e->stop_ptr;
     t.reset_prop = nullptr; t.reset_center = nullptr; t.reset_disp = nullptr;
     t.reset_ctrl = nullptr; t.reset_ctrl_words = 0; t.reset_sweep_next = nullptr;
+    t.prev_center = nullptr; t.prev_disp = nullptr;
     t.use_ff = e->use_ff() ? 1 : 0;
     t.perm = e->perm;
     t.ffq = e->ffq;
@@ -678,6 +693,9 @@ struct SweepCtx {
     int slot_base = 0;   // first flag slot of the round window (the blind initial sweep takes a slot of its own)
     // NCEM pipelined loop: fold the iteration's bookkeeping into the last round of the first batch
     bool post = false; bool post_moved = false; CtrlArgs post_ctrl{};
+    // shadow-verify schedule: the last round of the first batch is not launched but left here, bookkeeping and loop
+    // control included, for the next density launch; the round before it makes the class masks and "moved"
+    SweepArgs* hold = nullptr;
 };
 
 int clear_sweep_flags(nemgpu_engine* e)
@@ -776,7 +794,19 @@ int sweep_launch_rounds(nemgpu_engine* e, SweepCtx& c, int count)
         c.a.prev_changed = (r == r0) ? nullptr : (e->round_flags(c.slot_base + r - 1) + FLAG_CHANGED);
         c.a.stop = e->stop_ptr;
         c.a.post_on = 0;
-        if (c.post && ncem && r0 == 0 && b == count - 1) {
+        if (c.hold != nullptr && c.post && ncem && r0 == 0 && count >= 2 && b >= count - 2) {
+            c.a.post_on = 1; c.a.post_skip_guess = (r % 2 == 1) ? 1 : 0;
+            c.a.post_nw64 = e->nw64; c.a.post_mask = e->mask; c.a.post_flags = e->iter_flags();
+            if (b == count - 2) {
+                // the masks and "moved" from this round's output: final whenever the next round changes nothing
+                c.a.post_from_guess = 0; c.a.post_moved = c.post_moved ? 1 : 0; c.a.post_no_masks = 0; c.a.post_ctrl = CtrlArgs{};
+            } else {
+                // the verifying round: the loop control in its last-block ticket, nothing else
+                c.a.post_from_guess = 1; c.a.post_moved = 0; c.a.post_no_masks = 1; c.a.post_ctrl = c.post_ctrl;
+                *c.hold = c.a;
+                continue;
+            }
+        } else if (c.post && ncem && r0 == 0 && b == count - 1) {
             // (the sweep's final labels are in buffer Q, the out buffer of even rounds)
             c.a.post_on = 1; c.a.post_from_guess = (r % 2 == 1) ? 1 : 0; c.a.post_moved = c.post_moved ? 1 : 0;
             c.a.post_skip_guess = c.a.post_from_guess;
@@ -809,11 +839,11 @@ int sweep_setup(nemgpu_engine* e, float beta, SweepCtx& c, bool id_by_value)
 }
 
 int sweep_enqueue(nemgpu_engine* e, float beta, SweepCtx& c, bool id_by_value = false, const CtrlArgs* post_ctrl = nullptr,
-                  bool post_moved = false, int slot_base = 0, int rounds = 0)
+                  bool post_moved = false, int slot_base = 0, int rounds = 0, SweepArgs* hold = nullptr)
 {
     c = SweepCtx();
     c.slot_base = slot_base;
-    if (post_ctrl != nullptr && e->ncem()) { c.post = true; c.post_moved = post_moved; c.post_ctrl = *post_ctrl; }
+    if (post_ctrl != nullptr && e->ncem()) { c.post = true; c.post_moved = post_moved; c.post_ctrl = *post_ctrl; c.hold = hold; }
     { int r = sweep_setup(e, beta, c, id_by_value); if (r) return r; }
     if (!e->flags_clean) { int r = clear_sweep_flags(e); if (r) return r; }
     e->flags_clean = false;
@@ -916,7 +946,7 @@ int do_mstep(nemgpu_engine* e, const CtrlArgs* prev_ctrl = nullptr)
 
 int read_iter_flags(nemgpu_engine* e)
 {
-    HIPCHK(hipMemcpyAsync(e->flags_host, e->flags_dev, (C_WORDS + FLAG_ITER_STRIDE) * sizeof(int),
+    HIPCHK(hipMemcpyAsync(e->flags_host, e->flags_dev, (C_WORDS + (size_t)e->fset * kFlagSetWords + FLAG_ITER_STRIDE) * sizeof(int),
                           hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return check_fault(e);
@@ -1085,7 +1115,9 @@ static int init_beta_rounds(const nemgpu_engine* e)
     return n;
 }
 
-int enqueue_init(nemgpu_engine* e, bool defer_ctrl)
+// hold (shadow-verify schedule, NCEM): the beta sweep's last round and the loop control are left in *hold for the first
+// iteration's density launch (defer_ctrl is then ignored)
+int enqueue_init(nemgpu_engine* e, bool defer_ctrl, SweepArgs* hold = nullptr)
 {
     int r;
     // one launch: initial parameters back in place, loop control cleared, density tables built
@@ -1118,10 +1150,10 @@ int enqueue_init(nemgpu_engine* e, bool defer_ctrl)
     ca.is_init = 1;
     ca.blind = e->round_flags(kRoundCap - ra);
     ca.blind_rounds = libc ? ra : 0;
-    const bool defer = defer_ctrl && e->ncem() && !e->cfg.param_fix;
+    const bool defer = defer_ctrl && e->ncem() && !e->cfg.param_fix && hold == nullptr;
     CtrlArgs none{};
     if (libc) e->draw_extra_once = e->round_flags(kRoundCap - 1) + FLAG_NTIES;
-    if ((r = sweep_enqueue(e, e->cfg.beta, c1, true, e->ncem() ? (defer ? &none : &ca) : nullptr, false, 0, ca.n_rounds))) return r;   // 1 -> 2 (and 0 as the pong buffer)
+    if ((r = sweep_enqueue(e, e->cfg.beta, c1, true, e->ncem() ? (defer ? &none : &ca) : nullptr, false, 0, ca.n_rounds, hold))) return r;   // 1 -> 2 (and 0 as the pong buffer)
     e->draw_extra_once = nullptr;
     if (defer) { e->ctrl_deferred = ca; e->ctrl_pending = true; }
     if (e->ncem()) e->masks_valid = true;
@@ -1286,6 +1318,7 @@ struct LoopCursor {
     int g = 0, base = 0; uint32_t sweep0 = 0; bool batch_first = false;
     int deep = 0;                 // leading iterations of the batch that get round_batch relaxation rounds
     int pos0 = 0;                 // run-relative number of the batch's first iteration (fuzzy: selects the learned round counts)
+    bool shadow = false;          // the batch takes the shadow-verify schedule (shadow_batch_enqueue)
     bool active() const { return remaining > 0 || first; }
 };
 
@@ -1313,6 +1346,8 @@ bool loop_wants_batch(const nemgpu_engine* e, const LoopCursor& lc)
     return lc.active() && !e->converged && e->status == NEMGPU_OK;
 }
 
+bool shadow_engine(const nemgpu_engine* e);
+
 // what the next batch is; the state every batch may rely on (issued / recorded ahead of it)
 int batch_plan(nemgpu_engine* e, LoopCursor& lc)
 {
@@ -1323,6 +1358,8 @@ int batch_plan(nemgpu_engine* e, LoopCursor& lc)
     lc.sweep0 = lc.first ? 2u : e->sweep_counter;
     lc.deep = current_recorder() != nullptr ? lc.g : std::max(0, std::min(lc.g, e->deep_iters - (lc.first ? 0 : e->iters)));
     lc.pos0 = lc.first ? 0 : e->iters;
+    // (a batch with a sweep behind which an iteration follows; g and `first` are part of a captured batch's key)
+    lc.shadow = shadow_engine(e) && (lc.g >= 2 || (lc.first && lc.g >= 1));
     // (fuzzy: the round counts of a batch's iterations depend on where in the run it starts; the graph table's last
     //  index tells the classes apart -- a stale class would only enqueue another number of rounds, never change a result)
     if (!e->ncem() && current_recorder() == nullptr) lc.deep = lc.pos0 >= kFzPositions ? 0 : std::min(7, 1 + lc.pos0 / kPipeDepth);
@@ -1345,6 +1382,109 @@ int batch_plan(nemgpu_engine* e, LoopCursor& lc)
     return NEMGPU_OK;
 }
 
+// ---- shadow-verify schedule (NCEM, fused parameter update, one engine alone) -------------------------------------------
+// A sweep's last, verifying round changes nothing in steady state; what it decides is whether the iteration stands.  The
+// next iteration's counts and density do not need that decision: they need the labels of the round before, final
+// whenever the verifying round confirms them.  So that round (and the loop control in its last-block ticket) runs in the
+// next iteration's density launch (k_density_verify), and the round before it makes the class masks and "moved":
+//   today:  counts(t+1)[+ctrl(t)] -> density(t+1) -> R0(t+1) -> R1(t+1) -> counts(t+2)[+ctrl(t+1)] -> ...
+//   here:   R0(t) -> counts(t+1) -> [density(t+1) | R1(t) + ctrl(t)] -> R0(t+1) -> ...
+// If the verifying round changes something, the loop control stops the batch and batch_finish finishes the sweep from
+// the host as before.  density(t+1) runs before t is accepted, so it writes a copy of its own of the parameters, the
+// densities and the flag block: iteration j of a batch of g writes copy shadow_copy(j, g) -- the batch's last iteration
+// copy 0, the copy everything outside a batch reads, the ones before it 1 and 2 in turn (j = -1: the restart head).  A
+// batch that stops elsewhere has its accepted copy moved to 0 afterwards (accept_copy).  The copies depend on (first
+// batch, g, j) only, so a captured batch replays with the same ones.
+int shadow_copy(int j, int g) { return j == g - 1 ? 0 : 1 + (g - 2 - j) % 2; }
+
+void use_copy(nemgpu_engine* e, int c)
+{
+    e->fset = c;
+    e->prop = e->par_copy[c]; e->center = e->prop + e->par_o_center; e->disp = e->prop + e->par_o_disp; e->nbobs_k = e->prop + e->par_o_nb;
+    e->pkfki = e->pkfki_copy[c]; e->logpkfki = e->logpkfki_copy[c];
+}
+
+// copy c (parameters, densities, flag block -- the host mirror's too) becomes copy 0
+int accept_copy(nemgpu_engine* e, int c)
+{
+    const size_t kn = (size_t)e->k * e->npad;
+    HIPCHK(hipMemcpyAsync(e->par_copy[0], e->par_copy[c], e->par_words * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->pkfki_copy[0], e->pkfki_copy[c], kn * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->logpkfki_copy[0], e->logpkfki_copy[c], kn * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->flags_dev + C_WORDS, e->flags_dev + C_WORDS + (size_t)c * kFlagSetWords, kFlagSetWords * sizeof(int),
+                          hipMemcpyDeviceToDevice, e->stream));
+    memcpy(e->flags_host + C_WORDS, e->flags_host + C_WORDS + (size_t)c * kFlagSetWords, kFlagSetWords * sizeof(int));
+    return NEMGPU_OK;
+}
+
+// does this engine's pipelined loop take the shadow-verify schedule?  (Everything else keeps the one above: lock-step
+// twins, TIE_LIBC, fuzzy NEM, fixed or k_finish-updated parameters, sharded runs, sweeps without neighbours.)
+bool shadow_engine(const nemgpu_engine* e)
+{
+    return e->flag_sets == 3 && e->parent == nullptr && current_recorder() == nullptr && e->ncem() && !e->cfg.param_fix &&
+           e->fused_update() && e->has_graph && e->cfg.beta != 0.0f && e->lo == 0 && e->hi == e->n_total &&
+           density_verify_supported(e->n, e->k, e->cfg.tie_rule);
+}
+
+// iteration `cur` of a shadow-verify batch: counts, then the density (with the previous sweep's verifying round when
+// *pending), then the sweep's rounds -- its last one left in *held (*pending set) when `hold`
+int enqueue_iteration_shadow(nemgpu_engine* e, int cur, uint32_t sweep_id, bool hold, bool deep, int pos, int prev, int copy,
+                             SweepArgs* held, bool* pending)
+{
+    int r;
+    const int saved = e->cur;
+    e->cur = cur;
+    if (!e->masks_valid) { if ((r = do_labels_post(e, e->cur, -1))) { e->cur = saved; return r; } }
+    launch_mstep_counts(e->k, e->d, e->nw64, e->xt, e->mask, e->stats, e->stop_ptr, nullptr, e->stream);
+    use_copy(e, copy);
+    FinishArgs t = finish_args(e, 1, e->stats);
+    t.prev_center = e->par_copy[prev] + e->par_o_center; t.prev_disp = e->par_copy[prev] + e->par_o_disp;
+    if (*pending) launch_density_verify(t, e->xws, e->n, e->npad, e->pkfki, e->logpkfki, e->iter_flags() + FLAG_MOVED,
+                                        kSweepFlagWords, *held, e->stream);
+    else launch_density_fused(t, e->xws, e->n, e->npad, e->pkfki, e->logpkfki, e->iter_flags() + FLAG_MOVED, kSweepFlagWords, e->stream);
+    *pending = false;
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) { e->cur = saved; set_error(std::string("launch failed: ") + hipGetErrorString(le)); return NEMGPU_E_DEVICE; }
+    e->flags_clean = true;
+    e->tables_fresh = false;
+    e->density_fresh = true;
+    SweepCtx c;
+    e->sweep_counter = sweep_id;
+    CtrlArgs ca{};
+    const int it_rounds = iteration_rounds(e, pos, deep);
+    ca.ctrl = e->ctrl(); ca.iter_flags = e->iter_flags(); ca.round0 = e->round_flags(0); ca.n_rounds = it_rounds;
+    ca.param_fix = 0; ca.use_nei = 1; ca.cvtest = e->cfg.cvtest;
+    ca.ncem = 1; ca.cvthres = e->cfg.cvthres; ca.sweep_next = e->sweep_next; ca.ticket = e->sweep_next + 32;
+    if (hold) *held = SweepArgs{};
+    if ((r = sweep_enqueue(e, e->cfg.beta, c, false, &ca, true, 0, it_rounds, hold ? held : nullptr))) { e->cur = saved; return r; }
+    *pending = hold && held->post_ctrl.ctrl != nullptr;    // (a sweep of one round has nothing to hold back)
+    e->masks_valid = true;
+    e->cur = saved;
+    return NEMGPU_OK;
+}
+
+int shadow_batch_enqueue(nemgpu_engine* e, const LoopCursor& lc)
+{
+    int r = NEMGPU_OK;
+    SweepArgs held{};
+    bool pending = false;
+    int prev = 0;                                          // the copy the next density keeps an empty class's parameters from
+    if (lc.batch_first) {
+        prev = shadow_copy(-1, lc.g);
+        use_copy(e, prev);
+        r = enqueue_init(e, false, &held);
+        pending = r == NEMGPU_OK && held.post_ctrl.ctrl != nullptr;
+    }
+    for (int j = 0; j < lc.g && r == NEMGPU_OK; j++) {
+        const int copy = shadow_copy(j, lc.g);
+        r = enqueue_iteration_shadow(e, (lc.base + j) % 3, lc.sweep0 + j, j + 1 < lc.g, j < lc.deep, lc.pos0 + j, prev, copy,
+                                     &held, &pending);
+        prev = copy;
+    }
+    use_copy(e, 0);
+    return r;
+}
+
 // the batch's launches (issued, captured or recorded by the caller's choice), ending with the copy of the control block
 // after_iter (optional): called behind the launches of every iteration of the batch (the logged run's snapshots)
 int batch_enqueue(nemgpu_engine* e, LoopCursor& lc, bool with_copy, const std::function<int(int)>* after_iter = nullptr)
@@ -1357,8 +1497,10 @@ int batch_enqueue(nemgpu_engine* e, LoopCursor& lc, bool with_copy, const std::f
         else herr = hipMemsetAsync(e->ctrl(), 0, C_WORDS * sizeof(int), e->stream);
     }
     e->stop_ptr = e->ctrl() + C_STOP;
-    if (lc.batch_first && herr == hipSuccess) r = enqueue_init(e, lc.g > 0);
-    for (int j = 0; j < lc.g && r == NEMGPU_OK && herr == hipSuccess; j++) {
+    lc.shadow = lc.shadow && after_iter == nullptr && current_recorder() == nullptr;
+    if (lc.shadow && herr == hipSuccess) r = shadow_batch_enqueue(e, lc);
+    else if (lc.batch_first && herr == hipSuccess) r = enqueue_init(e, lc.g > 0);
+    for (int j = 0; j < lc.g && !lc.shadow && r == NEMGPU_OK && herr == hipSuccess; j++) {
         r = enqueue_iteration(e, (lc.base + j) % 3, lc.sweep0 + j, j + 1 < lc.g && after_iter == nullptr, e->ncem() ? j < lc.deep : false, lc.pos0 + j);
         if (r == NEMGPU_OK && after_iter != nullptr) r = (*after_iter)(j);
     }
@@ -1381,6 +1523,10 @@ int batch_finish(nemgpu_engine* e, LoopCursor& lc)
     const bool first = lc.batch_first;
     const int base = lc.base;
     const uint32_t sweep0 = lc.sweep0;
+    if (lc.shadow) {                                           // the copy of the last iteration the loop control saw
+        const int acc = shadow_copy(done - 1, lc.g);
+        if (acc != 0 && (r = accept_copy(e, acc))) return r;
+    }
     if (first && e->libc()) {
         if (c[C_NEED_ROUNDS] >= 2) {
             // TIE_LIBC: one of the two initial sweeps was not through in the rounds enqueued (or a draw left the table):
@@ -1729,7 +1875,7 @@ int lockstep(std::vector<nemgpu_engine*>& E, const std::vector<int>& members, st
         if (r) return r;
     }
     const auto t1 = std::chrono::steady_clock::now();
-    const size_t fw = lead->flag_words();
+    const size_t fw = C_WORDS + kFlagSetWords;             // (members of a lock-step batch use flag set 0 only)
     nemgpu_engine::ZipContext* z = zip_context(lead);
     if (fetch_flags) {
         // every member's flag block goes to one staging area on the device (a last zipped launch) and from there
@@ -2339,6 +2485,8 @@ int nemgpu_create(nemgpu_engine** out, int n_total, int d, int k, int site_lo, i
     e->cfg.cvtest = NEMGPU_CV_CLAS; e->cfg.cvthres = 1e-8f; e->cfg.it_max = 100; e->cfg.param_fix = 0;
     e->cfg.tie_rule = NEMGPU_TIE_HASH; e->cfg.tie_seed = 0;
     if (const char* g = getenv("NEM_MI355X_GRAPHS")) e->use_graphs = (g[0] != '0');   // 0: plain launches only
+    if (const char* g = getenv("NEM_MI355X_SHADOW_VERIFY")) e->shadow_verify = (g[0] != '0');   // 0: every verifying round on its own
+    e->flag_sets = e->shadow_verify ? 3 : 1;
     if (const char* g = getenv("NEM_MI355X_ROUNDS")) e->round_batch = std::max(2, std::min(kRoundBatchMax, atoi(g)));
     if (const char* g = getenv("NEM_MI355X_ROUNDS_ITER")) e->rounds_iter = std::max(2, std::min(e->round_batch, atoi(g)));
     e->rounds_iter = std::min(e->rounds_iter, e->round_batch);

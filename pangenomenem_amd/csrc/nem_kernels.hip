@@ -562,7 +562,9 @@ __device__ __forceinline__ void density_body(const DensityArgs& a)
 // ComputeMedian's rule, inertia in closed form, dispersion, proportion, the two logs -- instead of
 // waiting for a single-block "finish" launch to publish tables.  K*D is tiny, so the redundancy
 // across blocks is cheaper than a kernel boundary.  Block (0, k) also publishes class k's new
-// centre / dispersion / proportion / size; block (0, 0) the empty-class flag.
+// centre / dispersion / proportion / size; block (0, 0) the empty-class flag.  An empty class keeps the centre and
+// dispersions of center_in / disp_in: the same arrays, or (the shadow-verify schedule, see k_density_verify) the
+// previous iteration's copy, which block (0, k) then copies over.
 // ------------------------------------------------------------------------------------------
 constexpr int FD_MAXD = kFusedMaxD; // organisms the fused kernel supports (iner/eps staged in LDS as floats)
 constexpr int FD_CH = 256;        // organisms per general-path table chunk
@@ -571,6 +573,7 @@ struct FusedDensityArgs {
     const uint4* xw; int n, npad, dpad, D, K, n_total, disper, propor;
     const int* stats; int stats_ranks, stats_rank_stride;
     float* center; float* disp; float* prop; float* nbobs_k;
+    const float* center_in; const float* disp_in;        // where an empty class keeps its centre and dispersions from
     int* iter_flags;
     double* pkfki; float* logpkfki;
     int* zero_flags; int n_zero_flags;
@@ -627,10 +630,10 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
                 if (s0f > half) { mu = 0.0f; in = (float)s1; }
                 else if (s0f == half) { mu = 0.5f; in = 0.5f * nkf; }
                 else { mu = 1.0f; in = s0f; }
-                if (writer) a.center[k * D + d] = mu;
             } else {
-                mu = a.center[k * D + d];                // empty class keeps its centre (nem_mod.c:1405)
+                mu = a.center_in[k * D + d];             // empty class keeps its centre (nem_mod.c:1405)
             }
+            if (writer) a.center[k * D + d] = mu;
             const int ad0 = abs((int)(0.0f - mu)), ad1 = abs((int)(1.0f - mu));
             a0 = (ad0 != 0); a1 = (ad1 != 0);
             if (ad0 > 1 || ad1 > 1) general = 1;
@@ -687,15 +690,19 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
         } else {
             // empty class keeps whatever dispersions it had (possibly different per organism)
             __syncthreads();
-            for (int d = tid; d < D; d += 256) sVal[d] = a.disp[k * D + d];
+            for (int d = tid; d < D; d += 256) {
+                sVal[d] = a.disp_in[k * D + d];
+                if (writer) a.disp[k * D + d] = sVal[d];
+            }
             eps_per_d = true;
         }
     } else {                                             // NEMGPU_DISP_KD
         __syncthreads();
         for (int d = tid; d < D; d += 256) {
             float e;
-            if (nonempty) { e = sVal[d] / nkf; if (writer) a.disp[k * D + d] = e; }
-            else e = a.disp[k * D + d];
+            if (nonempty) e = sVal[d] / nkf;
+            else e = a.disp_in[k * D + d];
+            if (writer) a.disp[k * D + d] = e;
             sVal[d] = e;
         }
         eps_per_d = true;
@@ -743,7 +750,7 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
                     const float eps = eps_per_d ? sVal[d] : eps_u;
                     int ad0, ad1;
                     if (nonempty) { ad0 = (sAm[d >> 5].x >> (d & 31)) & 1; ad1 = (sAm[d >> 5].y >> (d & 31)) & 1; }
-                    else { const float mu = a.center[k * D + d]; ad0 = abs((int)(0.0f - mu)); ad1 = abs((int)(1.0f - mu)); }
+                    else { const float mu = a.center_in[k * D + d]; ad0 = abs((int)(0.0f - mu)); ad1 = abs((int)(1.0f - mu)); }
                     if ((double)eps > kEpsilonD) {
                         const double ll1 = log((double)((1.0f - eps) / eps));
                         ll0 = log((double)(1.0f - eps));
@@ -2122,6 +2129,20 @@ __global__ __launch_bounds__(256) void k_sweep_counts(SweepArgs s, CountsArgs c,
     mstep_counts_body<R>(c.K, c.D, c.nw64, c.xt, c.mask, c.stats, c.stop, CtrlArgs{}, (int)blockIdx.x - nsweep, (int)gridDim.x - nsweep);
 }
 
+// The density of iteration t + 1 (blocks [0, nd): the parameter update and E1, first so that a tile keeps its place on
+// the XCDs and its waves are the older ones) beside the last relaxation round of iteration t's sweep (the other blocks,
+// block index blockIdx.x - nd), whose last-block ticket -- among the round's blocks only -- runs iteration t's loop
+// control.  Neither half reads what the other writes: the density writes the parameter, density and flag copies of
+// iteration t + 1 (see the shadow-verify schedule, nem_engine.hip), the round reads those of t.  If the loop control
+// stops after t, what the density blocks wrote is never used; density blocks that start after the stop word is set
+// return at once.
+template <int KT>
+__global__ __launch_bounds__(256) void k_density_verify(FusedDensityArgs d, SweepArgs s, int nd)
+{
+    if ((int)blockIdx.x < nd) { (void)density_fused_body(d); return; }
+    sweep_body<KT, true, 256, false>(s, (int)blockIdx.x - nd, (int)gridDim.x - nd);
+}
+
 __global__ void k_ctrl(CtrlArgs a) { ctrl_logic(a); }
 __global__ void k_ctrl_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(CtrlArgs) ctrl_logic(a); }
 __global__ void k_labels_post(LabelsPostArgs a)
@@ -2278,19 +2299,45 @@ void launch_density(const FinishArgs& t, const uint32_t* xw, int n, int npad, do
     hipLaunchKernelGGL(k_density, grid, dim3(256), 0, s, a);
 }
 
-void launch_density_fused(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
-                          int* zero_flags, int n_zero_flags, hipStream_t s)
+static FusedDensityArgs fused_density_args(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki,
+                                           float* logpkfki, int* zero_flags, int n_zero_flags)
 {
     FusedDensityArgs a;
     a.xw = (const uint4*)xw; a.n = n; a.npad = npad; a.dpad = t.dpad; a.D = t.D; a.K = t.K; a.n_total = t.n_total;
     a.disper = t.disper; a.propor = t.propor; a.stats = t.stats;
     a.stats_ranks = t.stats_ranks; a.stats_rank_stride = t.stats_rank_stride;
     a.center = t.center; a.disp = t.disp; a.prop = t.prop; a.nbobs_k = t.nbobs_k; a.iter_flags = t.flags;
+    a.center_in = t.prev_center != nullptr ? t.prev_center : t.center;
+    a.disp_in = t.prev_disp != nullptr ? t.prev_disp : t.disp;
     a.pkfki = pkfki; a.logpkfki = logpkfki; a.zero_flags = zero_flags; a.n_zero_flags = n_zero_flags; a.stop = t.stop;
     a.use_ff = t.use_ff; a.perm = t.perm;
+    return a;
+}
+
+void launch_density_fused(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
+                          int* zero_flags, int n_zero_flags, hipStream_t s)
+{
+    const FusedDensityArgs a = fused_density_args(t, xw, n, npad, pkfki, logpkfki, zero_flags, n_zero_flags);
     const dim3 grid(((npad / 256 + 7) / 8) * 8 * t.K);
     if (record_op(OP_DENSITY_FUSED, 0, grid, 256, a)) return;
     hipLaunchKernelGGL(k_density_fused, grid, dim3(256), 0, s, a);
+}
+
+bool density_verify_supported(int n_local, int K, int tie_rule)
+{
+    return n_local < 65536 && K >= 1 && K <= 10 && tie_rule != NEMGPU_TIE_LIBC;
+}
+
+void launch_density_verify(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
+                           int* zero_flags, int n_zero_flags, const SweepArgs& sw, hipStream_t s)
+{
+    const FusedDensityArgs a = fused_density_args(t, xw, n, npad, pkfki, logpkfki, zero_flags, n_zero_flags);
+    const int nd = ((npad / 256 + 7) / 8) * 8 * t.K;
+    const int ns = (sw.n_local + 255) / 256;
+    const dim3 grid(nd + ns);
+#define NEM_DV(KT_) case KT_: hipLaunchKernelGGL((k_density_verify<KT_>), grid, dim3(256), 0, s, a, sw, nd); break;
+    switch (sw.K) { NEM_DV(1) NEM_DV(2) NEM_DV(3) NEM_DV(4) NEM_DV(5) NEM_DV(6) NEM_DV(7) NEM_DV(8) NEM_DV(9) NEM_DV(10) default: break; }
+#undef NEM_DV
 }
 
 // an NCEM relaxation round and M-step counts in one launch (k_sweep_counts); false: not for this shape (the caller

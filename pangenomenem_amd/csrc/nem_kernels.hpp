@@ -19,7 +19,8 @@ constexpr double kEpsilonD = 1e-20;   // EPSILON, reference nem_typ.h:63
 enum { FLAG_CHANGED = 0, FLAG_NZERO = 1, FLAG_FIRSTZERO = 2, FLAG_NTIES = 3, FLAG_ROUND_STRIDE = 4 };
 // per-iteration flag block.  FLAG_EMPTYK is overwritten by every k_mstep_disp; FLAG_MOVED and the
 // relaxation-round window that follows this block are zeroed by k_density, which precedes every
-// sweep of the EM loop (so no memset launches are needed).
+// sweep of the EM loop (so no memset launches are needed).  Under the shadow-verify schedule (nem_engine.hip) an engine
+// keeps three such blocks, each with its round window, and a density launch clears only the one of its own iteration.
 // FLAG_FAULT: a kernel could not finish its work (bit 0: a hand-over of k_mstep_fuzzy_pc never completed).  Sticky: only
 // a reset clears it; the host turns it into NEMGPU_E_INTERNAL wherever it reads the flags back.
 enum { FLAG_EMPTYK = 0, FLAG_EMPTY_PROP = 1, FLAG_FAULT = 2, FLAG_MOVED = 3, FLAG_ITER_STRIDE = 4 };
@@ -166,6 +167,8 @@ struct FinishArgs {
     const int* perm;               // density kernels: lane i of the (sorted) matrix copy is family perm[i]
     int use_ff;                    // density kernels: fast-forward the uniform chain inside float binades (nem_ff.hpp)
     uint2* ffq;                    // [K][256] (q0, q1 - q0): the fast-forward increments per class, built next to the tables
+    // fused density (mode 1): where an empty class keeps its centre and dispersions from (nullptr: center / disp)
+    const float* prev_center; const float* prev_disp;
 };
 void launch_finish(const FinishArgs& a, hipStream_t s);
 void launch_density(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
@@ -174,6 +177,11 @@ void launch_density(const FinishArgs& t, const uint32_t* xw, int n, int npad, do
 constexpr int kFusedMaxD = 1024;   // beyond this the per-block parameter derivation costs more than a k_finish launch
 void launch_density_fused(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
                           int* zero_flags, int n_zero_flags, hipStream_t s);
+// ... and the same density beside the last relaxation round of the previous iteration's sweep, in ONE launch
+// (k_density_verify); the round's arguments are complete, its last-block ticket included.  Not recordable.
+bool density_verify_supported(int n_local, int K, int tie_rule);
+void launch_density_verify(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
+                           int* zero_flags, int n_zero_flags, const SweepArgs& sw, hipStream_t s);
 void launch_sweep(const SweepArgs& a, bool ncem, hipStream_t s);
 // one NCEM relaxation round and the M-step counts (of the partition whose class masks exist already) in ONE launch;
 // returns false when the shape has no such kernel (2 <= K <= 5, fewer than 65 536 families, not recordable)

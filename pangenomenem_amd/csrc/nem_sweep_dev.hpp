@@ -151,14 +151,17 @@ __device__ inline void ctrl_logic(const CtrlArgs& a)
 
 // last-block-done ticket: returns true in exactly one thread of the grid, after every block's global
 // writes (made before its call) are visible to it
+// `bx`: the block's index among the `nblocks` that take part (default blockIdx.x; a launch whose ticket covers a
+// trailing range of its blocks passes the index within that range).
 // Two levels (groups of blocks, then the groups) once the grid is larger than 32 blocks: same-address atomics
 // are served one after the other (~45 ns each on MI355X), so a flat counter costs 9 us at 200 blocks; with at most
 // 32 groups on counters 128 bytes apart it is ~sqrt of that.  `ticket` points at kTicketWords zeroed ints.
 // The counters are 64-bit: arrivals in the low word, and in the high word an optional grid-wide sum (`tally`, this
 // block's share; the last block stores the total to *tally_out) that rides on the same atomics -- a sum that would
 // otherwise cost one same-address atomic per block.
-__device__ inline bool last_block_ticket(int* ticket, int nblocks, int tally = 0, int* tally_out = nullptr)
+__device__ inline bool last_block_ticket(int* ticket, int nblocks, int tally = 0, int* tally_out = nullptr, int bx = -1)
 {
+    const int b = bx >= 0 ? bx : (int)blockIdx.x;
     __shared__ int s_last;
     // What the last block reads of the others are FLAGS, all of them updated by device-scope atomics: every wave waits
     // until its own are performed (vmcnt(0)), the block meets, one thread adds the arrival.  (A device-scope release
@@ -174,7 +177,7 @@ __device__ inline bool last_block_ticket(int* ticket, int nblocks, int tally = 0
             if (last) *ticket = 0;
         } else {
             const int gsz = (nblocks + 31) / 32;
-            const int g = blockIdx.x / gsz;
+            const int g = b / gsz;
             const int ng = (nblocks + gsz - 1) / gsz;
             const int members = min(gsz, nblocks - g * gsz);
             int* gc = ticket + 32 * (1 + g);
@@ -197,7 +200,7 @@ __device__ inline bool last_block_ticket(int* ticket, int nblocks, int tally = 0
             if (last) { *tc = 0; total = (t >> 32) + (u64)(unsigned)tally; }
         } else {
             const int gsz = (nblocks + 31) / 32;                   // blocks per group; at most 32 groups
-            const int g = blockIdx.x / gsz;
+            const int g = b / gsz;
             const int ng = (nblocks + gsz - 1) / gsz;
             const int members = min(gsz, nblocks - g * gsz);
             u64* gc = reinterpret_cast<u64*>(ticket + 32 * (1 + g));
@@ -624,7 +627,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     const bool post_ctrl = NCEM && a.post_on && a.post_ctrl.ctrl != nullptr;
     if (a.publish_byte != nullptr || post_ctrl || fold) {
         int* ticket = a.publish_byte != nullptr ? a.publish_ticket : (post_ctrl ? a.post_ctrl.ticket : a.fold_ticket);
-        if (last_block_ticket(ticket, nblk, fold ? s_nzero : 0, fold ? &a.flags[FLAG_NZERO] : nullptr)) {
+        if (last_block_ticket(ticket, nblk, fold ? s_nzero : 0, fold ? &a.flags[FLAG_NZERO] : nullptr, bx)) {
             if (a.publish_byte != nullptr) {
                 *a.publish_byte = (uint8_t)(__hip_atomic_load(&a.flags[FLAG_CHANGED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0);
                 if (NCEM && a.post_on && a.post_moved)          // (sharded: this rank's 'a label moved' byte rides next to it)

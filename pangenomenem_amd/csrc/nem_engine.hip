@@ -179,6 +179,13 @@ struct nemgpu_engine {
     // copy of the last accepted iteration.  (flag_sets: 3 when the copies exist, else 1.)
     bool shadow_verify = true;
     int flag_sets = 1, fset = 0;
+    // ... and under it (NEM_MI355X_ROUND_COUNTS, default on; see shadow_batch_enqueue) the round that makes a held sweep's
+    // class masks also adds up the next iteration's M-step counts, so that iteration has no k_mstep_counts launch.  They
+    // go to one of two statistics slots (stats_slot[0] is `stats`); stats_last is the slot with the counts a batch left
+    // last, which is what a reader of the statistics outside a batch gets.
+    bool round_counts = true;
+    int* stats_slot[2] = {};
+    int* stats_last = nullptr;
     float* par_copy[3] = {}; double* pkfki_copy[3] = {}; float* logpkfki_copy[3] = {};
     // relaxation rounds enqueued per sweep before anybody looks (round 0, its verification, and one more that costs
     // an early-exit launch when it is not needed and a host round trip when it is missing); NEM_MI355X_ROUNDS=2..4
@@ -583,6 +590,8 @@ int alloc_model_buffers(nemgpu_engine* e)
     }
     A(dev_alloc(&e->mask, (size_t)k * e->nw64));
     A(dev_alloc(&e->stats, (size_t)k + kd));
+    e->stats_slot[0] = e->stats; e->stats_last = e->stats;
+    if (e->flag_sets == 3 && e->round_counts) A(dev_alloc(&e->stats_slot[1], (size_t)k + kd));
     A(dev_alloc(&e->flags_dev, e->flag_words()));
     return r;
 }
@@ -652,6 +661,7 @@ FinishArgs finish_args(nemgpu_engine* e, int mode, const int* stats)
     t.reset_prop = nullptr; t.reset_center = nullptr; t.reset_disp = nullptr;
     t.reset_ctrl = nullptr; t.reset_ctrl_words = 0; t.reset_sweep_next = nullptr;
     t.prev_center = nullptr; t.prev_disp = nullptr;
+    t.zero_stats = nullptr; t.n_zero_stats = 0;
     t.use_ff = e->use_ff() ? 1 : 0;
     t.perm = e->perm;
     t.ffq = e->ffq;
@@ -696,6 +706,8 @@ struct SweepCtx {
     // shadow-verify schedule: the last round of the first batch is not launched but left here, bookkeeping and loop
     // control included, for the next density launch; the round before it makes the class masks and "moved"
     SweepArgs* hold = nullptr;
+    // ... and the round that makes the masks adds the M-step counts of its labels into this (zeroed) slot (nullptr: no)
+    int* count_into = nullptr;
 };
 
 int clear_sweep_flags(nemgpu_engine* e)
@@ -794,12 +806,14 @@ int sweep_launch_rounds(nemgpu_engine* e, SweepCtx& c, int count)
         c.a.prev_changed = (r == r0) ? nullptr : (e->round_flags(c.slot_base + r - 1) + FLAG_CHANGED);
         c.a.stop = e->stop_ptr;
         c.a.post_on = 0;
+        c.a.post_stats = nullptr;
         if (c.hold != nullptr && c.post && ncem && r0 == 0 && count >= 2 && b >= count - 2) {
             c.a.post_on = 1; c.a.post_skip_guess = (r % 2 == 1) ? 1 : 0;
             c.a.post_nw64 = e->nw64; c.a.post_mask = e->mask; c.a.post_flags = e->iter_flags();
             if (b == count - 2) {
                 // the masks and "moved" from this round's output: final whenever the next round changes nothing
                 c.a.post_from_guess = 0; c.a.post_moved = c.post_moved ? 1 : 0; c.a.post_no_masks = 0; c.a.post_ctrl = CtrlArgs{};
+                if (c.count_into != nullptr) { c.a.post_stats = c.count_into; c.a.post_xt = e->xt; c.a.post_D = e->d; }
             } else {
                 // the verifying round: the loop control in its last-block ticket, nothing else
                 c.a.post_from_guess = 1; c.a.post_moved = 0; c.a.post_no_masks = 1; c.a.post_ctrl = c.post_ctrl;
@@ -839,11 +853,14 @@ int sweep_setup(nemgpu_engine* e, float beta, SweepCtx& c, bool id_by_value)
 }
 
 int sweep_enqueue(nemgpu_engine* e, float beta, SweepCtx& c, bool id_by_value = false, const CtrlArgs* post_ctrl = nullptr,
-                  bool post_moved = false, int slot_base = 0, int rounds = 0, SweepArgs* hold = nullptr)
+                  bool post_moved = false, int slot_base = 0, int rounds = 0, SweepArgs* hold = nullptr, int* count_into = nullptr)
 {
     c = SweepCtx();
     c.slot_base = slot_base;
-    if (post_ctrl != nullptr && e->ncem()) { c.post = true; c.post_moved = post_moved; c.post_ctrl = *post_ctrl; c.hold = hold; }
+    if (post_ctrl != nullptr && e->ncem()) {
+        c.post = true; c.post_moved = post_moved; c.post_ctrl = *post_ctrl; c.hold = hold;
+        c.count_into = hold != nullptr ? count_into : nullptr;
+    }
     { int r = sweep_setup(e, beta, c, id_by_value); if (r) return r; }
     if (!e->flags_clean) { int r = clear_sweep_flags(e); if (r) return r; }
     e->flags_clean = false;
@@ -931,6 +948,7 @@ int do_mstep(nemgpu_engine* e, const CtrlArgs* prev_ctrl = nullptr)
         if (!e->masks_valid) { int r = do_labels_post(e, e->cur, -1); if (r) return r; }
         launch_mstep_counts(e->k, e->d, e->nw64, e->xt, e->mask, e->stats, e->stop_ptr, prev_ctrl, e->stream);
         launch_finish(finish_args(e, 1, e->stats), e->stream);
+        e->stats_last = e->stats;
     } else {
         launch_mstep_fuzzy(e->n, e->npad, e->k, e->d, e->xw, e->xt, e->nw64, e->cbuf[e->cur] + (size_t)e->lo * e->k,
                            e->fz_ct, e->nbobs_k,
@@ -1116,8 +1134,9 @@ static int init_beta_rounds(const nemgpu_engine* e)
 }
 
 // hold (shadow-verify schedule, NCEM): the beta sweep's last round and the loop control are left in *hold for the first
-// iteration's density launch (defer_ctrl is then ignored)
-int enqueue_init(nemgpu_engine* e, bool defer_ctrl, SweepArgs* hold = nullptr)
+// iteration's density launch (defer_ctrl is then ignored); count_into (with hold): the round before it adds the first
+// iteration's M-step counts into these statistics, which this launch's restart head zeroes
+int enqueue_init(nemgpu_engine* e, bool defer_ctrl, SweepArgs* hold = nullptr, int* count_into = nullptr)
 {
     int r;
     // one launch: initial parameters back in place, loop control cleared, density tables built
@@ -1125,6 +1144,7 @@ int enqueue_init(nemgpu_engine* e, bool defer_ctrl, SweepArgs* hold = nullptr)
         FinishArgs t = finish_args(e, 0, nullptr);
         t.reset_prop = e->prop0; t.reset_center = e->center0; t.reset_disp = e->disp0;
         t.reset_ctrl = e->ctrl(); t.reset_ctrl_words = C_WORDS; t.reset_sweep_next = e->sweep_next;
+        if (hold != nullptr && count_into != nullptr) { t.zero_stats = count_into; t.n_zero_stats = e->k + e->k * e->d; }
         launch_finish(t, e->stream);
         HIPCHK(hipGetLastError());
     }
@@ -1153,7 +1173,8 @@ int enqueue_init(nemgpu_engine* e, bool defer_ctrl, SweepArgs* hold = nullptr)
     const bool defer = defer_ctrl && e->ncem() && !e->cfg.param_fix && hold == nullptr;
     CtrlArgs none{};
     if (libc) e->draw_extra_once = e->round_flags(kRoundCap - 1) + FLAG_NTIES;
-    if ((r = sweep_enqueue(e, e->cfg.beta, c1, true, e->ncem() ? (defer ? &none : &ca) : nullptr, false, 0, ca.n_rounds, hold))) return r;   // 1 -> 2 (and 0 as the pong buffer)
+    if ((r = sweep_enqueue(e, e->cfg.beta, c1, true, e->ncem() ? (defer ? &none : &ca) : nullptr, false, 0, ca.n_rounds, hold,
+                           count_into))) return r;   // 1 -> 2 (and 0 as the pong buffer)
     e->draw_extra_once = nullptr;
     if (defer) { e->ctrl_deferred = ca; e->ctrl_pending = true; }
     if (e->ncem()) e->masks_valid = true;
@@ -1396,6 +1417,18 @@ int batch_plan(nemgpu_engine* e, LoopCursor& lc)
 // batch that stops elsewhere has its accepted copy moved to 0 afterwards (accept_copy).  The copies depend on (first
 // batch, g, j) only, so a captured batch replays with the same ones.
 int shadow_copy(int j, int g) { return j == g - 1 ? 0 : 1 + (g - 2 - j) % 2; }
+// ... and (NEM_MI355X_ROUND_COUNTS) its M-step counts slot shadow_stats(j, g): the last iteration's are in `stats`, the
+// ones before alternate, so that the slot a mask round adds into is never the one the density beside it reads
+int shadow_stats(int j, int g) { return (g - 1 - j) % 2; }
+// Does the mask round count (NEM_MI355X_ROUND_COUNTS and the shape)?  Its tail grows with the partial counts it adds, one
+// atomic per (block, class, organism), all blocks on the same K*D words; the launch it saves does not.  Measured on
+// MI355X (NOTES_negative_results.md section 12): 79 blocks x 1 500 (configs[1]) made the round 1.7 us longer and the step
+// 1 us shorter; 196 x 3 000 (50 000 x 1 000) made the step 5.4 us longer.
+constexpr long kRoundCountsMaxAdds = 1l << 17;
+bool round_counts_on(const nemgpu_engine* e)
+{
+    return e->round_counts && (long)((e->n + 255) / 256) * e->k * e->d <= kRoundCountsMaxAdds;
+}
 
 void use_copy(nemgpu_engine* e, int c)
 {
@@ -1426,18 +1459,24 @@ bool shadow_engine(const nemgpu_engine* e)
            density_verify_supported(e->n, e->k, e->cfg.tie_rule);
 }
 
-// iteration `cur` of a shadow-verify batch: counts, then the density (with the previous sweep's verifying round when
-// *pending), then the sweep's rounds -- its last one left in *held (*pending set) when `hold`
+// iteration `cur` of a shadow-verify batch: counts into `stats` (unless the held sweep's mask round added them up
+// there: *pending and *counted), then the density (with the previous sweep's verifying round when *pending), then the
+// sweep's rounds -- its last one left in *held (*pending set) when `hold`.  count_into (with hold): the mask round adds
+// the next iteration's counts into these statistics (*counted set), which the density launch zeroes first.
 int enqueue_iteration_shadow(nemgpu_engine* e, int cur, uint32_t sweep_id, bool hold, bool deep, int pos, int prev, int copy,
-                             SweepArgs* held, bool* pending)
+                             SweepArgs* held, bool* pending, int* stats, int* count_into, bool* counted)
 {
     int r;
     const int saved = e->cur;
     e->cur = cur;
-    if (!e->masks_valid) { if ((r = do_labels_post(e, e->cur, -1))) { e->cur = saved; return r; } }
-    launch_mstep_counts(e->k, e->d, e->nw64, e->xt, e->mask, e->stats, e->stop_ptr, nullptr, e->stream);
+    if (!(*pending && *counted)) {
+        if (!e->masks_valid) { if ((r = do_labels_post(e, e->cur, -1))) { e->cur = saved; return r; } }
+        launch_mstep_counts(e->k, e->d, e->nw64, e->xt, e->mask, stats, e->stop_ptr, nullptr, e->stream);
+    }
+    if (!hold) count_into = nullptr;
     use_copy(e, copy);
-    FinishArgs t = finish_args(e, 1, e->stats);
+    FinishArgs t = finish_args(e, 1, stats);
+    if (count_into != nullptr) { t.zero_stats = count_into; t.n_zero_stats = e->k + e->k * e->d; }
     t.prev_center = e->par_copy[prev] + e->par_o_center; t.prev_disp = e->par_copy[prev] + e->par_o_disp;
     if (*pending) launch_density_verify(t, e->xws, e->n, e->npad, e->pkfki, e->logpkfki, e->iter_flags() + FLAG_MOVED,
                                         kSweepFlagWords, *held, e->stream);
@@ -1456,8 +1495,9 @@ int enqueue_iteration_shadow(nemgpu_engine* e, int cur, uint32_t sweep_id, bool 
     ca.param_fix = 0; ca.use_nei = 1; ca.cvtest = e->cfg.cvtest;
     ca.ncem = 1; ca.cvthres = e->cfg.cvthres; ca.sweep_next = e->sweep_next; ca.ticket = e->sweep_next + 32;
     if (hold) *held = SweepArgs{};
-    if ((r = sweep_enqueue(e, e->cfg.beta, c, false, &ca, true, 0, it_rounds, hold ? held : nullptr))) { e->cur = saved; return r; }
+    if ((r = sweep_enqueue(e, e->cfg.beta, c, false, &ca, true, 0, it_rounds, hold ? held : nullptr, count_into))) { e->cur = saved; return r; }
     *pending = hold && held->post_ctrl.ctrl != nullptr;    // (a sweep of one round has nothing to hold back)
+    *counted = *pending && count_into != nullptr;
     e->masks_valid = true;
     e->cur = saved;
     return NEMGPU_OK;
@@ -1467,18 +1507,23 @@ int shadow_batch_enqueue(nemgpu_engine* e, const LoopCursor& lc)
 {
     int r = NEMGPU_OK;
     SweepArgs held{};
-    bool pending = false;
+    bool pending = false, counted = false;
     int prev = 0;                                          // the copy the next density keeps an empty class's parameters from
+    // the statistics of iteration j: slot shadow_stats(j, g) -- added up by the mask round of the sweep before (zeroed by
+    // the launch before that round: the restart head or the density of j - 1), or stored by a counts launch
+    const bool rc = round_counts_on(e);
+    auto stats = [&](int j) { return rc ? e->stats_slot[shadow_stats(j, lc.g)] : e->stats; };
     if (lc.batch_first) {
         prev = shadow_copy(-1, lc.g);
         use_copy(e, prev);
-        r = enqueue_init(e, false, &held);
+        r = enqueue_init(e, false, &held, rc ? stats(0) : nullptr);
         pending = r == NEMGPU_OK && held.post_ctrl.ctrl != nullptr;
+        counted = pending && rc;
     }
     for (int j = 0; j < lc.g && r == NEMGPU_OK; j++) {
         const int copy = shadow_copy(j, lc.g);
         r = enqueue_iteration_shadow(e, (lc.base + j) % 3, lc.sweep0 + j, j + 1 < lc.g, j < lc.deep, lc.pos0 + j, prev, copy,
-                                     &held, &pending);
+                                     &held, &pending, stats(j), rc && j + 1 < lc.g ? stats(j + 1) : nullptr, &counted);
         prev = copy;
     }
     use_copy(e, 0);
@@ -1527,6 +1572,9 @@ int batch_finish(nemgpu_engine* e, LoopCursor& lc)
         const int acc = shadow_copy(done - 1, lc.g);
         if (acc != 0 && (r = accept_copy(e, acc))) return r;
     }
+    // the statistics the batch counted last: those of the iteration behind the one whose loop control stopped it (its
+    // counts were added up, or launched, before that control ran), else of the batch's last iteration
+    e->stats_last = lc.shadow && round_counts_on(e) ? e->stats_slot[shadow_stats(std::min(done, lc.g - 1), lc.g)] : e->stats;
     if (first && e->libc()) {
         if (c[C_NEED_ROUNDS] >= 2) {
             // TIE_LIBC: one of the two initial sweeps was not through in the rounds enqueued (or a draw left the table):
@@ -2487,6 +2535,7 @@ int nemgpu_create(nemgpu_engine** out, int n_total, int d, int k, int site_lo, i
     if (const char* g = getenv("NEM_MI355X_GRAPHS")) e->use_graphs = (g[0] != '0');   // 0: plain launches only
     if (const char* g = getenv("NEM_MI355X_SHADOW_VERIFY")) e->shadow_verify = (g[0] != '0');   // 0: every verifying round on its own
     e->flag_sets = e->shadow_verify ? 3 : 1;
+    if (const char* g = getenv("NEM_MI355X_ROUND_COUNTS")) e->round_counts = (g[0] != '0');   // 0: a counts launch per iteration
     if (const char* g = getenv("NEM_MI355X_ROUNDS")) e->round_batch = std::max(2, std::min(kRoundBatchMax, atoi(g)));
     if (const char* g = getenv("NEM_MI355X_ROUNDS_ITER")) e->rounds_iter = std::max(2, std::min(e->round_batch, atoi(g)));
     e->rounds_iter = std::min(e->rounds_iter, e->round_batch);
@@ -5161,7 +5210,7 @@ int nemgpu_profile_density(nemgpu_engine* e, int reps, double* avg_ms, double* a
     for (int i = 0; i < reps; i++) {
         HIPCHK(hipEventRecord(e->ev0, e->stream));
         if (fused) {
-            launch_density_fused(finish_args(e, 1, e->stats), e->xws, e->n, e->npad, e->pkfki, e->logpkfki,
+            launch_density_fused(finish_args(e, 1, e->stats_last), e->xws, e->n, e->npad, e->pkfki, e->logpkfki,
                                  e->iter_flags() + FLAG_MOVED, kSweepFlagWords, e->stream);
             HIPCHK(hipGetLastError());
         } else if ((r = do_density(e))) return r;
@@ -5271,6 +5320,7 @@ int nemgpu_profile_kernels(nemgpu_engine* e, int reps, double avg_ms[3], double 
     };
     // M-step counts first: they leave the statistics the fused E1 derives its parameters from
     if ((r = timed([&] { launch_mstep_counts(e->k, e->d, e->nw64, e->xt, e->mask, e->stats, nullptr, nullptr, e->stream); }, &avg_ms[2]))) return r;
+    e->stats_last = e->stats;
     if ((r = timed([&] {
             if (fused) launch_density_fused(finish_args(e, 1, e->stats), e->xws, e->n, e->npad, e->pkfki, e->logpkfki,
                                             e->iter_flags() + FLAG_MOVED, kSweepFlagWords, e->stream);

@@ -577,6 +577,7 @@ struct FusedDensityArgs {
     int* iter_flags;
     double* pkfki; float* logpkfki;
     int* zero_flags; int n_zero_flags;
+    int* zero_stats; int n_zero_stats;                   // the statistics the next counting round adds into (nullptr: none)
     const int* stop;
     int use_ff;
     const int* perm;
@@ -603,6 +604,7 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
     const bool writer = (tile == 0);                     // this block publishes class k's parameters
     if (tile == 0 && k == 0) {
         for (int t = tid; t < a.n_zero_flags; t += 256) a.zero_flags[t] = 0;
+        for (int t = tid; t < a.n_zero_stats; t += 256) a.zero_stats[t] = 0;
         if (tid == 0) {                                  // EstimLaplaceCenters, nem_mod.c:1404-1408
             int ek = 0;
             for (int c = 0; c < K; c++)
@@ -1115,6 +1117,7 @@ __device__ __forceinline__ void finish_lean(const FinishArgs& a)
         if (k == 0) {
             if (tid < a.reset_ctrl_words && tid != C_FOLD) a.reset_ctrl[tid] = 0;
             if (tid == 0) a.reset_sweep_next[0] = 0;
+            for (int t = tid; t < a.n_zero_stats; t += 1024) a.zero_stats[t] = 0;   // (k_finish: 1024 threads)
         }
     } else if (a.stop != nullptr && *a.stop) return;
     NEM_PHASE(0);
@@ -1378,6 +1381,7 @@ __device__ __forceinline__ void finish_body(const FinishArgs& a, const int nblk)
         if (blockIdx.x == 0) {
             if (tid < a.reset_ctrl_words && tid != C_FOLD) a.reset_ctrl[tid] = 0;
             if (tid == 0) a.reset_sweep_next[0] = 0;
+            for (int t = tid; t < a.n_zero_stats; t += 1024) a.zero_stats[t] = 0;   // (k_finish: 1024 threads)
         }
         __syncthreads();
     } else if (a.stop != nullptr && *a.stop) return;
@@ -2310,6 +2314,7 @@ static FusedDensityArgs fused_density_args(const FinishArgs& t, const uint32_t* 
     a.center_in = t.prev_center != nullptr ? t.prev_center : t.center;
     a.disp_in = t.prev_disp != nullptr ? t.prev_disp : t.disp;
     a.pkfki = pkfki; a.logpkfki = logpkfki; a.zero_flags = zero_flags; a.n_zero_flags = n_zero_flags; a.stop = t.stop;
+    a.zero_stats = t.zero_stats; a.n_zero_stats = t.zero_stats != nullptr ? t.n_zero_stats : 0;
     a.use_ff = t.use_ff; a.perm = t.perm;
     return a;
 }

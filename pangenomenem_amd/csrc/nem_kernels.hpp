@@ -98,6 +98,10 @@ struct SweepArgs {
     const uint8_t* rank_tot_in; int rank_index; uint8_t* rank_tot_out;
     // sites per block of the large-shard kernel instances (set by launch_sweep; 0: the kernel's block size)
     int spb;
+    // shadow-verify schedule, the round that makes the class masks of a held sweep: the M-step counts of those masks
+    // (k_mstep_counts' {N_k, S1[k][d]}) added into post_stats, zeroed by an earlier launch -- every block its 256
+    // families' share, from the organism-major bit rows post_xt ([post_D][post_nw64]).  nullptr: no counting.
+    int* post_stats; const uint64_t* post_xt; int post_D;
 };
 // argument blocks of the kernels whose launch wrappers take scalars (the batched launches need them as structs)
 struct LabelsPostArgs { int n_local, lo, K, nw64; const uint8_t* lab_new; const uint8_t* lab_old; uint64_t* mask; int* flags;
@@ -169,6 +173,8 @@ struct FinishArgs {
     uint2* ffq;                    // [K][256] (q0, q1 - q0): the fast-forward increments per class, built next to the tables
     // fused density (mode 1): where an empty class keeps its centre and dispersions from (nullptr: center / disp)
     const float* prev_center; const float* prev_disp;
+    // statistics words to clear for a counting round that follows (fused density and the restart head; nullptr: none)
+    int* zero_stats; int n_zero_stats;
 };
 void launch_finish(const FinishArgs& a, hipStream_t s);
 void launch_density(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,

@@ -4,14 +4,16 @@
 // compile time, and build.py compiles the units side by side.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 
 #include "nem_kernels.hpp"
 #include "nem_sweep_dev.hpp"
 
 namespace nemk {
 
-template <int KT, bool NCEM, int BS, bool LIBC = false>
-__global__ __launch_bounds__(BS) void k_sweep(SweepArgs a) { sweep_body<KT, NCEM, BS, LIBC>(a, blockIdx.x, gridDim.x); }
+template <int KT, bool NCEM, int BS, bool LIBC = false, bool COUNT = false>
+__global__ __launch_bounds__(BS) void k_sweep(SweepArgs a) { sweep_body<KT, NCEM, BS, LIBC, COUNT>(a, blockIdx.x, gridDim.x); }
 template <int KT, bool NCEM, int BS, bool LIBC = false>
 __global__ __launch_bounds__(BS) void k_sweep_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(SweepArgs) sweep_body<KT, NCEM, BS, LIBC>(a, blockIdx.x, nblk); }
 
@@ -68,6 +70,19 @@ void launch_sweep(const SweepArgs& a0, bool ncem, hipStream_t s)
     a.spb = big ? bs : 0;
     dim3 grid((a.n_local + bs - 1) / bs);
     const int variant = sweep_variant(a.K, ncem, big, a.tie_rule == NEMGPU_TIE_LIBC);
+    if (a.post_stats != nullptr) {
+        // the counting round (SweepArgs::post_stats): an instance of its own, so that no other round carries its registers
+        // (not recordable: the batched twins have no such instance)
+        if (!(current_recorder() == nullptr && ncem && !big && a.K >= 1 && a.K <= 10 && a.tie_rule != NEMGPU_TIE_LIBC &&
+              a.post_on && !a.post_no_masks && a.post_D >= 1 && a.post_D <= kFusedMaxD)) {
+            fprintf(stderr, "launch_sweep: no counting round for this shape\n");
+            abort();
+        }
+#define NEM_SWC(KT_) case KT_: hipLaunchKernelGGL((k_sweep<KT_, true, 256, false, true>), grid, dim3(256), 0, s, a); break;
+        switch (a.K) { NEM_SWC(1) NEM_SWC(2) NEM_SWC(3) NEM_SWC(4) NEM_SWC(5) NEM_SWC(6) NEM_SWC(7) NEM_SWC(8) NEM_SWC(9) NEM_SWC(10) default: break; }
+#undef NEM_SWC
+        return;
+    }
     if (record_op(OP_SWEEP, variant, grid, (unsigned)bs, a)) return;
     sweep_dispatch<false>(variant, grid, (unsigned)bs, s, &a, nullptr, 0, nullptr);
 }

@@ -303,9 +303,12 @@ __device__ __forceinline__ int wave_sum_i32(int v)
 
 // LIBC: the reference's tie stream (TIE_LIBC) -- its bookkeeping (who drew, per wave and block, at every block-local
 // step) is compiled into the instances that need it only
-template <int KT, bool NCEM, int BS, bool LIBC = false>
+// COUNT: the round also adds its block's M-step counts into SweepArgs::post_stats (the round that makes the class masks
+// of a held sweep, see the shadow-verify schedule in nem_engine.hip); NCEM, 256 sites per block, D <= kFusedMaxD only
+template <int KT, bool NCEM, int BS, bool LIBC = false, bool COUNT = false>
 __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, const int nblk)
 {
+    static_assert(!COUNT || (NCEM && BS == 256 && !LIBC && KT > 0), "the counting round: NCEM, 256 sites per block");
     int fold_hint = 0;
     if (a.stop != nullptr) {
         static_assert(C_STOP == 0 && C_FOLD == 1, "one 8-byte load");
@@ -359,6 +362,20 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     //  the tail is a memory latency added to the block's run time)
     int blk_cnt_guess = 0;
     if (LIBC && threadIdx.x == 0 && a.tie_cnt_guess != nullptr) blk_cnt_guess = a.tie_cnt_guess[bx];
+    // COUNT: the block's four words of organism rows d = threadIdx.x + 256 q, requested here for the same reason: they
+    // do not depend on the labels, and the tail only ANDs them with the class masks
+    constexpr int kCntRows = COUNT ? kFusedMaxD / BS : 1;
+    uint64_t xs[kCntRows][4];
+    if (COUNT) {
+        const int w0 = 4 * bx;
+#pragma unroll
+        for (int q = 0; q < kCntRows; q++) {
+            const int d = (int)threadIdx.x + q * BS;
+#pragma unroll
+            for (int w = 0; w < 4; w++)
+                xs[q][w] = (d < a.post_D && w0 + w < a.post_nw64) ? a.post_xt[(size_t)d * a.post_nw64 + w0 + w] : 0ull;
+        }
+    }
     __shared__ int s_anydrew;                            // TIE_LIBC: a site of the block drew at some local step of this launch
     if (threadIdx.x == 0) { s_nzero = 0; s_first = 0; s_chg = 0; s_mov = 0; s_anydrew = 0; }
     if (NCEM) s_lab[threadIdx.x] = (uint8_t)my_guess;
@@ -615,13 +632,47 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
         if (NCEM && a.post_on && s_mov && __hip_atomic_load(&a.post_flags[FLAG_MOVED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
             atomicOr(&a.post_flags[FLAG_MOVED], 1);
     }
+    __shared__ uint64_t s_cmask[COUNT ? KA : 1][4];      // COUNT: the block's class masks, [class][wave]
     if (NCEM && a.post_on) {                             // k_labels_post's work, see SweepArgs
         const int wave = i >> 6;
-        if (wave < a.post_nw64 && !a.post_no_masks) {
+        if (COUNT) {                                     // (every wave: one past the labels has empty masks)
+            for (int k = 0; k < K; k++) {
+                const uint64_t m = __ballot(post_lab == k);
+                if ((threadIdx.x & 63) == 0) {
+                    if (wave < a.post_nw64) a.post_mask[(size_t)k * a.post_nw64 + wave] = m;
+                    s_cmask[k][threadIdx.x >> 6] = m;
+                }
+            }
+        } else if (wave < a.post_nw64 && !a.post_no_masks) {
             for (int k = 0; k < K; k++) {
                 const uint64_t m = __ballot(post_lab == k);
                 if ((threadIdx.x & 63) == 0) a.post_mask[(size_t)k * a.post_nw64 + wave] = m;
             }
+        }
+    }
+    if (COUNT) {
+        // k_mstep_counts' work for this block's 256 families: S1[k][d] and N_k are integer counts, so the blocks' partial
+        // counts add up to the same statistics in any order -- one no-return device-scope atomic per nonzero partial, into
+        // words an earlier launch of the batch zeroed; the launch boundary behind this round publishes the sums
+        __syncthreads();
+        const int D = a.post_D;
+        int* st = a.post_stats;
+#pragma unroll
+        for (int q = 0; q < kCntRows; q++) {
+            const int d = (int)threadIdx.x + q * BS;
+            if (d < D) {
+#pragma unroll
+                for (int k = 0; k < KA; k++) {
+                    const int v = __popcll(xs[q][0] & s_cmask[k][0]) + __popcll(xs[q][1] & s_cmask[k][1]) +
+                                  __popcll(xs[q][2] & s_cmask[k][2]) + __popcll(xs[q][3] & s_cmask[k][3]);
+                    if (v != 0) atomicAdd(&st[K + k * D + d], v);
+                }
+            }
+        }
+        if ((int)threadIdx.x < K) {
+            const int k = threadIdx.x;
+            const int v = __popcll(s_cmask[k][0]) + __popcll(s_cmask[k][1]) + __popcll(s_cmask[k][2]) + __popcll(s_cmask[k][3]);
+            if (v != 0) atomicAdd(&st[k], v);
         }
     }
     const bool post_ctrl = NCEM && a.post_on && a.post_ctrl.ctrl != nullptr;

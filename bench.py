@@ -23,9 +23,16 @@ the inputs are the same from run to run (seeded generators), so two builds can b
 the tree, bench_outputs/ is the place for them (git ignores it): --dump-outputs bench_outputs/<build>.
 
 N = 1 (default): BASELINE configs[1], 20 000 families x 500 organisms, K=3, beta=0.5, contiguity graph,
-ncem / sk_ / pk exactly as ppanggolin.py:1769-1826 calls nem().  The JSON line also carries `north_star_target`:
-the 50 000 x 1 000 problem of BASELINE.json's north_star on this GPU next to the compiled reference's own loop on
-one host core, timed in the same run (--no-north-star skips it).
+ncem / sk_ / pk exactly as ppanggolin.py:1769-1826 calls nem().
+
+A plain run does what the headline needs and no more: it sets up, warms up, times the steps, writes --dump-outputs and
+prints the line.  --full measures everything else as well, each part in runs of its own after the headline's:
+  N = 1    `roofline` per kernel (E1, a sweep round, the counts, timed live with HIP events), `cpu_baseline` (the
+           compiled reference on one host core, same workload), `north_star_target` (the 50 000 x 1 000 problem of
+           BASELINE.json's north_star on this GPU next to the reference's own loop, timed in the same run) and `also`;
+  N > 1    the collective's own time, `single_gpu_same_workload`, per-kernel `roofline` and `also`.
+--no-cpu-baseline, --no-north-star and --no-extras leave their part out of a --full run.  A plain line's `roofline`
+carries the whole iteration's algorithmic GB/s alone.
 
 N > 1: one process per GPU (torch.distributed over RCCL).  `python bench.py --gpus N` starts its own ranks
 (a torch.distributed.run child, before this process touches the GPU); under an existing launcher (RANK /
@@ -33,14 +40,15 @@ WORLD_SIZE in the environment) it is one of the ranks.  --scaling selects what t
   strong   (default) BASELINE configs[2]: ONE 50 000 x 1 000 problem (--families / --organisms: any), families
            sharded in contiguous blocks; per EM iteration two RCCL all-gathers of the label blocks (one per relaxation
            round), the second also carrying every rank's partial integer M-step statistics -- no separate all-reduce
-           (pangenomenem_amd/distributed.py).  Rank 0 also times the same problem on ONE GPU in the same run
-           (`single_gpu_same_workload`);
+           (pangenomenem_amd/distributed.py).  With --full, rank 0 also times the same problem on ONE GPU in the same
+           run (`single_gpu_same_workload`);
   weak     the same sharded EM with a configs[1]-sized shard per rank (one problem of N x 20 000 families);
   replicas N independent configs[1]-sized problems, one per GPU, NO collective on the data path -- the reference's own
            form of parallelism (one NEM problem per organism chunk, ppanggolin.py:1039-1095).
-An N > 1 line also carries `collective` (time of one all-gather, measured on the job's own path) and, unless
---no-extras, `also`: the replicas figure and the strong-scaling figure of 200 000 x 5 000 (BASELINE configs[3]), the
-shape large enough for sharding to pay, each with its own single-GPU reference.
+An N > 1 line also carries `collective` (what the job gathers per iteration; with --full, the time of one all-gather,
+measured on the job's own path) and, with --full unless --no-extras, `also`: the replicas figure and the
+strong-scaling figure of 200 000 x 5 000 (BASELINE configs[3]), the shape large enough for sharding to pay, each with
+its own single-GPU reference.
 
 Before a timed region every batch shape it will enqueue is captured into its hipGraph (independent of --warmup);
 `graphs_primed` in the output asserts that nothing was captured or sent as plain launches while timing.
@@ -87,10 +95,14 @@ def parse_args(argv=None):
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak", "replicas"])
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: host-staged collectives, several ranks may share one GPU (rehearsal only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-north-star", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the `also` block (N = 1: coverage weights, 64 problems in lock "
-                    "step, 50 random starts on the tie stream, 200 000 x 5 000, 256 whole chunks; N > 1: replicas, 200 000 x 5 000)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else in runs of their own: per-kernel roofline, CPU baseline, "
+                         "north-star block and `also` (N = 1); the collective's time, the single-GPU comparison, per-kernel "
+                         "roofline and `also` (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-north-star", action="store_true", help="with --full: skip the north-star block")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the `also` block (N = 1: coverage weights, 64 problems in "
+                    "lock step, 50 random starts on the tie stream, 200 000 x 5 000, 256 whole chunks; N > 1: replicas, 200 000 x 5 000)")
     ap.add_argument("--extras-strong-shape", default="200000x5000", help="families x organisms of the `also` block's strong-scaling problem")
     ap.add_argument("--dist", action="store_true", help="use the sharded torch.distributed path even with 1 GPU")
     ap.add_argument("--cpu-iters", type=int, default=24, help="reference iterations timed for the CPU baseline")
@@ -756,9 +768,10 @@ class Ranks:
         return float(t.item())
 
 
-def sharded_run(args, ranks, n_tot, d, k, beta, seed, steps, warmup, repeats, want_solo):
+def sharded_run(args, ranks, n_tot, d, k, beta, seed, steps, warmup, repeats, want_solo, full):
     """ONE n_tot x d problem sharded over the ranks: timed blocks (max over ranks each), the job's facts, and -- rank 0,
-    want_solo -- the same problem on one GPU in the same run."""
+    want_solo -- the same problem on one GPU in the same run.  full: the collective's time and the kernels' too (kernels
+    is None otherwise)."""
     from pangenomenem_amd import distributed as nd
     rank, world, device = ranks.rank, ranks.world, ranks.device
     job = nd.ShardedNem.synthetic(n_tot, d, k, beta, rank, world, device, algo=args.algo, spectrum=args.spectrum, seed=seed)
@@ -778,17 +791,19 @@ def sharded_run(args, ranks, n_tot, d, k, beta, seed, steps, warmup, repeats, wa
         ranks.torch.cuda.synchronize()
         blocks.append(ranks.sync(time.perf_counter() - t0))
     nb1, nh1 = job.n_batches, job.n_host_sweeps
-    coll = job.time_collective(100)
     stride_bytes = int(job.stride)
+    collective = dict(what="in-place all-gather of the ranks' label blocks (labels, flag bytes, int32 M-step statistics)",
+                      bytes_per_rank=stride_bytes, per_iteration=2)
+    if full:
+        coll = job.time_collective(100)
+        collective.update(per_allgather_ms=coll * 1e3, per_iteration_ms=2 * coll * 1e3,
+                          how="100 back-to-back all-gathers between one pair of HIP events"
+                          if job.native else "100 all-gathers through torch.distributed, wall clock")
     facts = dict(iters_to_converge=cycle, cycle_iterations=cycle, native_rccl=bool(job.native), rccl_ranks=job.eng.rccl_ranks(),
                  batches_timed=nb1 - nb0, host_finished_sweeps_timed=nh1 - nh0, pipe_depth=job.PIPE_DEPTH,
-                 backend=args.backend, batch_graphs=bool(job.use_graphs or job.library_graphs),
-                 collective=dict(what="in-place all-gather of the ranks' label blocks (labels, flag bytes, int32 M-step statistics)",
-                                 bytes_per_rank=stride_bytes, per_allgather_ms=coll * 1e3, per_iteration=2,
-                                 per_iteration_ms=2 * coll * 1e3, how="100 back-to-back all-gathers between one pair of HIP events"
-                                 if job.native else "100 all-gathers through torch.distributed, wall clock"))
+                 backend=args.backend, batch_graphs=bool(job.use_graphs or job.library_graphs), collective=collective)
     facts["library_graph_counters"] = job.eng.graph_counters()
-    kernels = kernel_probe(job.eng)
+    kernels = kernel_probe(job.eng) if full else None
     n_loc = job.hi - job.lo
     solo = None
     if want_solo and rank == 0:
@@ -809,20 +824,21 @@ def sharded_run(args, ranks, n_tot, d, k, beta, seed, steps, warmup, repeats, wa
     return blocks, facts, kernels, n_loc, solo
 
 
-def replicas_run(args, ranks, n, d, k, beta, steps, warmup, repeats):
+def replicas_run(args, ranks, n, d, k, beta, steps, warmup, repeats, full):
     """N independent problems, one per GPU, no collective on the data path (the barrier brackets the timed blocks only):
-    every rank solves its own n x d problem -- another seed, another chunk of organisms."""
+    every rank solves its own n x d problem -- another seed, another chunk of organisms.  full: the kernels' times too
+    (kernels is None otherwise)."""
     x, nei, prop, center, disp, disper, what = make_workload(n, d, k, args.spectrum, 2 + ranks.rank)
     run = EngineRun(x, nei, k, prop, center, disp, args.algo, beta, args.disper or disper, device=ranks.device)
     blocks, info = run.timed(steps, warmup, repeats, sync=ranks.sync)
     solves = ranks.sum(steps / run.cycle)                 # whole solves all ranks complete per block
-    kernels = kernel_probe(run.eng)
+    kernels = kernel_probe(run.eng) if full else None
     run.eng.close()
     return blocks, info, kernels, solves, what
 
 
 def assemble_line(args, world, k, beta, n_tot, n_loc, d, nnz, blocks, extra, kernels, scaling, parallelism, what, ksweep, multi):
-    """the JSON record of a finished measurement (rank 0)"""
+    """the JSON record of a finished measurement (rank 0); kernels None: no per-kernel figures (a plain run)"""
     tf, med = timing_fields(blocks, args.steps)
     cells_per_s = n_tot * d * args.steps / med
     shape = ("BASELINE configs[4] (K sweep)" if (n_tot, d) == (20000, 500) and args.disper == "skd" else "custom model") \
@@ -851,10 +867,14 @@ def assemble_line(args, world, k, beta, n_tot, n_loc, d, nnz, blocks, extra, ker
             "cycle_iterations": extra.get("cycle_iterations"),
             "parallelism": parallelism,
         },
-        "roofline": roofline_block(kernels, n_loc, d, profiled_workload=(args.algo == "ncem" and args.disper == "sk_" and not ksweep
-                                                                          and args.spectrum == "ushape" and not multi
-                                                                          and args.weights == "small")),
     }
+    if kernels is not None:
+        out["roofline"] = roofline_block(kernels, n_loc, d, profiled_workload=(args.algo == "ncem" and args.disper == "sk_" and not ksweep
+                                                                                and args.spectrum == "ushape" and not multi
+                                                                                and args.weights == "small"))
+    else:
+        out["roofline"] = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "note": "the whole iteration from the timed steps alone; per-kernel figures: --full"}
     out["roofline"]["whole_iteration_algorithmic_GBps"] = whole_iteration_bytes(n_tot, d, k, nnz) * args.steps / med / 1e9
     out.update(extra)
     return out, cells_per_s
@@ -909,9 +929,9 @@ def main():
         blocks, extra = run.timed(args.steps, args.warmup, args.repeats, split=True)
         if args.dump_outputs:
             dump_outputs(args.dump_outputs, run)
-        # kernel durations: HIP events on the engine's stream around strings of launches, on the state the timed region
-        # just left (the timed region itself replays captured graphs, which carry no events)
-        kernels = kernel_probe(run.eng)
+        # kernel durations (--full): HIP events on the engine's stream around strings of launches, on the state the timed
+        # region just left (the timed region itself replays captured graphs, which carry no events)
+        kernels = kernel_probe(run.eng) if args.full else None
         n_loc, nnz = n_tot, int(nei[0][-1])
         scaling, parallelism = "weak", "1 GPU"
     else:
@@ -934,11 +954,11 @@ def main():
         what = make_workload(64, 32, 3, args.spectrum, 1)[6]
         replicas_line = None
 
-        def replicas_measure(steps, warmup, repeats):
+        def replicas_measure(steps, warmup, repeats, full):
             n_r, d_r = args.families or 20000, args.organisms or 500
             if args.scaling != "replicas":
                 n_r, d_r = 20000, 500
-            b, info, kern, solves, w = replicas_run(args, ranks, n_r, d_r, k, beta, steps, warmup, repeats)
+            b, info, kern, solves, w = replicas_run(args, ranks, n_r, d_r, k, beta, steps, warmup, repeats, full)
             info = dict(info)
             info.update(whole_solves_per_block=solves, rccl_ranks=0, backend=args.backend,
                         collective=dict(what="none on the data path (independent problems); a barrier brackets each timed block",
@@ -949,7 +969,7 @@ def main():
 
         if args.scaling == "replicas":
             wd.phase("replicas", args.phase_timeout)
-            n_loc, d, blocks, extra, kernels, solves, what, parallelism = replicas_measure(args.steps, args.warmup, args.repeats)
+            n_loc, d, blocks, extra, kernels, solves, what, parallelism = replicas_measure(args.steps, args.warmup, args.repeats, args.full)
             n_tot = n_loc * world
             nnz = int(2.1 * n_tot)
             scaling = "weak"
@@ -957,13 +977,13 @@ def main():
             # The mode with NO collective on the data path goes first (N > 1): it cannot hang on a collective, and its
             # record is what rank 0 prints if the sharded mode -- whose native RCCL path has never run with more than one
             # rank on the development box -- fails or passes its deadline.
-            if world > 1 and not args.no_extras:
+            if world > 1 and args.full and not args.no_extras:
                 saved = args.steps
                 try:
                     wd.phase("replicas (also)", args.phase_timeout)
                     st2 = max(args.steps, 140)
                     args.steps = st2
-                    n_r, d_r, b2, i2, kern2, solves, w2, par2 = replicas_measure(st2, 14, min(args.repeats, 9))
+                    n_r, d_r, b2, i2, kern2, solves, w2, par2 = replicas_measure(st2, 14, min(args.repeats, 9), True)
                     tf2, med2 = timing_fields(b2, st2)
                     also = {"replicas_20000x500_per_gpu": dict(
                         value=world * n_r * d_r * st2 / med2, unit="cells/s", ms_per_step=tf2["ms_per_step"],
@@ -990,7 +1010,8 @@ def main():
             fallback_reason = None
             try:
                 blocks, extra, kernels, n_loc, solo = sharded_run(args, ranks, n_tot, d, k, beta, seed, args.steps, args.warmup,
-                                                                  args.repeats, want_solo=(world > 1 and args.scaling == "strong"))
+                                                                  args.repeats, want_solo=(world > 1 and args.full and args.scaling == "strong"),
+                                                                  full=args.full)
             except Exception as exc:
                 # every rank that got an exception here takes the same second route: all collectives through
                 # torch.distributed (a rank that did NOT get one is stuck in a collective; the deadline ends the job)
@@ -998,7 +1019,8 @@ def main():
                 os.environ["NEM_DIST_NATIVE"] = "0"
                 wd.phase("sharded EM (%s scaling), torch collectives" % args.scaling, args.phase_timeout)
                 blocks, extra, kernels, n_loc, solo = sharded_run(args, ranks, n_tot, d, k, beta, seed, args.steps, args.warmup,
-                                                                  args.repeats, want_solo=(world > 1 and args.scaling == "strong"))
+                                                                  args.repeats, want_solo=(world > 1 and args.full and args.scaling == "strong"),
+                                                                  full=args.full)
             if fallback_reason:
                 extra["fallback_reason"] = fallback_reason
             nnz = int(2.1 * n_tot)
@@ -1020,14 +1042,15 @@ def main():
         wd.set_fallback(out)                      # from here on a phase that hangs costs its own entry only
 
     # ---- what else N GPUs can do with this path, in the same run: the strong-scaling figure of the shape where it can pay
-    if multi and world > 1 and not args.no_extras and args.scaling != "replicas":
+    if multi and world > 1 and args.full and not args.no_extras and args.scaling != "replicas":
         n3, d3 = (int(v) for v in args.extras_strong_shape.lower().split("x"))
         if (n_tot, d) != (n3, d3):
             key3 = "strong_%dx%d" % (n3, d3)
             try:
                 wd.phase(key3, args.phase_timeout)
                 st3 = 60
-                b3, f3, _, _, solo3 = sharded_run(args, ranks, n3, d3, k, beta, 2, st3, 6, min(args.repeats, 7), want_solo=True)
+                b3, f3, _, _, solo3 = sharded_run(args, ranks, n3, d3, k, beta, 2, st3, 6, min(args.repeats, 7), want_solo=True,
+                                                  full=True)
                 tf3, med3 = timing_fields(b3, st3)
                 rec = dict(value=float(n3) * d3 * st3 / med3, unit="cells/s", ms_per_step=tf3["ms_per_step"], scaling="strong",
                            families=n3, organisms=d3,
@@ -1042,7 +1065,7 @@ def main():
     wd.done()
 
     if rank == 0:
-        if not multi and not args.no_cpu_baseline:
+        if not multi and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(x, nei, k, prop, center, disp, beta, args.algo, args.disper,
                                                    args.cpu_iters)
@@ -1050,13 +1073,13 @@ def main():
             except Exception as exc:   # the checker is optional on the box; the GPU number stands on its own
                 out["cpu_baseline"] = {"value": None, "unit": "cells/s", "cores": 1, "kind": "unavailable",
                                        "sample": "failed: %r" % (exc,)}
-        if not multi and not args.no_north_star and not ksweep:
+        if not multi and args.full and not args.no_north_star and not ksweep:
             try:
                 run.eng.close()
                 out["north_star_target"] = north_star_target(args)
             except Exception as exc:
                 out["north_star_target"] = {"error": repr(exc)}
-        if not multi and not args.no_extras and not ksweep and args.algo == "ncem":
+        if not multi and args.full and not args.no_extras and not ksweep and args.algo == "ncem":
             try:
                 run.eng.close()
             except Exception:

@@ -11,23 +11,23 @@ R=r03
 mkdir -p $O
 Q="--no-cpu-baseline --no-north-star"
 # the default bench line (configs[1], CPU baseline and north-star block) and the line as the driver asks for it
-python3 bench.py > $O/${R}_bench_c2.json 2> $O/${R}_bench_c2.err
+python3 bench.py --full > $O/${R}_bench_c2.json 2> $O/${R}_bench_c2.err
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${R}_bench_c2_driver.json 2> /dev/null
 echo "[collect] bench lines done"
 # per-kernel durations: C2 (default command), C3, C4, the fuzzy path, a lock-step batch of 16
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_c2 -- python3 bench.py --steps 210 --warmup 21 --repeats 3 $Q > $O/${R}_c2_prof.json 2> $O/${R}_c2_prof.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_c3 -- python3 bench.py --families 50000 --organisms 1000 --steps 220 --warmup 22 --repeats 5 $Q > $O/${R}_c3_prof.json 2> $O/${R}_c3_prof.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_c4 -- python3 bench.py --families 200000 --organisms 5000 --steps 20 --warmup 4 --repeats 3 $Q > $O/${R}_c4_prof.json 2> $O/${R}_c4_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_c2 -- python3 bench.py --full --steps 210 --warmup 21 --repeats 3 $Q > $O/${R}_c2_prof.json 2> $O/${R}_c2_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_c3 -- python3 bench.py --full --families 50000 --organisms 1000 --steps 220 --warmup 22 --repeats 5 $Q > $O/${R}_c3_prof.json 2> $O/${R}_c3_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_c4 -- python3 bench.py --full --families 200000 --organisms 5000 --steps 20 --warmup 4 --repeats 3 $Q > $O/${R}_c4_prof.json 2> $O/${R}_c4_prof.err
 echo "[collect] kernel traces c2 c3 c4 done"; ls $O | grep -c ${R}_c
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_c2_fuzzy -- python3 bench.py --algo nem --steps 50 --warmup 5 --repeats 3 $Q > $O/${R}_c2_fuzzy_prof.json 2> $O/${R}_c2_fuzzy_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_c2_fuzzy -- python3 bench.py --full --algo nem --steps 50 --warmup 5 --repeats 3 $Q > $O/${R}_c2_fuzzy_prof.json 2> $O/${R}_c2_fuzzy_prof.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_b16 -- python3 profiles/batch_lockstep.py 20000 500 16 > $O/${R}_b16_prof.json 2> $O/${R}_b16_prof.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_dist1 -- python3 bench.py --dist --steps 220 --warmup 22 --repeats 5 --no-cpu-baseline > $O/${R}_dist1_prof.json 2> $O/${R}_dist1_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${R}_dist1 -- python3 bench.py --full --dist --steps 220 --warmup 22 --repeats 5 --no-cpu-baseline > $O/${R}_dist1_prof.json 2> $O/${R}_dist1_prof.err
 echo "[collect] kernel traces done"
 # HBM traffic counters, one counter per run: C2, C4, the lock-step batch of 16
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${R}_c2_fetch -- python3 bench.py --steps 56 --warmup 7 --repeats 3 $Q > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${R}_c2_write -- python3 bench.py --steps 56 --warmup 7 --repeats 3 $Q > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${R}_c4_fetch -- python3 bench.py --families 200000 --organisms 5000 --steps 10 --warmup 2 --repeats 2 $Q > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${R}_c4_write -- python3 bench.py --families 200000 --organisms 5000 --steps 10 --warmup 2 --repeats 2 $Q > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${R}_c2_fetch -- python3 bench.py --full --steps 56 --warmup 7 --repeats 3 $Q > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${R}_c2_write -- python3 bench.py --full --steps 56 --warmup 7 --repeats 3 $Q > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${R}_c4_fetch -- python3 bench.py --full --families 200000 --organisms 5000 --steps 10 --warmup 2 --repeats 2 $Q > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${R}_c4_write -- python3 bench.py --full --families 200000 --organisms 5000 --steps 10 --warmup 2 --repeats 2 $Q > /dev/null 2>&1
 echo "[collect] counters c2 c4 done"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${R}_b16_fetch -- python3 profiles/batch_lockstep.py 20000 500 16 > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${R}_b16_write -- python3 profiles/batch_lockstep.py 20000 500 16 > /dev/null 2>&1
@@ -35,24 +35,24 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${R}_b16_wri
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${R}_calib -- python3 -c "from pangenomenem_amd.engine import calibrate_fetch; calibrate_fetch(1 << 30, 3)" > /dev/null 2>&1
 echo "[collect] counters done"
 # unprofiled bench lines of the same build (C3, C4), the fuzzy path, free dispersion
-python3 bench.py --families 50000 --organisms 1000 --steps 1100 --warmup 110 $Q > $O/${R}_bench_50000x1000.json 2> /dev/null
-python3 bench.py --families 200000 --organisms 5000 --steps 300 --warmup 30 --repeats 9 $Q > $O/${R}_bench_200000x5000.json 2> /dev/null
-python3 bench.py --spectrum latent3 $Q > $O/${R}_bench_20000x500_latent3.json 2> /dev/null
-python3 bench.py --algo nem --steps 300 --warmup 30 --repeats 9 $Q > $O/${R}_bench_20000x500_fuzzy.json 2> /dev/null
-python3 bench.py --disper skd $Q > $O/${R}_bench_20000x500_skd.json 2> /dev/null
+python3 bench.py --full --families 50000 --organisms 1000 --steps 1100 --warmup 110 $Q > $O/${R}_bench_50000x1000.json 2> /dev/null
+python3 bench.py --full --families 200000 --organisms 5000 --steps 300 --warmup 30 --repeats 9 $Q > $O/${R}_bench_200000x5000.json 2> /dev/null
+python3 bench.py --full --spectrum latent3 $Q > $O/${R}_bench_20000x500_latent3.json 2> /dev/null
+python3 bench.py --full --algo nem --steps 300 --warmup 30 --repeats 9 $Q > $O/${R}_bench_20000x500_fuzzy.json 2> /dev/null
+python3 bench.py --full --disper skd $Q > $O/${R}_bench_20000x500_skd.json 2> /dev/null
 echo "[collect] bench variants done"
 # the multi-GPU modes on the one GPU of the box: one rank over RCCL through the sharded driver (the 1-rank ratio against
 # the single engine on the same problem), two ranks over gloo (host-staged collectives: a rehearsal of the protocol,
 # not of its speed) in the three modes
-python3 bench.py --dist --steps 1100 --warmup 110 --no-cpu-baseline > $O/${R}_dist_world1.json 2> /dev/null
-python3 bench.py --dist --families 20000 --organisms 500 --steps 700 --warmup 70 --no-cpu-baseline > $O/${R}_dist_world1_20000x500.json 2> /dev/null
-python3 bench.py --gpus 2 --backend gloo --steps 110 --warmup 11 --repeats 5 --extras-strong-shape 100000x2500 > $O/${R}_dist_2ranks_gloo_strong.json 2> /dev/null
-python3 bench.py --gpus 2 --backend gloo --scaling replicas --steps 140 --warmup 14 --repeats 5 > $O/${R}_dist_2ranks_gloo_replicas.json 2> /dev/null
-python3 bench.py --gpus 2 --backend gloo --scaling weak --steps 70 --warmup 7 --repeats 5 > $O/${R}_dist_2ranks_gloo_weak.json 2> /dev/null
+python3 bench.py --full --dist --steps 1100 --warmup 110 --no-cpu-baseline > $O/${R}_dist_world1.json 2> /dev/null
+python3 bench.py --full --dist --families 20000 --organisms 500 --steps 700 --warmup 70 --no-cpu-baseline > $O/${R}_dist_world1_20000x500.json 2> /dev/null
+python3 bench.py --full --gpus 2 --backend gloo --steps 110 --warmup 11 --repeats 5 --extras-strong-shape 100000x2500 > $O/${R}_dist_2ranks_gloo_strong.json 2> /dev/null
+python3 bench.py --full --gpus 2 --backend gloo --scaling replicas --steps 140 --warmup 14 --repeats 5 > $O/${R}_dist_2ranks_gloo_replicas.json 2> /dev/null
+python3 bench.py --full --gpus 2 --backend gloo --scaling weak --steps 70 --warmup 7 --repeats 5 > $O/${R}_dist_2ranks_gloo_weak.json 2> /dev/null
 echo "[collect] multi-GPU modes done"
 # BASELINE configs[4]: the K sweep (20 000 x 500, skd), one line per K
 rm -f $O/${R}_ksweep.jsonl
-for k in 2 3 4 5 6 7 8 9 10; do python3 bench.py --k $k --steps 200 --warmup 20 --repeats 9 $Q >> $O/${R}_ksweep.jsonl 2> /dev/null; done
+for k in 2 3 4 5 6 7 8 9 10; do python3 bench.py --full --k $k --steps 200 --warmup 20 --repeats 9 $Q >> $O/${R}_ksweep.jsonl 2> /dev/null; done
 echo "[collect] K sweep done"
 # lock-step batches, random starts, whole chunks (one device, and the device list), host-buffer-inclusive solve, the fuzzy M-step alone
 python3 profiles/batch_lockstep.py > $O/${R}_batch_lockstep.json 2> /dev/null

@@ -130,13 +130,13 @@ def test_bench_starts_its_own_ranks(gpu_lib):
     GPU of the box, host-staged gloo collectives) and prints the one JSON line; the default multi-GPU workload is
     the strong-scaling split of ONE problem."""
     rec = _bench("--gpus", "2", "--backend", "gloo", "--steps", "12", "--warmup", "3", "--families", "6000",
-                 "--organisms", "200", "--repeats", "3", "--extras-strong-shape", "9000x300")
+                 "--organisms", "200", "--repeats", "3", "--extras-strong-shape", "9000x300", "--full")
     assert rec["n_gpus"] == 2 and rec["scaling"] == "strong" and rec["steps"] == 12 and rec["warmup"] == 3
     assert rec["config"]["families_total"] == 6000 and rec["config"]["families_per_gpu"] == 3000
     assert rec["value"] > 0 and rec["iters_to_converge"] >= 1 and rec["repeats"] == 3
     assert rec["ms_per_step_min"] <= rec["ms_per_step"] <= rec["ms_per_step_max"]
-    # an N-rank line says what its collectives cost, what one GPU does with the same problem, and what else N GPUs can
-    # do with this path: independent problems (no collective) and the strong scaling of a larger problem
+    # an N-rank --full line says what its collectives cost, what one GPU does with the same problem, and what else N GPUs
+    # can do with this path: independent problems (no collective) and the strong scaling of a larger problem
     assert rec["collective"]["per_iteration"] == 2 and rec["collective"]["per_iteration_ms"] > 0
     assert rec["single_gpu_same_workload"]["ms_per_step"] > 0 and rec["speedup_vs_single_gpu_same_workload"] > 0
     also = rec["also"]

@@ -234,6 +234,36 @@ typedef struct {
 int nemgpu_solve_chunks(nemgpu_master* m, nemgpu_chunk* chunks, int count, int k, const float* prop, const float* center_k,
                         const float* disp_k, const nemgpu_config* cfg, int workers, int group);
 
+/* ---- The vote of partition()'s loop over the samples ----------------------------------------------------------
+   partition() (ppanggolin.py:1015-1105) counts, per family of the pangenome, the P/S/C/U votes of the samples' runs
+   (run_partitioning, :1886-1980: P/S/C if the class with the most non-zero centres is class 0 and the one with the
+   largest sum of dispersions class 1, else everything U; a run that emptied a class: everything U), sample after sample.
+   A family is validated by the vote that makes its total exceed len(organisms) / chunk_size with an absolute majority,
+   or exceed len(organisms) (U is forced if it then has no majority); votes after validation still count.  The loop
+   stops after the sample that validates the last family; the final class is the first largest count in the order
+   P, S, C, U.  A nemgpu_votes holds those counts on the device for one master and one selection organisms[d_sel]
+   (distinct indices into the master's organisms; the pangenome = the families with a selected organism). */
+typedef struct nemgpu_votes nemgpu_votes;
+int nemgpu_votes_create(nemgpu_votes** out, nemgpu_master* m, const int32_t* organisms, int d_sel, int chunk_size, int batch);
+void nemgpu_votes_destroy(nemgpu_votes* v);
+/* count <= batch samples solved as nemgpu_solve_chunks solves them (k = 3, NCEM; labels / out_* may be NULL) and voted
+   in order on the device, straight from the runs' labels and parameters.  *stop_index: the sample of this call after
+   which every family is validated (the samples after it are solved, not counted), or -1.  A sample that keeps no family
+   votes nothing (rc NEMGPU_OK, n = 0).  An engine error is returned and nothing of the call is counted. */
+int nemgpu_votes_solve(nemgpu_votes* v, nemgpu_chunk* chunks, int count, int k, const float* prop, const float* center_k,
+                       const float* disp_k, const nemgpu_config* cfg, int workers, int group, int* stop_index);
+/* Synthetic samples through the same vote: keep[count][ceil(n_master / 64)] (the kept families, as nemgpu_chunk.keep),
+   labels[count][n_master] (label 0 .. 2 of the sample's kept family j at j), maps[count][3] (the code, 0 .. 3, that
+   each label votes). */
+int nemgpu_votes_add_host(nemgpu_votes* v, int count, const uint64_t* keep, const uint8_t* labels, const uint8_t* maps, int* stop_index);
+/* The code map of `count` runs of k = 3 classes from their final parameters: center / disp = per sample [k][dc[s]],
+   the samples one after another; status[s] = the run's status.  maps[count][3]. */
+int nemgpu_vote_classmap_host(int count, int k, const int* dc, const float* center, const float* disp, const int* status, uint8_t* maps);
+/* cnt[n_master][4] (votes P, S, C, U), final_code[n_master] (0 .. 3; 0xFF: not in the pangenome), validated[n_master]
+   (the sample, counted over all calls, whose vote validated the family; -1: not validated), samples_voted.  Any may be
+   NULL. */
+int nemgpu_votes_result(nemgpu_votes* v, int32_t* cnt, uint8_t* final_code, int32_t* validated, int64_t* samples_voted);
+
 /* Whole run from random starts (the reference's init_mode = INIT_RANDOM, RandNemAlgo nem_alg.c:1574-1742): n_starts
    starts (the reference uses 50), centres drawn from the data with the reference's generator -- glibc random()
    after srandom(seed), restated in csrc/nem_rng.hpp -- best start by criterion M, EstimPara on the best partition.

@@ -13,8 +13,14 @@ input files from ONE graph (``__write_nem_input_files``, ppanggolin.py:821-930):
 samples in ONE library call (``nemgpu_solve_chunks``): the device forms every sample's problem straight into its engine's
 buffers, the lock-step pipeline of ``batch.solve_many`` runs them.  ``form_chunk_host`` is the same formation in numpy --
 what the tests hold the device against (through ``batch.solve_many``) and what documents the index maps.
+
+``Master.partition`` is the whole loop: the samples drawn as the reference draws them, solved ``batch`` at a time and
+voted on the device (``nemgpu_votes_solve``: validate_family, ppanggolin.py:1015-1037) until every family is validated;
+``partitioning.vote_host`` is the same vote in numpy.
 """
 import ctypes as C
+import random
+from collections import defaultdict
 
 import numpy as np
 
@@ -88,6 +94,7 @@ class Master:
         self.n, self.d = x.shape
         self.wf = (self.d + 31) // 32
         rows = pack_rows(x)
+        self._rows = rows                                     # (partition(): which families are core exact)
         ptr = np.ascontiguousarray(ptr, np.int32)
         idx = np.ascontiguousarray(idx, np.int32)
         edge_bits = np.ascontiguousarray(edge_bits, np.uint32).reshape(len(idx), self.wf) if len(idx) else np.zeros((1, self.wf), np.uint32)
@@ -109,14 +116,8 @@ class Master:
         except Exception:
             pass
 
-    def solve_chunks(self, samples, k=3, prop=(0.33333, 0.33333, None), center_k=(1.0, 0.5, 0.0), disp_k=(0.1, 0.5, 0.1),
-                     workers=8, group=32, algo="ncem", beta=0.5, disper="sk_", propor="pk", cvtest="clas", cvthres=1e-8,
-                     it_max=100, param_fix=False, tie="hash", seed=0, want_params=True):
-        """samples: sequences of organism indices (a chunk's columns, in order).  Initial parameters as PPanGGOLiN's
-        default .m (ppanggolin.py:893-901): proportions (the last one None = the float remainder ReadParamFile computes,
-        nem_exe.c:1022-1034), ONE centre and ONE dispersion per class.  Returns one dict per sample: families (master
-        index of the chunk's family j), labels (uint8 per kept family), prop / center / disp / nbobs_k, iters, status, ..."""
-        lib = self.lib
+    @staticmethod
+    def _config(k, prop, center_k, disp_k, algo, beta, disper, propor, cvtest, cvthres, it_max, param_fix, tie, seed):
         prop = list(prop)
         if prop[-1] is None:
             rem = np.float32(1.0)
@@ -128,6 +129,98 @@ class Master:
         disp_k = np.ascontiguousarray(disp_k, np.float32)
         assert len(prop) == k and len(center_k) == k and len(disp_k) == k
         cfg = Config(ALGO[algo], beta, DISP[disper], PROP[propor], CVT[cvtest], cvthres, it_max, int(param_fix), TIE[tie], seed)
+        return prop, center_k, disp_k, cfg
+
+    def partition(self, organisms=None, chunk_size=500, beta=0.5, free_dispersion=False, rng=None, batch=64, tie="libc", seed=0,
+                  max_samples=100000, names=None, just_stats=False, workers=8, group=32):
+        """PPanGGOLiN's partition() (ppanggolin.py:932-1173, algo ncem, the default .m, its sequential loop) on this master:
+        organisms = an ordered selection of the master's organisms (default: all).  More than chunk_size of them: samples
+        drawn one at a time as rng.sample(organisms, chunk_size) (rng: the `random` module by default, as the reference's
+        `from random import sample`), solved `batch` at a time (nemgpu_votes_solve) and voted on the device until every
+        family of the pangenome is validated; rng is left as the reference's loop leaves it.  Otherwise one run on
+        exactly `organisms`.  Returns (partitions, cnt, samples): {name: 'P'|'S'|'C'|'U'} for the families of the
+        pangenome in the master's order (with just_stats the reference's stats: accessory / core_exact / persistent /
+        shell / cloud / undefined counts), the votes int32 [n][4] (P, S, C, U) and the number of samples voted.
+        More than max_samples samples without an end raise NemGpuError (the reference would loop forever)."""
+        from .partitioning import CODES
+        lib = self.lib
+        _bind_votes(lib)
+        organisms = np.ascontiguousarray(np.arange(self.d) if organisms is None else organisms, np.int32)
+        d_sel = len(organisms)
+        if d_sel == 0 or len(np.unique(organisms)) != d_sel or organisms.min() < 0 or organisms.max() >= self.d:
+            raise ValueError("organisms: distinct indices of the master's organisms")
+        rng = random if rng is None else rng
+        small = d_sel <= chunk_size
+        prop, center_k, disp_k, cfg = self._config(3, (0.33333, 0.33333, None), (1.0, 0.5, 0.0), (0.1, 0.5, 0.1), "ncem", beta,
+                                                   "skd" if free_dispersion else "sk_", "pk", "clas", 1e-8, 100, False, tie, seed)
+        h = C.c_void_p()
+        rc = lib.nemgpu_votes_create(C.byref(h), self._h, organisms.ctypes.data, d_sel, int(chunk_size), 1 if small else int(batch))
+        if rc != STATUS_OK:
+            raise NemGpuError("nemgpu_votes_create failed (status %d): %s" % (rc, lib.nemgpu_last_error().decode()))
+        try:
+            cnt = np.zeros((self.n, 4), np.int32)
+            final = np.zeros(self.n, np.uint8)
+            first = np.zeros(self.n, np.int32)
+            nvoted = C.c_int64()
+            lib.nemgpu_votes_result(h, None, final.ctypes.data, None, None)
+            pan = final != 0xFF
+
+            def run(samples):
+                arr = (Chunk * len(samples))()
+                hold = [np.ascontiguousarray(smp, np.int32) for smp in samples]
+                for q, org in zip(arr, hold):
+                    q.organisms, q.dc = org.ctypes.data, len(org)
+                stop = C.c_int(-1)
+                rc = lib.nemgpu_votes_solve(h, arr, len(samples), 3, prop.ctypes.data, center_k.ctypes.data, disp_k.ctypes.data,
+                                            C.byref(cfg), int(workers), int(group), C.byref(stop))
+                if rc != STATUS_OK:
+                    raise NemGpuError("nemgpu_votes_solve failed (status %d): %s" % (rc, lib.nemgpu_last_error().decode()))
+                return stop.value
+
+            if not pan.any():
+                pass                                          # (no family: the reference's loop draws nothing)
+            elif small:
+                run([organisms])                              # (one run, its labels are the partition: ppanggolin.py:1122-1125)
+            else:
+                partition_loop(d_sel, chunk_size, rng, batch, max_samples, lambda pos: run([organisms[p] for p in pos]))
+            rc = lib.nemgpu_votes_result(h, cnt.ctypes.data, final.ctypes.data, first.ctypes.data, C.byref(nvoted))
+            if rc != STATUS_OK:
+                raise NemGpuError("nemgpu_votes_result failed (status %d): %s" % (rc, lib.nemgpu_last_error().decode()))
+        finally:
+            lib.nemgpu_votes_destroy(h)
+        names = list(names) if names is not None else ["fam%d" % (i + 1) for i in range(self.n)]
+        fam = np.flatnonzero(pan)
+        partitions = {names[i]: CODES[final[i]] for i in fam}
+        if just_stats:
+            stats = defaultdict(int)
+            core = self.core_exact(organisms)
+            stats["accessory"] = int(np.count_nonzero(pan & ~core))
+            stats["core_exact"] = int(np.count_nonzero(core))
+            long = {"P": "persistent", "S": "shell", "C": "cloud", "U": "undefined"}
+            for c in partitions.values():
+                stats[long[c]] += 1
+            return stats, cnt, int(nvoted.value)
+        return partitions, cnt, int(nvoted.value)
+
+    def core_exact(self, organisms):
+        """bool [n]: the families present in every one of `organisms` (ppanggolin.py:982-993)"""
+        mask = np.zeros(self.wf * 32, np.uint8)
+        mask[np.asarray(organisms, np.int64)] = 1
+        words = np.packbits(mask, bitorder="little").view(np.uint32)
+        ones = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1)
+        hit = ones[np.bitwise_and(self._rows, words[None, :]).view(np.uint8)].sum(axis=1)
+        return hit == len(organisms)
+
+    def solve_chunks(self, samples, k=3, prop=(0.33333, 0.33333, None), center_k=(1.0, 0.5, 0.0), disp_k=(0.1, 0.5, 0.1),
+                     workers=8, group=32, algo="ncem", beta=0.5, disper="sk_", propor="pk", cvtest="clas", cvthres=1e-8,
+                     it_max=100, param_fix=False, tie="hash", seed=0, want_params=True):
+        """samples: sequences of organism indices (a chunk's columns, in order).  Initial parameters as PPanGGOLiN's
+        default .m (ppanggolin.py:893-901): proportions (the last one None = the float remainder ReadParamFile computes,
+        nem_exe.c:1022-1034), ONE centre and ONE dispersion per class.  Returns one dict per sample: families (master
+        index of the chunk's family j), labels (uint8 per kept family), prop / center / disp / nbobs_k, iters, status, ..."""
+        lib = self.lib
+        prop, center_k, disp_k, cfg = self._config(k, prop, center_k, disp_k, algo, beta, disper, propor, cvtest, cvthres, it_max,
+                                                   param_fix, tie, seed)
         arr = (Chunk * len(samples))()
         hold, outs = [], []
         nw64 = (self.n + 63) // 64
@@ -164,3 +257,112 @@ class Master:
                     meta[f] = o[f]
             res.append(meta)
         return res
+
+
+def partition_loop(n_sel, chunk_size, rng, batch, max_samples, run_batch):
+    """partition()'s sampling loop (ppanggolin.py:1045-1086) in batches: draws up to `batch` samples, each
+    rng.sample(range(n_sel), chunk_size) (random.sample picks by position: the same positions as sampling the
+    organisms themselves), hands their positions to run_batch, which returns the index of the sample after which every
+    family is validated, or -1; repeats until it is not -1.  The draws after that sample are undone: rng ends in the
+    state the reference's loop leaves it in.  Returns the number of samples the loop counted."""
+    done = 0
+    while True:
+        if done >= max_samples:
+            raise NemGpuError("partition: no end after %d samples (max_samples)" % done)
+        states, samples = [], []
+        for _ in range(min(batch, max_samples - done)):
+            states.append(rng.getstate())
+            samples.append(rng.sample(range(n_sel), chunk_size))
+        stop = run_batch(samples)
+        if stop >= 0:
+            if stop + 1 < len(samples):
+                rng.setstate(states[stop + 1])
+            return done + stop + 1
+        done += len(samples)
+
+
+def _bind_votes(lib):
+    if getattr(lib, "_votes_bound", False):
+        return
+    lib.nemgpu_votes_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib.nemgpu_votes_destroy.argtypes = [C.c_void_p]
+    lib.nemgpu_votes_destroy.restype = None
+    lib.nemgpu_votes_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(Config), C.c_int, C.c_int, C.POINTER(C.c_int)]
+    lib.nemgpu_votes_add_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    lib.nemgpu_vote_classmap_host.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.nemgpu_votes_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib._votes_bound = True
+
+
+class Votes:
+    """A nemgpu_votes of a Master, driven with synthetic samples (nemgpu_votes_add_host): the vote rule on the device
+    without the runs."""
+
+    def __init__(self, master, organisms, chunk_size, batch):
+        self.lib = master.lib
+        _bind_votes(self.lib)
+        self.n = master.n
+        org = np.ascontiguousarray(organisms, np.int32)
+        self._h = C.c_void_p()
+        rc = self.lib.nemgpu_votes_create(C.byref(self._h), master._h, org.ctypes.data, len(org), int(chunk_size), int(batch))
+        if rc != STATUS_OK:
+            raise NemGpuError("nemgpu_votes_create failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+
+    def add(self, samples):
+        """samples: (families, labels, codes) as partitioning.vote_host takes them.  Returns the stop index or -1."""
+        nw64 = (self.n + 63) // 64
+        cnt = len(samples)
+        keep = np.zeros((cnt, nw64 * 64), np.uint8)
+        lab = np.zeros((cnt, self.n), np.uint8)
+        maps = np.zeros((cnt, 3), np.uint8)
+        for s, (fam, l, codes) in enumerate(samples):
+            fam = np.asarray(fam, np.int64)
+            order = np.argsort(fam, kind="stable")
+            keep[s, fam] = 1
+            lab[s, :len(fam)] = np.asarray(l, np.uint8)[order]
+            maps[s] = codes
+        keep = np.packbits(keep, axis=1, bitorder="little").view(np.uint64)
+        stop = C.c_int(-1)
+        rc = self.lib.nemgpu_votes_add_host(self._h, cnt, keep.ctypes.data, lab.ctypes.data, maps.ctypes.data, C.byref(stop))
+        if rc != STATUS_OK:
+            raise NemGpuError("nemgpu_votes_add_host failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+        return stop.value
+
+    def result(self):
+        cnt = np.zeros((self.n, 4), np.int32)
+        final = np.zeros(self.n, np.uint8)
+        first = np.zeros(self.n, np.int32)
+        nv = C.c_int64()
+        rc = self.lib.nemgpu_votes_result(self._h, cnt.ctypes.data, final.ctypes.data, first.ctypes.data, C.byref(nv))
+        if rc != STATUS_OK:
+            raise NemGpuError("nemgpu_votes_result failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+        return dict(cnt=cnt, final=final, first=first, samples=int(nv.value))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.nemgpu_votes_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def vote_classmap_device(status, centers, disps):
+    """nemgpu_vote_classmap_host: the code map (uint8 [count][3]) of runs with these statuses and final parameters
+    (each [3][dc])."""
+    lib = load_library()
+    _bind_votes(lib)
+    cnt = len(status)
+    dc = np.ascontiguousarray([np.asarray(c).shape[1] for c in centers], np.int32)
+    cen = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).ravel() for c in centers]), np.float32)
+    dis = np.ascontiguousarray(np.concatenate([np.asarray(e, np.float32).ravel() for e in disps]), np.float32)
+    st = np.ascontiguousarray(status, np.int32)
+    maps = np.zeros((cnt, 3), np.uint8)
+    rc = lib.nemgpu_vote_classmap_host(cnt, 3, dc.ctypes.data, cen.ctypes.data, dis.ctypes.data, st.ctypes.data, maps.ctypes.data)
+    if rc != STATUS_OK:
+        raise NemGpuError("nemgpu_vote_classmap_host failed (status %d): %s" % (rc, lib.nemgpu_last_error().decode()))
+    return maps

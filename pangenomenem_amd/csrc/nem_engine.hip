@@ -33,6 +33,7 @@
 #include "nem_rng.hpp"
 #include "nem_kernels.hpp"
 #include "nem_chunks.hpp"
+#include "nem_vote.hpp"
 
 using namespace nemk;
 
@@ -293,6 +294,25 @@ struct ChunkSource {
     const nemk::ChunkPlan* plans = nullptr;           // host copies (device pointers inside), one per problem
     const int* nnz = nullptr;                         // directed edges of each chunk's graph
     uint8_t* const* labels = nullptr;                 // per problem: where the NCEM labels go (or null)
+    nemgpu_votes* votes = nullptr;                    // (nemgpu_votes_solve) every group's runs voted on the device ...
+    const int* slot = nullptr;                        // ... problem i into row slot[i] of the vote matrix
+};
+// The vote over the samples of partition()'s loop for one master and one organism selection (nem_vote.hpp): the
+// counts stay on the device, a batch of samples goes through a vote matrix of `batch` rows.
+struct nemgpu_votes {
+    const nemgpu_master* master = nullptr;
+    int device = 0, n = 0, d_sel = 0, chunk_size = 0, batch = 0;
+    double quotient = 0.0;                            // len(organisms) / chunk_size, as Python divides
+    int64_t samples_voted = 0;
+    bool done = false;                                // every family of the pangenome validated
+    hipStream_t stream = nullptr;
+    char* block = nullptr;                            // cnt | st | first | V | maps | desc | words
+    nemk::VoteState state{};
+    uint8_t* V = nullptr;
+    uint8_t* maps = nullptr;
+    nemk::VoteDesc* desc = nullptr;
+    int* words = nullptr;
+    int* words_host = nullptr;                        // (pinned)
 };
 
 namespace {
@@ -3254,6 +3274,8 @@ static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, ne
 // the engines while later groups are being built.  What PPanGGOLiN's chunk loop is when its chunks are arrays.
 static int solve_many_one(nemgpu_problem* P, int count, const nemgpu_config* cfg, int device, int workers, int group, const ChunkSource* src = nullptr);
 static int adopt_chunk(nemgpu_engine* e, const nemgpu_master* M, const nemk::ChunkPlan& plan, int nnz_c);
+static int vote_group(nemgpu_votes* v, const std::vector<nemgpu_engine*>& E, const std::vector<int>& who,
+                      const std::vector<nemgpu_result>& R, const ChunkSource* src);
 static thread_local bool tl_runner = false;                  // this thread is one of nemgpu_solve_many_devices' runners
 
 // Four groups and more, six workers and more: two runners on the device (nemgpu_solve_many_devices with the device named
@@ -3450,6 +3472,8 @@ static int solve_many_one(nemgpu_problem* P, int count, const nemgpu_config* cfg
                     for (size_t j = 0; j < E.size(); j++) gslot[(size_t)who[j]] = (int)j;
                 } else if (gf.host) pool_put(device, true, gf.host, host_size);
             }
+            // the group's votes, read from the engines' own label and parameter buffers before the fetches recycle them
+            if (r == NEMGPU_OK && src != nullptr && src->votes != nullptr) r = vote_group(src->votes, E, who, R, src);
             t_run += since(t0);
             for (size_t j = 0; j < E.size(); j++) { P[who[j]].result = R[j]; if (r != NEMGPU_OK) P[who[j]].rc = r; }
             if (r != NEMGPU_OK && rc == NEMGPU_OK) { rc = r; first_err = g_last_error; }
@@ -3593,8 +3617,10 @@ static int adopt_chunk(nemgpu_engine* e, const nemgpu_master* M, const nemk::Chu
     return NEMGPU_OK;
 }
 
-int nemgpu_solve_chunks(nemgpu_master* M, nemgpu_chunk* chunks, int count, int k, const float* prop, const float* center_k,
-                        const float* disp_k, const nemgpu_config* cfg, int workers, int group)
+// nemgpu_solve_chunks; with `votes`, every run is also voted (vote_group) and a sample that keeps no family is skipped
+// (the reference writes empty files for it and gets no .uf) instead of refused
+static int solve_chunks_impl(nemgpu_master* M, nemgpu_chunk* chunks, int count, int k, const float* prop, const float* center_k,
+                             const float* disp_k, const nemgpu_config* cfg, int workers, int group, nemgpu_votes* votes)
 {
     if (!M || !chunks || count <= 0 || k <= 0 || k > kMaxKernelK || !prop || !center_k || !disp_k || !cfg) return NEMGPU_E_FUNCARG;
     HIPCHK(hipSetDevice(M->device));
@@ -3659,16 +3685,21 @@ int nemgpu_solve_chunks(nemgpu_master* M, nemgpu_chunk* chunks, int count, int k
         for (int c = 0; c < count; c++) if (chunks[c].keep) memcpy(chunks[c].keep, keeps.data() + b_keep * (size_t)c, (size_t)nw64 * 8);
     const auto t_plan = std::chrono::steady_clock::now();
     // ---- the problems: sizes from phase 1, PPanGGOLiN-style initial parameters (one value per class and kind)
-    std::vector<nemgpu_problem> P((size_t)count);
-    std::vector<int> nnzc((size_t)count);
-    std::vector<uint8_t*> labels((size_t)count, nullptr);
+    std::vector<nemgpu_problem> P;
+    std::vector<nemk::ChunkPlan> pplans;
+    std::vector<int> nnzc, slot;                              // (per problem: the chunk it solves)
+    std::vector<uint8_t*> labels;
+    P.reserve((size_t)count); pplans.reserve((size_t)count); nnzc.reserve((size_t)count); slot.reserve((size_t)count); labels.reserve((size_t)count);
     std::map<int, std::vector<float>> init;                   // sample size -> prop | center | disp
     for (int c = 0; c < count; c++) {
         nemgpu_chunk& q = chunks[c];
         q.n = counts[(size_t)c * 2]; q.nnz = counts[(size_t)c * 2 + 1];
+        if (q.n <= 0 && votes != nullptr) continue;
         if (q.n <= 0) { set_error("nemgpu_solve_chunks: chunk " + std::to_string(c) + " holds no family"); q.rc = NEMGPU_E_ARG; return NEMGPU_E_ARG; }
-        nnzc[(size_t)c] = q.nnz;
-        labels[(size_t)c] = q.labels;
+        pplans.push_back(plans[(size_t)c]);
+        nnzc.push_back(q.nnz);
+        slot.push_back(c);
+        labels.push_back(q.labels);
         std::vector<float>& v = init[q.dc];
         if (v.empty()) {
             v.resize((size_t)k + 2 * (size_t)k * q.dc);
@@ -3677,23 +3708,263 @@ int nemgpu_solve_chunks(nemgpu_master* M, nemgpu_chunk* chunks, int count, int k
                 for (int o = 0; o < q.dc; o++) { v[(size_t)k + (size_t)h * q.dc + o] = center_k[h]; v[(size_t)k + (size_t)k * q.dc + (size_t)h * q.dc + o] = disp_k[h]; }
             }
         }
-        nemgpu_problem& p = P[(size_t)c];
-        p = nemgpu_problem{};
+        P.emplace_back();
+        nemgpu_problem& p = P.back();
         p.n = q.n; p.d = q.dc; p.k = k;
         p.prop = v.data(); p.center = v.data() + k; p.disp = v.data() + k + (size_t)k * q.dc;
         p.out_prop = q.out_prop; p.out_center = q.out_center; p.out_disp = q.out_disp; p.out_nbobs_k = q.out_nbobs_k; p.out_c = nullptr;
     }
     ChunkSource src;
-    src.master = M; src.plans = plans.data(); src.nnz = nnzc.data(); src.labels = labels.data();
+    src.master = M; src.plans = pplans.data(); src.nnz = nnzc.data(); src.labels = labels.data();
+    src.votes = votes; src.slot = slot.data();
     const auto t_prep = std::chrono::steady_clock::now();
-    const int rc = solve_many_one(P.data(), count, cfg, M->device, workers, group, &src);
-    for (int c = 0; c < count; c++) { chunks[c].rc = P[(size_t)c].rc; chunks[c].result = P[(size_t)c].result; }
+    const int np = (int)P.size();
+    const int rc = np > 0 ? solve_many_one(P.data(), np, cfg, M->device, workers, group, &src) : NEMGPU_OK;
+    for (int i = 0; i < np; i++) { chunks[slot[(size_t)i]].rc = P[(size_t)i].rc; chunks[slot[(size_t)i]].result = P[(size_t)i].result; }
     if (prof) {
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         fprintf(stderr, "[solve_chunks] %d chunks: plans (which families, which edges; one wait) %.2f ms, problem records %.2f ms, pipeline %.2f ms\n",
                 count, ms(t_begin, t_plan), ms(t_plan, t_prep), ms(t_prep, std::chrono::steady_clock::now()));
     }
     return rc;
+}
+
+int nemgpu_solve_chunks(nemgpu_master* M, nemgpu_chunk* chunks, int count, int k, const float* prop, const float* center_k,
+                        const float* disp_k, const nemgpu_config* cfg, int workers, int group)
+{
+    return solve_chunks_impl(M, chunks, count, k, prop, center_k, disp_k, cfg, workers, group, nullptr);
+}
+
+// ============================================================================================
+// The vote of partition()'s loop over the samples (validate_family, ppanggolin.py:1015-1037, and the loop around it,
+// :1045-1105) on the device: nem_vote.hpp / nem_vote.hip.
+// ============================================================================================
+int nemgpu_votes_create(nemgpu_votes** out, nemgpu_master* M, const int32_t* organisms, int d_sel, int chunk_size, int batch)
+{
+    if (!out) return NEMGPU_E_FUNCARG;
+    *out = nullptr;
+    if (!M || !organisms || d_sel <= 0 || chunk_size <= 0 || batch <= 0) { set_error("nemgpu_votes_create: a master, organisms, chunk size and batch are needed"); return NEMGPU_E_FUNCARG; }
+    if (d_sel > M->d || batch > 4096) { set_error("nemgpu_votes_create: more organisms than the master's, or a batch above 4096"); return NEMGPU_E_ARG; }
+    std::vector<uint8_t> seen((size_t)M->d, 0);
+    for (int t = 0; t < d_sel; t++) {
+        const int o = organisms[t];
+        if (o < 0 || o >= M->d || seen[(size_t)o]) { set_error("nemgpu_votes_create: organism index out of range or repeated"); return NEMGPU_E_ARG; }
+        seen[(size_t)o] = 1;
+    }
+    HIPCHK(hipSetDevice(M->device));
+    const int n = M->n;
+    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t b_cnt = a256((size_t)n * 16), b_st = a256((size_t)n), b_first = a256((size_t)n * 4), b_V = a256((size_t)batch * n),
+                 b_maps = a256((size_t)batch * nemk::kVoteMapStride), b_desc = a256((size_t)batch * sizeof(nemk::VoteDesc)), b_words = 256,
+                 b_sel = a256((size_t)d_sel * 4);
+    nemgpu_votes* v = new nemgpu_votes();
+    v->master = M; v->device = M->device; v->n = n; v->d_sel = d_sel; v->chunk_size = chunk_size; v->batch = batch;
+    v->quotient = (double)d_sel / (double)chunk_size;
+    auto fail = [&](const char* what) { nemgpu_votes_destroy(v); set_error(what); return NEMGPU_E_DEVICE; };
+    if (hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate failed");
+    if (hipMalloc(&v->block, b_cnt + b_st + b_first + b_V + b_maps + b_desc + b_words + b_sel) != hipSuccess) return fail("nemgpu_votes_create: device memory");
+    if (hipHostMalloc((void**)&v->words_host, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess) { v->words_host = nullptr; return fail("nemgpu_votes_create: pinned memory"); }
+    char* b = v->block;
+    v->state.n = n;
+    v->state.cnt = (int32_t*)b; b += b_cnt;
+    v->state.st = (uint8_t*)b; b += b_st;
+    v->state.first = (int32_t*)b; b += b_first;
+    v->V = (uint8_t*)b; b += b_V;
+    v->maps = (uint8_t*)b; b += b_maps;
+    v->desc = (nemk::VoteDesc*)b; b += b_desc;
+    v->words = (int*)b; b += b_words;
+    int* sel = (int*)b;
+    hipError_t err = hipMemcpyAsync(sel, organisms, (size_t)d_sel * 4, hipMemcpyHostToDevice, v->stream);
+    if (err == hipSuccess) { nemk::launch_vote_init(v->state, M->dev.xt, M->nw64, sel, d_sel, v->stream); err = hipGetLastError(); }
+    if (err == hipSuccess) err = hipStreamSynchronize(v->stream);
+    if (err != hipSuccess) return fail("nemgpu_votes_create: initialisation failed");
+    *out = v;
+    return NEMGPU_OK;
+}
+
+void nemgpu_votes_destroy(nemgpu_votes* v)
+{
+    if (!v) return;
+    (void)hipSetDevice(v->device);
+    if (v->stream) { (void)hipStreamSynchronize(v->stream); (void)hipStreamDestroy(v->stream); }
+    if (v->block) (void)hipFree(v->block);
+    if (v->words_host) (void)hipHostFree(v->words_host);
+    delete v;
+}
+
+// one group of nemgpu_solve_many's pipeline, run and waited for: every member's code map from its final parameters and
+// its labels into its row of the vote matrix, straight from the engine's buffers (labels and parameters stay on the device)
+static int vote_group(nemgpu_votes* v, const std::vector<nemgpu_engine*>& E, const std::vector<int>& who,
+                      const std::vector<nemgpu_result>& R, const ChunkSource* src)
+{
+    const int B = (int)E.size();
+    if (B > v->batch) { set_error("vote: a group larger than the vote batch"); return NEMGPU_E_INTERNAL; }
+    std::vector<nemk::VoteDesc> d((size_t)B);
+    int max_n = 0;
+    for (int j = 0; j < B; j++) {
+        const nemgpu_engine* e = E[(size_t)j];
+        if (!e->ncem() || e->k != 3) { set_error("vote: NCEM runs of three classes are voted"); return NEMGPU_E_ARG; }
+        const int i = who[(size_t)j];
+        d[(size_t)j] = nemk::VoteDesc{e->lab[e->cur] + e->lo, src->plans[i].list, e->prop + e->par_o_center, e->prop + e->par_o_disp,
+                                      e->n, e->d, R[(size_t)j].status, src->slot[i]};
+        max_n = std::max(max_n, e->n);
+    }
+    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipMemcpyAsync(v->desc, d.data(), (size_t)B * sizeof(nemk::VoteDesc), hipMemcpyHostToDevice, v->stream));
+    nemk::launch_vote_classmap(v->desc, B, 3, v->maps, v->stream);
+    nemk::launch_vote_scatter(v->desc, B, max_n, v->maps, v->V, v->n, v->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(v->stream));          // (the engines go to the fetches next, and d goes out of scope)
+    return NEMGPU_OK;
+}
+
+// the batch's `count` rows of V into the counts; *stop_index = the row after which every family is validated, or -1
+static int vote_commit_batch(nemgpu_votes* v, int count, int* stop_index)
+{
+    HIPCHK(hipMemsetAsync(v->words, 0, 2 * sizeof(int), v->stream));
+    nemk::launch_vote_scan(v->state, v->V, count, v->quotient, v->d_sel, v->samples_voted, v->words, v->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(v->words_host, v->words, 2 * sizeof(int), hipMemcpyDeviceToHost, v->stream));
+    HIPCHK(hipStreamSynchronize(v->stream));
+    int stop = -1;
+    if (v->words_host[0] == 0) { stop = v->words_host[1] - 1; v->done = true; }
+    v->samples_voted += stop >= 0 ? stop + 1 : (v->done ? 0 : count);
+    if (stop_index) *stop_index = stop;
+    return NEMGPU_OK;
+}
+
+static int votes_begin(nemgpu_votes* v, int count, const char* who)
+{
+    if (count <= 0 || count > v->batch) { set_error(std::string(who) + ": 1 .. batch samples per call"); return NEMGPU_E_ARG; }
+    if (v->done) { set_error(std::string(who) + ": every family is validated already"); return NEMGPU_E_ARG; }
+    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipMemsetAsync(v->V, nemk::kVoteNone, (size_t)count * v->n, v->stream));
+    return NEMGPU_OK;
+}
+
+int nemgpu_votes_solve(nemgpu_votes* v, nemgpu_chunk* chunks, int count, int k, const float* prop, const float* center_k,
+                       const float* disp_k, const nemgpu_config* cfg, int workers, int group, int* stop_index)
+{
+    if (stop_index) *stop_index = -1;
+    if (!v || !chunks || !cfg) return NEMGPU_E_FUNCARG;
+    if (k != 3 || cfg->algo != NEMGPU_ALGO_NCEM) { set_error("nemgpu_votes_solve: the vote takes NCEM runs of three classes"); return NEMGPU_E_ARG; }
+    int r = votes_begin(v, count, "nemgpu_votes_solve");
+    if (r != NEMGPU_OK) return r;
+    r = solve_chunks_impl(const_cast<nemgpu_master*>(v->master), chunks, count, k, prop, center_k, disp_k, cfg, workers, group, v);
+    if (r != NEMGPU_OK) return r;
+    return vote_commit_batch(v, count, stop_index);
+}
+
+int nemgpu_votes_add_host(nemgpu_votes* v, int count, const uint64_t* keep, const uint8_t* labels, const uint8_t* maps, int* stop_index)
+{
+    if (stop_index) *stop_index = -1;
+    if (!v || !keep || !labels || !maps) return NEMGPU_E_FUNCARG;
+    const int n = v->n, nw64 = (n + 63) / 64;
+    for (int s = 0; s < count; s++)
+        for (int c = 0; c < 3; c++) if (maps[(size_t)s * 3 + c] > 3) { set_error("nemgpu_votes_add_host: codes are 0 .. 3"); return NEMGPU_E_ARG; }
+    int r = votes_begin(v, count, "nemgpu_votes_add_host");
+    if (r != NEMGPU_OK) return r;
+    // the samples as the pipeline leaves them on the device: per sample its kept families' master indices and labels
+    std::vector<int> list((size_t)count * n);
+    std::vector<uint8_t> lab((size_t)count * n), map4((size_t)count * nemk::kVoteMapStride);
+    std::vector<int> nk((size_t)count, 0);
+    for (int s = 0; s < count; s++) {
+        int j = 0;
+        for (int f = 0; f < n; f++) {
+            if (!((keep[(size_t)s * nw64 + (f >> 6)] >> (f & 63)) & 1ull)) continue;
+            const uint8_t l = labels[(size_t)s * n + j];
+            if (l > 2) { set_error("nemgpu_votes_add_host: labels are 0 .. 2"); return NEMGPU_E_ARG; }
+            list[(size_t)s * n + j] = f; lab[(size_t)s * n + j] = l; j++;
+        }
+        nk[(size_t)s] = j;
+        for (int c = 0; c < nemk::kVoteMapStride; c++) map4[(size_t)s * nemk::kVoteMapStride + c] = c < 3 ? maps[(size_t)s * 3 + c] : 3;
+    }
+    char* tmp = nullptr;
+    const size_t b_list = (size_t)count * n * 4;
+    HIPCHK(hipMalloc(&tmp, b_list + (size_t)count * n));
+    struct TmpFree { char* p; ~TmpFree() { (void)hipFree(p); } } tmp_free{tmp};
+    std::vector<nemk::VoteDesc> d((size_t)count);
+    int max_n = 0;
+    for (int s = 0; s < count; s++) {
+        d[(size_t)s] = nemk::VoteDesc{(const uint8_t*)(tmp + b_list) + (size_t)s * n, (const int*)tmp + (size_t)s * n, nullptr, nullptr,
+                                      nk[(size_t)s], 0, 0, s};
+        max_n = std::max(max_n, nk[(size_t)s]);
+    }
+    HIPCHK(hipMemcpyAsync(tmp, list.data(), b_list, hipMemcpyHostToDevice, v->stream));
+    HIPCHK(hipMemcpyAsync(tmp + b_list, lab.data(), (size_t)count * n, hipMemcpyHostToDevice, v->stream));
+    HIPCHK(hipMemcpyAsync(v->maps, map4.data(), map4.size(), hipMemcpyHostToDevice, v->stream));
+    HIPCHK(hipMemcpyAsync(v->desc, d.data(), (size_t)count * sizeof(nemk::VoteDesc), hipMemcpyHostToDevice, v->stream));
+    nemk::launch_vote_scatter(v->desc, count, max_n, v->maps, v->V, n, v->stream);
+    HIPCHK(hipGetLastError());
+    r = vote_commit_batch(v, count, stop_index);      // (waits for the stream: the host arrays outlive their copies)
+    return r;
+}
+
+int nemgpu_vote_classmap_host(int count, int k, const int* dc, const float* center, const float* disp, const int* status, uint8_t* maps)
+{
+    if (count <= 0 || !dc || !center || !disp || !status || !maps) return NEMGPU_E_FUNCARG;
+    if (k != 3) { set_error("nemgpu_vote_classmap_host: the class map is PPanGGOLiN's, for three classes"); return NEMGPU_E_ARG; }
+    size_t total = 0;
+    for (int s = 0; s < count; s++) {
+        if (dc[s] <= 0) { set_error("nemgpu_vote_classmap_host: a sample has organisms"); return NEMGPU_E_ARG; }
+        total += (size_t)k * dc[s];
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no usable HIP device: this library has no CPU fallback"); return NEMGPU_E_DEVICE; }
+    g_hip_used.store(true);
+    hipStream_t st = nullptr;
+    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    struct StreamFree { hipStream_t s; ~StreamFree() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } st_free{st};
+    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t b_par = a256(total * 4), b_desc = a256((size_t)count * sizeof(nemk::VoteDesc));
+    char* tmp = nullptr;
+    HIPCHK(hipMalloc(&tmp, 2 * b_par + b_desc + (size_t)count * nemk::kVoteMapStride));
+    struct TmpFree { hipStream_t s; char* p; ~TmpFree() { (void)hipStreamSynchronize(s); (void)hipFree(p); } } tmp_free{st, tmp};
+    float* dcen = (float*)tmp;
+    float* ddis = (float*)(tmp + b_par);
+    nemk::VoteDesc* ddesc = (nemk::VoteDesc*)(tmp + 2 * b_par);
+    uint8_t* dmaps = (uint8_t*)(tmp + 2 * b_par + b_desc);
+    std::vector<nemk::VoteDesc> d((size_t)count);
+    size_t off = 0;
+    for (int s = 0; s < count; s++) {
+        d[(size_t)s] = nemk::VoteDesc{nullptr, nullptr, dcen + off, ddis + off, 0, dc[s], status[s], s};
+        off += (size_t)k * dc[s];
+    }
+    std::vector<uint8_t> m4((size_t)count * nemk::kVoteMapStride);
+    HIPCHK(hipMemcpyAsync(dcen, center, total * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ddis, disp, total * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ddesc, d.data(), (size_t)count * sizeof(nemk::VoteDesc), hipMemcpyHostToDevice, st));
+    nemk::launch_vote_classmap(ddesc, count, k, dmaps, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(m4.data(), dmaps, m4.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s = 0; s < count; s++)
+        for (int c = 0; c < 3; c++) maps[(size_t)s * 3 + c] = m4[(size_t)s * nemk::kVoteMapStride + c];
+    return NEMGPU_OK;
+}
+
+int nemgpu_votes_result(nemgpu_votes* v, int32_t* cnt, uint8_t* final_code, int32_t* validated, int64_t* samples_voted)
+{
+    if (!v) return NEMGPU_E_FUNCARG;
+    const int n = v->n;
+    std::vector<int32_t> c((size_t)n * 4), first((size_t)n);
+    std::vector<uint8_t> st((size_t)n);
+    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipMemcpyAsync(c.data(), v->state.cnt, c.size() * 4, hipMemcpyDeviceToHost, v->stream));
+    HIPCHK(hipMemcpyAsync(st.data(), v->state.st, st.size(), hipMemcpyDeviceToHost, v->stream));
+    HIPCHK(hipMemcpyAsync(first.data(), v->state.first, first.size() * 4, hipMemcpyDeviceToHost, v->stream));
+    HIPCHK(hipStreamSynchronize(v->stream));
+    if (cnt) memcpy(cnt, c.data(), c.size() * 4);
+    if (validated) memcpy(validated, first.data(), first.size() * 4);
+    if (final_code)
+        for (int f = 0; f < n; f++) {
+            // max(cnt, key=cnt.get) in the order P, S, C, U (ppanggolin.py:1104-1105); a forced U is sys.maxsize votes
+            uint8_t best = 0;
+            for (uint8_t k = 1; k < 4; k++) if (c[(size_t)f * 4 + k] > c[(size_t)f * 4 + best]) best = k;
+            final_code[f] = !(st[(size_t)f] & nemk::VOTE_IN_PAN) ? nemk::kVoteNone : (st[(size_t)f] & nemk::VOTE_FORCED_U) ? 3 : best;
+        }
+    if (samples_voted) *samples_voted = v->samples_voted;
+    return NEMGPU_OK;
 }
 
 // Which device solves which problem when nemgpu_solve_many_devices deals the lock-step groups: group g (problems

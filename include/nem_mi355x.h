@@ -201,14 +201,28 @@ int nemgpu_deal_groups(int count, int group, int n_devices, int* slot_of_problem
    organisms (ppanggolin.py:1045-1086: `orgs = sample(organisms, chunck_size)`), and writes every sample's input files
    from ONE graph (__write_nem_input_files, ppanggolin.py:821-930): columns = the sampled organisms in sample order
    (:850); families without a sampled organism dropped, the others numbered in the graph's order (:849-852); an edge's
-   weight = the number of sampled organisms that carry the adjacency, an edge none carries dropped (:866-878), a
-   family's neighbours in the order the master lists them.  nemgpu_master_create puts that ONE pangenome on the device:
-   the presence/absence bit rows xbits[n][ceil(d/32)] (family-major, bit o of a row = organism o), the graph in CSR
-   (nei_ptr[n + 1], nei_idx[nnz]) and, per directed edge, the bit set of the organisms that carry it
-   (edge_bits[nnz][ceil(d/32)]).  HOST memory, copied once. */
+   weight = its coverage, the SUM over the sampled organisms of the adjacency's occurrence count in that organism
+   (graph[a][b][org], which __add_link increments, :451; for a directed graph sens + antisens, graph[a][b][org] +
+   graph[b][a][org]), an edge of coverage 0 dropped (:866-878), a family's neighbours in the order the master lists them.
+   nemgpu_master_create puts that ONE pangenome on the device: the presence/absence bit rows xbits[n][ceil(d/32)]
+   (family-major, bit o of a row = organism o), the graph in CSR (nei_ptr[n + 1], nei_idx[nnz]) and, per directed edge,
+   the bit set of the organisms that carry it (edge_bits[nnz][ceil(d/32)], count >= 1).  Such a bits-only master takes
+   every count as 1: its weights are the reference's only where no adjacency occurs twice in an organism (no tandem
+   duplicate, no repeated operon, no directed graph).  HOST memory, copied once. */
 typedef struct nemgpu_master nemgpu_master;
 int nemgpu_master_create(nemgpu_master** out, int device, int n, int d, const uint32_t* xbits, const int32_t* nei_ptr,
                          const int32_t* nei_idx, const uint32_t* edge_bits);
+/* The same with the counts: count[e][o] = what the reference sums for (family i, neighbour nei_idx[e]) in organism o,
+   whose presence bit edge_bits holds (count >= 1).  Only the pairs with count >= 2 are listed, in CSR over the directed
+   edges: extra_ptr[nnz + 1] (from 0, non-decreasing), extra_org[extra_ptr[nnz]] (per edge strictly increasing, in
+   [0, d), set in that edge's edge_bits), extra_count[extra_ptr[nnz]] (>= 2).  The coverage of edge e in a sample =
+   popc(edge_bits[e] & sample) + the sum of (count - 1) over e's listed organisms in the sample.  An edge's total count
+   over all organisms may not exceed 2^24 (its weight stays exact in float).  Every argument is checked on the host
+   before any HIP call (NEMGPU_E_ARG, nemgpu_last_error says why).  extra_ptr NULL, or no pair listed: exactly
+   nemgpu_master_create. */
+int nemgpu_master_create_counts(nemgpu_master** out, int device, int n, int d, const uint32_t* xbits, const int32_t* nei_ptr,
+                                const int32_t* nei_idx, const uint32_t* edge_bits, const int32_t* extra_ptr,
+                                const int32_t* extra_org, const int32_t* extra_count);
 void nemgpu_master_destroy(nemgpu_master* m);
 /* One sample.  in: organisms[dc] (indices into the master's, the chunk's column order).  out: n = families with at least
    one sampled organism, nnz = directed edges of the chunk's graph; optional arrays (NULL: not wanted): keep[ceil(n_master

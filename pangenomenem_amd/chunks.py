@@ -6,10 +6,18 @@ input files from ONE graph (``__write_nem_input_files``, ppanggolin.py:821-930):
 
   * the matrix columns are the sampled organisms, in sample order (:850);
   * a family with no sampled organism is dropped, the others are numbered in the graph's order (:849-852);
-  * an edge's weight is the number of sampled organisms that carry the adjacency (``coverage``, :866-878), an edge none
-    of them carries is dropped; a family's neighbours keep the order the master lists them in.
+  * an edge's weight is its ``coverage`` (:866-878): the sum over the sampled organisms of the adjacency's occurrence
+    count in that organism (``graph[a][b][org]``, which ``__add_link`` increments, :451), sens + antisens
+    (``graph[a][b][org] + graph[b][a][org]``) when the graph is directed; an edge of coverage 0 is dropped; a family's
+    neighbours keep the order the master lists them in.
 
-``Master`` puts that one pangenome on the device (``nemgpu_master_create``); ``solve_chunks`` solves any number of
+A master carries, per directed edge, the bit set of the organisms with count >= 1 (``edge_bits``) and, optionally,
+``edge_counts = (extra_ptr, extra_org, extra_count)``: the (edge, organism) pairs whose count is 2 or more, in CSR over
+the edges.  A bits-only master takes every count as 1, which is the reference's weight only where no adjacency occurs
+twice in an organism (tandem duplicates, repeated operons and every edge of a directed graph do).
+``master_arrays_from_graph`` / ``Master.from_graph`` take PPanGGOLiN's graph as it is and make the counts.
+
+``Master`` puts that one pangenome on the device (``nemgpu_master_create[_counts]``); ``solve_chunks`` solves any number of
 samples in ONE library call (``nemgpu_solve_chunks``): the device forms every sample's problem straight into its engine's
 buffers, the lock-step pipeline of ``batch.solve_many`` runs them.  ``form_chunk_host`` is the same formation in numpy --
 what the tests hold the device against (through ``batch.solve_many``) and what documents the index maps.
@@ -46,11 +54,13 @@ def pack_rows(x):
     return rows.view(np.uint32)
 
 
-def form_chunk_host(x, ptr, idx, edge_bits, organisms):
+def form_chunk_host(x, ptr, idx, edge_bits, organisms, edge_counts=None):
     """One sample's NEM problem the way __write_nem_input_files makes it (ppanggolin.py:821-930), in numpy.
     x: uint8 [n][d]; (ptr, idx): the master graph in CSR; edge_bits: uint32 [nnz][ceil(d/32)], the organisms that carry
-    each directed edge; organisms: the sample (column order).  Returns (x_chunk uint8 [n_c][d_c], (ptr_c, idx_c, w_c),
-    families int64 [n_c]: the master index of the chunk's family j)."""
+    each directed edge (count >= 1); edge_counts: None (every count 1) or (extra_ptr, extra_org, extra_count), the
+    pairs with count >= 2 (nemgpu_master_create_counts); organisms: the sample (column order).  An edge's weight is the
+    sum of its counts over the sample.  Returns (x_chunk uint8 [n_c][d_c], (ptr_c, idx_c, w_c), families int64 [n_c]:
+    the master index of the chunk's family j)."""
     x = np.asarray(x, np.uint8)
     organisms = np.asarray(organisms, np.int64)
     n, d = x.shape
@@ -67,6 +77,10 @@ def form_chunk_host(x, ptr, idx, edge_bits, organisms):
     if nnz:
         anded = np.bitwise_and(np.asarray(edge_bits, np.uint32), mask_words[None, :])
         cov = np.unpackbits(anded.view(np.uint8), axis=1).sum(axis=1).astype(np.int64)     # coverage, :866-876
+    if nnz and edge_counts is not None:
+        extra_ptr, extra_org, extra_count = (np.asarray(a, np.int64) for a in edge_counts)
+        edge_of = np.repeat(np.arange(nnz), np.diff(extra_ptr))
+        np.add.at(cov, edge_of, (extra_count - 1) * mask[extra_org])      # the copies beyond the first
     src = np.repeat(np.arange(n), np.diff(ptr))
     ok = (cov > 0) & keep[src] & (renum[np.asarray(idx, np.int64)] >= 0) if nnz else np.zeros(0, bool)   # `if coverage == 0: continue`, :877
     deg = np.bincount(renum[src[ok]], minlength=len(families)) if nnz else np.zeros(len(families), np.int64)
@@ -77,13 +91,89 @@ def form_chunk_host(x, ptr, idx, edge_bits, organisms):
     return np.ascontiguousarray(sub[keep]), (ptr_c, idx_c, w_c), families
 
 
+RESERVED_WORDS = frozenset(["id", "label", "name", "weight", "partition", "partition_exact", "length", "length_min", "length_max",
+                            "length_avg", "length_med", "product", "nb_genes", "subpartition_shell", "viz"])   # ppanggolin.py:31
+
+
+def master_arrays_from_graph(graph, organisms=None):
+    """A master's arrays from PPanGGOLiN's neighbours graph as it builds it (a networkx Graph or DiGraph, read through
+    nodes(data=True), graph[a], is_directed() and, when directed, graph.pred[a]; networkx itself is not needed):
+    node data = organism name -> genes (plus RESERVED_WORDS attributes), edge data = organism name -> occurrence count
+    (plus weight / length).  organisms: the master's organisms in column order (default: every non-reserved node key,
+    in the order first met walking the nodes).  Keys that are not among them, reserved words included, are ignored.
+    Families come in graph node order (index_fam's order, ppanggolin.py:843).  A family's neighbours are
+    nx.all_neighbors, each once: for a Graph its adjacency in graph[a] order; for a DiGraph its predecessors in
+    graph.pred[a] order, then its successors not already listed, in graph[a] order.  count[e][o] is graph[a][b][o],
+    or graph[a][b][o] + graph[b][a][o] for a DiGraph (a directed self-loop counts twice), as the coverage sums them.
+    Returns x uint8 [n][d], (ptr, idx), edge_bits uint32 [nnz][ceil(d/32)], edge_counts (extra_ptr, extra_org,
+    extra_count: the pairs with count >= 2), family names, organism names."""
+    nodes = list(graph.nodes(data=True))
+    families = [f for f, _ in nodes]
+    if organisms is None:
+        seen = {}
+        for _, data in nodes:
+            for key in data:
+                if key not in RESERVED_WORDS and key not in seen:
+                    seen[key] = len(seen)
+        organisms = list(seen)
+    organisms = list(organisms)
+    col = {o: c for c, o in enumerate(organisms)}
+    if len(col) != len(organisms):
+        raise ValueError("organisms: distinct names")
+    fam_index = {f: i for i, f in enumerate(families)}
+    n, d = len(families), len(organisms)
+    wf = (d + 31) // 32
+    x = np.zeros((n, d), np.uint8)
+    for i, (_, data) in enumerate(nodes):
+        for key in data:
+            c = col.get(key)
+            if c is not None and key not in RESERVED_WORDS:
+                x[i, c] = 1
+    directed = bool(graph.is_directed())
+
+    def counts_of(a, b):
+        out = defaultdict(int)
+        pairs = [(a, b), (b, a)] if directed else [(a, b)]
+        for u, v in pairs:
+            if v in graph[u]:
+                for key, val in graph[u][v].items():
+                    c = col.get(key)
+                    if c is not None and key not in RESERVED_WORDS:
+                        out[c] += int(val)
+        return out
+
+    ptr = np.zeros(n + 1, np.int32)
+    idx, bits, xptr, xorg, xcnt = [], [], [0], [], []
+    for i, a in enumerate(families):
+        nbrs = list(graph.pred[a]) + [b for b in graph[a] if b not in graph.pred[a]] if directed else list(graph[a])
+        for b in nbrs:
+            idx.append(fam_index[b])
+            row = np.zeros(wf * 32, np.uint8)
+            for c, k in sorted(counts_of(a, b).items()):
+                if k >= 1:
+                    row[c] = 1
+                if k >= 2:
+                    xorg.append(c)
+                    xcnt.append(k)
+            bits.append(np.packbits(row, bitorder="little").view(np.uint32))
+            xptr.append(len(xorg))
+        ptr[i + 1] = len(idx)
+    edge_bits = np.stack(bits) if bits else np.zeros((0, wf), np.uint32)
+    edge_counts = (np.asarray(xptr, np.int32), np.asarray(xorg, np.int32), np.asarray(xcnt, np.int32))
+    return x, (ptr, np.asarray(idx, np.int32)), edge_bits, edge_counts, families, organisms
+
+
 class Master:
     """One pangenome on the device: presence/absence matrix, neighbourhood graph, per directed edge its organisms."""
 
-    def __init__(self, x, ptr, idx, edge_bits, device=0):
+    def __init__(self, x, ptr, idx, edge_bits, device=0, edge_counts=None):
+        """edge_counts: None (every count 1: nemgpu_master_create) or (extra_ptr, extra_org, extra_count), the
+        (edge, organism) pairs whose occurrence count is 2 or more (nemgpu_master_create_counts)"""
         self.lib = load_library()
         lib = self.lib
         lib.nemgpu_master_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.nemgpu_master_create_counts.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.nemgpu_master_destroy.argtypes = [C.c_void_p]
         lib.nemgpu_master_destroy.restype = None
         lib.nemgpu_solve_chunks.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -100,10 +190,30 @@ class Master:
         edge_bits = np.ascontiguousarray(edge_bits, np.uint32).reshape(len(idx), self.wf) if len(idx) else np.zeros((1, self.wf), np.uint32)
         assert ptr.shape == (self.n + 1,)
         self._h = C.c_void_p()
-        rc = lib.nemgpu_master_create(C.byref(self._h), int(device), self.n, self.d, rows.ctypes.data, ptr.ctypes.data,
-                                      idx.ctypes.data if len(idx) else None, edge_bits.ctypes.data if len(idx) else None)
+        if edge_counts is None:
+            rc = lib.nemgpu_master_create(C.byref(self._h), int(device), self.n, self.d, rows.ctypes.data, ptr.ctypes.data,
+                                          idx.ctypes.data if len(idx) else None, edge_bits.ctypes.data if len(idx) else None)
+            what = "nemgpu_master_create"
+        else:
+            xptr, xorg, xcnt = (np.ascontiguousarray(a, np.int32) for a in edge_counts)
+            if xptr.shape != (len(idx) + 1,) or len(xorg) != len(xcnt) or len(xorg) != int(xptr[-1]):
+                raise ValueError("edge_counts: extra_ptr [nnz + 1], extra_org and extra_count [extra_ptr[nnz]]")
+            rc = lib.nemgpu_master_create_counts(C.byref(self._h), int(device), self.n, self.d, rows.ctypes.data, ptr.ctypes.data,
+                                                 idx.ctypes.data if len(idx) else None, edge_bits.ctypes.data if len(idx) else None,
+                                                 xptr.ctypes.data, xorg.ctypes.data if len(xorg) else None,
+                                                 xcnt.ctypes.data if len(xcnt) else None)
+            what = "nemgpu_master_create_counts"
         if rc != 0:
-            raise NemGpuError("nemgpu_master_create failed (status %d): %s" % (rc, lib.nemgpu_last_error().decode()))
+            raise NemGpuError("%s failed (status %d): %s" % (what, rc, lib.nemgpu_last_error().decode()))
+
+    @classmethod
+    def from_graph(cls, graph, organisms=None, device=0):
+        """A counts master of PPanGGOLiN's neighbours graph (master_arrays_from_graph); its family and organism names are
+        kept (.names, .organism_names): partition() names its families by them"""
+        x, (ptr, idx), edge_bits, edge_counts, families, orgs = master_arrays_from_graph(graph, organisms)
+        m = cls(x, ptr, idx, edge_bits, device=device, edge_counts=edge_counts)
+        m.names, m.organism_names = list(families), list(orgs)
+        return m
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -139,8 +249,9 @@ class Master:
         `from random import sample`), solved `batch` at a time (nemgpu_votes_solve) and voted on the device until every
         family of the pangenome is validated; rng is left as the reference's loop leaves it.  Otherwise one run on
         exactly `organisms`.  Returns (partitions, cnt, samples): {name: 'P'|'S'|'C'|'U'} for the families of the
-        pangenome in the master's order (with just_stats the reference's stats: accessory / core_exact / persistent /
-        shell / cloud / undefined counts), the votes int32 [n][4] (P, S, C, U) and the number of samples voted.
+        pangenome in the master's order (names: "fam1", ... or, for Master.from_graph, the graph's; with just_stats the
+        reference's stats: accessory / core_exact / persistent / shell / cloud / undefined counts), the votes int32
+        [n][4] (P, S, C, U) and the number of samples voted.
         More than max_samples samples without an end raise NemGpuError (the reference would loop forever)."""
         from .partitioning import CODES
         lib = self.lib
@@ -188,6 +299,8 @@ class Master:
                 raise NemGpuError("nemgpu_votes_result failed (status %d): %s" % (rc, lib.nemgpu_last_error().decode()))
         finally:
             lib.nemgpu_votes_destroy(h)
+        if names is None:
+            names = getattr(self, "names", None)                # (Master.from_graph: the graph's family names)
         names = list(names) if names is not None else ["fam%d" % (i + 1) for i in range(self.n)]
         fam = np.flatnonzero(pan)
         partitions = {names[i]: CODES[final[i]] for i in fam}

@@ -101,19 +101,51 @@ __global__ __launch_bounds__(1024) void k_chunk_index(const ChunkPlan* __restric
     if (threadIdx.x == 0) p.counts[0] = base;
 }
 
-// coverage of every directed master edge in the sample: the organisms of the sample that carry it (ppanggolin.py:866-876)
-__global__ __launch_bounds__(256) void k_chunk_cov(const ChunkPlan* __restrict__ plans, const uint32_t* __restrict__ edge_bits, int nnz, int wf)
+// coverage of every directed master edge in the sample (ppanggolin.py:866-876): the sampled organisms that carry it and,
+// with kExtras, (count - 1) for each of its multi-copy organisms in the sample.  An edge with at most kLaneExtras extras is
+// walked by its own lane; a longer list (a tandem self-loop in every organism: thousands) by the whole wave, 64 entries
+// a step, and reduced to the owner lane.
+constexpr int kLaneExtras = 32;
+template <bool kExtras>
+__global__ __launch_bounds__(256) void k_chunk_cov(const ChunkPlan* __restrict__ plans, const uint32_t* __restrict__ edge_bits, int nnz, int wf,
+                                                  const int* __restrict__ extra_ptr, const int* __restrict__ extra_org,
+                                                  const int* __restrict__ extra_add)
 {
     __shared__ uint32_t s_mask[kMaskWordsMax];
     const ChunkPlan p = plans[blockIdx.y];
     for (int w = threadIdx.x; w < wf; w += 256) s_mask[w] = p.mask[w];
     __syncthreads();
     const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= nnz) return;
-    const uint32_t* __restrict__ row = edge_bits + (size_t)e * wf;
-    int c = 0;
-    for (int w = 0; w < wf; w++) c += __popc(row[w] & s_mask[w]);
-    p.cov[e] = (uint16_t)(c > 65535 ? 65535 : c);
+    if constexpr (!kExtras) {
+        if (e >= nnz) return;
+        const uint32_t* __restrict__ row = edge_bits + (size_t)e * wf;
+        int c = 0;
+        for (int w = 0; w < wf; w++) c += __popc(row[w] & s_mask[w]);
+        p.cov[e] = (uint32_t)c;
+    } else {
+        // (every lane stays to the end: the wave walks the long lists together)
+        const bool live = e < nnz;
+        const int lane = threadIdx.x & 63;
+        int c = 0, x0 = 0, x1 = 0;
+        if (live) {
+            const uint32_t* __restrict__ row = edge_bits + (size_t)e * wf;
+            for (int w = 0; w < wf; w++) c += __popc(row[w] & s_mask[w]);
+            x0 = extra_ptr[e]; x1 = extra_ptr[e + 1];
+        }
+        const bool wide = x1 - x0 > kLaneExtras;
+        if (!wide)
+            for (int t = x0; t < x1; t++) { const int o = extra_org[t]; if ((s_mask[o >> 5] >> (o & 31)) & 1u) c += extra_add[t]; }
+        for (uint64_t todo = __ballot(wide); todo != 0ull; todo &= todo - 1ull) {
+            const int owner = __ffsll((unsigned long long)todo) - 1;
+            const int h0 = __shfl(x0, owner, 64), h1 = __shfl(x1, owner, 64);
+            int part = 0;
+            for (int t = h0 + lane; t < h1; t += 64) { const int o = extra_org[t]; if ((s_mask[o >> 5] >> (o & 31)) & 1u) part += extra_add[t]; }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+            if (lane == owner) c += part;
+        }
+        if (live) p.cov[e] = (uint32_t)c;
+    }
 }
 
 // an edge of the chunk's graph: carried by a sampled organism (`if coverage == 0: continue`, ppanggolin.py:877), between
@@ -200,7 +232,8 @@ __global__ __launch_bounds__(256) void k_chunk_rows(ChunkPlan p, ChunkFill f, co
     } else if (j < f.npad) f.perm[j] = j;
 }
 
-// the chunk's graph in the engine's CSR block: neighbours in the master's order, weights = coverage
+// the chunk's graph in the engine's CSR block: neighbours in the master's order, weights = coverage (exact in float:
+// nemgpu_master_create_counts bounds every edge's total count by 2^24)
 __global__ __launch_bounds__(256) void k_chunk_graph(ChunkPlan p, ChunkFill f, const int* __restrict__ nei_ptr, const int* __restrict__ nei_idx)
 {
     const int j = blockIdx.x * 256 + threadIdx.x;
@@ -225,7 +258,12 @@ void launch_chunk_plan(const MasterDev& m, const ChunkPlan* plans_dev, int count
     hipLaunchKernelGGL(k_chunk_mask, dim3(count), dim3(256), 0, s, plans_dev, m.wf);
     hipLaunchKernelGGL(k_chunk_keep, dim3((m.nw64 + 255) / 256, count), dim3(256), 0, s, plans_dev, m.xt, m.nw64);
     hipLaunchKernelGGL(k_chunk_index, dim3(count), dim3(1024), 0, s, plans_dev, m.n, m.nw64);
-    if (m.nnz > 0) hipLaunchKernelGGL(k_chunk_cov, dim3((m.nnz + 255) / 256, count), dim3(256), 0, s, plans_dev, m.edge_bits, m.nnz, m.wf);
+    if (m.nnz > 0) {
+        if (m.extra_ptr) hipLaunchKernelGGL(k_chunk_cov<true>, dim3((m.nnz + 255) / 256, count), dim3(256), 0, s, plans_dev, m.edge_bits, m.nnz, m.wf,
+                                            m.extra_ptr, m.extra_org, m.extra_add);
+        else hipLaunchKernelGGL(k_chunk_cov<false>, dim3((m.nnz + 255) / 256, count), dim3(256), 0, s, plans_dev, m.edge_bits, m.nnz, m.wf,
+                                nullptr, nullptr, nullptr);
+    }
     hipLaunchKernelGGL(k_chunk_ptr, dim3(count), dim3(1024), 0, s, plans_dev, m.nei_ptr, m.nei_idx);
 }
 

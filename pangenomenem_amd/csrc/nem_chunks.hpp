@@ -5,10 +5,14 @@
 // five input files from ONE graph (`__write_nem_input_files`, ppanggolin.py:821-930):
 //   * the columns of the presence/absence matrix are the sampled organisms, in sample order (:850);
 //   * a family with no sampled organism is dropped, the others are numbered in the master's order (:849-852);
-//   * an edge's weight is the number of sampled organisms that carry the adjacency (`coverage`, :866-878); an edge
-//     nobody in the sample carries is dropped, the neighbours of a family keep the master's order.
-// Here the master lives on the device (organism-major bit rows, the graph in CSR, per directed edge the bit set of its
-// organisms) and a problem is FORMED there: no matrix, no graph crosses PCIe per chunk.
+//   * an edge's weight is its `coverage` (:866-878): the sum over the sampled organisms of the adjacency's occurrence
+//     count in that organism (`graph[a][b][org]`, which __add_link increments, :451), sens + antisens when the graph is
+//     directed; an edge with coverage 0 is dropped, the neighbours of a family keep the master's order.
+// Here the master lives on the device (organism-major bit rows, the graph in CSR, per directed edge the bit set of the
+// organisms that carry it, count >= 1, and sparse extras for the (edge, organism) pairs whose count is 2 or more) and a
+// problem is FORMED there: no matrix, no graph crosses PCIe per chunk.  The coverage of edge e in a sample is
+// popc(edge_bits[e] & mask) + sum over e's extras in the sample of (count - 1); a master without extras (every count 1)
+// is the bits alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -21,7 +25,10 @@ struct MasterDev {
     const uint64_t* xt;           // [d][nw64]: bit i of row o = family i present in organism o
     const int* nei_ptr;           // [n + 1]
     const int* nei_idx;           // [nnz]
-    const uint32_t* edge_bits;    // [nnz][wf]: organisms that carry the directed edge
+    const uint32_t* edge_bits;    // [nnz][wf]: organisms that carry the directed edge (count >= 1)
+    const int* extra_ptr;         // [nnz + 1] CSR over the edges of the pairs with count >= 2; null: every count is 1
+    const int* extra_org;         // [extra_ptr[nnz]] their organisms, increasing per edge
+    const int* extra_add;         // [extra_ptr[nnz]] count - 1
 };
 
 // per chunk, phase 1 (what decides the problem's sizes) ...
@@ -32,7 +39,7 @@ struct ChunkPlan {
     uint64_t* keep;               // [nw64]   families with at least one sampled organism
     int* list;                    // [n]      kept family j -> master index
     int* map;                     // [n]      master index -> kept number, -1: dropped
-    uint16_t* cov;                // [nnz]    coverage of every directed master edge in the sample
+    uint32_t* cov;                // [nnz]    coverage of every directed master edge in the sample
     int* ptr;                     // [n + 1]  CSR row pointers of the chunk's graph (kept rows)
     int* counts;                  // [2]      {kept families, kept directed edges}
 };

@@ -3533,6 +3533,40 @@ static int solve_many_one(nemgpu_problem* P, int count, const nemgpu_config* cfg
 int nemgpu_master_create(nemgpu_master** out, int device, int n, int d, const uint32_t* xbits, const int32_t* nei_ptr,
                          const int32_t* nei_idx, const uint32_t* edge_bits)
 {
+    return nemgpu_master_create_counts(out, device, n, d, xbits, nei_ptr, nei_idx, edge_bits, nullptr, nullptr, nullptr);
+}
+
+// the multi-copy pairs of a counts master, checked on the host (no HIP call before them: testable without a device);
+// *total = extra_ptr[nnz]
+static int check_extras(int d, int nnz, int wf, const uint32_t* edge_bits, const int32_t* extra_ptr, const int32_t* extra_org,
+                        const int32_t* extra_count, int* total)
+{
+    if (extra_ptr[0] != 0) { set_error("edge counts: extra_ptr[0] must be 0"); return NEMGPU_E_ARG; }
+    for (int e = 0; e < nnz; e++) if (extra_ptr[e + 1] < extra_ptr[e]) { set_error("edge counts: extra_ptr not monotone"); return NEMGPU_E_ARG; }
+    *total = extra_ptr[nnz];
+    if (*total > 0 && (!extra_org || !extra_count)) { set_error("edge counts: extras need their organisms and counts"); return NEMGPU_E_FUNCARG; }
+    const uint32_t last = (d & 31) ? (1u << (d & 31)) - 1u : ~0u;
+    for (int e = 0; e < nnz; e++) {
+        const uint32_t* row = edge_bits + (size_t)e * wf;
+        long long sum = 0;                                    // the edge's count over all organisms
+        for (int w = 0; w < wf; w++) sum += __builtin_popcount(w == wf - 1 ? row[w] & last : row[w]);
+        for (int t = extra_ptr[e]; t < extra_ptr[e + 1]; t++) {
+            const int o = extra_org[t];
+            if (o < 0 || o >= d) { set_error("edge counts: edge " + std::to_string(e) + ": organism out of range"); return NEMGPU_E_ARG; }
+            if (t > extra_ptr[e] && o <= extra_org[t - 1]) { set_error("edge counts: edge " + std::to_string(e) + ": organisms not strictly increasing"); return NEMGPU_E_ARG; }
+            if (!((row[o >> 5] >> (o & 31)) & 1u)) { set_error("edge counts: edge " + std::to_string(e) + ": organism " + std::to_string(o) + " not in its edge_bits"); return NEMGPU_E_ARG; }
+            if (extra_count[t] < 2) { set_error("edge counts: edge " + std::to_string(e) + ": a count below 2"); return NEMGPU_E_ARG; }
+            sum += extra_count[t] - 1;
+        }
+        if (sum > (1ll << 24)) { set_error("edge counts: edge " + std::to_string(e) + ": total count above 2^24 (a float weight would not be exact)"); return NEMGPU_E_ARG; }
+    }
+    return NEMGPU_OK;
+}
+
+int nemgpu_master_create_counts(nemgpu_master** out, int device, int n, int d, const uint32_t* xbits, const int32_t* nei_ptr,
+                                const int32_t* nei_idx, const uint32_t* edge_bits, const int32_t* extra_ptr, const int32_t* extra_org,
+                                const int32_t* extra_count)
+{
     if (!out) return NEMGPU_E_FUNCARG;
     *out = nullptr;
     if (n <= 0 || d <= 0 || !xbits || !nei_ptr) { set_error("nemgpu_master_create: sizes, bit rows and row pointers are needed"); return NEMGPU_E_FUNCARG; }
@@ -3544,6 +3578,8 @@ int nemgpu_master_create(nemgpu_master** out, int device, int n, int d, const ui
     for (int i = 0; i < n; i++) if (nei_ptr[i + 1] < nei_ptr[i]) { set_error("graph: ptr not monotone"); return NEMGPU_E_ARG; }
     if (nnz > 0 && (!nei_idx || !edge_bits)) { set_error("nemgpu_master_create: a graph needs neighbour indices and edge organism sets"); return NEMGPU_E_FUNCARG; }
     for (int t = 0; t < nnz; t++) if (nei_idx[t] < 0 || nei_idx[t] >= n) { set_error("graph: neighbour index out of range"); return NEMGPU_E_ARG; }
+    int nx = 0;                                               // multi-copy (edge, organism) pairs
+    if (extra_ptr) { const int r = check_extras(d, nnz, wf, edge_bits, extra_ptr, extra_org, extra_count, &nx); if (r != NEMGPU_OK) return r; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no usable HIP device: this library has no CPU fallback"); return NEMGPU_E_DEVICE; }
     if (device < 0 || device >= ndev) { set_error("nemgpu_master_create: bad device index"); return NEMGPU_E_ARG; }
@@ -3554,16 +3590,23 @@ int nemgpu_master_create(nemgpu_master** out, int device, int n, int d, const ui
     auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t b_xt = a256((size_t)d * nw64 * 8), b_ptr = a256(((size_t)n + 1) * 4), b_idx = a256((size_t)std::max(nnz, 1) * 4),
                  b_eb = a256((size_t)std::max(nnz, 1) * wf * 4), b_xf = a256((size_t)n * wf * 4);
+    // (no multi-copy pair: no extras at all, the bits-only kernels)
+    const size_t b_xptr = nx > 0 ? a256(((size_t)nnz + 1) * 4) : 0, b_xorg = nx > 0 ? a256((size_t)nx * 4) : 0;
     uint32_t* xf_tmp = nullptr;
     auto fail = [&](const char* what) { if (xf_tmp) (void)hipFree(xf_tmp); if (m->block) (void)hipFree(m->block);
                                         if (m->stream) (void)hipStreamDestroy(m->stream); delete m; set_error(what); return NEMGPU_E_DEVICE; };
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate failed");
-    if (hipMalloc(&m->block, b_xt + b_ptr + b_idx + b_eb) != hipSuccess) return fail("nemgpu_master_create: device memory");
+    if (hipMalloc(&m->block, b_xt + b_ptr + b_idx + b_eb + b_xptr + 2 * b_xorg) != hipSuccess) return fail("nemgpu_master_create: device memory");
     if (hipMalloc(&xf_tmp, b_xf) != hipSuccess) return fail("nemgpu_master_create: device memory");
     uint64_t* xt = (uint64_t*)m->block;
     int* dptr = (int*)(m->block + b_xt);
     int* didx = (int*)(m->block + b_xt + b_ptr);
     uint32_t* deb = (uint32_t*)(m->block + b_xt + b_ptr + b_idx);
+    int* dxptr = nx > 0 ? (int*)(m->block + b_xt + b_ptr + b_idx + b_eb) : nullptr;
+    int* dxorg = nx > 0 ? (int*)(m->block + b_xt + b_ptr + b_idx + b_eb + b_xptr) : nullptr;
+    int* dxadd = nx > 0 ? (int*)(m->block + b_xt + b_ptr + b_idx + b_eb + b_xptr + b_xorg) : nullptr;
+    std::vector<int32_t> xadd(extra_count ? (size_t)nx : 0);
+    for (int t = 0; t < nx; t++) xadd[(size_t)t] = extra_count[t] - 1;
     // the bits above organism d - 1 in a row's last word are not data
     std::vector<uint32_t> rows(xbits, xbits + (size_t)n * wf);
     if (d & 31) { const uint32_t keep = (1u << (d & 31)) - 1u; for (int i = 0; i < n; i++) rows[(size_t)i * wf + wf - 1] &= keep; }
@@ -3571,11 +3614,14 @@ int nemgpu_master_create(nemgpu_master** out, int device, int n, int d, const ui
     if (err == hipSuccess) err = hipMemcpyAsync(dptr, nei_ptr, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, m->stream);
     if (err == hipSuccess && nnz > 0) err = hipMemcpyAsync(didx, nei_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, m->stream);
     if (err == hipSuccess && nnz > 0) err = hipMemcpyAsync(deb, edge_bits, (size_t)nnz * wf * 4, hipMemcpyHostToDevice, m->stream);
+    if (err == hipSuccess && nx > 0) err = hipMemcpyAsync(dxptr, extra_ptr, ((size_t)nnz + 1) * 4, hipMemcpyHostToDevice, m->stream);
+    if (err == hipSuccess && nx > 0) err = hipMemcpyAsync(dxorg, extra_org, (size_t)nx * 4, hipMemcpyHostToDevice, m->stream);
+    if (err == hipSuccess && nx > 0) err = hipMemcpyAsync(dxadd, xadd.data(), (size_t)nx * 4, hipMemcpyHostToDevice, m->stream);
     if (err == hipSuccess) { nemk::launch_master_transpose(xf_tmp, n, wf, d, nw64, xt, m->stream); err = hipGetLastError(); }
     if (err == hipSuccess) err = hipStreamSynchronize(m->stream);
     if (err != hipSuccess) return fail("nemgpu_master_create: upload failed");
     (void)hipFree(xf_tmp);
-    m->dev = nemk::MasterDev{n, d, wf, nw64, nnz, xt, dptr, didx, deb};
+    m->dev = nemk::MasterDev{n, d, wf, nw64, nnz, xt, dptr, didx, deb, dxptr, dxorg, dxadd};
     *out = m;
     return NEMGPU_OK;
 }
@@ -3638,7 +3684,7 @@ static int solve_chunks_impl(nemgpu_master* M, nemgpu_chunk* chunks, int count, 
     }
     // ---- phase 1, all chunks: which families, which edges, how many of each
     auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t b_mask = a256((size_t)wf * 4), b_keep = a256((size_t)nw64 * 8), b_list = a256((size_t)n * 4), b_cov = a256((size_t)std::max(nnz, 1) * 2),
+    const size_t b_mask = a256((size_t)wf * 4), b_keep = a256((size_t)nw64 * 8), b_list = a256((size_t)n * 4), b_cov = a256((size_t)std::max(nnz, 1) * 4),
                  b_ptr = a256(((size_t)n + 1) * 4), b_cnt = 256;
     (void)b_cnt;
     const size_t per = b_mask + 2 * b_list + b_cov + b_ptr;
@@ -3665,7 +3711,7 @@ static int solve_chunks_impl(nemgpu_master* M, nemgpu_chunk* chunks, int count, 
             p.keep = (uint64_t*)(slab + o_keeps + b_keep * (size_t)c);
             p.list = (int*)b; b += b_list;
             p.map = (int*)b; b += b_list;
-            p.cov = (uint16_t*)b; b += b_cov;
+            p.cov = (uint32_t*)b; b += b_cov;
             p.ptr = (int*)b;
             p.counts = (int*)(slab + o_counts) + 2 * (size_t)c;
         }

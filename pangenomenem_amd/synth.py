@@ -174,6 +174,65 @@ def master_pangenome(n, d, seed, chord_frac=0.05, carry_path=0.8, carry_chord=0.
     return x, (ptr, idx), np.ascontiguousarray(edge_bits)
 
 
+def master_pangenome_counts(n, d, seed, multi_frac=0.02, max_count=4, loops=0.01, dense_loops=0, directed=False,
+                            chord_frac=0.05, carry_path=0.8, carry_chord=0.08):
+    """master_pangenome with occurrence counts (nemgpu_master_create_counts): the same matrix and carried organisms, plus
+    tandem self-loops i -> i on about n*loops families (carried by about half the organisms that hold the family) and
+    on the dense_loops families present in the most organisms (carried by all of them: the long extra lists).  A carried
+    (adjacency, organism) pair occurs 2 .. max_count times with probability multi_frac (a loop's: always at least twice),
+    the same count from both endpoints.  directed: the counts of a DiGraph as the coverage sums them, sens + antisens --
+    an adjacency's count plus, in half the pairs, a second draw for the other direction; a self-loop's doubled.  A
+    self-loop is listed once, at the end of its family's row.  Returns x, (ptr, idx), edge_bits, (extra_ptr, extra_org,
+    extra_count)."""
+    x, (ptr, idx), eb = master_pangenome(n, d, seed, chord_frac=chord_frac, carry_path=carry_path, carry_chord=carry_chord)
+    rng = np.random.Generator(np.random.PCG64(seed + 32452843))
+    wf = (d + 31) // 32
+    src = np.repeat(np.arange(n), np.diff(ptr)).astype(np.int64)
+    dst = idx.astype(np.int64)
+    lo, hi = np.minimum(src, dst), np.maximum(src, dst)
+    _, first, inv = np.unique(lo * n + hi, return_index=True, return_inverse=True)
+    pair_bits = eb[first]                                    # per adjacency its organisms (both directions agree)
+    # the self-loops: new adjacencies
+    pc = x.sum(axis=1)
+    sparse = rng.permutation(n)[:int(n * loops)]
+    dense = np.argsort(-pc, kind="stable")[:dense_loops]
+    fam = np.unique(np.concatenate([sparse, dense])).astype(np.int64)
+    loop_bits = np.zeros((len(fam), wf * 4), np.uint8)
+    for r, i in enumerate(fam):
+        carry = x[i].astype(bool) & ((rng.random(d) < 0.5) | np.isin(i, dense))
+        packed = np.packbits(carry.astype(np.uint8), bitorder="little")
+        loop_bits[r, :len(packed)] = packed
+    pair_bits = np.concatenate([pair_bits, loop_bits.view(np.uint32)])
+    npair = len(pair_bits)
+    is_loop = np.arange(npair) >= len(first)
+    # counts per carried (adjacency, organism)
+    p_idx, p_org = np.nonzero(np.unpackbits(pair_bits.view(np.uint8), axis=1, bitorder="little")[:, :d])
+    loop = is_loop[p_idx]
+    cnt = np.where((rng.random(len(p_idx)) < multi_frac) | loop, rng.integers(2, max_count + 1, len(p_idx)), 1)
+    if directed:
+        other = np.where(rng.random(len(p_idx)) < 0.5, np.where(rng.random(len(p_idx)) < multi_frac, rng.integers(2, max_count + 1, len(p_idx)), 1), 0)
+        cnt = np.where(loop, 2 * cnt, cnt + other)
+    # the master's edges: the old rows, a loop appended to its family's row
+    e_src = np.concatenate([src, fam])
+    e_dst = np.concatenate([dst, fam])
+    e_pair = np.concatenate([inv.ravel(), len(first) + np.arange(len(fam))])
+    order = np.lexsort((np.arange(len(e_src)), e_src))
+    e_src, e_dst, e_pair = e_src[order], e_dst[order], e_pair[order]
+    new_ptr = np.zeros(n + 1, np.int32)
+    new_ptr[1:] = np.cumsum(np.bincount(e_src, minlength=n))
+    edge_bits = np.ascontiguousarray(pair_bits[e_pair])
+    multi = cnt >= 2                                         # (p_idx is sorted, p_org increasing inside a pair)
+    m_pair, m_org, m_cnt = p_idx[multi], p_org[multi], cnt[multi]
+    per_pair = np.bincount(m_pair, minlength=npair)
+    pair_start = np.concatenate([[0], np.cumsum(per_pair)])
+    lens = per_pair[e_pair]
+    extra_ptr = np.zeros(len(e_pair) + 1, np.int64)
+    extra_ptr[1:] = np.cumsum(lens)
+    take = np.repeat(pair_start[e_pair] - extra_ptr[:-1], lens) + np.arange(int(extra_ptr[-1]))
+    edge_counts = (extra_ptr.astype(np.int32), m_org[take].astype(np.int32), m_cnt[take].astype(np.int32))
+    return x, (new_ptr, e_dst.astype(np.int32)), edge_bits, edge_counts
+
+
 def default_init(d, low_disp=0.1):
     """PPanGGOLiN's default .m (ppanggolin.py:893-901): pi 0.33333/0.33333/rest, mu 1/0.5/0,
     eps low/0.5/low.  pi_K is computed as ReadParamFile does (float 1 - p0 - p1, nem_exe.c:1022-1034)."""

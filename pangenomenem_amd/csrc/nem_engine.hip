@@ -59,6 +59,35 @@ constexpr int kFlagSetWords = FLAG_ITER_STRIDE + kRoundCap * FLAG_ROUND_STRIDE; 
 constexpr int kRoundBatchMax = 4;
 constexpr int kRoundsMax = 7;       // most rounds a sweep of the pipelined loop is given ahead (ctrl_logic reads 8 slots)
 constexpr int kFzPositions = 16;    // fuzzy NEM: leading iterations of a run whose round counts are learned
+
+// an engine's freshness flags (tables_fresh, density_fresh, flags_clean, masks_valid)
+struct HostFlags { bool tables_fresh = false, density_fresh = false, flags_clean = false, masks_valid = false; };
+
+// Launch sequences captured into hipGraphs (run_graphed), one slot per shape.  desc: everything the captured launches
+// depend on, compared on a key hit -- a 64-bit hash alone would replay the wrong graph on a collision.  A full cache
+// starts over.  host_flags: a replay sets the owner's freshness flags as the captured enqueue left them (post).
+// sticky: clear() keeps the slots and their sightings, so a shape seen before the graphs were dropped is captured
+// the next time it comes.
+struct GraphCache {
+    struct Slot { uint64_t key; std::vector<uint64_t> desc; int asked; hipGraphExec_t exec; HostFlags post; };
+    size_t capacity; bool host_flags, sticky;
+    std::vector<Slot> slots;
+    GraphCache(size_t cap, bool flags, bool keep_sightings) : capacity(cap), host_flags(flags), sticky(keep_sightings) {}
+    Slot& find_or_add(const std::vector<uint64_t>& desc)
+    {
+        uint64_t key = 1469598103934665603ull;                    // FNV-1a
+        for (uint64_t v : desc) key = (key ^ v) * 1099511628211ull;
+        for (Slot& s : slots) if (s.key == key && s.desc == desc) return s;
+        if (slots.size() >= capacity) { clear(); slots.clear(); }
+        slots.push_back({key, desc, 0, nullptr, {}});
+        return slots.back();
+    }
+    void clear()                                                  // destroys the captured graphs
+    {
+        for (Slot& s : slots) if (s.exec) { (void)hipGraphExecDestroy(s.exec); s.exec = nullptr; }
+        if (!sticky) slots.clear();
+    }
+};
 }  // namespace
 
 struct nemgpu_engine {
@@ -169,9 +198,9 @@ struct nemgpu_engine {
     bool masks_valid = false;
     bool flags_clean = false;     // MOVED + round window are zero (set by k_density, consumed by a sweep)
 
-    // captured batches of the pipelined loop, keyed by (current buffer, iterations in the batch)
-    hipGraphExec_t graphs[2][3][8][8] = {};   // [with initial sweeps][current buffer][iterations][leading iterations with one round more]
-    uint8_t graph_asked[2][3][8][8] = {};   // how often a batch shape was enqueued before it got a graph
+    // captured batches of the pipelined loop, keyed by (with initial sweeps, current buffer, iterations, leading
+    // iterations with one round more): room for every such shape, so nothing is evicted
+    GraphCache batch_graphs{2 * 3 * 8 * 8, true, true};
     bool use_graphs = true;
     // Shadow-verify schedule (NEM_MI355X_SHADOW_VERIFY, default on; see shadow_batch_enqueue): a sweep's verifying round
     // runs in the next iteration's density launch, so an iteration's parameters, densities and flag block are written
@@ -253,22 +282,17 @@ struct nemgpu_engine {
     // area their flag blocks are gathered in, and the launch sequences captured so far (they hold the slabs'
     // addresses).  It belongs to the device, not to the engine: a lead takes one from the device's pool and hands it
     // back when it is destroyed, so the next group of problems of the same shape REPLAYS the graphs this one captured.
-    // desc: everything the captured launches depend on (kernel, variant, members, strides, grids, slab offsets),
-    // compared on a key hit -- a 64-bit hash alone would replay the wrong graph on a collision
-    struct ZipGraph { uint64_t key; int asked; hipGraphExec_t exec; std::vector<uint64_t> desc; };
+    // (the graphs' desc: kernel, variant, members, strides, grids, slab offsets; the lead's host state is not theirs)
     struct ZipContext {
         char* zip_host = nullptr; char* zip_dev = nullptr; size_t zip_cap = 0;
         int* zip_flags_host = nullptr; int* zip_flags_dev = nullptr; size_t zip_flags_cap = 0;
         size_t zip_host_size = 0, zip_dev_size = 0, zip_flags_host_size = 0, zip_flags_dev_size = 0;
-        std::vector<ZipGraph> zip_graphs;
+        GraphCache zip_graphs{64, false, false};
     };
     ZipContext* zc = nullptr;
     // a rank alone in the sharded EM (no collective inside a batch): its batches as hipGraphs of the library's own,
     // captured the second time a shape is enqueued (nemgpu_shard_enqueue_batch)
-    // (post_*: the host flags the captured body left behind -- a replay launches the graph only, so it sets them itself)
-    struct ShardGraph { uint64_t key; std::vector<uint64_t> desc; int asked; hipGraphExec_t exec;
-                        bool post_tables_fresh = false, post_density_fresh = false, post_flags_clean = false, post_masks_valid = false; };
-    std::vector<ShardGraph> shard_graphs;
+    GraphCache shard_graphs{64, true, false};
 
     bool ncem() const { return cfg.algo == NEMGPU_ALGO_NCEM; }
     int* ctrl() const { return flags_dev; }
@@ -490,7 +514,7 @@ nemgpu_engine::ZipContext* zip_context(nemgpu_engine* lead)
 }
 void zip_context_free(int device, nemgpu_engine::ZipContext* z)
 {
-    for (auto& g : z->zip_graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    z->zip_graphs.clear();
     pool_put(device, true, z->zip_host, z->zip_host_size);
     pool_put(device, false, z->zip_dev, z->zip_dev_size);
     pool_put(device, true, (char*)z->zip_flags_host, z->zip_flags_host_size);
@@ -993,7 +1017,6 @@ int read_iter_flags(nemgpu_engine* e)
 int reset_device(nemgpu_engine* e);
 int reset_state(nemgpu_engine* e, bool lazy = false);
 int flush_reset(nemgpu_engine* e);
-void drop_graphs(nemgpu_engine* e);
 int criteria_enqueue(nemgpu_engine* e, int buf);
 void fill_result(nemgpu_engine* e, nemgpu_result* res);
 
@@ -1703,6 +1726,65 @@ int batch_finish(nemgpu_engine* e, LoopCursor& lc)
     return NEMGPU_OK;
 }
 
+void drop_graphs(nemgpu_engine* e)
+{
+    e->batch_graphs.clear();
+    e->shard_graphs.clear();
+}
+
+// What run_graphed did with a batch (none: the capture failed with enqueue()'s error, which it returns).
+enum class Graphed { none, plain, captured, replayed };
+
+// One batch on stream s: the captured graph of desc's slot in `cache` is replayed if there is one; else the batch is
+// enqueued (enqueue()) as plain launches, or -- once the shape has been asked for capture_after times, or at once
+// under owner->capture_first -- captured, and the graph launched.  A failed capture turns owner->use_graphs off for
+// good; nothing of it ran, so the owner's freshness flags go back to what they were, rewind() puts back the rest of
+// the host state enqueue() changed, and the batch goes out as plain launches.  cache == nullptr: plain launches.
+template <typename Enqueue, typename Rewind>
+int run_graphed(nemgpu_engine* owner, GraphCache* cache, const std::vector<uint64_t>& desc, int capture_after, hipStream_t s,
+                Enqueue&& enqueue, Rewind&& rewind, Graphed* how)
+{
+    auto get_flags = [owner]() { return HostFlags{owner->tables_fresh, owner->density_fresh, owner->flags_clean, owner->masks_valid}; };
+    auto set_flags = [owner](const HostFlags& f) {
+        owner->tables_fresh = f.tables_fresh; owner->density_fresh = f.density_fresh;
+        owner->flags_clean = f.flags_clean; owner->masks_valid = f.masks_valid;
+    };
+    *how = Graphed::none;
+    GraphCache::Slot* slot = cache != nullptr && owner->use_graphs ? &cache->find_or_add(desc) : nullptr;
+    if (slot != nullptr && slot->exec != nullptr) {
+        HIPCHK(hipGraphLaunch(slot->exec, s));
+        if (cache->host_flags) set_flags(slot->post);
+        *how = Graphed::replayed;
+        return NEMGPU_OK;
+    }
+    if (slot != nullptr && (slot->asked++ >= capture_after - 1 || owner->capture_first)) {
+        const HostFlags before = get_flags();
+        HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        const int r = enqueue();
+        hipGraph_t graph = nullptr;
+        const hipError_t cerr = hipStreamEndCapture(s, &graph);
+        hipGraphExec_t exec = nullptr;
+        if (r == NEMGPU_OK && cerr == hipSuccess && graph != nullptr && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
+            (void)hipGraphDestroy(graph);
+            slot->exec = exec;
+            slot->post = get_flags();
+            *how = Graphed::captured;
+            HIPCHK(hipGraphLaunch(exec, s));
+            return NEMGPU_OK;
+        }
+        if (graph) (void)hipGraphDestroy(graph);
+        if (getenv("NEM_MI355X_DEBUG"))
+            fprintf(stderr, "[nem] batch capture failed: enqueue rc %d (%s), end-capture %s\n", r, g_last_error.c_str(), hipGetErrorString(cerr));
+        (void)hipGetLastError();
+        owner->use_graphs = false;                                 // plain launches from now on
+        if (r != NEMGPU_OK) return r;
+        set_flags(before);
+        rewind();
+    }
+    *how = Graphed::plain;
+    return enqueue();
+}
+
 int iterate_pipelined(nemgpu_engine* e, int n_iters, bool with_init)
 {
     int r;
@@ -1716,40 +1798,18 @@ int iterate_pipelined(nemgpu_engine* e, int n_iters, bool with_init)
     }
     while (loop_wants_batch(e, lc)) {
         if ((r = batch_plan(e, lc))) return r;
-        const int g = lc.g, base = lc.base;
-        const bool first = lc.batch_first;
-        bool graphed = e->use_graphs && g < 8;
-        const int deep = lc.deep;
-        hipGraphExec_t exec = graphed ? e->graphs[first ? 1 : 0][base][g][deep] : nullptr;
         // the first batch of a shape goes out as plain launches: capturing and instantiating a graph costs more than
-        // it saves unless the batch is replayed, and a nem() call's engine enqueues most shapes once
-        if (graphed && exec == nullptr && e->graph_asked[first ? 1 : 0][base][g][deep]++ == 0 && !e->capture_first) graphed = false;
-        if (exec == nullptr) {
-            if (graphed) e->n_captured++; else e->n_plain++;
-            if (graphed) HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-            r = batch_enqueue(e, lc, true);
-            if (graphed) {
-                hipGraph_t graph = nullptr;
-                hipError_t cerr = hipStreamEndCapture(e->stream, &graph);
-                if (r == NEMGPU_OK && cerr == hipSuccess && graph != nullptr &&
-                    hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                    e->graphs[first ? 1 : 0][base][g][deep] = exec;
-                } else {
-                    exec = nullptr;
-                    e->n_captured--;
-                    e->use_graphs = false;                         // fall back to plain launches for good
-                    if (r == NEMGPU_OK && cerr != hipSuccess) { set_error(std::string("graph capture failed: ") + hipGetErrorString(cerr)); }
-                }
-                if (graph) (void)hipGraphDestroy(graph);
-                if (exec == nullptr && r == NEMGPU_OK) {           // redo this batch ungraphed
-                    e->sweep_counter = lc.sweep0;
-                    if (first) e->cur = 0;
-                    continue;
-                }
-            }
-            if (r) return r;
-        }
-        if (exec != nullptr) { HIPCHK(hipGraphLaunch(exec, e->stream)); e->n_replayed++; }
+        // it saves unless the batch is replayed, and a nem() call's engine enqueues most shapes once.  (A batch's
+        // enqueue changes cur and sweep_counter besides the freshness flags; a capture counts as a replay too.)
+        const int cur0 = e->cur; const uint32_t sweep_counter0 = e->sweep_counter;
+        Graphed how;
+        r = run_graphed(e, lc.g < 8 ? &e->batch_graphs : nullptr, {(uint64_t)lc.batch_first, (uint64_t)lc.base, (uint64_t)lc.g, (uint64_t)lc.deep},
+                        2, e->stream, [&]() { return batch_enqueue(e, lc, true); },
+                        [&]() { e->cur = cur0; e->sweep_counter = sweep_counter0; }, &how);
+        e->n_plain += how == Graphed::plain;
+        e->n_captured += how == Graphed::captured;
+        e->n_replayed += how == Graphed::replayed || (how == Graphed::captured && r == NEMGPU_OK);
+        if (r) return r;
         HIPCHK(hipStreamSynchronize(e->stream));
         if ((r = batch_finish(e, lc))) return r;
     }
@@ -1812,8 +1872,7 @@ int zip_reserve(nemgpu_engine* lead, size_t bytes)
     nemgpu_engine::ZipContext* z = zip_context(lead);
     if (z->zip_cap >= bytes) return NEMGPU_OK;
     HIPCHK(hipStreamSynchronize(lead->stream));
-    for (auto& g : z->zip_graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);   // (they hold the old slab's addresses)
-    z->zip_graphs.clear();
+    z->zip_graphs.clear();                                        // (they hold the old slab's addresses)
     pool_put(lead->device, true, z->zip_host, z->zip_host_size);
     pool_put(lead->device, false, z->zip_dev, z->zip_dev_size);
     z->zip_host = nullptr; z->zip_dev = nullptr; z->zip_cap = 0;
@@ -1853,9 +1912,7 @@ int zip_and_launch(nemgpu_engine* lead, const std::vector<Recorder>& recs, const
     struct Launch { int kind, variant, B, stride; size_t args_off, gx_off; unsigned max_gx, gy, block; };
     std::vector<Launch> launches;
     size_t off = 0;
-    uint64_t key = 1469598103934665603ull;                        // FNV-1a over everything a captured sequence depends on
-    std::vector<uint64_t> desc;                                   // ... and the list itself (compared on a key hit)
-    auto mix = [&](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
+    std::vector<uint64_t> desc;                                   // everything a captured sequence depends on
     for (const auto& g : groups) {
         const int B = (int)g.size();
         for (size_t t = 0; t < recs[g[0]].ops.size(); t++) {
@@ -1870,24 +1927,14 @@ int zip_and_launch(nemgpu_engine* lead, const std::vector<Recorder>& recs, const
             off += ((size_t)B * sizeof(int) + 15) & ~(size_t)15;
             launches.push_back(L);
             for (uint64_t v : {(uint64_t)L.kind, (uint64_t)L.variant, (uint64_t)B, (uint64_t)stride, (uint64_t)L.max_gx, (uint64_t)L.gy,
-                               (uint64_t)L.block, (uint64_t)L.args_off, (uint64_t)L.gx_off}) { mix(v); desc.push_back(v); }
+                               (uint64_t)L.block, (uint64_t)L.args_off, (uint64_t)L.gx_off}) desc.push_back(v);
         }
     }
-    mix(flags_words); desc.push_back(flags_words);
+    desc.push_back(flags_words);
     if (off == 0 && flags_words == 0) return NEMGPU_OK;
     if (off) HIPCHK(hipMemcpyAsync(z->zip_dev, z->zip_host, off, hipMemcpyHostToDevice, lead->stream));
     // The launches themselves depend only on the shape (kernels, grids, slab offsets), not on the argument blocks'
     // content: a shape seen before is replayed from its captured graph
-    nemgpu_engine::ZipGraph* slot = nullptr;
-    for (auto& g : z->zip_graphs) if (g.key == key && g.desc == desc) { slot = &g; break; }
-    if (slot == nullptr && lead->use_graphs) {
-        if (z->zip_graphs.size() >= 64) {
-            for (auto& g : z->zip_graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-            z->zip_graphs.clear();
-        }
-        z->zip_graphs.push_back({key, 0, nullptr, desc});
-        slot = &z->zip_graphs.back();
-    }
     auto issue = [&]() -> int {
         for (const Launch& L : launches)
             launch_zipped(L.kind, L.variant, L.B, z->zip_dev + L.args_off, L.stride, reinterpret_cast<const int*>(z->zip_dev + L.gx_off),
@@ -1896,31 +1943,11 @@ int zip_and_launch(nemgpu_engine* lead, const std::vector<Recorder>& recs, const
             HIPCHK(hipMemcpyAsync(z->zip_flags_host, z->zip_flags_dev, flags_words * sizeof(int), hipMemcpyDeviceToHost, lead->stream));
         return NEMGPU_OK;
     };
-    if (slot != nullptr && slot->exec != nullptr) {
-        HIPCHK(hipGraphLaunch(slot->exec, lead->stream));
-        return NEMGPU_OK;
-    }
     // Capturing and instantiating costs ~160 us per node (8 ms for a batch of 7 iterations) and a replay saves
     // 0.15-0.35 ms of issue time: a shape pays for its graph after some thirty replays.  The contexts live as long as
     // the process (a pangenome's chunks are hundreds of batches of one shape), so: from the fourth sighting on.
-    const bool capture = slot != nullptr && (slot->asked++ >= 3 || lead->capture_first);
-    if (capture) {
-        HIPCHK(hipStreamBeginCapture(lead->stream, hipStreamCaptureModeThreadLocal));
-        r = issue();
-        hipGraph_t graph = nullptr;
-        const hipError_t cerr = hipStreamEndCapture(lead->stream, &graph);
-        hipGraphExec_t exec = nullptr;
-        if (r == NEMGPU_OK && cerr == hipSuccess && graph != nullptr && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-            slot->exec = exec;
-            if (graph) (void)hipGraphDestroy(graph);
-            HIPCHK(hipGraphLaunch(exec, lead->stream));
-            return NEMGPU_OK;
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-        (void)hipGetLastError();
-        lead->use_graphs = false;                                  // plain launches from now on
-    }
-    if ((r = issue())) return r;
+    Graphed how;
+    if ((r = run_graphed(lead, &z->zip_graphs, desc, 4, lead->stream, issue, []() {}, &how))) return r;
     HIPCHK(hipGetLastError());
     return NEMGPU_OK;
 }
@@ -1953,7 +1980,6 @@ int lockstep(std::vector<nemgpu_engine*>& E, const std::vector<int>& members, st
             pool_put(lead->device, true, (char*)z->zip_flags_host, z->zip_flags_host_size);
             pool_put(lead->device, false, (char*)z->zip_flags_dev, z->zip_flags_dev_size);
             z->zip_flags_host = nullptr; z->zip_flags_dev = nullptr; z->zip_flags_cap = 0;
-            for (auto& g : z->zip_graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
             z->zip_graphs.clear();
             HIPCHK(pool_get(lead->device, true, need * sizeof(int), (char**)&z->zip_flags_host, &z->zip_flags_host_size));
             HIPCHK(pool_get(lead->device, false, need * sizeof(int), (char**)&z->zip_flags_dev, &z->zip_flags_dev_size));
@@ -2286,17 +2312,6 @@ int run_many(std::vector<nemgpu_engine*>& E, nemgpu_result* results, GroupFetch*
     if (prof) fprintf(stderr, "[run_many] %d members: waits for the uploads %.0f us, loop_begin %.0f, iterations %.0f, it_max 0 %.0f, criteria + results %.0f, streams back %.0f\n",
                       B, laps[0], laps[1], laps[2], laps[3], laps[4], laps[5]);
     return r;
-}
-
-void drop_graphs(nemgpu_engine* e)
-{
-    for (auto& g : e->shard_graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    e->shard_graphs.clear();
-    for (auto& plane : e->graphs)
-        for (auto& row : plane)
-            for (auto& col : row)
-                for (auto& g : col)
-                    if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
 }
 
 int ensure_crit_buffers(nemgpu_engine* e)
@@ -5320,68 +5335,37 @@ int nemgpu_shard_enqueue_batch(nemgpu_engine* e, int with_init, int n_iters, int
     // A rank alone has no collective inside its batches: they go out as hipGraphs of the library's own, captured the
     // second time a shape is enqueued (as the single engine's batches are).  With more ranks the batch holds RCCL
     // calls and is issued launch by launch -- one C call either way.
-    nemgpu_engine::ShardGraph* slot = nullptr;
     if (e->sh_world == 1 && e->use_graphs && !e->libc()) {        // (TIE_LIBC: the stream's position is a launch argument)
-        uint32_t bb; memcpy(&bb, &beta, 4);
         //  Everything that decides WHICH launches the body issues is part of the key: besides the call's
-        // arguments, the host state the body branches on.  A batch that does not start with the restart launch first
-        // flushes a pending reset -- outside the capture, below -- so that state is the same at capture and at replay.
+        // arguments, the host state the body branches on.  So a pending reset is flushed here, outside the capture, and
+        // a restart clears a reported fault and does the host half of its reset here: a replay only launches the graph,
+        // and a reset left pending would later copy the initial parameters over the estimated ones.  (The body does the
+        // same again, to the same effect; besides that it changes only the freshness flags: no rewind of its own.)
+        { const int cr = shard_check(e); if (cr) return cr; }
+        HIPCHK(hipSetDevice(e->device));
         if (with_init == 0) { const int fr = flush_reset(e); if (fr) return fr; }
-        else { HIPCHK(hipSetDevice(e->device)); const int cf = clear_fault(e); if (cf) return cf; }   // (a restart clears a reported fault: not inside a capture)
+        else {
+            if (!e->have_matrix || !e->have_params) { set_error("matrix and parameters must be set first"); return NEMGPU_E_FUNCARG; }
+            const int rr = reset_state(e, true);
+            if (rr) return rr;
+            e->reset_pending = false;                              // (the device half is the batch's first launch)
+            const int cf = clear_fault(e);
+            if (cf) return cf;
+        }
+        e->stop_ptr = nullptr;                                     // (where the body's last call leaves it)
+        uint32_t bb; memcpy(&bb, &beta, 4);
         const std::vector<uint64_t> desc = {(uint64_t)with_init, (uint64_t)n_iters, (uint64_t)base, (uint64_t)bb, (uint64_t)want_stats,
                                             (uint64_t)(uintptr_t)lab0, (uint64_t)(uintptr_t)lab1, (uint64_t)(uintptr_t)lab2, (uint64_t)stats_off,
                                             (uint64_t)((with_init ? 0 : ((e->tables_fresh ? 1 : 0) | (e->density_fresh ? 2 : 0) | (e->flags_clean ? 4 : 0) |
                                                                          (e->masks_valid ? 8 : 0))))};
-        uint64_t key = 1469598103934665603ull;
-        for (uint64_t v : desc) key = (key ^ v) * 1099511628211ull;
-        for (auto& g : e->shard_graphs) if (g.key == key && g.desc == desc) { slot = &g; break; }
-        if (slot == nullptr) {
-            if (e->shard_graphs.size() >= 64) drop_graphs(e);
-            e->shard_graphs.push_back({key, desc, 0, nullptr});
-            slot = &e->shard_graphs.back();
-        }
-        if (slot->exec != nullptr) {
-            { const int cr = shard_check(e); if (cr) return cr; }
-            HIPCHK(hipSetDevice(e->device));
-            // the host half of what the captured body did (nemgpu_shard_begin_restart / the round functions): a replay
-            // only launches the graph -- a reset left pending here would later copy the initial parameters over the
-            // estimated ones
-            if (with_init) {
-                if (!e->have_matrix || !e->have_params) { set_error("matrix and parameters must be set first"); return NEMGPU_E_FUNCARG; }
-                const int rr = reset_state(e, true);
-                if (rr) return rr;
-                e->reset_pending = false;                          // (the device half is the graph's first launch)
-            }
-            HIPCHK(hipGraphLaunch(slot->exec, e->stream));
-            e->tables_fresh = slot->post_tables_fresh; e->density_fresh = slot->post_density_fresh;
-            e->flags_clean = slot->post_flags_clean; e->masks_valid = slot->post_masks_valid;
-            e->n_replayed++;
-            e->stop_ptr = nullptr;
-            return NEMGPU_OK;
-        }
-        if (slot->asked++ >= 1 || e->capture_first) {
-            HIPCHK(hipSetDevice(e->device));
-            HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-            const int r = shard_batch_body(e, with_init, n_iters, base, beta, want_stats, lab0, lab1, lab2, stats_off);
-            hipGraph_t graph = nullptr;
-            const hipError_t cerr = hipStreamEndCapture(e->stream, &graph);
-            hipGraphExec_t exec = nullptr;
-            if (r == NEMGPU_OK && cerr == hipSuccess && graph != nullptr && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                if (graph) (void)hipGraphDestroy(graph);
-                slot->exec = exec;
-                slot->post_tables_fresh = e->tables_fresh; slot->post_density_fresh = e->density_fresh;
-                slot->post_flags_clean = e->flags_clean; slot->post_masks_valid = e->masks_valid;
-                e->n_captured++;
-                HIPCHK(hipGraphLaunch(exec, e->stream));
-                return NEMGPU_OK;
-            }
-            if (graph) (void)hipGraphDestroy(graph);
-            if (getenv("NEM_MI355X_DEBUG"))
-                fprintf(stderr, "[nem] sharded batch capture failed: body rc %d (%s), end-capture %s\n", r, g_last_error.c_str(), hipGetErrorString(cerr));
-            (void)hipGetLastError();
-            e->use_graphs = false;                                 // plain launches from now on
-            if (r != NEMGPU_OK) return r;
-        }
+        Graphed how;
+        const int r = run_graphed(e, &e->shard_graphs, desc, 2, e->stream, [&]() {
+            return shard_batch_body(e, with_init, n_iters, base, beta, want_stats, lab0, lab1, lab2, stats_off);
+        }, []() {}, &how);
+        e->n_plain += how == Graphed::plain;
+        e->n_captured += how == Graphed::captured;
+        e->n_replayed += how == Graphed::replayed;
+        return r;
     }
     e->n_plain++;
     return shard_batch_body(e, with_init, n_iters, base, beta, want_stats, lab0, lab1, lab2, stats_off);

@@ -278,6 +278,16 @@ int nemgpu_vote_classmap_host(int count, int k, const int* dc, const float* cent
    NULL. */
 int nemgpu_votes_result(nemgpu_votes* v, int32_t* cnt, uint8_t* final_code, int32_t* validated, int64_t* samples_voted);
 
+/* PPanGGOLiN's evolution curve (command_line.py:262-281): count samples of the master solved as nemgpu_solve_chunks
+   solves them (k = 3, NCEM), each reduced on the device to the stats of partition(just_stats=True):
+   stats[count][6] = persistent, shell, cloud, undefined, core_exact, accessory.  labels / out_* of the chunks may be
+   NULL (no label crosses PCIe then).  A sample that keeps no family is not solved: its stats are all 0, its rc
+   NEMGPU_OK.  A sample is a set: an organism repeated in it, or out of range, is refused (NEMGPU_E_ARG) before anything
+   is launched. */
+int nemgpu_resamples_solve(nemgpu_master* m, nemgpu_chunk* chunks, int count, int k, const float* prop,
+                           const float* center_k, const float* disp_k, const nemgpu_config* cfg, int workers,
+                           int group, int32_t* stats);
+
 /* Whole run from random starts (the reference's init_mode = INIT_RANDOM, RandNemAlgo nem_alg.c:1574-1742): n_starts
    starts (the reference uses 50), centres drawn from the data with the reference's generator -- glibc random()
    after srandom(seed), restated in csrc/nem_rng.hpp -- best start by criterion M, EstimPara on the best partition.

@@ -315,6 +315,36 @@ class Master:
             return stats, cnt, int(nvoted.value)
         return partitions, cnt, int(nvoted.value)
 
+    def resample_stats(self, samples, beta=0.5, free_dispersion=False, tie="libc", seed=0, workers=8, group=32):
+        """evolution.resample_stats: every sample (a list of distinct organism indices) as partition(just_stats=True)
+        solves a selection of at most chunk_size organisms, in one library call (nemgpu_resamples_solve).  Returns
+        int32 [count][6]: persistent, shell, cloud, undefined, core_exact, accessory."""
+        from . import evolution
+        return evolution.resample_stats(self, samples, beta=beta, free_dispersion=free_dispersion, tie=tie, seed=seed,
+                                        workers=workers, group=group)
+
+    def evolution(self, rng=None, ratio=0.1, rmin=10, rmax=30, step=1, limit=None, chunk_size=500, beta=0.5, free_dispersion=False,
+                  tie="libc", seed=0, batch=64, workers=8, group=32, max_samples=100000):
+        """The CLI's --evolution on this master as its --cpu 1 run makes it (command_line.py:591-625, evolution.py): the
+        resamples drawn and shuffled on rng (the `random` module by default) with -ep ratio rmin rmax step limit (None:
+        Inf), every resample of at most chunk_size organisms solved in one resample_stats call, the larger ones through
+        partition()'s vote loop on rng in shuffled order.  rng is left where the reference leaves it.  Returns int64
+        [count][7] in shuffled order: nb_org, persistent, shell, cloud, undefined, core_exact, accessory
+        (evolution.write_evol_stats writes them)."""
+        from . import evolution
+        rng = random if rng is None else rng
+        resamples = evolution.evolution_resamples(self.d, ratio, rmin, rmax, step, limit, rng)
+
+        def small(rs):
+            return self.resample_stats(rs, beta=beta, free_dispersion=free_dispersion, tie=tie, seed=seed, workers=workers, group=group)
+
+        def large(r, rng):
+            return evolution.partition_stats_row(self.partition(organisms=r, chunk_size=chunk_size, beta=beta, free_dispersion=free_dispersion,
+                                                                rng=rng, batch=batch, tie=tie, seed=seed, max_samples=max_samples,
+                                                                just_stats=True, workers=workers, group=group))
+
+        return evolution.evolution_rows(resamples, rng, chunk_size, small, large)
+
     def core_exact(self, organisms):
         """bool [n]: the families present in every one of `organisms` (ppanggolin.py:982-993)"""
         mask = np.zeros(self.wf * 32, np.uint8)

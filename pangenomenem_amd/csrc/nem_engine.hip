@@ -34,6 +34,7 @@
 #include "nem_kernels.hpp"
 #include "nem_chunks.hpp"
 #include "nem_vote.hpp"
+#include "nem_resample.hpp"
 
 using namespace nemk;
 
@@ -312,6 +313,15 @@ struct nemgpu_master {
     char* block = nullptr;
     nemk::MasterDev dev{};
 };
+// nemgpu_resamples_solve: where every lock-step group's runs are reduced to their P/S/C/U counts (nem_resample.hpp)
+struct ResampleTally {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    nemk::VoteDesc* desc = nullptr;                   // [kTallyGroupCap]
+    uint8_t* maps = nullptr;                          // [kTallyGroupCap][kVoteMapStride]
+    int32_t* stats = nullptr;                         // [count][kResampleStats], row = the sample's index in the call
+};
+constexpr int kTallyGroupCap = 256;                   // (solve_many_one's largest lock-step group)
 // what nemgpu_solve_chunks hands to the builders of nemgpu_solve_many's pipeline instead of host matrices and graphs
 struct ChunkSource {
     const nemgpu_master* master = nullptr;
@@ -320,6 +330,7 @@ struct ChunkSource {
     uint8_t* const* labels = nullptr;                 // per problem: where the NCEM labels go (or null)
     nemgpu_votes* votes = nullptr;                    // (nemgpu_votes_solve) every group's runs voted on the device ...
     const int* slot = nullptr;                        // ... problem i into row slot[i] of the vote matrix
+    ResampleTally* tally = nullptr;                   // (nemgpu_resamples_solve) every group's runs counted into stats[slot[i]]
 };
 // The vote over the samples of partition()'s loop for one master and one organism selection (nem_vote.hpp): the
 // counts stay on the device, a batch of samples goes through a vote matrix of `batch` rows.
@@ -3291,6 +3302,8 @@ static int solve_many_one(nemgpu_problem* P, int count, const nemgpu_config* cfg
 static int adopt_chunk(nemgpu_engine* e, const nemgpu_master* M, const nemk::ChunkPlan& plan, int nnz_c);
 static int vote_group(nemgpu_votes* v, const std::vector<nemgpu_engine*>& E, const std::vector<int>& who,
                       const std::vector<nemgpu_result>& R, const ChunkSource* src);
+static int tally_group(ResampleTally* t, const std::vector<nemgpu_engine*>& E, const std::vector<int>& who,
+                       const std::vector<nemgpu_result>& R, const ChunkSource* src);
 static thread_local bool tl_runner = false;                  // this thread is one of nemgpu_solve_many_devices' runners
 
 // Four groups and more, six workers and more: two runners on the device (nemgpu_solve_many_devices with the device named
@@ -3489,6 +3502,7 @@ static int solve_many_one(nemgpu_problem* P, int count, const nemgpu_config* cfg
             }
             // the group's votes, read from the engines' own label and parameter buffers before the fetches recycle them
             if (r == NEMGPU_OK && src != nullptr && src->votes != nullptr) r = vote_group(src->votes, E, who, R, src);
+            if (r == NEMGPU_OK && src != nullptr && src->tally != nullptr) r = tally_group(src->tally, E, who, R, src);
             t_run += since(t0);
             for (size_t j = 0; j < E.size(); j++) { P[who[j]].result = R[j]; if (r != NEMGPU_OK) P[who[j]].rc = r; }
             if (r != NEMGPU_OK && rc == NEMGPU_OK) { rc = r; first_err = g_last_error; }
@@ -3678,10 +3692,12 @@ static int adopt_chunk(nemgpu_engine* e, const nemgpu_master* M, const nemk::Chu
     return NEMGPU_OK;
 }
 
-// nemgpu_solve_chunks; with `votes`, every run is also voted (vote_group) and a sample that keeps no family is skipped
-// (the reference writes empty files for it and gets no .uf) instead of refused
+// nemgpu_solve_chunks; with `votes`, every run is also voted (vote_group), with `tally` counted into its stats row
+// (tally_group), and then a sample that keeps no family is skipped (the reference writes empty files for it and gets no
+// .uf) instead of refused
 static int solve_chunks_impl(nemgpu_master* M, nemgpu_chunk* chunks, int count, int k, const float* prop, const float* center_k,
-                             const float* disp_k, const nemgpu_config* cfg, int workers, int group, nemgpu_votes* votes)
+                             const float* disp_k, const nemgpu_config* cfg, int workers, int group, nemgpu_votes* votes,
+                             ResampleTally* tally = nullptr)
 {
     if (!M || !chunks || count <= 0 || k <= 0 || k > kMaxKernelK || !prop || !center_k || !disp_k || !cfg) return NEMGPU_E_FUNCARG;
     HIPCHK(hipSetDevice(M->device));
@@ -3755,7 +3771,7 @@ static int solve_chunks_impl(nemgpu_master* M, nemgpu_chunk* chunks, int count, 
     for (int c = 0; c < count; c++) {
         nemgpu_chunk& q = chunks[c];
         q.n = counts[(size_t)c * 2]; q.nnz = counts[(size_t)c * 2 + 1];
-        if (q.n <= 0 && votes != nullptr) continue;
+        if (q.n <= 0 && (votes != nullptr || tally != nullptr)) continue;
         if (q.n <= 0) { set_error("nemgpu_solve_chunks: chunk " + std::to_string(c) + " holds no family"); q.rc = NEMGPU_E_ARG; return NEMGPU_E_ARG; }
         pplans.push_back(plans[(size_t)c]);
         nnzc.push_back(q.nnz);
@@ -3777,7 +3793,7 @@ static int solve_chunks_impl(nemgpu_master* M, nemgpu_chunk* chunks, int count, 
     }
     ChunkSource src;
     src.master = M; src.plans = pplans.data(); src.nnz = nnzc.data(); src.labels = labels.data();
-    src.votes = votes; src.slot = slot.data();
+    src.votes = votes; src.slot = slot.data(); src.tally = tally;
     const auto t_prep = std::chrono::steady_clock::now();
     const int np = (int)P.size();
     const int rc = np > 0 ? solve_many_one(P.data(), np, cfg, M->device, workers, group, &src) : NEMGPU_OK;
@@ -4025,6 +4041,90 @@ int nemgpu_votes_result(nemgpu_votes* v, int32_t* cnt, uint8_t* final_code, int3
             final_code[f] = !(st[(size_t)f] & nemk::VOTE_IN_PAN) ? nemk::kVoteNone : (st[(size_t)f] & nemk::VOTE_FORCED_U) ? 3 : best;
         }
     if (samples_voted) *samples_voted = v->samples_voted;
+    return NEMGPU_OK;
+}
+
+// ============================================================================================
+// The evolution curve's resamples (command_line.py:262-281, 591-625): many samples of one master solved as
+// nemgpu_solve_chunks solves them, each reduced on the device to the stats of partition(just_stats=True)
+// (nem_resample.hpp / nem_resample.hip).
+// ============================================================================================
+
+// one group of nemgpu_solve_many's pipeline, run and waited for: every member's code map from its final parameters
+// (launch_vote_classmap, as vote_group) and its labels counted into its stats row, straight from the engine's buffers
+static int tally_group(ResampleTally* t, const std::vector<nemgpu_engine*>& E, const std::vector<int>& who,
+                       const std::vector<nemgpu_result>& R, const ChunkSource* src)
+{
+    const int B = (int)E.size();
+    if (B > kTallyGroupCap) { set_error("resamples: a group larger than the tally's"); return NEMGPU_E_INTERNAL; }
+    std::vector<nemk::VoteDesc> d((size_t)B);
+    for (int j = 0; j < B; j++) {
+        const nemgpu_engine* e = E[(size_t)j];
+        if (!e->ncem() || e->k != 3) { set_error("resamples: NCEM runs of three classes are counted"); return NEMGPU_E_ARG; }
+        const int i = who[(size_t)j];
+        d[(size_t)j] = nemk::VoteDesc{e->lab[e->cur] + e->lo, src->plans[i].list, e->prop + e->par_o_center, e->prop + e->par_o_disp,
+                                      e->n, e->d, R[(size_t)j].status, src->slot[i]};
+    }
+    HIPCHK(hipSetDevice(t->device));
+    HIPCHK(hipMemcpyAsync(t->desc, d.data(), (size_t)B * sizeof(nemk::VoteDesc), hipMemcpyHostToDevice, t->stream));
+    nemk::launch_vote_classmap(t->desc, B, 3, t->maps, t->stream);
+    nemk::launch_resample_tally(t->desc, B, t->maps, t->stats, t->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(t->stream));          // (the engines go to the fetches next, and d goes out of scope)
+    return NEMGPU_OK;
+}
+
+int nemgpu_resamples_solve(nemgpu_master* M, nemgpu_chunk* chunks, int count, int k, const float* prop, const float* center_k,
+                           const float* disp_k, const nemgpu_config* cfg, int workers, int group, int32_t* stats)
+{
+    if (!M || !chunks || count <= 0 || !prop || !center_k || !disp_k || !cfg || !stats) return NEMGPU_E_FUNCARG;
+    if (k != 3 || cfg->algo != NEMGPU_ALGO_NCEM) { set_error("nemgpu_resamples_solve: the stats take NCEM runs of three classes"); return NEMGPU_E_ARG; }
+    // every check before anything is launched; a resample is an ordered SET of organisms (the reference's OrderedSet)
+    std::vector<int> seen((size_t)M->d, -1), off((size_t)count + 1, 0);
+    for (int c = 0; c < count; c++) {
+        const nemgpu_chunk& q = chunks[c];
+        if (!q.organisms || q.dc <= 0 || q.dc > M->d) { set_error("nemgpu_resamples_solve: sample " + std::to_string(c) + ": 1 .. d organisms are needed"); return NEMGPU_E_FUNCARG; }
+        for (int t = 0; t < q.dc; t++) {
+            const int o = q.organisms[t];
+            if (o < 0 || o >= M->d) { set_error("nemgpu_resamples_solve: sample " + std::to_string(c) + ": organism index out of range"); return NEMGPU_E_ARG; }
+            if (seen[(size_t)o] == c) { set_error("nemgpu_resamples_solve: sample " + std::to_string(c) + ": organism " + std::to_string(o) + " repeated"); return NEMGPU_E_ARG; }
+            seen[(size_t)o] = c;
+        }
+        off[(size_t)c + 1] = off[(size_t)c] + q.dc;
+    }
+    HIPCHK(hipSetDevice(M->device));
+    const int total = off[(size_t)count];
+    std::vector<int> org((size_t)total);
+    for (int c = 0; c < count; c++) memcpy(org.data() + off[(size_t)c], chunks[c].organisms, (size_t)chunks[c].dc * 4);
+    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t b_stats = a256((size_t)count * nemk::kResampleStats * 4), b_desc = a256((size_t)kTallyGroupCap * sizeof(nemk::VoteDesc)),
+                 b_maps = a256((size_t)kTallyGroupCap * nemk::kVoteMapStride), b_off = a256(((size_t)count + 1) * 4), b_org = a256((size_t)total * 4);
+    ResampleTally t;
+    t.device = M->device;
+    char* block = nullptr;
+    struct Free {
+        ResampleTally& t; char*& p;
+        ~Free() { if (t.stream) { (void)hipStreamSynchronize(t.stream); (void)hipStreamDestroy(t.stream); } if (p) (void)hipFree(p); }
+    } release{t, block};
+    HIPCHK(hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking));
+    if (hipMalloc(&block, b_stats + b_desc + b_maps + b_off + b_org) != hipSuccess) {
+        (void)hipGetLastError(); block = nullptr; set_error("nemgpu_resamples_solve: device memory"); return NEMGPU_E_MEMORY;
+    }
+    t.stats = (int32_t*)block;
+    t.desc = (nemk::VoteDesc*)(block + b_stats);
+    t.maps = (uint8_t*)(block + b_stats + b_desc);
+    int* d_off = (int*)(block + b_stats + b_desc + b_maps);
+    int* d_org = (int*)(block + b_stats + b_desc + b_maps + b_off);
+    // core_exact / accessory of every sample on the tally's stream, beside the chunk pipeline's phase 1
+    HIPCHK(hipMemsetAsync(t.stats, 0, (size_t)count * nemk::kResampleStats * 4, t.stream));
+    HIPCHK(hipMemcpyAsync(d_off, off.data(), ((size_t)count + 1) * 4, hipMemcpyHostToDevice, t.stream));
+    HIPCHK(hipMemcpyAsync(d_org, org.data(), (size_t)total * 4, hipMemcpyHostToDevice, t.stream));
+    nemk::launch_resample_core(M->dev.xt, M->n, M->nw64, d_org, d_off, count, t.stats, t.stream);
+    HIPCHK(hipGetLastError());
+    const int rc = solve_chunks_impl(M, chunks, count, k, prop, center_k, disp_k, cfg, workers, group, nullptr, &t);
+    if (rc != NEMGPU_OK) return rc;
+    HIPCHK(hipMemcpyAsync(stats, t.stats, (size_t)count * nemk::kResampleStats * 4, hipMemcpyDeviceToHost, t.stream));
+    HIPCHK(hipStreamSynchronize(t.stream));
     return NEMGPU_OK;
 }
 

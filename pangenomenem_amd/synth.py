@@ -147,12 +147,14 @@ def ring_graph(n, seed, deg, wlo, whi):
     return ptr, dst.astype(np.int32), wu[inv].astype(np.float32)
 
 
-def master_pangenome(n, d, seed, chord_frac=0.05, carry_path=0.8, carry_chord=0.08):
+def master_pangenome(n, d, seed, chord_frac=0.05, carry_path=0.8, carry_chord=0.08, a=0.3, b=0.3):
     """A whole pangenome for the chunk voting loop (ppanggolin.py:995-1097): the U-shaped presence/absence matrix over ALL
     d organisms, the contiguity graph's structure, and per directed edge the organisms that carry the adjacency -- a
     subset of those where both families are present (a path edge in most of them, a chord in few), the same set in both
-    directions.  Returns x uint8 [n][d], (ptr, idx), edge_bits uint32 [nnz][ceil(d/32)]."""
-    x, _ = ushaped_pa_matrix(n, d, seed)
+    directions.  a, b: the Beta spectrum of ushaped_pa_matrix (a = 0.05, b = 1: mostly cloud, as real pangenomes are, so a
+    sample of few organisms keeps a small, sparse share of the families).  Returns x uint8 [n][d], (ptr, idx), edge_bits
+    uint32 [nnz][ceil(d/32)]."""
+    x, _ = ushaped_pa_matrix(n, d, seed, a=a, b=b)
     ptr, idx, _ = contiguity_graph(n, seed, chord_frac=chord_frac)
     rng = np.random.Generator(np.random.PCG64(seed + 15485863))
     src = np.repeat(np.arange(n), np.diff(ptr)).astype(np.int64)
@@ -175,7 +177,7 @@ def master_pangenome(n, d, seed, chord_frac=0.05, carry_path=0.8, carry_chord=0.
 
 
 def master_pangenome_counts(n, d, seed, multi_frac=0.02, max_count=4, loops=0.01, dense_loops=0, directed=False,
-                            chord_frac=0.05, carry_path=0.8, carry_chord=0.08):
+                            chord_frac=0.05, carry_path=0.8, carry_chord=0.08, a=0.3, b=0.3):
     """master_pangenome with occurrence counts (nemgpu_master_create_counts): the same matrix and carried organisms, plus
     tandem self-loops i -> i on about n*loops families (carried by about half the organisms that hold the family) and
     on the dense_loops families present in the most organisms (carried by all of them: the long extra lists).  A carried
@@ -183,8 +185,8 @@ def master_pangenome_counts(n, d, seed, multi_frac=0.02, max_count=4, loops=0.01
     the same count from both endpoints.  directed: the counts of a DiGraph as the coverage sums them, sens + antisens --
     an adjacency's count plus, in half the pairs, a second draw for the other direction; a self-loop's doubled.  A
     self-loop is listed once, at the end of its family's row.  Returns x, (ptr, idx), edge_bits, (extra_ptr, extra_org,
-    extra_count)."""
-    x, (ptr, idx), eb = master_pangenome(n, d, seed, chord_frac=chord_frac, carry_path=carry_path, carry_chord=carry_chord)
+    extra_count).  a, b: as master_pangenome."""
+    x, (ptr, idx), eb = master_pangenome(n, d, seed, chord_frac=chord_frac, carry_path=carry_path, carry_chord=carry_chord, a=a, b=b)
     rng = np.random.Generator(np.random.PCG64(seed + 32452843))
     wf = (d + 31) // 32
     src = np.repeat(np.arange(n), np.diff(ptr)).astype(np.int64)

@@ -10,20 +10,13 @@ import numpy as np
 import pytest
 
 from pangenomenem_amd import synth
-from pangenomenem_amd.partitioning import CODES, partition_dicts, vote_final, vote_host, vote_map, vote_state
+from pangenomenem_amd.partitioning import CODES, partition_dicts, vote_final
+from tests.master_shapes import host_partition, host_solve
 from tests.util import maxdiff
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nei_counts")
-
-
-def host_solve(x, ptr, idx, eb, counts, subs, **cfg):
-    from pangenomenem_amd.batch import solve_many
-    from pangenomenem_amd.chunks import form_chunk_host
-    host = [form_chunk_host(x, ptr, idx, eb, s, edge_counts=counts) for s in subs]
-    probs = [(xc, nei, 3) + synth.default_init(xc.shape[1]) for xc, nei, _ in host]
-    return host, solve_many(probs, workers=4, group=8, **cfg)
 
 
 def same_run(g, w, fam):
@@ -102,27 +95,6 @@ def test_coverage_above_65535(gpu_lib):
     want, want16 = solve_many([(xc, nei, 3) + init, (xc, clamped, 3) + init], workers=1, group=1, **cfg)
     same_run(got, want, fam)
     assert not np.array_equal(want["crit"], want16["crit"])
-
-
-def host_partition(x, ptr, idx, eb, counts, organisms, chunk_size, rng, tie, seed, batch=16, max_samples=5000):
-    """partition()'s sequential loop on the host: the samples formed by form_chunk_host, solved by solve_many, voted by
-    vote_map and vote_host; the draws after the stop undone"""
-    organisms = np.asarray(organisms)
-    st = vote_state(x.shape[0], x[:, organisms].any(axis=1))
-    cfg = dict(algo="ncem", beta=0.5, disper="sk_", it_max=100, tie=tie, seed=seed)
-    while st["samples"] < max_samples:
-        states, samples = [], []
-        for _ in range(batch):
-            states.append(rng.getstate())
-            samples.append(organisms[rng.sample(range(len(organisms)), chunk_size)])
-        host, res = host_solve(x, ptr, idx, eb, counts, samples, **cfg)
-        votes = [(fam, r["c"].argmax(1), vote_map(r["status"], r["center"], r["disp"])) for (_, _, fam), r in zip(host, res)]
-        stop = vote_host(st, votes, len(organisms), chunk_size)
-        if stop >= 0:
-            if stop + 1 < batch:
-                rng.setstate(states[stop + 1])
-            return st
-    raise AssertionError("no end")
 
 
 @pytest.mark.parametrize("tie,directed,batch", [("hash", False, 64), ("libc", True, 7)])

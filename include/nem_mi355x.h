@@ -223,6 +223,33 @@ int nemgpu_master_create(nemgpu_master** out, int device, int n, int d, const ui
 int nemgpu_master_create_counts(nemgpu_master** out, int device, int n, int d, const uint32_t* xbits, const int32_t* nei_ptr,
                                 const int32_t* nei_idx, const uint32_t* edge_bits, const int32_t* extra_ptr,
                                 const int32_t* extra_org, const int32_t* extra_count);
+/* The same master built ON THE DEVICE from the organisms' gene orders: exactly what nemgpu_master_create_counts makes of
+   the graph that PPanGGOLiN's __neighborhood_computation (ppanggolin.py:463-530) builds from the same annotations, with
+   no graph, no n x d byte matrix and no per-edge byte row on either side.  HOST arrays, copied once:
+     genes[g]             the family id (0 <= id < f, the caller's numbering) of every gene in walk order: organisms in
+                          the order of `annotations`, inside one its contigs, inside a contig its genes;
+     contig_ptr[c + 1]    contig j is genes[contig_ptr[j] .. contig_ptr[j + 1]) (from 0 to g, non-decreasing);
+     contig_org[c]        the contig's organism = its column of the master (< d; walk order is array order);
+     contig_circular[c]   0 / 1;     repeated[f]: 0 / 1 per family id (families_repeted), or NULL;
+     directed             0: nx.Graph (what PPanGGOLiN's CLI builds), 1: nx.DiGraph.
+   A gene of a repeated family does not exist (links bridge over it); master family i is the i-th family id in the order
+   of first kept gene (nemgpu_master_fetch's `order`), a family without a kept gene is not in the master; every kept
+   gene but its contig's first links (its family, the previous kept gene's family, organism), a circular contig then
+   (first kept, last kept, organism), also with one or two kept genes; counts as __add_link makes them; a family's
+   neighbours in nx.all_neighbors order (chunks.master_arrays_from_graph's docstring is the rule).  Every argument is
+   checked on the host before any HIP call (NEMGPU_E_ARG, nemgpu_last_error says why); g + c < 2^30; 2 bits(n) + bits(d)
+   <= 63; the limits of nemgpu_master_create_counts.  The master is destroyed by nemgpu_master_destroy. */
+int nemgpu_master_create_orders(nemgpu_master** out, int device, int d, int f, int directed, const int32_t* genes, int g,
+                                const int32_t* contig_ptr, const int32_t* contig_org, const uint8_t* contig_circular, int c,
+                                const uint8_t* repeated);
+/* What a master holds, of whichever constructor: sizes (n families, d organisms, nnz CSR entries, n_extra pairs with
+   count >= 2; any pointer may be NULL), and the arrays as nemgpu_master_create_counts takes them, read back from the
+   device: xbits[n][ceil(d/32)], nei_ptr[n + 1], nei_idx[nnz], edge_bits[nnz][ceil(d/32)], extra_ptr[nnz + 1],
+   extra_org[n_extra], extra_count[n_extra], order[n] (master family i = caller id order[i]; 0, 1, ... for a master
+   made from arrays).  HOST buffers; any may be NULL. */
+int nemgpu_master_shape(const nemgpu_master* m, int* n, int* d, int* nnz, int* n_extra);
+int nemgpu_master_fetch(const nemgpu_master* m, uint32_t* xbits, int32_t* nei_ptr, int32_t* nei_idx, uint32_t* edge_bits,
+                        int32_t* extra_ptr, int32_t* extra_org, int32_t* extra_count, int32_t* order);
 void nemgpu_master_destroy(nemgpu_master* m);
 /* One sample.  in: organisms[dc] (indices into the master's, the chunk's column order).  out: n = families with at least
    one sampled organism, nnz = directed edges of the chunk's graph; optional arrays (NULL: not wanted): keep[ceil(n_master

@@ -17,6 +17,10 @@ the edges.  A bits-only master takes every count as 1, which is the reference's 
 twice in an organism (tandem duplicates, repeated operons and every edge of a directed graph do).
 ``master_arrays_from_graph`` / ``Master.from_graph`` take PPanGGOLiN's graph as it is and make the counts.
 
+``Master.from_orders`` / ``Master.from_annotations`` build the same master on the device from the organisms' gene orders
+(``nemgpu_master_create_orders``, csrc/nem_orders.hip): no graph, no networkx; ``master_arrays_from_orders`` is that build
+in numpy.
+
 ``Master`` puts that one pangenome on the device (``nemgpu_master_create[_counts]``); ``solve_chunks`` solves any number of
 samples in ONE library call (``nemgpu_solve_chunks``): the device forms every sample's problem straight into its engine's
 buffers, the lock-step pipeline of ``batch.solve_many`` runs them.  ``form_chunk_host`` is the same formation in numpy --
@@ -52,6 +56,21 @@ def pack_rows(x):
     bits = np.packbits(x, axis=1, bitorder="little")
     rows[:, :bits.shape[1]] = bits
     return rows.view(np.uint32)
+
+
+def _bind_master(lib):
+    lib.nemgpu_master_create_orders.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.nemgpu_master_shape.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
+    lib.nemgpu_master_fetch.argtypes = [C.c_void_p] * 9
+    lib.nemgpu_master_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.nemgpu_master_create_counts.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.nemgpu_master_destroy.argtypes = [C.c_void_p]
+    lib.nemgpu_master_destroy.restype = None
+    lib.nemgpu_solve_chunks.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(Config), C.c_int, C.c_int]
+    return lib
 
 
 def form_chunk_host(x, ptr, idx, edge_bits, organisms, edge_counts=None):
@@ -163,28 +182,153 @@ def master_arrays_from_graph(graph, organisms=None):
     return x, (ptr, np.asarray(idx, np.int32)), edge_bits, edge_counts, families, organisms
 
 
+FAMILY = 1                  # index of the family in a gene's annotation (ppanggolin.py:25)
+
+
+def orders_from_annotations(annotations, organisms, circular_contigs=(), repeated=(), family=FAMILY):
+    """PPanGGOLiN's ``annotations`` ({organism: {contig: OrderedDict(gene -> info)}}, the family at info[family]) as the
+    flat gene orders of nemgpu_master_create_orders.  organisms: the master's organisms in column order (every organism
+    of annotations must be among them); circular_contigs: the contig names of circular_contig_size; repeated: the
+    family names of families_repeted.  The walk is __neighborhood_computation's (ppanggolin.py:478-481): annotations'
+    organisms, their contigs, their genes, each in dict order.  Returns a dict: genes int32 [G], contig_ptr int32
+    [C + 1], contig_org int32 [C], contig_circular uint8 [C], repeated uint8 [F], d, families (the family name of every
+    id, in order of first gene), organisms."""
+    organisms = list(organisms)
+    col = {o: c for c, o in enumerate(organisms)}
+    if len(col) != len(organisms):
+        raise ValueError("organisms: distinct names")
+    circular_contigs = set(circular_contigs)
+    fam_id = {}
+    genes, cptr, corg, circ = [], [0], [], []
+    for org, contigs in annotations.items():
+        if org not in col:
+            raise ValueError("organism %r of the annotations is not among `organisms`" % (org,))
+        for contig, annot in contigs.items():
+            for info in annot.values():
+                genes.append(fam_id.setdefault(info[family], len(fam_id)))
+            cptr.append(len(genes))
+            corg.append(col[org])
+            circ.append(1 if contig in circular_contigs else 0)
+    rep = np.zeros(max(len(fam_id), 1), np.uint8)
+    for name in repeated:
+        if name in fam_id:
+            rep[fam_id[name]] = 1
+    return dict(genes=np.asarray(genes, np.int32), contig_ptr=np.asarray(cptr, np.int32), contig_org=np.asarray(corg, np.int32),
+                contig_circular=np.asarray(circ, np.uint8), repeated=rep, d=len(organisms), families=list(fam_id), organisms=organisms)
+
+
+def _check_orders(genes, contig_ptr, contig_org, contig_circular, repeated, d, f):
+    genes = np.ascontiguousarray(genes, np.int32)
+    contig_ptr = np.ascontiguousarray(contig_ptr, np.int32)
+    contig_org = np.ascontiguousarray(contig_org, np.int32)
+    contig_circular = np.ascontiguousarray(contig_circular, np.uint8)
+    c = len(contig_org)
+    if genes.ndim != 1 or contig_ptr.shape != (c + 1,) or contig_circular.shape != (c,):
+        raise ValueError("orders: genes [G], contig_ptr [C + 1], contig_org [C], contig_circular [C]")
+    if f is None:
+        f = len(repeated) if repeated is not None else (int(genes.max()) + 1 if len(genes) else 1)
+    if repeated is not None:
+        repeated = np.ascontiguousarray(repeated, np.uint8)
+        if repeated.shape != (f,):
+            raise ValueError("orders: repeated [F]")
+    if d <= 0 or f <= 0:
+        raise ValueError("orders: D and F must be positive")
+    if c == 0 or contig_ptr[0] != 0 or contig_ptr[-1] != len(genes) or (np.diff(contig_ptr) < 0).any():
+        raise ValueError("orders: contig_ptr must run from 0 to the number of genes, monotone")
+    if len(genes) and (genes.min() < 0 or genes.max() >= f):
+        raise ValueError("orders: family id out of range")
+    if contig_org.min() < 0 or contig_org.max() >= d:
+        raise ValueError("orders: contig organism out of range")
+    return genes, contig_ptr, contig_org, contig_circular, repeated, int(d), int(f)
+
+
+def master_arrays_from_orders(genes, contig_ptr, contig_org, contig_circular, d, repeated=None, f=None, directed=False):
+    """The master that master_arrays_from_graph makes of the graph __neighborhood_computation (ppanggolin.py:463-530)
+    builds, from the flat gene orders (nemgpu_master_create_orders' arguments; include/nem_mi355x.h), in numpy: the
+    statement of what csrc/nem_orders.hip computes, step by step the same.
+      * a gene of a repeated family does not exist; a gene's previous kept gene is the last kept one before it, if in its contig;
+      * families in the order of their first kept gene;
+      * a link per kept gene that has a previous one (time: its position + its contig's index), a link (first kept, last
+        kept) per circular contig with a kept gene (time: the contig's end + its index);
+      * a link (a, b) is the half-edges (row a, neighbour b) and (row b, neighbour a) -- one when a = b and the graph is
+        undirected; in a DiGraph the first is a successor entry, the second a predecessor entry;
+      * count[row, neighbour, organism] = its half-edges; a row's neighbours: those with a predecessor entry (always, for
+        a Graph) by the first time of one, then the others by the first time of a successor entry.
+    Returns x uint8 [n][d], (ptr, idx), edge_bits uint32 [nnz][ceil(d/32)], edge_counts (extra_ptr, extra_org,
+    extra_count), order int32 [n] (master family i = caller id order[i]), range(d)."""
+    genes, contig_ptr, contig_org, contig_circular, repeated, d, f = _check_orders(genes, contig_ptr, contig_org, contig_circular, repeated, d, f)
+    g, c = len(genes), len(contig_org)
+    wf = (d + 31) // 32
+    pos = np.arange(g, dtype=np.int64)
+    kept = np.ones(g, bool) if repeated is None else repeated[genes] == 0
+    contig_of = np.repeat(np.arange(c, dtype=np.int64), np.diff(contig_ptr))
+    last = np.maximum.accumulate(np.where(kept, pos, -1)) if g else pos
+    prev = np.concatenate([[-1], last[:-1]]) if g else pos
+    kp = np.flatnonzero(kept)
+    fam_of, first = np.unique(genes[kp], return_index=True)
+    order = fam_of[np.argsort(first, kind="stable")].astype(np.int32)
+    n = len(order)
+    newid = np.full(f, -1, np.int64)
+    newid[order] = np.arange(n)
+    x = np.zeros((n, d), np.uint8)
+    x[newid[genes[kp]], contig_org[contig_of[kp]]] = 1
+    cj = contig_of[kp]
+    start, end = contig_ptr[cj].astype(np.int64), contig_ptr[cj + 1].astype(np.int64)
+    linked = prev[kp] >= start
+    closing = ~linked & (contig_circular[cj] != 0)
+    has = linked | closing
+    other = np.where(linked, prev[kp], last[np.maximum(end - 1, 0)])[has]
+    t = np.where(linked, kp + cj, end + cj)[has]
+    a, b, o = newid[genes[kp[has]]], newid[genes[other]], contig_org[cj[has]].astype(np.int64)
+    if directed:
+        row, nbr, org, key = np.concatenate([a, b]), np.concatenate([b, a]), np.concatenate([o, o]), np.concatenate([t + (1 << 31), t])
+    else:
+        two = a != b
+        row, nbr, org, key = np.concatenate([a, b[two]]), np.concatenate([b, a[two]]), np.concatenate([o, o[two]]), np.concatenate([t, t[two]])
+    srt = np.lexsort((org, nbr, row))
+    row, nbr, org, key = row[srt], nbr[srt], org[srt], key[srt]
+    m = len(row)
+    new_pair = np.ones(m, bool)
+    new_pair[1:] = (row[1:] != row[:-1]) | (nbr[1:] != nbr[:-1]) | (org[1:] != org[:-1])
+    new_edge = np.ones(m, bool)
+    new_edge[1:] = (row[1:] != row[:-1]) | (nbr[1:] != nbr[:-1])
+    pair_at, edge_at = np.flatnonzero(new_pair), np.flatnonzero(new_edge)
+    pair_count = np.diff(np.append(pair_at, m))
+    pair_edge = np.cumsum(new_edge)[pair_at] - 1
+    nnz = len(edge_at)
+    edge_first = np.minimum.reduceat(key, edge_at) if nnz else np.zeros(0, np.int64)
+    perm = np.lexsort((edge_first, row[edge_at]))             # CSR entry e is edge perm[e]
+    inv = np.empty(nnz, np.int64)
+    inv[perm] = np.arange(nnz)
+    ptr = np.zeros(n + 1, np.int32)
+    ptr[1:] = np.cumsum(np.bincount(row[edge_at], minlength=n))
+    idx = nbr[edge_at][perm].astype(np.int32)
+    edge_bits = np.zeros((nnz, wf), np.uint32)
+    entry = inv[pair_edge]
+    np.bitwise_or.at(edge_bits, (entry, org[pair_at] >> 5), (np.uint32(1) << (org[pair_at] & 31).astype(np.uint32)))
+    multi = pair_count >= 2
+    xs = np.lexsort((org[pair_at][multi], entry[multi]))
+    xptr = np.zeros(nnz + 1, np.int32)
+    xptr[1:] = np.cumsum(np.bincount(entry[multi], minlength=nnz))
+    edge_counts = (xptr, org[pair_at][multi][xs].astype(np.int32), pair_count[multi][xs].astype(np.int32))
+    return x, (ptr, idx), edge_bits, edge_counts, order, list(range(d))
+
+
 class Master:
     """One pangenome on the device: presence/absence matrix, neighbourhood graph, per directed edge its organisms."""
 
     def __init__(self, x, ptr, idx, edge_bits, device=0, edge_counts=None):
         """edge_counts: None (every count 1: nemgpu_master_create) or (extra_ptr, extra_org, extra_count), the
         (edge, organism) pairs whose occurrence count is 2 or more (nemgpu_master_create_counts)"""
-        self.lib = load_library()
+        self.lib = _bind_master(load_library())
         lib = self.lib
-        lib.nemgpu_master_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.nemgpu_master_create_counts.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.nemgpu_master_destroy.argtypes = [C.c_void_p]
-        lib.nemgpu_master_destroy.restype = None
-        lib.nemgpu_solve_chunks.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.POINTER(Config), C.c_int, C.c_int]
         x = np.asarray(x)
         if x.dtype == np.uint32:
             raise ValueError("Master takes the 0/1 byte matrix (it packs the rows itself)")
         self.n, self.d = x.shape
         self.wf = (self.d + 31) // 32
         rows = pack_rows(x)
-        self._rows = rows                                     # (partition(): which families are core exact)
+        self._rows_host = rows                                # (partition(): which families are core exact)
         ptr = np.ascontiguousarray(ptr, np.int32)
         idx = np.ascontiguousarray(idx, np.int32)
         edge_bits = np.ascontiguousarray(edge_bits, np.uint32).reshape(len(idx), self.wf) if len(idx) else np.zeros((1, self.wf), np.uint32)
@@ -214,6 +358,70 @@ class Master:
         m = cls(x, ptr, idx, edge_bits, device=device, edge_counts=edge_counts)
         m.names, m.organism_names = list(families), list(orgs)
         return m
+
+    @classmethod
+    def from_orders(cls, genes, contig_ptr, contig_org, contig_circular, d, repeated=None, f=None, directed=False, device=0):
+        """The master of these gene orders, built on the device (nemgpu_master_create_orders; the arguments of
+        master_arrays_from_orders, which states what it computes).  .order int32 [n]: master family i is the caller's
+        family id order[i]."""
+        genes, contig_ptr, contig_org, contig_circular, repeated, d, f = _check_orders(genes, contig_ptr, contig_org, contig_circular, repeated, d, f)
+        m = cls.__new__(cls)
+        m.lib = _bind_master(load_library())
+        m._h = C.c_void_p()
+        rc = m.lib.nemgpu_master_create_orders(C.byref(m._h), int(device), d, f, 1 if directed else 0, genes.ctypes.data, len(genes),
+                                               contig_ptr.ctypes.data, contig_org.ctypes.data, contig_circular.ctypes.data, len(contig_org),
+                                               repeated.ctypes.data if repeated is not None else None)
+        if rc != 0:
+            raise NemGpuError("nemgpu_master_create_orders failed (status %d): %s" % (rc, m.lib.nemgpu_last_error().decode()))
+        m.n, m.d, _, _ = m.shape()
+        m.wf = (m.d + 31) // 32
+        m.order = np.zeros(m.n, np.int32)
+        m._fetch(order=m.order)
+        return m
+
+    @classmethod
+    def from_annotations(cls, annotations, organisms, circular_contigs=(), repeated=(), directed=False, device=0, family=FAMILY):
+        """Master.from_orders of orders_from_annotations(...): PPanGGOLiN's annotations straight to the device.  Keeps the
+        family and organism names (.names, .organism_names) as Master.from_graph does."""
+        o = orders_from_annotations(annotations, organisms, circular_contigs, repeated, family)
+        m = cls.from_orders(o["genes"], o["contig_ptr"], o["contig_org"], o["contig_circular"], o["d"], repeated=o["repeated"],
+                            directed=directed, device=device)
+        m.names, m.organism_names = [o["families"][i] for i in m.order], list(o["organisms"])
+        return m
+
+    def shape(self):
+        """(n families, d organisms, nnz CSR entries, pairs with count >= 2) as the device holds them (nemgpu_master_shape)"""
+        v = [C.c_int() for _ in range(4)]
+        rc = self.lib.nemgpu_master_shape(self._h, *(C.byref(a) for a in v))
+        if rc != 0:
+            raise NemGpuError("nemgpu_master_shape failed (status %d)" % rc)
+        return tuple(a.value for a in v)
+
+    def _fetch(self, rows=None, ptr=None, idx=None, edge_bits=None, xptr=None, xorg=None, xcnt=None, order=None):
+        args = [a.ctypes.data if a is not None and a.size else None for a in (rows, ptr, idx, edge_bits, xptr, xorg, xcnt, order)]
+        rc = self.lib.nemgpu_master_fetch(self._h, *args)
+        if rc != 0:
+            raise NemGpuError("nemgpu_master_fetch failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+
+    @property
+    def _rows(self):
+        """the packed rows uint32 [n][ceil(d/32)] on the host; a master built on the device fetches them once"""
+        if getattr(self, "_rows_host", None) is None:
+            self._rows_host = np.zeros((self.n, self.wf), np.uint32)
+            self._fetch(rows=self._rows_host)
+        return self._rows_host
+
+    def arrays(self):
+        """The master read back from the device (nemgpu_master_fetch), of whichever constructor: rows uint32
+        [n][ceil(d/32)] (packed: pack_rows of the byte matrix), (ptr, idx), edge_bits uint32 [nnz][ceil(d/32)],
+        edge_counts (extra_ptr, extra_org, extra_count), order int32 [n]."""
+        n, d, nnz, nx = self.shape()
+        wf = (d + 31) // 32
+        rows, ptr, idx = np.zeros((n, wf), np.uint32), np.zeros(n + 1, np.int32), np.zeros(nnz, np.int32)
+        eb, xptr = np.zeros((nnz, wf), np.uint32), np.zeros(nnz + 1, np.int32)
+        xorg, xcnt, order = np.zeros(nx, np.int32), np.zeros(nx, np.int32), np.zeros(n, np.int32)
+        self._fetch(rows, ptr, idx, eb, xptr, xorg, xcnt, order)
+        return rows, (ptr, idx), eb, (xptr, xorg, xcnt), order
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -33,6 +33,7 @@
 #include "nem_rng.hpp"
 #include "nem_kernels.hpp"
 #include "nem_chunks.hpp"
+#include "nem_orders.hpp"
 #include "nem_vote.hpp"
 #include "nem_resample.hpp"
 
@@ -309,9 +310,11 @@ struct nemgpu_engine {
 // (nem_chunks.hpp).  One allocation; the stream carries the formation's phase 1.
 struct nemgpu_master {
     int device = 0, n = 0, d = 0, wf = 0, nw64 = 0, nnz = 0;
+    int nx = 0;                                       // (edge, organism) pairs with count >= 2
     hipStream_t stream = nullptr;
     char* block = nullptr;
     nemk::MasterDev dev{};
+    std::vector<int32_t> order;                       // nemgpu_master_create_orders: family i = caller id order[i] (else empty: i)
 };
 // nemgpu_resamples_solve: where every lock-step group's runs are reduced to their P/S/C/U counts (nem_resample.hpp)
 struct ResampleTally {
@@ -3651,7 +3654,115 @@ int nemgpu_master_create_counts(nemgpu_master** out, int device, int n, int d, c
     if (err != hipSuccess) return fail("nemgpu_master_create: upload failed");
     (void)hipFree(xf_tmp);
     m->dev = nemk::MasterDev{n, d, wf, nw64, nnz, xt, dptr, didx, deb, dxptr, dxorg, dxadd};
+    m->nx = nx;
     *out = m;
+    return NEMGPU_OK;
+}
+
+// The gene orders of nemgpu_master_create_orders, checked on the host (no HIP call before them)
+static int check_orders(int d, int f, int g, int c, const int32_t* genes, const int32_t* contig_ptr, const int32_t* contig_org,
+                        const uint8_t* contig_circular)
+{
+    if (d <= 0 || f <= 0 || g <= 0 || c <= 0 || !genes || !contig_ptr || !contig_org || !contig_circular) {
+        set_error("nemgpu_master_create_orders: sizes, genes and contigs are needed"); return NEMGPU_E_FUNCARG;
+    }
+    if ((d + 31) / 32 > nemk::chunk_mask_words_max()) { set_error("nemgpu_master_create_orders: more than 131 072 organisms"); return NEMGPU_E_ARG; }
+    if ((long long)g + c >= (1ll << 30)) { set_error("orders: genes + contigs must stay below 2^30"); return NEMGPU_E_ARG; }
+    if (contig_ptr[0] != 0 || contig_ptr[c] != g) { set_error("orders: contig_ptr must run from 0 to the number of genes"); return NEMGPU_E_ARG; }
+    for (int j = 0; j < c; j++) {
+        if (contig_ptr[j + 1] < contig_ptr[j]) { set_error("orders: contig_ptr not monotone"); return NEMGPU_E_ARG; }
+        if (contig_org[j] < 0 || contig_org[j] >= d) { set_error("orders: contig " + std::to_string(j) + ": organism out of range"); return NEMGPU_E_ARG; }
+    }
+    for (int p = 0; p < g; p++)
+        if (genes[p] < 0 || genes[p] >= f) { set_error("orders: gene " + std::to_string(p) + ": family id out of range"); return NEMGPU_E_ARG; }
+    return NEMGPU_OK;
+}
+
+int nemgpu_master_create_orders(nemgpu_master** out, int device, int d, int f, int directed, const int32_t* genes, int g,
+                                const int32_t* contig_ptr, const int32_t* contig_org, const uint8_t* contig_circular, int c,
+                                const uint8_t* repeated)
+{
+    if (!out) return NEMGPU_E_FUNCARG;
+    *out = nullptr;
+    { const int r = check_orders(d, f, g, c, genes, contig_ptr, contig_org, contig_circular); if (r != NEMGPU_OK) return r; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no usable HIP device: this library has no CPU fallback"); return NEMGPU_E_DEVICE; }
+    if (device < 0 || device >= ndev) { set_error("nemgpu_master_create_orders: bad device index"); return NEMGPU_E_ARG; }
+    g_hip_used.store(true);
+    HIPCHK(hipSetDevice(device));
+    nemgpu_master* m = new nemgpu_master();
+    nemk::OrdersBuild* build = nullptr;
+    auto fail = [&](int rc, const std::string& what) { nemk::orders_free(build); if (m->block) (void)hipFree(m->block);
+                                                       if (m->stream) (void)hipStreamDestroy(m->stream); delete m; set_error(what); return rc; };
+    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) return fail(NEMGPU_E_DEVICE, "hipStreamCreate failed");
+    const nemk::OrdersIn in{d, f, directed ? 1 : 0, g, c, genes, contig_ptr, contig_org, contig_circular, repeated};
+    int n = 0, nnz = 0, nx = 0;
+    hipError_t err = nemk::orders_stage(in, m->stream, &build, &n, &nnz, &nx);
+    if (err == hipErrorInvalidValue && n == 0) return fail(NEMGPU_E_ARG, "orders: no gene is kept (every family is repeated)");
+    if (err == hipErrorInvalidValue) return fail(NEMGPU_E_ARG, "orders: too many families for this many organisms (2 bits(n) + bits(d) > 63)");
+    if (err != hipSuccess) return fail(NEMGPU_E_DEVICE, std::string("nemgpu_master_create_orders: ") + hipGetErrorString(err));
+    const int wf = (d + 31) / 32, nw64 = (n + 63) / 64;
+    m->device = device; m->n = n; m->d = d; m->wf = wf; m->nw64 = nw64; m->nnz = nnz; m->nx = nx;
+    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t b_xt = a256((size_t)d * nw64 * 8), b_ptr = a256(((size_t)n + 1) * 4), b_idx = a256((size_t)std::max(nnz, 1) * 4),
+                 b_eb = a256((size_t)std::max(nnz, 1) * wf * 4);
+    const size_t b_xptr = nx > 0 ? a256(((size_t)nnz + 1) * 4) : 0, b_xorg = nx > 0 ? a256((size_t)nx * 4) : 0;
+    if (hipMalloc(&m->block, b_xt + b_ptr + b_idx + b_eb + b_xptr + 2 * b_xorg) != hipSuccess) return fail(NEMGPU_E_DEVICE, "nemgpu_master_create_orders: device memory");
+    uint64_t* xt = (uint64_t*)m->block;
+    int* dptr = (int*)(m->block + b_xt);
+    int* didx = (int*)(m->block + b_xt + b_ptr);
+    uint32_t* deb = (uint32_t*)(m->block + b_xt + b_ptr + b_idx);
+    int* dxptr = nx > 0 ? (int*)(m->block + b_xt + b_ptr + b_idx + b_eb) : nullptr;
+    int* dxorg = nx > 0 ? (int*)(m->block + b_xt + b_ptr + b_idx + b_eb + b_xptr) : nullptr;
+    int* dxadd = nx > 0 ? (int*)(m->block + b_xt + b_ptr + b_idx + b_eb + b_xptr + b_xorg) : nullptr;
+    m->order.resize((size_t)n);
+    int over = 0;
+    err = nemk::orders_fill(build, xt, nw64, dptr, didx, deb, wf, dxptr, dxorg, dxadd, m->order.data(), &over, m->stream);
+    if (err != hipSuccess) return fail(NEMGPU_E_DEVICE, std::string("nemgpu_master_create_orders: ") + hipGetErrorString(err));
+    if (over) return fail(NEMGPU_E_ARG, "edge counts: an edge's total count above 2^24 (a float weight would not be exact)");
+    nemk::orders_free(build);
+    m->dev = nemk::MasterDev{n, d, wf, nw64, nnz, xt, dptr, didx, deb, dxptr, dxorg, dxadd};
+    *out = m;
+    return NEMGPU_OK;
+}
+
+int nemgpu_master_shape(const nemgpu_master* m, int* n, int* d, int* nnz, int* n_extra)
+{
+    if (!m) return NEMGPU_E_FUNCARG;
+    if (n) *n = m->n;
+    if (d) *d = m->d;
+    if (nnz) *nnz = m->nnz;
+    if (n_extra) *n_extra = m->nx;
+    return NEMGPU_OK;
+}
+
+int nemgpu_master_fetch(const nemgpu_master* m, uint32_t* xbits, int32_t* nei_ptr, int32_t* nei_idx, uint32_t* edge_bits,
+                        int32_t* extra_ptr, int32_t* extra_org, int32_t* extra_count, int32_t* order)
+{
+    if (!m) return NEMGPU_E_FUNCARG;
+    HIPCHK(hipSetDevice(m->device));
+    const nemk::MasterDev& M = m->dev;
+    uint32_t* xf = nullptr;
+    if (xbits) {
+        HIPCHK(hipMalloc(&xf, (size_t)m->n * m->wf * 4));
+        nemk::launch_master_rows(M.xt, m->n, m->wf, m->d, m->nw64, xf, m->stream);
+    }
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess && xbits) err = hipMemcpyAsync(xbits, xf, (size_t)m->n * m->wf * 4, hipMemcpyDeviceToHost, m->stream);
+    if (err == hipSuccess && nei_ptr) err = hipMemcpyAsync(nei_ptr, M.nei_ptr, ((size_t)m->n + 1) * 4, hipMemcpyDeviceToHost, m->stream);
+    if (err == hipSuccess && nei_idx && m->nnz > 0) err = hipMemcpyAsync(nei_idx, M.nei_idx, (size_t)m->nnz * 4, hipMemcpyDeviceToHost, m->stream);
+    if (err == hipSuccess && edge_bits && m->nnz > 0) err = hipMemcpyAsync(edge_bits, M.edge_bits, (size_t)m->nnz * m->wf * 4, hipMemcpyDeviceToHost, m->stream);
+    if (err == hipSuccess && m->nx > 0) {
+        if (extra_ptr) err = hipMemcpyAsync(extra_ptr, M.extra_ptr, ((size_t)m->nnz + 1) * 4, hipMemcpyDeviceToHost, m->stream);
+        if (err == hipSuccess && extra_org) err = hipMemcpyAsync(extra_org, M.extra_org, (size_t)m->nx * 4, hipMemcpyDeviceToHost, m->stream);
+        if (err == hipSuccess && extra_count) err = hipMemcpyAsync(extra_count, M.extra_add, (size_t)m->nx * 4, hipMemcpyDeviceToHost, m->stream);
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(m->stream);
+    if (xf) (void)hipFree(xf);
+    if (err != hipSuccess) { set_error(std::string("nemgpu_master_fetch: ") + hipGetErrorString(err)); return NEMGPU_E_DEVICE; }
+    if (m->nx > 0 && extra_count) for (int t = 0; t < m->nx; t++) extra_count[t] += 1;       // (the device keeps count - 1)
+    if (m->nx == 0 && extra_ptr) std::fill(extra_ptr, extra_ptr + (size_t)m->nnz + 1, 0);
+    if (order) { if (m->order.empty()) for (int i = 0; i < m->n; i++) order[i] = i; else std::copy(m->order.begin(), m->order.end(), order); }
     return NEMGPU_OK;
 }
 

@@ -1,0 +1,513 @@
+// nem_orders.hip -- see nem_orders.hpp.
+#include "nem_orders.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <algorithm>
+#include <vector>
+
+namespace nemk {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kScanItems = 8, kScanTile = kThreads * kScanItems;
+constexpr uint32_t kNoPos = 0xffffffffu;          // first position of a family without a kept gene
+constexpr uint32_t kSuccBit = 0x80000000u;        // a successor record's time (sorts after every predecessor's)
+
+struct OpMax { __device__ int operator()(int a, int b) const { return a > b ? a : b; } };
+struct OpMin { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a < b ? a : b; } };
+struct OpOr { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a | b; } };
+template <class T> struct OpSum { __device__ T operator()(T a, T b) const { return a + b; } };
+
+__device__ inline int lane_id() { return threadIdx.x & 63; }
+
+// ---- scans ----------------------------------------------------------------------------------------------------
+// exclusive prefix of v over the block's 256 threads (4 waves); *total (may be null): the block's total
+template <class T, class Op> __device__ inline T block_exclusive(T v, Op op, T ident, T* s_tot, T* total)
+{
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    T inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const T o = __shfl_up(inc, off); if (lane >= off) inc = op(o, inc); }
+    if (lane == 63) s_tot[w] = inc;
+    T ex = __shfl_up(inc, 1);
+    if (lane == 0) ex = ident;
+    __syncthreads();
+    T pre = ident, all = ident;
+    for (int j = 0; j < kThreads / 64; j++) { if (j < w) pre = op(pre, s_tot[j]); all = op(all, s_tot[j]); }
+    if (total) *total = all;
+    __syncthreads();
+    return op(pre, ex);
+}
+
+template <class T, class Op> __global__ __launch_bounds__(kThreads) void k_scan_reduce(const T* __restrict__ in, int n, Op op, T ident,
+                                                                                     T* __restrict__ partial)
+{
+    __shared__ T s_tot[kThreads / 64];
+    const long long base = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanItems;
+    T v = ident;
+#pragma unroll
+    for (int j = 0; j < kScanItems; j++) if (base + j < n) v = op(v, in[base + j]);
+    T all;
+    (void)block_exclusive(v, op, ident, s_tot, &all);
+    if (threadIdx.x == 0) partial[blockIdx.x] = all;
+}
+
+// the tiles' totals -> their exclusive prefixes, in place (one block); *total_out (may be null) = the grand total
+template <class T, class Op> __global__ __launch_bounds__(kThreads) void k_scan_partials(T* __restrict__ partial, int nb, Op op, T ident,
+                                                                                       T* __restrict__ total_out)
+{
+    __shared__ T s_tot[kThreads / 64];
+    T carry = ident;
+    for (int base = 0; base < nb; base += kThreads) {
+        const int i = base + threadIdx.x;
+        const T v = i < nb ? partial[i] : ident;
+        T all;
+        const T ex = block_exclusive(v, op, ident, s_tot, &all);
+        if (i < nb) partial[i] = op(carry, ex);
+        carry = op(carry, all);
+    }
+    if (total_out && threadIdx.x == 0) *total_out = carry;
+}
+
+template <class T, class Op, bool kInclusive>
+__global__ __launch_bounds__(kThreads) void k_scan_apply(const T* in, int n, Op op, T ident, const T* __restrict__ partial, T* out)
+{
+    __shared__ T s_tot[kThreads / 64];
+    const long long base = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanItems;
+    T item[kScanItems];
+    T v = ident;
+#pragma unroll
+    for (int j = 0; j < kScanItems; j++) { item[j] = base + j < n ? in[base + j] : ident; v = op(v, item[j]); }
+    T run = op(partial[blockIdx.x], block_exclusive(v, op, ident, s_tot, (T*)nullptr));
+#pragma unroll
+    for (int j = 0; j < kScanItems; j++) {
+        const T next = op(run, item[j]);
+        if (base + j < n) out[base + j] = kInclusive ? next : run;
+        run = next;
+    }
+}
+
+// out = scan of in over n items (in place allowed); partial: room for ceil(n / kScanTile) items
+template <class T, class Op, bool kInclusive> void scan(const T* in, T* out, int n, Op op, T ident, T* partial, T* total_out, hipStream_t s)
+{
+    const int nb = (n + kScanTile - 1) / kScanTile;
+    if (nb == 0) { if (total_out) (void)hipMemsetAsync(total_out, 0, sizeof(T), s); return; }   // (only the sums are called with n = 0)
+    hipLaunchKernelGGL((k_scan_reduce<T, Op>), dim3(nb), dim3(kThreads), 0, s, in, n, op, ident, partial);
+    hipLaunchKernelGGL((k_scan_partials<T, Op>), dim3(1), dim3(kThreads), 0, s, partial, nb, op, ident, total_out);
+    hipLaunchKernelGGL((k_scan_apply<T, Op, kInclusive>), dim3(nb), dim3(kThreads), 0, s, in, n, op, ident, (const T*)partial, out);
+}
+
+// inclusive scan of val over the wave's lanes of equal key (equal keys are adjacent); tail: the segment's last lane
+template <class K, class V, class Op> __device__ inline V wave_segment(K key, V val, Op op, bool& tail)
+{
+    const int lane = lane_id();
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const K k2 = __shfl_up(key, off);
+        const V v2 = __shfl_up(val, off);
+        if (lane >= off && k2 == key) val = op(v2, val);
+    }
+    const K kn = __shfl_down(key, 1);
+    tail = lane == 63 || kn != key;
+    return val;
+}
+
+// ---- stage 1 ----------------------------------------------------------------------------------------------------
+// last[p] = p for a kept gene, -1 for one of a repeated family; the first kept position of every family id
+__global__ __launch_bounds__(kThreads) void k_orders_kept(const int* __restrict__ genes, int g, const uint8_t* __restrict__ repeated,
+                                                         int* __restrict__ last, uint32_t* firstpos)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= g) return;
+    const int fam = genes[p];
+    const bool kept = !(repeated && repeated[fam]);
+    last[p] = kept ? p : -1;
+    if (kept && firstpos[fam] > (uint32_t)p) atomicMin(&firstpos[fam], (uint32_t)p);   // (the plain read only ever errs high)
+}
+
+__global__ __launch_bounds__(kThreads) void k_orders_iota(uint32_t* __restrict__ v, int n)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) v[i] = (uint32_t)i;
+}
+
+// families by first kept position: newid of every caller id (-1: no kept gene), *n = the families with one
+__global__ __launch_bounds__(kThreads) void k_orders_number(const uint32_t* __restrict__ pos_sorted, const uint32_t* __restrict__ fam_sorted, int f,
+                                                           int* __restrict__ newid, int* __restrict__ n_out)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= f) return;
+    const bool has = pos_sorted[i] != kNoPos;
+    newid[fam_sorted[i]] = has ? i : -1;
+    if (has && (i + 1 == f || pos_sorted[i + 1] == kNoPos)) *n_out = i + 1;
+}
+
+struct KeyBits { int bn, bd; };
+__device__ inline uint64_t make_key(KeyBits kb, int row, int nbr, int org)
+{
+    return ((uint64_t)(uint32_t)row << (kb.bn + kb.bd)) | ((uint64_t)(uint32_t)nbr << kb.bd) | (uint64_t)(uint32_t)org;
+}
+
+// the two record slots of every gene (2p, 2p + 1); an unused slot's key is 1 << (2 bn + bd): it sorts behind all
+__global__ __launch_bounds__(kThreads) void k_orders_records(const int* __restrict__ genes, int g, const int* __restrict__ last,
+                                                            const int* __restrict__ cptr, int c, const int* __restrict__ corg,
+                                                            const uint8_t* __restrict__ circ, const int* __restrict__ newid, int directed,
+                                                            KeyBits kb, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                            int* __restrict__ gene_org)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= g) return;
+    const uint64_t none = (uint64_t)1 << (2 * kb.bn + kb.bd);
+    uint64_t k0 = none, k1 = none;
+    uint32_t v0 = 0, v1 = 0;
+    int org = -1;
+    if (last[p] == p) {
+        int lo = 0, hi = c;                                   // the contig: the last j with cptr[j] <= p (cptr[j + 1] > p)
+        while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (cptr[mid] <= p) lo = mid; else hi = mid; }
+        const int j = lo, start = cptr[j], end = cptr[j + 1];
+        org = corg[j];
+        const int prev = p > 0 ? last[p - 1] : -1;
+        int other = -1;
+        uint32_t t = 0;
+        if (prev >= start) { other = prev; t = (uint32_t)p + (uint32_t)j; }                       // ppanggolin.py:513
+        else if (circ[j]) { other = last[end - 1]; t = (uint32_t)end + (uint32_t)j; }             // :518-519 (p is the contig's first kept gene)
+        if (other >= 0) {
+            const int a = newid[genes[p]], b = newid[genes[other]];
+            if (directed) { k0 = make_key(kb, a, b, org); v0 = t | kSuccBit; k1 = make_key(kb, b, a, org); v1 = t; }
+            else { k0 = make_key(kb, a, b, org); v0 = t; if (a != b) { k1 = make_key(kb, b, a, org); v1 = t; } }
+        }
+    }
+    gene_org[p] = org;
+    keys[2 * (size_t)p] = k0; keys[2 * (size_t)p + 1] = k1;
+    vals[2 * (size_t)p] = v0; vals[2 * (size_t)p + 1] = v1;
+}
+
+// per sorted record: (starts an edge) << 32 | (starts an (edge, organism) pair)
+__global__ __launch_bounds__(kThreads) void k_orders_heads(const uint64_t* __restrict__ keys, int n2, KeyBits kb, uint64_t* __restrict__ flags)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n2) return;
+    const uint64_t none = (uint64_t)1 << (2 * kb.bn + kb.bd);
+    const uint64_t k = keys[i];
+    uint64_t fl = 0;
+    if (k < none) {
+        const uint64_t kp = i > 0 ? keys[i - 1] : ~(uint64_t)0;
+        fl = ((uint64_t)(i == 0 || (kp >> kb.bd) != (k >> kb.bd)) << 32) | (uint64_t)(i == 0 || kp != k);
+    }
+    flags[i] = fl;
+}
+
+// the runs: where every pair starts and which edge it belongs to, where every edge's pairs start, an edge's first time
+__global__ __launch_bounds__(kThreads) void k_orders_runs(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int n2, KeyBits kb,
+                                                         const uint64_t* __restrict__ pos, int* __restrict__ trip_start,
+                                                         int* __restrict__ trip_edge, int* __restrict__ edge_tstart, uint32_t* edge_min)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t none = (uint64_t)1 << (2 * kb.bn + kb.bd);
+    const uint64_t k = i < n2 ? keys[i] : none;
+    const bool valid = k < none;
+    int e = -1;
+    uint32_t v = 0xffffffffu;
+    if (valid) {
+        const uint64_t kp = i > 0 ? keys[i - 1] : ~(uint64_t)0;
+        const bool hp = i == 0 || (kp >> kb.bd) != (k >> kb.bd), ht = i == 0 || kp != k;
+        const uint64_t before = pos[i];
+        e = (int)(before >> 32) + (hp ? 1 : 0) - 1;
+        const int t = (int)(uint32_t)before + (ht ? 1 : 0) - 1;
+        if (ht) { trip_start[t] = i; trip_edge[t] = e; }
+        if (hp) edge_tstart[e] = t;
+        if (i + 1 == n2 || keys[i + 1] >= none) { trip_start[t + 1] = i + 1; edge_tstart[e + 1] = t + 1; }   // (the last record)
+        v = vals[i];
+    }
+    bool tail;
+    v = wave_segment(e, v, OpMin(), tail);
+    if (valid && tail) atomicMin(&edge_min[e], v);
+}
+
+// pairs with count >= 2
+__global__ __launch_bounds__(kThreads) void k_orders_multi(const int* __restrict__ trip_start, int tn, int* __restrict__ flag)
+{
+    const int t = blockIdx.x * kThreads + threadIdx.x;
+    if (t < tn) flag[t] = trip_start[t + 1] - trip_start[t] >= 2 ? 1 : 0;
+}
+
+// (row << 32 | first time, edge) of every edge
+__global__ __launch_bounds__(kThreads) void k_orders_edge_keys(const uint64_t* __restrict__ keys, KeyBits kb, const int* __restrict__ trip_start,
+                                                              const int* __restrict__ edge_tstart, const uint32_t* __restrict__ edge_min, int nnz,
+                                                              uint64_t* __restrict__ ekeys, uint32_t* __restrict__ evals)
+{
+    const int e = blockIdx.x * kThreads + threadIdx.x;
+    if (e >= nnz) return;
+    const uint64_t row = keys[trip_start[edge_tstart[e]]] >> (kb.bn + kb.bd);
+    ekeys[e] = (row << 32) | edge_min[e];
+    evals[e] = (uint32_t)e;
+}
+
+// ---- stage 2 ----------------------------------------------------------------------------------------------------
+// CSR entry f = edge perm[f]: its neighbour, its number of multi-copy pairs (into extra_ptr, scanned next)
+__global__ __launch_bounds__(kThreads) void k_orders_entries(const uint32_t* __restrict__ perm, int nnz, const uint64_t* __restrict__ keys, KeyBits kb,
+                                                            const int* __restrict__ trip_start, const int* __restrict__ edge_tstart,
+                                                            const int* __restrict__ xs, int* __restrict__ inv, int* __restrict__ idx,
+                                                            int* __restrict__ xdeg, int* over)
+{
+    const int f = blockIdx.x * kThreads + threadIdx.x;
+    if (f >= nnz) return;
+    const int e = (int)perm[f];
+    const int t0 = edge_tstart[e], t1 = edge_tstart[e + 1];
+    inv[e] = f;
+    idx[f] = (int)((keys[trip_start[t0]] >> kb.bd) & (((uint64_t)1 << kb.bn) - 1));
+    if (xdeg) xdeg[f] = xs[t1] - xs[t0];
+    if (trip_start[t1] - trip_start[t0] > (1 << 24)) *over = 1;
+}
+
+// ptr[r] = the first CSR entry of a row >= r
+__global__ __launch_bounds__(kThreads) void k_orders_ptr(const uint64_t* __restrict__ ekeys_sorted, int nnz, int n, int* __restrict__ ptr)
+{
+    const int r = blockIdx.x * kThreads + threadIdx.x;
+    if (r > n) return;
+    int lo = 0, hi = nnz;
+    while (lo < hi) { const int mid = lo + (hi - lo) / 2; if ((int)(ekeys_sorted[mid] >> 32) < r) lo = mid + 1; else hi = mid; }
+    ptr[r] = lo;
+}
+
+// every (edge, organism) pair: its bit in the edge's organism set, and its entry of the extras when its count is >= 2
+__global__ __launch_bounds__(kThreads) void k_orders_pairs(const uint64_t* __restrict__ keys, KeyBits kb, const int* __restrict__ trip_start,
+                                                          const int* __restrict__ trip_edge, int tn, const int* __restrict__ edge_tstart,
+                                                          const int* __restrict__ inv, const int* __restrict__ xs, int wf, uint32_t* edge_bits,
+                                                          const int* __restrict__ extra_ptr, int* __restrict__ extra_org, int* __restrict__ extra_add)
+{
+    const int t = blockIdx.x * kThreads + threadIdx.x;
+    const bool valid = t < tn;
+    long long word = -1;
+    uint32_t bit = 0;
+    if (valid) {
+        const int e = trip_edge[t], f = inv[e];
+        const int i0 = trip_start[t], cnt = trip_start[t + 1] - i0;
+        const int org = (int)(keys[i0] & (((uint64_t)1 << kb.bd) - 1));
+        word = (long long)f * wf + (org >> 5);
+        bit = 1u << (org & 31);
+        if (cnt >= 2) {
+            const int dst = extra_ptr[f] + (xs[t] - xs[edge_tstart[e]]);
+            extra_org[dst] = org;
+            extra_add[dst] = cnt - 1;
+        }
+    }
+    bool tail;
+    bit = wave_segment(word, bit, OpOr(), tail);
+    if (valid && tail) atomicOr(&edge_bits[word], bit);
+}
+
+// x[family][organism] = 1 for every kept gene, into the organism-major rows
+__global__ __launch_bounds__(kThreads) void k_orders_presence(const int* __restrict__ genes, int g, const int* __restrict__ gene_org,
+                                                             const int* __restrict__ newid, int nw64, unsigned long long* xt)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= g) return;
+    const int org = gene_org[p];
+    if (org < 0) return;
+    const int fam = newid[genes[p]];
+    unsigned long long* w = xt + (size_t)org * nw64 + (fam >> 6);
+    const unsigned long long bit = 1ull << (fam & 63);
+    if (!(*w & bit)) atomicOr(w, bit);                        // (a stale read only costs the atomic)
+}
+
+__global__ __launch_bounds__(64) void k_master_rows(const uint64_t* __restrict__ xt, int n, int wf, int d, int nw64, uint32_t* __restrict__ xf)
+{
+    const int g = blockIdx.x, w = blockIdx.y, lane = threadIdx.x;
+    const int o = w * 32 + lane;
+    const uint64_t x = (lane < 32 && o < d) ? xt[(size_t)o * nw64 + g] : 0ull;
+    uint32_t mine = 0;
+#pragma unroll
+    for (int b = 0; b < 64; b++) {
+        const uint64_t bal = __ballot((x >> b) & 1ull);
+        if (lane == b) mine = (uint32_t)bal;
+    }
+    const int i = g * 64 + lane;
+    if (i < n) xf[(size_t)i * wf + w] = mine;
+}
+
+int bits_for(int count) { int b = 1; while (b < 31 && (1ll << b) < count) b++; return b; }
+int blocks(long long n) { return (int)((n + kThreads - 1) / kThreads); }
+
+}  // namespace
+
+struct OrdersBuild {
+    std::vector<void*> mem;
+    int d = 0, f = 0, g = 0, n = 0, nnz = 0, tn = 0, nx = 0, n2 = 0;
+    KeyBits kb{1, 1};
+    int *genes = nullptr, *gene_org = nullptr, *newid = nullptr;
+    uint32_t* fam_sorted = nullptr;
+    const uint64_t* keys = nullptr;                           // the sorted records
+    int *trip_start = nullptr, *trip_edge = nullptr, *xs = nullptr, *edge_tstart = nullptr;
+    const uint64_t* ekeys = nullptr;                          // the sorted edges
+    const uint32_t* perm = nullptr;
+    int* inv = nullptr;
+    int* partial = nullptr;
+    int* over = nullptr;
+    template <class T> hipError_t alloc(T** p, size_t count)
+    {
+        void* v = nullptr;
+        const hipError_t e = hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) mem.push_back(v);
+        *p = (T*)v;
+        return e;
+    }
+};
+
+void orders_free(OrdersBuild* b)
+{
+    if (!b) return;
+    for (void* p : b->mem) (void)hipFree(p);
+    delete b;
+}
+
+bool orders_key_fits(int n, int d) { return 2 * bits_for(n) + bits_for(d) <= 63; }
+
+#define ORD(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { orders_free(b); return e_; } } while (0)
+
+template <class K> static hipError_t sort_pairs(OrdersBuild* b, K* k0, K* k1, uint32_t* v0, uint32_t* v1, int count, int end_bit, const K** k_out,
+                                                const uint32_t** v_out, hipStream_t s)
+{
+    rocprim::double_buffer<K> keys(k0, k1);
+    rocprim::double_buffer<uint32_t> vals(v0, v1);
+    size_t bytes = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, bytes, keys, vals, (unsigned)count, 0u, (unsigned)end_bit, s);
+    if (e != hipSuccess) return e;
+    char* tmp = nullptr;
+    if ((e = b->alloc(&tmp, bytes)) != hipSuccess) return e;
+    if ((e = rocprim::radix_sort_pairs(tmp, bytes, keys, vals, (unsigned)count, 0u, (unsigned)end_bit, s)) != hipSuccess) return e;
+    *k_out = keys.current();
+    *v_out = vals.current();
+    return hipSuccess;
+}
+
+hipError_t orders_stage(const OrdersIn& in, hipStream_t s, OrdersBuild** out, int* n, int* nnz, int* nx)
+{
+    *out = nullptr; *n = 0; *nnz = 0; *nx = 0;
+    OrdersBuild* b = new OrdersBuild();
+    const int g = in.g, c = in.c, f = in.f;
+    b->d = in.d; b->f = f; b->g = g; b->n2 = 2 * g;
+    int *cptr, *corg, *last;
+    uint8_t *circ, *rep = nullptr;
+    uint32_t *fp0, *fp1, *fi0, *fi1;
+    uint64_t* totals;                                         // [0] the record flags' total, then int words: n, over
+    ORD(b->alloc(&b->genes, g)); ORD(b->alloc(&cptr, c + 1)); ORD(b->alloc(&corg, c)); ORD(b->alloc(&circ, c));
+    if (in.repeated) ORD(b->alloc(&rep, f));
+    ORD(b->alloc(&last, g)); ORD(b->alloc(&b->gene_org, g)); ORD(b->alloc(&b->newid, f));
+    ORD(b->alloc(&fp0, f)); ORD(b->alloc(&fp1, f)); ORD(b->alloc(&fi0, f)); ORD(b->alloc(&fi1, f));
+    ORD(b->alloc(&totals, 4));
+    uint64_t* partial64;
+    ORD(b->alloc(&partial64, (size_t)b->n2 / kScanTile + 2));
+    b->partial = (int*)partial64;
+    int* n_dev = (int*)(totals + 1);
+    b->over = n_dev + 1;
+    ORD(hipMemcpyAsync(b->genes, in.genes, (size_t)g * 4, hipMemcpyHostToDevice, s));
+    ORD(hipMemcpyAsync(cptr, in.contig_ptr, ((size_t)c + 1) * 4, hipMemcpyHostToDevice, s));
+    ORD(hipMemcpyAsync(corg, in.contig_org, (size_t)c * 4, hipMemcpyHostToDevice, s));
+    ORD(hipMemcpyAsync(circ, in.contig_circular, (size_t)c, hipMemcpyHostToDevice, s));
+    if (rep) ORD(hipMemcpyAsync(rep, in.repeated, (size_t)f, hipMemcpyHostToDevice, s));
+    ORD(hipMemsetAsync(totals, 0, 4 * sizeof(uint64_t), s));
+    ORD(hipMemsetAsync(fp0, 0xff, (size_t)f * 4, s));          // (kNoPos)
+    // 1. kept genes, every gene's last kept gene at or before it
+    hipLaunchKernelGGL(k_orders_kept, dim3(blocks(g)), dim3(kThreads), 0, s, b->genes, g, rep, last, fp0);
+    scan<int, OpMax, true>(last, last, g, OpMax(), -1, b->partial, (int*)nullptr, s);
+    // 2. the numbering: the family ids by first kept position (those without one last)
+    hipLaunchKernelGGL(k_orders_iota, dim3(blocks(f)), dim3(kThreads), 0, s, fi0, f);
+    ORD(hipGetLastError());
+    const uint32_t *fp_sorted, *fi_sorted;
+    ORD(sort_pairs<uint32_t>(b, fp0, fp1, fi0, fi1, f, 32, &fp_sorted, &fi_sorted, s));
+    b->fam_sorted = const_cast<uint32_t*>(fi_sorted);
+    hipLaunchKernelGGL(k_orders_number, dim3(blocks(f)), dim3(kThreads), 0, s, fp_sorted, fi_sorted, f, b->newid, n_dev);
+    ORD(hipGetLastError());
+    ORD(hipMemcpyAsync(n, n_dev, sizeof(int), hipMemcpyDeviceToHost, s));
+    ORD(hipStreamSynchronize(s));
+    b->n = *n;
+    if (*n <= 0 || !orders_key_fits(*n, in.d)) { orders_free(b); return hipErrorInvalidValue; }
+    b->kb = KeyBits{bits_for(*n), bits_for(in.d)};
+    // 3. the records
+    uint64_t *k0, *k1, *pos;
+    uint32_t *v0, *v1;
+    const int n2 = b->n2;
+    ORD(b->alloc(&k0, n2)); ORD(b->alloc(&k1, n2)); ORD(b->alloc(&v0, n2)); ORD(b->alloc(&v1, n2));
+    hipLaunchKernelGGL(k_orders_records, dim3(blocks(g)), dim3(kThreads), 0, s, b->genes, g, last, cptr, c, corg, circ, b->newid, in.directed, b->kb,
+                       k0, v0, b->gene_org);
+    ORD(hipGetLastError());
+    // 4. sorted; pairs and edges numbered by the scan of their first records
+    const uint64_t* keys;
+    const uint32_t* vals;
+    ORD(sort_pairs<uint64_t>(b, k0, k1, v0, v1, n2, 2 * b->kb.bn + b->kb.bd + 1, &keys, &vals, s));
+    b->keys = keys;
+    pos = keys == k0 ? k1 : k0;                               // (the sort's other buffer is free again)
+    hipLaunchKernelGGL(k_orders_heads, dim3(blocks(n2)), dim3(kThreads), 0, s, keys, n2, b->kb, pos);
+    scan<uint64_t, OpSum<uint64_t>, false>(pos, pos, n2, OpSum<uint64_t>(), (uint64_t)0, partial64, totals, s);
+    ORD(hipGetLastError());
+    uint64_t tot = 0;
+    ORD(hipMemcpyAsync(&tot, totals, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    ORD(hipStreamSynchronize(s));
+    b->nnz = (int)(tot >> 32); b->tn = (int)(uint32_t)tot;
+    uint32_t* edge_min;
+    ORD(b->alloc(&b->trip_start, (size_t)b->tn + 1)); ORD(b->alloc(&b->trip_edge, b->tn)); ORD(b->alloc(&b->xs, (size_t)b->tn + 1));
+    ORD(b->alloc(&b->edge_tstart, (size_t)b->nnz + 1)); ORD(b->alloc(&edge_min, b->nnz)); ORD(b->alloc(&b->inv, b->nnz));
+    ORD(hipMemsetAsync(b->trip_start, 0, sizeof(int), s));    // (no record at all: the sentinels)
+    ORD(hipMemsetAsync(b->edge_tstart, 0, sizeof(int), s));
+    ORD(hipMemsetAsync(edge_min, 0xff, (size_t)std::max(b->nnz, 1) * 4, s));
+    hipLaunchKernelGGL(k_orders_runs, dim3(blocks(n2)), dim3(kThreads), 0, s, keys, vals, n2, b->kb, (const uint64_t*)pos, b->trip_start,
+                       b->trip_edge, b->edge_tstart, edge_min);
+    if (b->tn > 0) hipLaunchKernelGGL(k_orders_multi, dim3(blocks(b->tn)), dim3(kThreads), 0, s, b->trip_start, b->tn, b->xs);
+    scan<int, OpSum<int>, false>(b->xs, b->xs, b->tn, OpSum<int>(), 0, b->partial, b->xs + b->tn, s);
+    ORD(hipGetLastError());
+    // 5. the edges in CSR order
+    if (b->nnz > 0) {
+        uint64_t *e0, *e1;
+        uint32_t *p0, *p1;
+        ORD(b->alloc(&e0, b->nnz)); ORD(b->alloc(&e1, b->nnz)); ORD(b->alloc(&p0, b->nnz)); ORD(b->alloc(&p1, b->nnz));
+        hipLaunchKernelGGL(k_orders_edge_keys, dim3(blocks(b->nnz)), dim3(kThreads), 0, s, keys, b->kb, b->trip_start, b->edge_tstart, edge_min,
+                           b->nnz, e0, p0);
+        ORD(hipGetLastError());
+        ORD(sort_pairs<uint64_t>(b, e0, e1, p0, p1, b->nnz, 32 + b->kb.bn, &b->ekeys, &b->perm, s));
+    }
+    ORD(hipMemcpyAsync(&b->nx, b->xs + b->tn, sizeof(int), hipMemcpyDeviceToHost, s));
+    ORD(hipStreamSynchronize(s));
+    *nnz = b->nnz; *nx = b->nx;
+    *out = b;
+    return hipSuccess;
+}
+
+#undef ORD
+#define ORD(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
+
+hipError_t orders_fill(OrdersBuild* b, uint64_t* xt, int nw64, int* ptr, int* idx, uint32_t* edge_bits, int wf, int* extra_ptr, int* extra_org,
+                       int* extra_add, int32_t* order_host, int* over, hipStream_t s)
+{
+    const int n = b->n, nnz = b->nnz, tn = b->tn;
+    *over = 0;
+    ORD(hipMemsetAsync(xt, 0, (size_t)b->d * nw64 * 8, s));
+    hipLaunchKernelGGL(k_orders_presence, dim3(blocks(b->g)), dim3(kThreads), 0, s, b->genes, b->g, b->gene_org, b->newid, nw64,
+                       (unsigned long long*)xt);
+    hipLaunchKernelGGL(k_orders_ptr, dim3(blocks((long long)n + 1)), dim3(kThreads), 0, s, b->ekeys, nnz, n, ptr);
+    if (nnz > 0) {
+        int* xptr = b->nx > 0 ? extra_ptr : nullptr;          // (no multi-copy pair: no extras at all)
+        ORD(hipMemsetAsync(edge_bits, 0, (size_t)nnz * wf * 4, s));
+        hipLaunchKernelGGL(k_orders_entries, dim3(blocks(nnz)), dim3(kThreads), 0, s, b->perm, nnz, b->keys, b->kb, b->trip_start, b->edge_tstart,
+                           b->xs, b->inv, idx, xptr, b->over);
+        if (xptr) scan<int, OpSum<int>, false>(xptr, xptr, nnz, OpSum<int>(), 0, b->partial, xptr + nnz, s);
+        hipLaunchKernelGGL(k_orders_pairs, dim3(blocks(tn)), dim3(kThreads), 0, s, b->keys, b->kb, b->trip_start, b->trip_edge, tn, b->edge_tstart,
+                           b->inv, b->xs, wf, edge_bits, xptr, extra_org, extra_add);
+    }
+    ORD(hipGetLastError());
+    ORD(hipMemcpyAsync(order_host, b->fam_sorted, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    ORD(hipMemcpyAsync(over, b->over, sizeof(int), hipMemcpyDeviceToHost, s));
+    ORD(hipStreamSynchronize(s));
+    return hipSuccess;
+}
+
+#undef ORD
+
+void launch_master_rows(const uint64_t* xt, int n, int wf, int d, int nw64, uint32_t* xf, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_master_rows, dim3(nw64, wf), dim3(64), 0, s, xt, n, wf, d, nw64, xf);
+}
+
+}  // namespace nemk

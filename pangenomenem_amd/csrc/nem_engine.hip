@@ -216,6 +216,9 @@ struct nemgpu_engine {
     // go to one of two statistics slots (stats_slot[0] is `stats`); stats_last is the slot with the counts a batch left
     // last, which is what a reader of the statistics outside a batch gets.
     bool round_counts = true;
+    // ... and (NEM_MI355X_START_FUSED, default on; see enqueue_init) a start's restart head runs inside its density launch
+    // (k_density_start) instead of as a k_finish launch ahead of k_density.
+    bool start_fused = true;
     int* stats_slot[2] = {};
     int* stats_last = nullptr;
     float* par_copy[3] = {}; double* pkfki_copy[3] = {}; float* logpkfki_copy[3] = {};
@@ -1190,24 +1193,33 @@ static int init_beta_rounds(const nemgpu_engine* e)
     return n;
 }
 
+bool shadow_engine(const nemgpu_engine* e);
+
 // hold (shadow-verify schedule, NCEM): the beta sweep's last round and the loop control are left in *hold for the first
 // iteration's density launch (defer_ctrl is then ignored); count_into (with hold): the round before it adds the first
 // iteration's M-step counts into these statistics, which this launch's restart head zeroes
 int enqueue_init(nemgpu_engine* e, bool defer_ctrl, SweepArgs* hold = nullptr, int* count_into = nullptr)
 {
     int r;
-    // one launch: initial parameters back in place, loop control cleared, density tables built
-    {
-        FinishArgs t = finish_args(e, 0, nullptr);
-        t.reset_prop = e->prop0; t.reset_center = e->center0; t.reset_disp = e->disp0;
-        t.reset_ctrl = e->ctrl(); t.reset_ctrl_words = C_WORDS; t.reset_sweep_next = e->sweep_next;
-        if (hold != nullptr && count_into != nullptr) { t.zero_stats = count_into; t.n_zero_stats = e->k + e->k * e->d; }
+    FinishArgs t = finish_args(e, 0, nullptr);
+    t.reset_prop = e->prop0; t.reset_center = e->center0; t.reset_disp = e->disp0;
+    t.reset_ctrl = e->ctrl(); t.reset_ctrl_words = C_WORDS; t.reset_sweep_next = e->sweep_next;
+    if (hold != nullptr && count_into != nullptr) { t.zero_stats = count_into; t.n_zero_stats = e->k + e->k * e->d; }
+    e->cur = 0;
+    if (e->start_fused && shadow_engine(e)) {
+        // one launch: initial parameters back in place, loop control and sweep flag slots cleared, and the density, every
+        // block deriving its class constants from the given parameters (k_density_start)
+        launch_density_start(t, e->xws, e->n, e->npad, e->pkfki, e->logpkfki, e->iter_flags() + FLAG_MOVED, kSweepFlagWords, e->stream);
+        HIPCHK(hipGetLastError());
+        e->tables_fresh = false;                                   // the table buffers were not rebuilt
+        e->flags_clean = true; e->density_fresh = true;
+    } else {
+        // one launch: initial parameters back in place, loop control cleared, density tables built
         launch_finish(t, e->stream);
         HIPCHK(hipGetLastError());
+        e->tables_fresh = true; e->density_fresh = false;
+        if ((r = do_density(e))) return r;                         // (also clears every sweep flag slot)
     }
-    e->tables_fresh = true; e->density_fresh = false;
-    e->cur = 0;
-    if ((r = do_density(e))) return r;                             // (also clears every sweep flag slot)
     SweepCtx c0, c1;
     e->sweep_counter = 0;
     // blind sweep: one round, 0 -> 1, on a flag slot of its own so that no clear is needed before the next sweep.
@@ -2585,6 +2597,7 @@ int nemgpu_create(nemgpu_engine** out, int n_total, int d, int k, int site_lo, i
     if (const char* g = getenv("NEM_MI355X_SHADOW_VERIFY")) e->shadow_verify = (g[0] != '0');   // 0: every verifying round on its own
     e->flag_sets = e->shadow_verify ? 3 : 1;
     if (const char* g = getenv("NEM_MI355X_ROUND_COUNTS")) e->round_counts = (g[0] != '0');   // 0: a counts launch per iteration
+    if (const char* g = getenv("NEM_MI355X_START_FUSED")) e->start_fused = (g[0] != '0');     // 0: k_finish + k_density start a run
     if (const char* g = getenv("NEM_MI355X_ROUNDS")) e->round_batch = std::max(2, std::min(kRoundBatchMax, atoi(g)));
     if (const char* g = getenv("NEM_MI355X_ROUNDS_ITER")) e->rounds_iter = std::max(2, std::min(e->round_batch, atoi(g)));
     e->rounds_iter = std::min(e->rounds_iter, e->round_batch);

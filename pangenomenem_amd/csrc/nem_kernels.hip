@@ -583,8 +583,21 @@ struct FusedDensityArgs {
     const int* perm;
 };
 
+// The start of a run (START): the class constants come from the GIVEN parameters st.prop0 | st.center0 | st.disp0 instead
+// of the statistics -- what k_finish's restart head and k_density did in two launches.  The tile-0 blocks copy their
+// class's initial parameters into the copy the batch reads and zero its size; block (0, 0) clears the loop control (so
+// this launch does not read the stop word: it may still be set from the run before, and every later kernel of the
+// batch reads it after this launch).  A class whose given dispersions are all the same bits, above EPSILON, with
+// finite logs and centres in {0, 1/2, 1} takes the uniform chain -- k_finish's rule (finish_lean) --, any other the
+// general chain with k_density's arithmetic.  The table buffers are not rebuilt.
+struct StartArgs {
+    const float* prop0; const float* center0; const float* disp0;
+    int* ctrl; int ctrl_words; int* sweep_next;
+};
+
 // returns the family tile the block worked on, -1 when it had nothing to do
-__device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
+template <bool START = false>
+__device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, const StartArgs* st = nullptr)
 {
     __shared__ __align__(16) float sVal[FD_MAXD];        // inertia per organism, later epsilon per organism
     __shared__ double2 sT[FD_CH];
@@ -595,7 +608,7 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
     __shared__ unsigned long long sTot2;
     __shared__ float sEps, sChain[2];
     __shared__ int sGeneral;
-    if (a.stop != nullptr && *a.stop) return -1;
+    if constexpr (!START) { if (a.stop != nullptr && *a.stop) return -1; }
     int k, tile;
     if (!density_tile(a.K, a.npad >> 8, tile, k)) return -1;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -605,7 +618,10 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
     if (tile == 0 && k == 0) {
         for (int t = tid; t < a.n_zero_flags; t += 256) a.zero_flags[t] = 0;
         for (int t = tid; t < a.n_zero_stats; t += 256) a.zero_stats[t] = 0;
-        if (tid == 0) {                                  // EstimLaplaceCenters, nem_mod.c:1404-1408
+        if constexpr (START) {
+            for (int t = tid; t < st->ctrl_words; t += 256) if (t != C_FOLD) st->ctrl[t] = 0;
+            if (tid == 0) st->sweep_next[0] = 0;
+        } else if (tid == 0) {                           // EstimLaplaceCenters, nem_mod.c:1404-1408
             int ek = 0;
             for (int c = 0; c < K; c++)
                 if (!((double)(float)stat_sum(a.stats, c, a.stats_ranks, a.stats_rank_stride) > kEpsilonD)) ek = c + 1;
@@ -616,16 +632,22 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
     __syncthreads();
 
     // ---- centres + inertia of class k from the counts (k_finish's centers_ncem_entry, per block)
-    const int nkI = stat_sum(a.stats, k, a.stats_ranks, a.stats_rank_stride);
+    const int nkI = START ? 0 : stat_sum(a.stats, k, a.stats_ranks, a.stats_rank_stride);
     const float nkf = (float)nkI;
-    const bool nonempty = (double)nkf > kEpsilonD;
+    const bool nonempty = (double)nkf > kEpsilonD;       // (START: false -- the general chain reads the given centres)
     long long acc2 = 0;
     int general = 0;
+    int differ = 0;                                      // START: a dispersion that is not the class's first, or not above EPSILON
     for (int d = tid; d < dpad; d += 256) {              // dpad % 64 == 0: whole waves reach the ballots
         float mu = 0.0f, in = 0.0f;
         int a0 = 0, a1 = 0;
         if (d < D) {
-            if (nonempty) {
+            if constexpr (START) {
+                mu = st->center0[k * D + d];
+                in = st->disp0[k * D + d];               // (sVal holds the given dispersions from here on)
+                if (writer) a.disp[k * D + d] = in;
+                differ |= (__float_as_uint(in) != __float_as_uint(st->disp0[k * D])) || !((double)in > kEpsilonD);
+            } else if (nonempty) {
                 const float half = nkf / 2;
                 const int s1 = stat_sum(a.stats, K + k * D + d, a.stats_ranks, a.stats_rank_stride);
                 const float s0f = (float)(nkI - s1);
@@ -640,7 +662,7 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
             a0 = (ad0 != 0); a1 = (ad1 != 0);
             if (ad0 > 1 || ad1 > 1) general = 1;
             sVal[d] = in;
-            acc2 += (long long)(2.0f * in);
+            if constexpr (!START) acc2 += (long long)(2.0f * in);
         }
         const uint64_t b0 = __ballot(a0), b1 = __ballot(a1);
         if (lane == 0) {
@@ -649,14 +671,19 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
             sAm[w + 1] = make_uint2((uint32_t)(b0 >> 32), (uint32_t)(b1 >> 32));
         }
     }
-    acc2 = wave_reduce_add_ll(acc2);
-    if (lane == 0 && acc2 != 0) atomicAdd(&sTot2, (unsigned long long)acc2);
+    if constexpr (!START) {
+        acc2 = wave_reduce_add_ll(acc2);
+        if (lane == 0 && acc2 != 0) atomicAdd(&sTot2, (unsigned long long)acc2);
+    }
     if (general) sGeneral = 1;
-    __syncthreads();
+    bool eps_per_d = false;                              // epsilon differs between organisms -> general chain
+    if constexpr (START) eps_per_d = __syncthreads_or(differ) != 0;      // (one ballot per wave, block-uniform)
+    else __syncthreads();
 
     // ---- dispersion (InerToDispK_ / InerToDispKD with MISSING_IGNORE, nem_mod.c:1043-1073, 1152-1170)
-    bool eps_per_d = false;                              // epsilon differs between organisms -> general chain
-    if (a.disper == NEMGPU_DISP_K_) {
+    if constexpr (START) {
+        if (tid == 0) sEps = st->disp0[k * D];
+    } else if (a.disper == NEMGPU_DISP_K_) {
         if (nkf > 0) {
             const long long cap = 1ll << 24;
             if ((long long)sTot2 <= cap && nkI < (1 << 24)) {                              // (block-uniform)
@@ -710,7 +737,7 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
         eps_per_d = true;
     }
     // ---- proportion (nem_mod.c:456-465) and the class constants of ComputePkFkiM (nem_alg.c:2262-2271)
-    const float propk = (a.propor == NEMGPU_PROP_K) ? nkf / (float)a.n_total : (float)(1.0 / K);
+    const float propk = START ? st->prop0[k] : (a.propor == NEMGPU_PROP_K) ? nkf / (float)a.n_total : (float)(1.0 / K);
     if (writer && tid == 0) { a.prop[k] = propk; a.nbobs_k[k] = nkf; }
     const double pkd = (double)propk;
     const float logpk = (pkd > kEpsilonD) ? (float)log(pkd) : -INFINITY;
@@ -740,7 +767,8 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
         // With every centre in {0, 1/2, 1} (sGeneral == 0; the class masks sAm are those of the new centres) an
         // organism's step is the uniform chain's, dk <- fma({2 | 0}, l1_d / 2, dk) - l0_d, with ITS two constants:
         // one 16-byte LDS read and six instructions instead of two reads, two selects and the same arithmetic.
-        const bool by_mask = nonempty && !sGeneral;
+        const bool by_mask = nonempty && !sGeneral;          // (START: false, k_density's general chain step for step)
+        const float* mu_in = START ? st->center0 : a.center_in;
         for (int d0 = 0; d0 < dpad; d0 += FD_CH) {
             const int dn = min(FD_CH, dpad - d0);
             __syncthreads();
@@ -752,7 +780,7 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a)
                     const float eps = eps_per_d ? sVal[d] : eps_u;
                     int ad0, ad1;
                     if (nonempty) { ad0 = (sAm[d >> 5].x >> (d & 31)) & 1; ad1 = (sAm[d >> 5].y >> (d & 31)) & 1; }
-                    else { const float mu = a.center_in[k * D + d]; ad0 = abs((int)(0.0f - mu)); ad1 = abs((int)(1.0f - mu)); }
+                    else { const float mu = mu_in[k * D + d]; ad0 = abs((int)(0.0f - mu)); ad1 = abs((int)(1.0f - mu)); }
                     if ((double)eps > kEpsilonD) {
                         const double ll1 = log((double)((1.0f - eps) / eps));
                         ll0 = log((double)(1.0f - eps));
@@ -2120,6 +2148,7 @@ __global__ __launch_bounds__(256) void k_density(DensityArgs a) { density_body(a
 __global__ __launch_bounds__(256) void k_density_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(DensityArgs) density_body(a); }
 __global__ __launch_bounds__(256) void k_density_fused(FusedDensityArgs a) { (void)density_fused_body(a); }
 __global__ __launch_bounds__(256) void k_density_fused_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FusedDensityArgs) (void)density_fused_body(a); }
+__global__ __launch_bounds__(256) void k_density_start(FusedDensityArgs a, StartArgs st) { (void)density_fused_body<true>(a, &st); }
 // (k_sweep / k_sweep_b: nem_sweep.hip)
 // One relaxation round (blocks [0, nsweep)) and the M-step counts of the partition it verifies (the other blocks: its
 // class masks were made by the round before) side by side in ONE launch -- the sharded iteration's second half, where
@@ -2326,6 +2355,17 @@ void launch_density_fused(const FinishArgs& t, const uint32_t* xw, int n, int np
     const dim3 grid(((npad / 256 + 7) / 8) * 8 * t.K);
     if (record_op(OP_DENSITY_FUSED, 0, grid, 256, a)) return;
     hipLaunchKernelGGL(k_density_fused, grid, dim3(256), 0, s, a);
+}
+
+void launch_density_start(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
+                          int* zero_flags, int n_zero_flags, hipStream_t s)
+{
+    const FusedDensityArgs a = fused_density_args(t, xw, n, npad, pkfki, logpkfki, zero_flags, n_zero_flags);
+    StartArgs st;
+    st.prop0 = t.reset_prop; st.center0 = t.reset_center; st.disp0 = t.reset_disp;
+    st.ctrl = t.reset_ctrl; st.ctrl_words = t.reset_ctrl_words; st.sweep_next = t.reset_sweep_next;
+    const dim3 grid(((npad / 256 + 7) / 8) * 8 * t.K);
+    hipLaunchKernelGGL(k_density_start, grid, dim3(256), 0, s, a, st);
 }
 
 bool density_verify_supported(int n_local, int K, int tie_rule)

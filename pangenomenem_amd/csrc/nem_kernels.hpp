@@ -183,6 +183,12 @@ void launch_density(const FinishArgs& t, const uint32_t* xw, int n, int npad, do
 constexpr int kFusedMaxD = 1024;   // beyond this the per-block parameter derivation costs more than a k_finish launch
 void launch_density_fused(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
                           int* zero_flags, int n_zero_flags, hipStream_t s);
+// the start of a run in ONE launch (k_density_start): the restart head (t.reset_*: initial parameters into t.prop / center /
+// disp, class sizes zeroed, loop control and sweep counter cleared, t.zero_stats cleared) and the density of the given
+// parameters, every block deriving its class constants from them.  The table buffers are not rebuilt.  Same shapes as
+// launch_density_fused; not recordable.
+void launch_density_start(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
+                          int* zero_flags, int n_zero_flags, hipStream_t s);
 // ... and the same density beside the last relaxation round of the previous iteration's sweep, in ONE launch
 // (k_density_verify); the round's arguments are complete, its last-block ticket included.  Not recordable.
 bool density_verify_supported(int n_local, int K, int tie_rule);

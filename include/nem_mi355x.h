@@ -242,6 +242,35 @@ int nemgpu_master_create_counts(nemgpu_master** out, int device, int n, int d, c
 int nemgpu_master_create_orders(nemgpu_master** out, int device, int d, int f, int directed, const int32_t* genes, int g,
                                 const int32_t* contig_ptr, const int32_t* contig_org, const uint8_t* contig_circular, int c,
                                 const uint8_t* repeated);
+/* A master GROWN by new organisms on the device: PPanGGOLiN.add_organism (ppanggolin.py:342-358), which keeps the graph
+   and walks only the new organisms (__neighborhood_computation(update=new_orgs), :463-530).  *out is a new master on
+   m's device (its own allocation and stream) = m + the gene orders of the new organisms alone; m is only read and stays
+   valid (a nemgpu_votes made for it or a nemgpu_solve_chunks running on it is not disturbed; the caller destroys it).
+   m's arrays do not cross PCIe: the update's orders and m's numbering (4 n bytes) go up, the new sizes come back.
+     d_new                the new organisms: columns d .. d + d_new - 1 behind m's d;
+     f                    the caller's id space now (>= the f the master was made with; made from arrays: >= n, family i
+                          is id i);     genes / contig_ptr / contig_circular as nemgpu_master_create_orders takes them;
+     contig_org[c]        ABSOLUTE columns, in [d, d + d_new);
+     repeated[f]          families_repeted as the caller holds it after add_organism (the union), or NULL.
+   The rules are nemgpu_master_create_orders', undirected, on the update's genes, and nx.Graph's on what is there:
+   an id the master has keeps its number (one repeated only from now on keeps its node and old edges; its new genes do
+   not exist and are bridged over), the other ids with a kept gene are numbered n, n + 1, ... in order of first kept
+   gene (ids below the old f that never had a kept gene among them); an existing (row, neighbour) keeps its place in its
+   row, a new one goes behind the row's old entries in order of first occurrence in the update (nx.all_neighbors after
+   add_edge); count[entry][new organism] = its half-edges, >= 1 sets the bit in edge_bits (stride now ceil((d + d_new) /
+   32), old words copied, bits above an old row's organism d - 1 dropped), >= 2 lists count behind the entry's old extras;
+   the presence rows are re-strided, new families absent from the old organisms.  With the same `repeated` for both
+   parts, appending B to the master of A is nemgpu_master_create_orders of A + B, array for array.
+   Refused on the host before any HIP call (NEMGPU_E_ARG, nemgpu_last_error says why): malformed orders (create's
+   rules), f below the master's, a contig_org outside [d, d + d_new), d_new <= 0, more than 131 072 organisms in all, a
+   master built with directed = 1 (a row's predecessor / successor order cannot be recovered from summed counts: rebuild),
+   a bits-only master of nemgpu_master_create (its counts are not known).  After numbering: 2 bits(n') + bits(d') <= 63;
+   an edge's old + new count may not exceed 2^24 (checked on the device, reported as create reports it).
+   A master made from arrays (nemgpu_master_create_counts) is taken as an undirected graph: a SYMMETRIC CSR (entry
+   (a, b) iff entry (b, a), equal counts) is the caller's contract and is not checked. */
+int nemgpu_master_append_orders(nemgpu_master** out, const nemgpu_master* m, int d_new, int f, const int32_t* genes, int g,
+                                const int32_t* contig_ptr, const int32_t* contig_org, const uint8_t* contig_circular, int c,
+                                const uint8_t* repeated);
 /* What a master holds, of whichever constructor: sizes (n families, d organisms, nnz CSR entries, n_extra pairs with
    count >= 2; any pointer may be NULL), and the arrays as nemgpu_master_create_counts takes them, read back from the
    device: xbits[n][ceil(d/32)], nei_ptr[n + 1], nei_idx[nnz], edge_bits[nnz][ceil(d/32)], extra_ptr[nnz + 1],

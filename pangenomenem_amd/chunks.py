@@ -19,7 +19,9 @@ twice in an organism (tandem duplicates, repeated operons and every edge of a di
 
 ``Master.from_orders`` / ``Master.from_annotations`` build the same master on the device from the organisms' gene orders
 (``nemgpu_master_create_orders``, csrc/nem_orders.hip): no graph, no networkx; ``master_arrays_from_orders`` is that build
-in numpy.
+in numpy.  ``Master.add_orders`` / ``Master.add_annotations`` grow a master by new organisms
+(PPanGGOLiN.add_organism, ppanggolin.py:342-358) from their gene orders alone (``nemgpu_master_append_orders``);
+``master_arrays_append_orders`` is that append in numpy.
 
 ``Master`` puts that one pangenome on the device (``nemgpu_master_create[_counts]``); ``solve_chunks`` solves any number of
 samples in ONE library call (``nemgpu_solve_chunks``): the device forms every sample's problem straight into its engine's
@@ -61,6 +63,8 @@ def pack_rows(x):
 def _bind_master(lib):
     lib.nemgpu_master_create_orders.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.nemgpu_master_append_orders.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.nemgpu_master_shape.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
     lib.nemgpu_master_fetch.argtypes = [C.c_void_p] * 9
     lib.nemgpu_master_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -185,20 +189,21 @@ def master_arrays_from_graph(graph, organisms=None):
 FAMILY = 1                  # index of the family in a gene's annotation (ppanggolin.py:25)
 
 
-def orders_from_annotations(annotations, organisms, circular_contigs=(), repeated=(), family=FAMILY):
+def orders_from_annotations(annotations, organisms, circular_contigs=(), repeated=(), family=FAMILY, families=()):
     """PPanGGOLiN's ``annotations`` ({organism: {contig: OrderedDict(gene -> info)}}, the family at info[family]) as the
     flat gene orders of nemgpu_master_create_orders.  organisms: the master's organisms in column order (every organism
     of annotations must be among them); circular_contigs: the contig names of circular_contig_size; repeated: the
     family names of families_repeted.  The walk is __neighborhood_computation's (ppanggolin.py:478-481): annotations'
     organisms, their contigs, their genes, each in dict order.  Returns a dict: genes int32 [G], contig_ptr int32
     [C + 1], contig_org int32 [C], contig_circular uint8 [C], repeated uint8 [F], d, families (the family name of every
-    id, in order of first gene), organisms."""
+    id, in order of first gene), organisms.  families: the names that have ids already (0, 1, ...: an earlier call's
+    `families`, for the orders of an update -- Master.add_annotations); the new names follow them."""
     organisms = list(organisms)
     col = {o: c for c, o in enumerate(organisms)}
     if len(col) != len(organisms):
         raise ValueError("organisms: distinct names")
     circular_contigs = set(circular_contigs)
-    fam_id = {}
+    fam_id = {name: i for i, name in enumerate(families)}
     genes, cptr, corg, circ = [], [0], [], []
     for org, contigs in annotations.items():
         if org not in col:
@@ -314,6 +319,130 @@ def master_arrays_from_orders(genes, contig_ptr, contig_org, contig_circular, d,
     return x, (ptr, idx), edge_bits, edge_counts, order, list(range(d))
 
 
+def master_arrays_append_orders(master_arrays, order, f_old, genes, contig_ptr, contig_org, contig_circular, d_new, repeated=None, f=None):
+    """The master that master_arrays_from_graph makes of the nx.Graph after PPanGGOLiN.add_organism (ppanggolin.py:342-358:
+    the graph kept, families_repeted united, __neighborhood_computation(update=new_orgs) walking the new organisms
+    alone), from the old master's arrays and the new organisms' gene orders, in numpy: the statement of what
+    nemgpu_master_append_orders computes.  master_arrays: (x uint8 [n][d], (ptr, idx), edge_bits, edge_counts, ...) of
+    an undirected master; order int32 [n]: its family i is caller id order[i]; f_old: the id space it was made with;
+    the orders as master_arrays_from_orders takes them with contig_org the ABSOLUTE columns d .. d + d_new - 1 and
+    repeated [f] the union after the update (f >= f_old).
+      * genes, links, times: master_arrays_from_orders' rules, undirected, on the update's genes;
+      * an id in the master keeps its number (repeated only from now on: its node and old edges stay, its new genes do
+        not exist); the other ids with a kept gene are numbered n, n + 1, ... by first kept gene;
+      * an existing (row, neighbour) keeps its place in its row; a new one goes behind the row's old entries, by the first
+        time among the update's records (nx.all_neighbors after add_edge);
+      * count[entry, new organism] = its half-edges: >= 1 sets the bit (stride ceil((d + d_new) / 32)), >= 2 lists the
+        count behind the entry's old extras; the old rows keep their bits, new families are absent from old organisms.
+    Returns what master_arrays_from_orders returns: x, (ptr, idx), edge_bits, edge_counts, order (grown), range(d + d_new)."""
+    x0 = np.asarray(master_arrays[0], np.uint8)
+    ptr0, idx0 = (np.asarray(a, np.int64) for a in master_arrays[1])
+    n0, d0 = x0.shape
+    nnz0 = len(idx0)
+    wf0 = (d0 + 31) // 32
+    eb0 = np.asarray(master_arrays[2], np.uint32).reshape(nnz0, wf0)
+    xptr0, xorg0, xcnt0 = (np.asarray(a, np.int64) for a in master_arrays[3])
+    order0 = np.asarray(order, np.int64)
+    if order0.shape != (n0,) or ptr0.shape != (n0 + 1,) or xptr0.shape != (nnz0 + 1,):
+        raise ValueError("append: the master's arrays and its order [n]")
+    if d_new <= 0:
+        raise ValueError("append: d_new must be positive")
+    d = d0 + int(d_new)
+    if f is None and repeated is None:
+        f = max(int(f_old), int(np.max(genes)) + 1 if len(genes) else 1)
+    genes, contig_ptr, contig_org, contig_circular, repeated, d, f = _check_orders(genes, contig_ptr, contig_org, contig_circular, repeated, d, f)
+    if f < f_old or (n0 and order0.max() >= f_old):
+        raise ValueError("append: f may not be below the master's id space")
+    if contig_org.min() < d0:
+        raise ValueError("orders: contig organism out of range (a column of the old master)")
+    g, c = len(genes), len(contig_org)
+    wf = (d + 31) // 32
+    pos = np.arange(g, dtype=np.int64)
+    kept = np.ones(g, bool) if repeated is None else repeated[genes] == 0
+    contig_of = np.repeat(np.arange(c, dtype=np.int64), np.diff(contig_ptr))
+    last = np.maximum.accumulate(np.where(kept, pos, -1)) if g else pos
+    prev = np.concatenate([[-1], last[:-1]]) if g else pos
+    kp = np.flatnonzero(kept)
+    # the numbering: the old one, then the ids it lacks by first kept gene
+    newid = np.full(f, -1, np.int64)
+    newid[order0] = np.arange(n0)
+    fresh = kp[newid[genes[kp]] < 0]
+    fam_of, first = np.unique(genes[fresh], return_index=True)
+    added = fam_of[np.argsort(first, kind="stable")]
+    n = n0 + len(added)
+    newid[added] = n0 + np.arange(len(added))
+    x = np.zeros((n, d), np.uint8)
+    x[:n0, :d0] = x0
+    x[newid[genes[kp]], contig_org[contig_of[kp]]] = 1
+    # the update's half-edge records, as master_arrays_from_orders makes them
+    cj = contig_of[kp]
+    start, end = contig_ptr[cj].astype(np.int64), contig_ptr[cj + 1].astype(np.int64)
+    linked = prev[kp] >= start
+    closing = ~linked & (contig_circular[cj] != 0)
+    has = linked | closing
+    other = np.where(linked, prev[kp], last[np.maximum(end - 1, 0)])[has]
+    t = np.where(linked, kp + cj, end + cj)[has]
+    a, b, o = newid[genes[kp[has]]], newid[genes[other]], contig_org[cj[has]].astype(np.int64)
+    two = a != b
+    row, nbr, org, key = np.concatenate([a, b[two]]), np.concatenate([b, a[two]]), np.concatenate([o, o[two]]), np.concatenate([t, t[two]])
+    srt = np.lexsort((org, nbr, row))
+    row, nbr, org, key = row[srt], nbr[srt], org[srt], key[srt]
+    m = len(row)
+    new_pair = np.ones(m, bool)
+    new_pair[1:] = (row[1:] != row[:-1]) | (nbr[1:] != nbr[:-1]) | (org[1:] != org[:-1])
+    new_edge = np.ones(m, bool)
+    new_edge[1:] = (row[1:] != row[:-1]) | (nbr[1:] != nbr[:-1])
+    pair_at, edge_at = np.flatnonzero(new_pair), np.flatnonzero(new_edge)
+    pair_count = np.diff(np.append(pair_at, m))
+    pair_edge = np.cumsum(new_edge)[pair_at] - 1
+    erow, enbr = row[edge_at], nbr[edge_at]
+    edge_first = np.minimum.reduceat(key, edge_at) if len(edge_at) else np.zeros(0, np.int64)
+    # every edge of the update in its old row, or new
+    row0 = np.repeat(np.arange(n0, dtype=np.int64), np.diff(ptr0))
+    okey = row0 * n + idx0
+    by = np.argsort(okey, kind="stable")
+    at = np.searchsorted(okey[by], erow * n + enbr)
+    found = np.zeros(len(edge_at), bool)
+    inside = at < nnz0
+    found[inside] = okey[by][at[inside]] == (erow * n + enbr)[inside]
+    oldpos = np.where(found, by[np.minimum(at, max(nnz0 - 1, 0))] if nnz0 else 0, -1)
+    deg0 = np.zeros(n, np.int64)
+    deg0[:n0] = np.diff(ptr0)
+    grown = np.bincount(erow[~found], minlength=n)
+    ptr = np.zeros(n + 1, np.int64)
+    ptr[1:] = np.cumsum(deg0 + grown)
+    nnz = int(ptr[-1])
+    fwd = ptr[row0] + (np.arange(nnz0) - ptr0[row0])          # old entry t -> its entry now
+    perm = np.lexsort((edge_first, erow))
+    fresh_e = perm[~found[perm]]                              # the new edges by (row, first time)
+    rank = np.arange(len(fresh_e)) - (np.cumsum(grown) - grown)[erow[fresh_e]]
+    entry = np.empty(len(edge_at), np.int64)
+    entry[found] = fwd[oldpos[found]]
+    entry[fresh_e] = ptr[erow[fresh_e]] + deg0[erow[fresh_e]] + rank
+    idx = np.empty(nnz, np.int32)
+    idx[fwd] = idx0
+    idx[entry[fresh_e]] = enbr[fresh_e]
+    edge_bits = np.zeros((nnz, wf), np.uint32)
+    if nnz0:
+        keep = eb0.copy()
+        if d0 & 31:
+            keep[:, -1] &= np.uint32((1 << (d0 & 31)) - 1)    # (the bits above the last old organism are not data)
+        edge_bits[fwd, :wf0] = keep
+    pe = entry[pair_edge]
+    np.bitwise_or.at(edge_bits, (pe, org[pair_at] >> 5), (np.uint32(1) << (org[pair_at] & 31).astype(np.uint32)))
+    # the extras: an entry's old ones, then the update's (every new column is larger than every old one)
+    multi = pair_count >= 2
+    xe = np.concatenate([fwd[np.repeat(np.arange(nnz0), np.diff(xptr0))], pe[multi]])
+    xo = np.concatenate([xorg0, org[pair_at][multi]])
+    xc = np.concatenate([xcnt0, pair_count[multi]])
+    xs = np.lexsort((xo, xe))
+    xptr = np.zeros(nnz + 1, np.int32)
+    xptr[1:] = np.cumsum(np.bincount(xe, minlength=nnz))
+    edge_counts = (xptr, xo[xs].astype(np.int32), xc[xs].astype(np.int32))
+    grown_order = np.concatenate([order0, added]).astype(np.int32)
+    return x, (ptr.astype(np.int32), idx), edge_bits, edge_counts, grown_order, list(range(d))
+
+
 class Master:
     """One pangenome on the device: presence/absence matrix, neighbourhood graph, per directed edge its organisms."""
 
@@ -349,6 +478,8 @@ class Master:
             what = "nemgpu_master_create_counts"
         if rc != 0:
             raise NemGpuError("%s failed (status %d): %s" % (what, rc, lib.nemgpu_last_error().decode()))
+        self.order = np.arange(self.n, dtype=np.int32)       # (made from arrays: family i is caller id i)
+        self.directed, self.f = False, self.n
 
     @classmethod
     def from_graph(cls, graph, organisms=None, device=0):
@@ -357,6 +488,8 @@ class Master:
         x, (ptr, idx), edge_bits, edge_counts, families, orgs = master_arrays_from_graph(graph, organisms)
         m = cls(x, ptr, idx, edge_bits, device=device, edge_counts=edge_counts)
         m.names, m.organism_names = list(families), list(orgs)
+        m.id_names = list(families)
+        m.directed = bool(graph.is_directed())
         return m
 
     @classmethod
@@ -377,6 +510,7 @@ class Master:
         m.wf = (m.d + 31) // 32
         m.order = np.zeros(m.n, np.int32)
         m._fetch(order=m.order)
+        m.directed, m.f = bool(directed), f
         return m
 
     @classmethod
@@ -387,6 +521,50 @@ class Master:
         m = cls.from_orders(o["genes"], o["contig_ptr"], o["contig_org"], o["contig_circular"], o["d"], repeated=o["repeated"],
                             directed=directed, device=device)
         m.names, m.organism_names = [o["families"][i] for i in m.order], list(o["organisms"])
+        m.id_names = list(o["families"])                      # (every caller id's name: add_annotations numbers on from them)
+        return m
+
+    def add_orders(self, genes, contig_ptr, contig_org, contig_circular, d_new, repeated=None, f=None):
+        """A NEW master = this one + the gene orders of d_new new organisms (nemgpu_master_append_orders;
+        master_arrays_append_orders states what it computes): contig_org holds their absolute columns d .. d + d_new - 1,
+        repeated [f] the union of the repeated families, f >= this master's .f.  This master is only read and stays
+        usable.  Not for a directed master, nor for a bits-only one."""
+        if f is None and repeated is None:
+            f = max(self.f, int(np.max(genes)) + 1 if len(genes) else 1)
+        genes, contig_ptr, contig_org, contig_circular, repeated, d, f = _check_orders(genes, contig_ptr, contig_org, contig_circular, repeated,
+                                                                                       self.d + int(d_new), f)
+        m = Master.__new__(Master)
+        m.lib = self.lib
+        m._h = C.c_void_p()
+        rc = m.lib.nemgpu_master_append_orders(C.byref(m._h), self._h, int(d_new), f, genes.ctypes.data, len(genes), contig_ptr.ctypes.data,
+                                               contig_org.ctypes.data, contig_circular.ctypes.data, len(contig_org),
+                                               repeated.ctypes.data if repeated is not None else None)
+        if rc != 0:
+            raise NemGpuError("nemgpu_master_append_orders failed (status %d): %s" % (rc, m.lib.nemgpu_last_error().decode()))
+        m.n, m.d, _, _ = m.shape()
+        m.wf = (m.d + 31) // 32
+        m.order = np.zeros(m.n, np.int32)
+        m._fetch(order=m.order)
+        m.directed, m.f = False, f
+        return m
+
+    def add_annotations(self, new_annotations, new_organisms, circular_contigs=(), repeated=(), family=FAMILY):
+        """PPanGGOLiN.add_organism (ppanggolin.py:342-358) on a master that carries names (from_annotations, from_graph or
+        an earlier add_annotations): new_annotations of new_organisms (their columns follow this master's), circular_contigs
+        the new contigs' names, repeated the UNION of the repeated families' names.  Returns the new master, its .names
+        and .organism_names grown."""
+        if getattr(self, "id_names", None) is None:
+            raise ValueError("add_annotations: this master carries no names (use add_orders)")
+        if self.directed:
+            raise NemGpuError("add_annotations: the master was built directed (a row's order cannot be recovered); rebuild it")
+        new_organisms = list(new_organisms)
+        if set(new_organisms) & set(self.organism_names):
+            raise ValueError("add_annotations: an organism the master already has")
+        o = orders_from_annotations(new_annotations, self.organism_names + new_organisms, circular_contigs, repeated, family,
+                                    families=self.id_names)
+        m = self.add_orders(o["genes"], o["contig_ptr"], o["contig_org"], o["contig_circular"], len(new_organisms), repeated=o["repeated"])
+        m.id_names = list(o["families"])
+        m.names, m.organism_names = [m.id_names[i] for i in m.order], list(o["organisms"])
         return m
 
     def shape(self):

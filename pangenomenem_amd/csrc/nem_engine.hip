@@ -318,6 +318,10 @@ struct nemgpu_master {
     char* block = nullptr;
     nemk::MasterDev dev{};
     std::vector<int32_t> order;                       // nemgpu_master_create_orders: family i = caller id order[i] (else empty: i)
+    // what nemgpu_master_append_orders must know of how the master was made
+    int f_old = 0;                                    // the caller-id space (made from arrays: n)
+    bool directed = false;                            // built as a DiGraph: a row's order cannot be continued
+    bool bits_only = false;                           // nemgpu_master_create: its counts are not known
 };
 // nemgpu_resamples_solve: where every lock-step group's runs are reduced to their P/S/C/U counts (nem_resample.hpp)
 struct ResampleTally {
@@ -3668,6 +3672,8 @@ int nemgpu_master_create_counts(nemgpu_master** out, int device, int n, int d, c
     (void)hipFree(xf_tmp);
     m->dev = nemk::MasterDev{n, d, wf, nw64, nnz, xt, dptr, didx, deb, dxptr, dxorg, dxadd};
     m->nx = nx;
+    m->f_old = n;
+    m->bits_only = extra_ptr == nullptr;
     *out = m;
     return NEMGPU_OK;
 }
@@ -3735,6 +3741,81 @@ int nemgpu_master_create_orders(nemgpu_master** out, int device, int d, int f, i
     if (over) return fail(NEMGPU_E_ARG, "edge counts: an edge's total count above 2^24 (a float weight would not be exact)");
     nemk::orders_free(build);
     m->dev = nemk::MasterDev{n, d, wf, nw64, nnz, xt, dptr, didx, deb, dxptr, dxorg, dxadd};
+    m->f_old = f;
+    m->directed = directed != 0;
+    *out = m;
+    return NEMGPU_OK;
+}
+
+int nemgpu_master_append_orders(nemgpu_master** out, const nemgpu_master* old, int d_new, int f, const int32_t* genes, int g,
+                                const int32_t* contig_ptr, const int32_t* contig_org, const uint8_t* contig_circular, int c,
+                                const uint8_t* repeated)
+{
+    if (!out) return NEMGPU_E_FUNCARG;
+    *out = nullptr;
+    // the orders first: what does not depend on the master is refused without one (testable without a device)
+    const int d_old = old ? old->d : 0;
+    if (d_new <= 0) { set_error("nemgpu_master_append_orders: d_new must be positive"); return NEMGPU_E_ARG; }
+    const long long d_ll = (long long)d_old + d_new;
+    if ((d_ll + 31) / 32 > nemk::chunk_mask_words_max()) { set_error("nemgpu_master_append_orders: more than 131 072 organisms"); return NEMGPU_E_ARG; }
+    const int d = (int)d_ll;
+    { const int r = check_orders(d, f, g, c, genes, contig_ptr, contig_org, contig_circular); if (r != NEMGPU_OK) return r; }
+    for (int j = 0; j < c; j++)
+        if (contig_org[j] < d_old) { set_error("orders: contig " + std::to_string(j) + ": organism out of range (a column of the old master)"); return NEMGPU_E_ARG; }
+    if (!old) { set_error("nemgpu_master_append_orders: a master is needed"); return NEMGPU_E_FUNCARG; }
+    if (old->directed) {
+        set_error("nemgpu_master_append_orders: the master was built directed (a row's predecessor / successor order cannot be "
+                  "recovered from its summed counts); rebuild it from all the orders");
+        return NEMGPU_E_ARG;
+    }
+    if (old->bits_only) {
+        set_error("nemgpu_master_append_orders: a bits-only master (nemgpu_master_create): its counts are not known");
+        return NEMGPU_E_ARG;
+    }
+    if (f < old->f_old) { set_error("nemgpu_master_append_orders: f is below the master's " + std::to_string(old->f_old) + " family ids"); return NEMGPU_E_ARG; }
+    g_hip_used.store(true);
+    HIPCHK(hipSetDevice(old->device));
+    nemgpu_master* m = new nemgpu_master();
+    nemk::OrdersBuild* build = nullptr;
+    auto fail = [&](int rc, const std::string& what) { nemk::orders_free(build); if (m->block) (void)hipFree(m->block);
+                                                       if (m->stream) (void)hipStreamDestroy(m->stream); delete m; set_error(what); return rc; };
+    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) return fail(NEMGPU_E_DEVICE, "hipStreamCreate failed");
+    nemk::OrdersIn in{d, f, 0, g, c, genes, contig_ptr, contig_org, contig_circular, repeated};
+    in.n_old = old->n;
+    in.order_old = old->order.empty() ? nullptr : old->order.data();
+    int n = 0, nnz_u = 0, nx_u = 0, nnz = 0;
+    hipError_t err = nemk::orders_stage(in, m->stream, &build, &n, &nnz_u, &nx_u);
+    if (err == hipErrorInvalidValue) return fail(NEMGPU_E_ARG, "orders: too many families for this many organisms (2 bits(n) + bits(d) > 63)");
+    if (err == hipSuccess) err = nemk::orders_append_plan(build, old->dev, m->stream, &nnz);
+    if (err == hipErrorInvalidValue) return fail(NEMGPU_E_ARG, "nemgpu_master_append_orders: more than 2^31 - 1 CSR entries");
+    if (err != hipSuccess) return fail(NEMGPU_E_DEVICE, std::string("nemgpu_master_append_orders: ") + hipGetErrorString(err));
+    if ((long long)old->nx + nx_u > 0x7fffffff) return fail(NEMGPU_E_ARG, "nemgpu_master_append_orders: more than 2^31 - 1 multi-copy pairs");
+    const int nx = old->nx + nx_u;
+    const int wf = (d + 31) / 32, nw64 = (n + 63) / 64;
+    m->device = old->device; m->n = n; m->d = d; m->wf = wf; m->nw64 = nw64; m->nnz = nnz; m->nx = nx;
+    auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t b_xt = a256((size_t)d * nw64 * 8), b_ptr = a256(((size_t)n + 1) * 4), b_idx = a256((size_t)std::max(nnz, 1) * 4),
+                 b_eb = a256((size_t)std::max(nnz, 1) * wf * 4);
+    const size_t b_xptr = nx > 0 ? a256(((size_t)nnz + 1) * 4) : 0, b_xorg = nx > 0 ? a256((size_t)nx * 4) : 0;
+    if (hipMalloc(&m->block, b_xt + b_ptr + b_idx + b_eb + b_xptr + 2 * b_xorg) != hipSuccess) return fail(NEMGPU_E_DEVICE, "nemgpu_master_append_orders: device memory");
+    uint64_t* xt = (uint64_t*)m->block;
+    int* dptr = (int*)(m->block + b_xt);
+    int* didx = (int*)(m->block + b_xt + b_ptr);
+    uint32_t* deb = (uint32_t*)(m->block + b_xt + b_ptr + b_idx);
+    int* dxptr = nx > 0 ? (int*)(m->block + b_xt + b_ptr + b_idx + b_eb) : nullptr;
+    int* dxorg = nx > 0 ? (int*)(m->block + b_xt + b_ptr + b_idx + b_eb + b_xptr) : nullptr;
+    int* dxadd = nx > 0 ? (int*)(m->block + b_xt + b_ptr + b_idx + b_eb + b_xptr + b_xorg) : nullptr;
+    m->order.resize((size_t)n);
+    if (old->order.empty()) for (int i = 0; i < old->n; i++) m->order[(size_t)i] = i;
+    else std::copy(old->order.begin(), old->order.end(), m->order.begin());
+    int over = 0;
+    err = nemk::orders_append_fill(build, old->dev, old->nx, nnz, xt, nw64, dptr, didx, deb, wf, dxptr, dxorg, dxadd,
+                                   m->order.data() + old->n, &over, m->stream);
+    if (err != hipSuccess) return fail(NEMGPU_E_DEVICE, std::string("nemgpu_master_append_orders: ") + hipGetErrorString(err));
+    if (over) return fail(NEMGPU_E_ARG, "edge counts: an edge's total count above 2^24 (a float weight would not be exact)");
+    nemk::orders_free(build);
+    m->dev = nemk::MasterDev{n, d, wf, nw64, nnz, xt, dptr, didx, deb, dxptr, dxorg, dxadd};
+    m->f_old = f;
     *out = m;
     return NEMGPU_OK;
 }

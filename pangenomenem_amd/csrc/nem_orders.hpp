@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "nem_chunks.hpp"
+
 namespace nemk {
 
 struct OrdersIn {                 // HOST arrays, checked by the caller
@@ -38,6 +40,10 @@ struct OrdersIn {                 // HOST arrays, checked by the caller
     const int32_t* contig_org;
     const uint8_t* contig_circular;
     const uint8_t* repeated;      // or null
+    // an append (n_old > 0): the families the old master has keep their numbers, order_old[i] = the caller id of family
+    // i (null: i); d is then the grown master's organisms, contig_org its columns
+    int n_old = 0;
+    const int32_t* order_old = nullptr;
 };
 
 struct OrdersBuild;               // the device buffers between the two stages
@@ -52,6 +58,22 @@ hipError_t orders_stage(const OrdersIn& in, hipStream_t s, OrdersBuild** out, in
 hipError_t orders_fill(OrdersBuild* b, uint64_t* xt, int nw64, int* ptr, int* idx, uint32_t* edge_bits, int wf, int* extra_ptr,
                        int* extra_org, int* extra_add, int32_t* order_host, int* over, hipStream_t s);
 void orders_free(OrdersBuild* b);
+
+// An append: a new master = an old one (undirected, its counts known) + the gene orders of new organisms alone, whose
+// columns lie behind the old ones.  orders_stage (n_old > 0) makes the update's records, runs and edges in the GROWN
+// numbering: an id the old master has keeps its number, the others with a kept gene follow in order of first kept gene.
+//   * every edge of the update is looked up in its old row (a walk); the edges not found are ranked per row by first
+//     time (the scan of their flags in (row, first time) order): a row = its old entries, then these;
+//   * ptr = the scan of old degree + new edges; old idx / edge_bits / extras scattered to their places, the old bit rows
+//     and presence rows re-strided; the update's organisms OR-ed in, its pairs with count >= 2 behind the entry's old
+//     extras (every new column is larger than every old one); old + new count bounded by 2^24.
+// orders_append_plan: *nnz_new = the grown master's CSR entries (its extras: nx_old + orders_stage's *nx).  Waits.
+hipError_t orders_append_plan(OrdersBuild* b, const MasterDev& old, hipStream_t s, int* nnz_new);
+// the grown master's arrays (device; extra_* null when it has no extras); order_host: room for the new families' caller
+// ids (n - old.n).  Waits.
+hipError_t orders_append_fill(OrdersBuild* b, const MasterDev& old, int nx_old, int nnz, uint64_t* xt, int nw64, int* ptr, int* idx,
+                              uint32_t* edge_bits, int wf, int* extra_ptr, int* extra_org, int* extra_add, int32_t* order_host, int* over,
+                              hipStream_t s);
 
 // organism-major bit rows [d][nw64] -> family-major bit rows [n][wf] (launch_master_transpose's inverse)
 void launch_master_rows(const uint64_t* xt, int n, int wf, int d, int nw64, uint32_t* xf, hipStream_t s);

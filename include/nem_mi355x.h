@@ -271,6 +271,36 @@ int nemgpu_master_create_orders(nemgpu_master** out, int device, int d, int f, i
 int nemgpu_master_append_orders(nemgpu_master** out, const nemgpu_master* m, int d_new, int f, const int32_t* genes, int g,
                                 const int32_t* contig_ptr, const int32_t* contig_org, const uint8_t* contig_circular, int c,
                                 const uint8_t* repeated);
+/* A partition PROJECTED onto the organisms from the master: what PPanGGOLiN.projection (ppanggolin.py:1698-1755; the
+   CLI's -pr; the first step of partition_shell(Q = "auto"), :1190-1192) counts and writes, as arrays, with no graph and
+   no per-gene loop on the host.  HOST arrays; m is only read and stays valid and unchanged; the work runs on m's stream
+   (as nemgpu_master_fetch does: not next to another call on the same master from another thread).
+     part[n]              every master family's class in the vote's codes: P 0, S 1, C 2, U 3 (nemgpu_votes_result's final);
+     f, genes[g], contig_ptr[c + 1], contig_org[c], repeated[f] or NULL
+                          the gene orders of the organisms to project as nemgpu_master_create_orders takes them (no
+                          contig_circular): contig_org are m's columns, any subset of them in any order, an organism's
+                          contigs need not be adjacent; ids in the numbering m was made with (nemgpu_master_fetch's
+                          `order`); g = 0 (and c = 0) is allowed.
+   Outputs, any may be NULL:
+     gene_family[g]       the master family of every gene; -1 for a gene of a repeated family (projection() skips it,
+                          :1719); -2 for an id that no master family has (the reference would raise KeyError).  The
+                          other genes are KEPT;
+     gene_copies[g]       for a kept gene the kept genes of its family in its organism among the contigs given
+                          (len(node[family][organism]), :1731); 0 for the others;
+     nei_counts[n][3]     per master family the entries of its CSR row whose neighbour is of class P, S, C
+                          (nx.all_neighbors of an nx.Graph, :1723: a self-loop is one entry; class U counts nowhere);
+     org_counts[d][7]     per master column over that organism's kept genes: persistent, shell, cloud, undefined (the
+                          family's class), core_exact (the family is present in all d organisms of m) or accessory
+                          (partition_exact, :1143-1148), pangenome (every kept gene); 0 for the organisms not given.
+   All integer: the results do not depend on the order of the device's additions.
+   Refused on the host before any launch (NEMGPU_E_ARG, nemgpu_last_error says why): malformed orders (create's rules:
+   ids in [0, f), contig_ptr monotone from 0 to g, contig_org in [0, d), g + c < 2^30), a part value above 3, a master
+   built with directed = 1 (nx.all_neighbors of a DiGraph lists a family that is both predecessor and successor of the
+   node twice, the master's row holds it once with the summed count: the reference's neighbour counts cannot be
+   recovered from it).  m == NULL: NEMGPU_E_FUNCARG. */
+int nemgpu_master_project(const nemgpu_master* m, const uint8_t* part, int f, const int32_t* genes, int g,
+                          const int32_t* contig_ptr, const int32_t* contig_org, int c, const uint8_t* repeated,
+                          int32_t* org_counts, int32_t* nei_counts, int32_t* gene_family, int32_t* gene_copies);
 /* What a master holds, of whichever constructor: sizes (n families, d organisms, nnz CSR entries, n_extra pairs with
    count >= 2; any pointer may be NULL), and the arrays as nemgpu_master_create_counts takes them, read back from the
    device: xbits[n][ceil(d/32)], nei_ptr[n + 1], nei_idx[nnz], edge_bits[nnz][ceil(d/32)], extra_ptr[nnz + 1],

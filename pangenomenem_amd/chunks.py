@@ -65,6 +65,7 @@ def _bind_master(lib):
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.nemgpu_master_append_orders.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.nemgpu_master_project.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
     lib.nemgpu_master_shape.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
     lib.nemgpu_master_fetch.argtypes = [C.c_void_p] * 9
     lib.nemgpu_master_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -566,6 +567,79 @@ class Master:
         m.id_names = list(o["families"])
         m.names, m.organism_names = [m.id_names[i] for i in m.order], list(o["organisms"])
         return m
+
+    def project_orders(self, part, genes, contig_ptr, contig_org, repeated=None, f=None):
+        """nemgpu_master_project on flat gene orders (projection.projection_arrays states what it computes and takes the
+        same orders): part uint8 [n]; contig_org the master's columns.  Returns gene_family int32 [g], gene_copies int32
+        [g], nei_counts int32 [n][3], org_counts int32 [d][7]."""
+        part = np.ascontiguousarray(part, np.uint8)
+        genes = np.ascontiguousarray(genes, np.int32)
+        contig_ptr = np.ascontiguousarray(contig_ptr, np.int32)
+        contig_org = np.ascontiguousarray(contig_org, np.int32)
+        if part.shape != (self.n,) or genes.ndim != 1 or contig_ptr.shape != (len(contig_org) + 1,):
+            raise ValueError("projection: part [n], genes [G], contig_ptr [C + 1], contig_org [C]")
+        if f is None:
+            f = len(repeated) if repeated is not None else max(self.f, int(genes.max()) + 1 if len(genes) else 1)
+        if repeated is not None:
+            repeated = np.ascontiguousarray(repeated, np.uint8)
+            if repeated.shape != (f,):
+                raise ValueError("projection: repeated [F]")
+        g = len(genes)
+        fam, copies = np.zeros(g, np.int32), np.zeros(g, np.int32)
+        nei, org = np.zeros((self.n, 3), np.int32), np.zeros((self.d, 7), np.int32)
+        rc = self.lib.nemgpu_master_project(self._h, part.ctypes.data, int(f), genes.ctypes.data if g else None, g, contig_ptr.ctypes.data,
+                                            contig_org.ctypes.data if len(contig_org) else None, len(contig_org),
+                                            repeated.ctypes.data if repeated is not None else None, org.ctypes.data, nei.ctypes.data,
+                                            fam.ctypes.data if g else None, copies.ctypes.data if g else None)
+        if rc != 0:
+            raise NemGpuError("nemgpu_master_project failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+        return fam, copies, nei, org
+
+    def projection(self, partitions, annotations=None, organisms=None, repeated=(), *, orders=None, family=FAMILY):
+        """PPanGGOLiN.projection (ppanggolin.py:1698-1755) of a finished partition on this master, on the device.
+        partitions: what Master.partition returned ({family name: 'P' | 'S' | 'C' | 'U'}; a family it does not name is
+        undefined) or uint8 [n] in the same codes.  annotations: PPanGGOLiN's (they go through orders_from_annotations
+        with this master's ids, so a master grown by add_annotations works); organisms: the names to project, in the
+        caller's order (default: all the master's); repeated: families_repeted.  orders=(genes, contig_ptr, contig_org[,
+        repeated[, f]]) instead of annotations: flat arrays, for a master without names (contig_org: its columns; the
+        projected organisms are then the columns in order of first contig).  A gene whose family the master does not
+        have raises KeyError naming it, as the reference would.  Returns a projection.Projection (the four arrays of
+        projection_arrays, means(), write())."""
+        from . import projection as pj
+        names = getattr(self, "names", None)
+        if isinstance(partitions, dict):
+            if names is None:
+                raise ValueError("projection: this master carries no names (give the classes as uint8 [n])")
+            part = pj.part_codes(partitions, names)
+        else:
+            part = np.ascontiguousarray(partitions, np.uint8)
+        if self.directed:
+            raise NemGpuError("projection: the master was built directed (nx.all_neighbors lists a predecessor that is also a successor "
+                              "twice, the master's row once: the neighbour counts cannot be recovered)")
+        if orders is not None:
+            if annotations is not None:
+                raise ValueError("projection: annotations or orders=, not both")
+            genes, contig_ptr, contig_org = orders[:3]
+            rep = orders[3] if len(orders) > 3 else None
+            fam, copies, nei, org = self.project_orders(part, genes, contig_ptr, contig_org, rep, orders[4] if len(orders) > 4 else None)
+            bad = np.flatnonzero(fam == pj.UNKNOWN)
+            if len(bad):
+                raise KeyError(int(np.asarray(genes)[bad[0]]))
+            columns = list(dict.fromkeys(int(o) for o in np.asarray(contig_org)))
+            return pj.Projection(fam, copies, nei, org, part, columns, names, getattr(self, "organism_names", None))
+        if annotations is None or getattr(self, "id_names", None) is None:
+            raise ValueError("projection: annotations and a master that carries names, or orders=")
+        organisms = list(self.organism_names if organisms is None else organisms)
+        col = {o: c for c, o in enumerate(self.organism_names)}
+        sub = {o: annotations[o] for o in organisms}          # (an organism without annotations: KeyError, as the reference's)
+        if len(sub) != len(organisms):
+            raise ValueError("projection: an organism named twice")
+        o = orders_from_annotations(sub, self.organism_names, (), repeated, family, families=self.id_names)
+        fam, copies, nei, org = self.project_orders(part, o["genes"], o["contig_ptr"], o["contig_org"], o["repeated"])
+        bad = np.flatnonzero(fam == pj.UNKNOWN)
+        if len(bad):
+            raise KeyError(o["families"][o["genes"][bad[0]]])
+        return pj.Projection(fam, copies, nei, org, part, [col[name] for name in organisms], names, self.organism_names)
 
     def shape(self):
         """(n families, d organisms, nnz CSR entries, pairs with count >= 2) as the device holds them (nemgpu_master_shape)"""

@@ -34,6 +34,7 @@
 #include "nem_kernels.hpp"
 #include "nem_chunks.hpp"
 #include "nem_orders.hpp"
+#include "nem_project.hpp"
 #include "nem_vote.hpp"
 #include "nem_resample.hpp"
 
@@ -3817,6 +3818,38 @@ int nemgpu_master_append_orders(nemgpu_master** out, const nemgpu_master* old, i
     m->dev = nemk::MasterDev{n, d, wf, nw64, nnz, xt, dptr, didx, deb, dxptr, dxorg, dxadd};
     m->f_old = f;
     *out = m;
+    return NEMGPU_OK;
+}
+
+// A partition projected onto the organisms (nem_project.hpp): everything refused is refused on the host, before any launch
+int nemgpu_master_project(const nemgpu_master* m, const uint8_t* part, int f, const int32_t* genes, int g,
+                          const int32_t* contig_ptr, const int32_t* contig_org, int c, const uint8_t* repeated,
+                          int32_t* org_counts, int32_t* nei_counts, int32_t* gene_family, int32_t* gene_copies)
+{
+    if (!m) return NEMGPU_E_FUNCARG;
+    if (!part || f <= 0 || g < 0 || c < 0 || !contig_ptr || (g > 0 && !genes) || (c > 0 && !contig_org)) {
+        set_error("nemgpu_master_project: the classes, f > 0, genes and contigs are needed"); return NEMGPU_E_FUNCARG;
+    }
+    if (m->directed) {
+        set_error("nemgpu_master_project: the master was built directed (nx.all_neighbors of a DiGraph lists a family that is both "
+                  "predecessor and successor twice, its row holds it once: the neighbour counts cannot be recovered)");
+        return NEMGPU_E_ARG;
+    }
+    for (int i = 0; i < m->n; i++)
+        if (part[i] > 3) { set_error("nemgpu_master_project: family " + std::to_string(i) + ": class " + std::to_string((int)part[i]) + " (P 0, S 1, C 2, U 3)"); return NEMGPU_E_ARG; }
+    if ((long long)g + c >= (1ll << 30)) { set_error("orders: genes + contigs must stay below 2^30"); return NEMGPU_E_ARG; }
+    if (contig_ptr[0] != 0 || contig_ptr[c] != g) { set_error("orders: contig_ptr must run from 0 to the number of genes"); return NEMGPU_E_ARG; }
+    for (int j = 0; j < c; j++) {
+        if (contig_ptr[j + 1] < contig_ptr[j]) { set_error("orders: contig_ptr not monotone"); return NEMGPU_E_ARG; }
+        if (contig_org[j] < 0 || contig_org[j] >= m->d) { set_error("orders: contig " + std::to_string(j) + ": organism out of range"); return NEMGPU_E_ARG; }
+    }
+    for (int p = 0; p < g; p++)
+        if (genes[p] < 0 || genes[p] >= f) { set_error("orders: gene " + std::to_string(p) + ": family id out of range"); return NEMGPU_E_ARG; }
+    g_hip_used.store(true);
+    HIPCHK(hipSetDevice(m->device));
+    const nemk::ProjectIn in{f, g, c, part, genes, contig_ptr, contig_org, repeated, m->order.empty() ? nullptr : m->order.data()};
+    const hipError_t err = nemk::project(m->dev, in, org_counts, nei_counts, gene_family, gene_copies, m->stream);
+    if (err != hipSuccess) { (void)hipGetLastError(); set_error(std::string("nemgpu_master_project: ") + hipGetErrorString(err)); return NEMGPU_E_DEVICE; }
     return NEMGPU_OK;
 }
 

@@ -1,0 +1,114 @@
+// nem_scan.hpp -- the block scans and the wave segment reduction that the units working on sorted records share
+// (nem_orders.hip: the master's build and append; nem_project.hip: a partition's projection).  256-thread blocks of 4
+// waves; a scan is three launches (tile totals, their prefixes, the tiles), in place allowed.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace nemk {
+namespace seg {
+
+constexpr int kThreads = 256;
+constexpr int kScanItems = 8, kScanTile = kThreads * kScanItems;
+
+struct OpMax { __device__ int operator()(int a, int b) const { return a > b ? a : b; } };
+struct OpMin { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a < b ? a : b; } };
+struct OpOr { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a | b; } };
+template <class T> struct OpSum { __device__ T operator()(T a, T b) const { return a + b; } };
+
+__device__ inline int lane_id() { return threadIdx.x & 63; }
+
+// ---- scans ----------------------------------------------------------------------------------------------------
+// exclusive prefix of v over the block's 256 threads (4 waves); *total (may be null): the block's total
+template <class T, class Op> __device__ inline T block_exclusive(T v, Op op, T ident, T* s_tot, T* total)
+{
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    T inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const T o = __shfl_up(inc, off); if (lane >= off) inc = op(o, inc); }
+    if (lane == 63) s_tot[w] = inc;
+    T ex = __shfl_up(inc, 1);
+    if (lane == 0) ex = ident;
+    __syncthreads();
+    T pre = ident, all = ident;
+    for (int j = 0; j < kThreads / 64; j++) { if (j < w) pre = op(pre, s_tot[j]); all = op(all, s_tot[j]); }
+    if (total) *total = all;
+    __syncthreads();
+    return op(pre, ex);
+}
+
+template <class T, class Op> __global__ __launch_bounds__(kThreads) void k_scan_reduce(const T* __restrict__ in, int n, Op op, T ident,
+                                                                                     T* __restrict__ partial)
+{
+    __shared__ T s_tot[kThreads / 64];
+    const long long base = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanItems;
+    T v = ident;
+#pragma unroll
+    for (int j = 0; j < kScanItems; j++) if (base + j < n) v = op(v, in[base + j]);
+    T all;
+    (void)block_exclusive(v, op, ident, s_tot, &all);
+    if (threadIdx.x == 0) partial[blockIdx.x] = all;
+}
+
+// the tiles' totals -> their exclusive prefixes, in place (one block); *total_out (may be null) = the grand total
+template <class T, class Op> __global__ __launch_bounds__(kThreads) void k_scan_partials(T* __restrict__ partial, int nb, Op op, T ident,
+                                                                                       T* __restrict__ total_out)
+{
+    __shared__ T s_tot[kThreads / 64];
+    T carry = ident;
+    for (int base = 0; base < nb; base += kThreads) {
+        const int i = base + threadIdx.x;
+        const T v = i < nb ? partial[i] : ident;
+        T all;
+        const T ex = block_exclusive(v, op, ident, s_tot, &all);
+        if (i < nb) partial[i] = op(carry, ex);
+        carry = op(carry, all);
+    }
+    if (total_out && threadIdx.x == 0) *total_out = carry;
+}
+
+template <class T, class Op, bool kInclusive>
+__global__ __launch_bounds__(kThreads) void k_scan_apply(const T* in, int n, Op op, T ident, const T* __restrict__ partial, T* out)
+{
+    __shared__ T s_tot[kThreads / 64];
+    const long long base = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanItems;
+    T item[kScanItems];
+    T v = ident;
+#pragma unroll
+    for (int j = 0; j < kScanItems; j++) { item[j] = base + j < n ? in[base + j] : ident; v = op(v, item[j]); }
+    T run = op(partial[blockIdx.x], block_exclusive(v, op, ident, s_tot, (T*)nullptr));
+#pragma unroll
+    for (int j = 0; j < kScanItems; j++) {
+        const T next = op(run, item[j]);
+        if (base + j < n) out[base + j] = kInclusive ? next : run;
+        run = next;
+    }
+}
+
+// out = scan of in over n items (in place allowed); partial: room for ceil(n / kScanTile) items
+template <class T, class Op, bool kInclusive> void scan(const T* in, T* out, int n, Op op, T ident, T* partial, T* total_out, hipStream_t s)
+{
+    const int nb = (n + kScanTile - 1) / kScanTile;
+    if (nb == 0) { if (total_out) (void)hipMemsetAsync(total_out, 0, sizeof(T), s); return; }   // (only the sums are called with n = 0)
+    hipLaunchKernelGGL((k_scan_reduce<T, Op>), dim3(nb), dim3(kThreads), 0, s, in, n, op, ident, partial);
+    hipLaunchKernelGGL((k_scan_partials<T, Op>), dim3(1), dim3(kThreads), 0, s, partial, nb, op, ident, total_out);
+    hipLaunchKernelGGL((k_scan_apply<T, Op, kInclusive>), dim3(nb), dim3(kThreads), 0, s, in, n, op, ident, (const T*)partial, out);
+}
+
+// inclusive scan of val over the wave's lanes of equal key (equal keys are adjacent); tail: the segment's last lane
+template <class K, class V, class Op> __device__ inline V wave_segment(K key, V val, Op op, bool& tail)
+{
+    const int lane = lane_id();
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const K k2 = __shfl_up(key, off);
+        const V v2 = __shfl_up(val, off);
+        if (lane >= off && k2 == key) val = op(v2, val);
+    }
+    const K kn = __shfl_down(key, 1);
+    tail = lane == 63 || kn != key;
+    return val;
+}
+
+}  // namespace seg
+}  // namespace nemk

@@ -39,6 +39,7 @@ from collections import defaultdict
 import numpy as np
 
 from .engine import ALGO, CVT, DISP, PROP, STATUS_OK, TIE, Config, NemGpuError, Result, load_library
+from .projection import check_orders
 
 
 class Chunk(C.Structure):
@@ -224,28 +225,8 @@ def orders_from_annotations(annotations, organisms, circular_contigs=(), repeate
 
 
 def _check_orders(genes, contig_ptr, contig_org, contig_circular, repeated, d, f):
-    genes = np.ascontiguousarray(genes, np.int32)
-    contig_ptr = np.ascontiguousarray(contig_ptr, np.int32)
-    contig_org = np.ascontiguousarray(contig_org, np.int32)
-    contig_circular = np.ascontiguousarray(contig_circular, np.uint8)
-    c = len(contig_org)
-    if genes.ndim != 1 or contig_ptr.shape != (c + 1,) or contig_circular.shape != (c,):
-        raise ValueError("orders: genes [G], contig_ptr [C + 1], contig_org [C], contig_circular [C]")
-    if f is None:
-        f = len(repeated) if repeated is not None else (int(genes.max()) + 1 if len(genes) else 1)
-    if repeated is not None:
-        repeated = np.ascontiguousarray(repeated, np.uint8)
-        if repeated.shape != (f,):
-            raise ValueError("orders: repeated [F]")
-    if d <= 0 or f <= 0:
-        raise ValueError("orders: D and F must be positive")
-    if c == 0 or contig_ptr[0] != 0 or contig_ptr[-1] != len(genes) or (np.diff(contig_ptr) < 0).any():
-        raise ValueError("orders: contig_ptr must run from 0 to the number of genes, monotone")
-    if len(genes) and (genes.min() < 0 or genes.max() >= f):
-        raise ValueError("orders: family id out of range")
-    if contig_org.min() < 0 or contig_org.max() >= d:
-        raise ValueError("orders: contig organism out of range")
-    return genes, contig_ptr, contig_org, contig_circular, repeated, int(d), int(f)
+    """the rules nemgpu_master_create_orders and nemgpu_master_append_orders refuse by"""
+    return check_orders(genes, contig_ptr, contig_org, repeated, d, f, circular=contig_circular)
 
 
 def master_arrays_from_orders(genes, contig_ptr, contig_org, contig_circular, d, repeated=None, f=None, directed=False):
@@ -499,19 +480,25 @@ class Master:
         master_arrays_from_orders, which states what it computes).  .order int32 [n]: master family i is the caller's
         family id order[i]."""
         genes, contig_ptr, contig_org, contig_circular, repeated, d, f = _check_orders(genes, contig_ptr, contig_org, contig_circular, repeated, d, f)
+        return cls._of_orders(_bind_master(load_library()), "nemgpu_master_create_orders", (int(device), d, f, 1 if directed else 0),
+                              genes, contig_ptr, contig_org, contig_circular, repeated, bool(directed), f)
+
+    @classmethod
+    def _of_orders(cls, lib, what, head, genes, contig_ptr, contig_org, contig_circular, repeated, directed, f):
+        """the master that the entry point `what` makes of checked gene orders (head: its arguments between the handle
+        and the orders), with its numbering read back"""
         m = cls.__new__(cls)
-        m.lib = _bind_master(load_library())
+        m.lib = lib
         m._h = C.c_void_p()
-        rc = m.lib.nemgpu_master_create_orders(C.byref(m._h), int(device), d, f, 1 if directed else 0, genes.ctypes.data, len(genes),
-                                               contig_ptr.ctypes.data, contig_org.ctypes.data, contig_circular.ctypes.data, len(contig_org),
-                                               repeated.ctypes.data if repeated is not None else None)
+        rc = getattr(lib, what)(C.byref(m._h), *head, genes.ctypes.data, len(genes), contig_ptr.ctypes.data, contig_org.ctypes.data,
+                                contig_circular.ctypes.data, len(contig_org), repeated.ctypes.data if repeated is not None else None)
         if rc != 0:
-            raise NemGpuError("nemgpu_master_create_orders failed (status %d): %s" % (rc, m.lib.nemgpu_last_error().decode()))
+            raise NemGpuError("%s failed (status %d): %s" % (what, rc, lib.nemgpu_last_error().decode()))
         m.n, m.d, _, _ = m.shape()
         m.wf = (m.d + 31) // 32
         m.order = np.zeros(m.n, np.int32)
         m._fetch(order=m.order)
-        m.directed, m.f = bool(directed), f
+        m.directed, m.f = directed, f
         return m
 
     @classmethod
@@ -534,20 +521,8 @@ class Master:
             f = max(self.f, int(np.max(genes)) + 1 if len(genes) else 1)
         genes, contig_ptr, contig_org, contig_circular, repeated, d, f = _check_orders(genes, contig_ptr, contig_org, contig_circular, repeated,
                                                                                        self.d + int(d_new), f)
-        m = Master.__new__(Master)
-        m.lib = self.lib
-        m._h = C.c_void_p()
-        rc = m.lib.nemgpu_master_append_orders(C.byref(m._h), self._h, int(d_new), f, genes.ctypes.data, len(genes), contig_ptr.ctypes.data,
-                                               contig_org.ctypes.data, contig_circular.ctypes.data, len(contig_org),
-                                               repeated.ctypes.data if repeated is not None else None)
-        if rc != 0:
-            raise NemGpuError("nemgpu_master_append_orders failed (status %d): %s" % (rc, m.lib.nemgpu_last_error().decode()))
-        m.n, m.d, _, _ = m.shape()
-        m.wf = (m.d + 31) // 32
-        m.order = np.zeros(m.n, np.int32)
-        m._fetch(order=m.order)
-        m.directed, m.f = False, f
-        return m
+        return Master._of_orders(self.lib, "nemgpu_master_append_orders", (self._h, int(d_new), f), genes, contig_ptr, contig_org,
+                                 contig_circular, repeated, False, f)
 
     def add_annotations(self, new_annotations, new_organisms, circular_contigs=(), repeated=(), family=FAMILY):
         """PPanGGOLiN.add_organism (ppanggolin.py:342-358) on a master that carries names (from_annotations, from_graph or

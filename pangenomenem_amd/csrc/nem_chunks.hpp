@@ -19,7 +19,7 @@
 
 namespace nemk {
 
-// the master on the device (pointers only; nem_engine.hip owns the memory)
+// the master on the device (pointers only; nem_master.hip owns the memory)
 struct MasterDev {
     int n, d, wf, nw64, nnz;
     const uint64_t* xt;           // [d][nw64]: bit i of row o = family i present in organism o

@@ -6,12 +6,24 @@
 
 #include "../../include/nem_mi355x.h"
 
+// for the units that include <hip/hip_runtime.h>, in a function that returns a status
+#define HIPCHK(call)                                                                            \
+    do {                                                                                        \
+        hipError_t err__ = (call);                                                              \
+        if (err__ != hipSuccess) {                                                              \
+            nemk::set_error(std::string(#call) + " failed: " + hipGetErrorString(err__));       \
+            return NEMGPU_E_DEVICE;                                                             \
+        }                                                                                       \
+    } while (0)
+
 namespace nemk {
 
 constexpr double kEpsilon = 1e-20;   // EPSILON, reference nem_typ.h:63
 constexpr int kMaxK = 32;            // classes supported by the kernels
 
 void set_error(const std::string& msg);
+// before a unit's first HIP call (nem_engine.hip: a child forked after it must not touch the runtime)
+void note_hip_used();
 
 // counter-based tie-break hash; identical to mix32() in nem_kernels.hip and orc_mix32() in the oracle
 inline uint32_t mix32_host(uint32_t seed, uint32_t sweep, uint32_t site)

@@ -2,10 +2,7 @@
 #include "nem_orders.hpp"
 #include "nem_scan.hpp"
 
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include <algorithm>
-#include <vector>
 
 namespace nemk {
 
@@ -76,9 +73,7 @@ __global__ __launch_bounds__(kThreads) void k_orders_records(const int* __restri
     uint32_t v0 = 0, v1 = 0;
     int org = -1;
     if (last[p] == p) {
-        int lo = 0, hi = c;                                   // the contig: the last j with cptr[j] <= p (cptr[j + 1] > p)
-        while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (cptr[mid] <= p) lo = mid; else hi = mid; }
-        const int j = lo, start = cptr[j], end = cptr[j + 1];
+        const int j = last_le(cptr, c, p), start = cptr[j], end = cptr[j + 1];   // the contig: cptr[j] <= p < cptr[j + 1]
         org = corg[j];
         const int prev = p > 0 ? last[p - 1] : -1;
         int other = -1;
@@ -288,9 +283,8 @@ __global__ __launch_bounds__(kThreads) void k_append_old_entries(int nnz_old, in
 {
     const int t = blockIdx.x * kThreads + threadIdx.x;
     if (t >= nnz_old) return;
-    int lo = 0, hi = n_old;                                   // the row: the last r with old_ptr[r] <= t
-    while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (old_ptr[mid] <= t) lo = mid; else hi = mid; }
-    const int f = ptr[lo] + (t - old_ptr[lo]);
+    const int r = last_le(old_ptr, n_old, t);                 // the entry's row
+    const int f = ptr[r] + (t - old_ptr[r]);
     const int x = old_xptr ? old_xptr[t + 1] - old_xptr[t] : 0;
     idx[f] = old_idx[t];
     src[f] = t;
@@ -358,9 +352,8 @@ __global__ __launch_bounds__(kThreads) void k_append_old_extras(int nx_old, int 
 {
     const int j = blockIdx.x * kThreads + threadIdx.x;
     if (j >= nx_old) return;
-    int lo = 0, hi = nnz_old;                                 // the entry: the last t with old_xptr[t] <= j
-    while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (old_xptr[mid] <= j) lo = mid; else hi = mid; }
-    const int dst = xptr[fwd[lo]] + (j - old_xptr[lo]);
+    const int t = last_le(old_xptr, nnz_old, j);              // the extra's entry
+    const int dst = xptr[fwd[t]] + (j - old_xptr[t]);
     xorg[dst] = old_xorg[j];
     xadd[dst] = old_xadd[j];
 }
@@ -376,13 +369,9 @@ __global__ __launch_bounds__(kThreads) void k_append_xt(long long words, int nw6
     xt[i] = (o < d_old && w < nw64_old) ? old_xt[(size_t)o * nw64_old + w] : 0ull;
 }
 
-int bits_for(int count) { int b = 1; while (b < 31 && (1ll << b) < count) b++; return b; }
-int blocks(long long n) { return (int)((n + kThreads - 1) / kThreads); }
-
 }  // namespace
 
-struct OrdersBuild {
-    std::vector<void*> mem;
+struct OrdersBuild : Scratch {
     int d = 0, f = 0, g = 0, n = 0, nnz = 0, tn = 0, nx = 0, n2 = 0;
     int n_old = 0;                                            // an append: the old master's families (else 0)
     int *oldpos = nullptr, *rank = nullptr, *ptr_u = nullptr; // an append (orders_append_plan)
@@ -396,42 +385,13 @@ struct OrdersBuild {
     int* inv = nullptr;
     int* partial = nullptr;
     int* over = nullptr;
-    template <class T> hipError_t alloc(T** p, size_t count)
-    {
-        void* v = nullptr;
-        const hipError_t e = hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) mem.push_back(v);
-        *p = (T*)v;
-        return e;
-    }
 };
 
-void orders_free(OrdersBuild* b)
-{
-    if (!b) return;
-    for (void* p : b->mem) (void)hipFree(p);
-    delete b;
-}
+void orders_free(OrdersBuild* b) { delete b; }
 
 bool orders_key_fits(int n, int d) { return 2 * bits_for(n) + bits_for(d) <= 63; }
 
-#define ORD(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { orders_free(b); return e_; } } while (0)
-
-template <class K> static hipError_t sort_pairs(OrdersBuild* b, K* k0, K* k1, uint32_t* v0, uint32_t* v1, int count, int end_bit, const K** k_out,
-                                                const uint32_t** v_out, hipStream_t s)
-{
-    rocprim::double_buffer<K> keys(k0, k1);
-    rocprim::double_buffer<uint32_t> vals(v0, v1);
-    size_t bytes = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, bytes, keys, vals, (unsigned)count, 0u, (unsigned)end_bit, s);
-    if (e != hipSuccess) return e;
-    char* tmp = nullptr;
-    if ((e = b->alloc(&tmp, bytes)) != hipSuccess) return e;
-    if ((e = rocprim::radix_sort_pairs(tmp, bytes, keys, vals, (unsigned)count, 0u, (unsigned)end_bit, s)) != hipSuccess) return e;
-    *k_out = keys.current();
-    *v_out = vals.current();
-    return hipSuccess;
-}
+#define ORD(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { delete b; return e_; } } while (0)
 
 hipError_t orders_stage(const OrdersIn& in, hipStream_t s, OrdersBuild** out, int* n, int* nnz, int* nx)
 {
@@ -474,7 +434,7 @@ hipError_t orders_stage(const OrdersIn& in, hipStream_t s, OrdersBuild** out, in
     hipLaunchKernelGGL(k_orders_iota, dim3(blocks(f)), dim3(kThreads), 0, s, fi0, f);
     ORD(hipGetLastError());
     const uint32_t *fp_sorted, *fi_sorted;
-    ORD(sort_pairs<uint32_t>(b, fp0, fp1, fi0, fi1, f, 32, &fp_sorted, &fi_sorted, s));
+    ORD(sort_pairs<uint32_t>(*b, fp0, fp1, fi0, fi1, f, 32, &fp_sorted, &fi_sorted, s));
     b->fam_sorted = const_cast<uint32_t*>(fi_sorted);
     hipLaunchKernelGGL(k_orders_number, dim3(blocks(f)), dim3(kThreads), 0, s, fp_sorted, fi_sorted, f, seed, in.n_old, b->newid, n_dev);
     ORD(hipGetLastError());
@@ -482,7 +442,7 @@ hipError_t orders_stage(const OrdersIn& in, hipStream_t s, OrdersBuild** out, in
     ORD(hipStreamSynchronize(s));
     *n += in.n_old;
     b->n = *n;
-    if (*n <= 0 || !orders_key_fits(*n, in.d)) { orders_free(b); return hipErrorInvalidValue; }
+    if (*n <= 0 || !orders_key_fits(*n, in.d)) { delete b; return hipErrorInvalidValue; }
     b->kb = KeyBits{bits_for(*n), bits_for(in.d)};
     // 3. the records
     uint64_t *k0, *k1, *pos;
@@ -495,7 +455,7 @@ hipError_t orders_stage(const OrdersIn& in, hipStream_t s, OrdersBuild** out, in
     // 4. sorted; pairs and edges numbered by the scan of their first records
     const uint64_t* keys;
     const uint32_t* vals;
-    ORD(sort_pairs<uint64_t>(b, k0, k1, v0, v1, n2, 2 * b->kb.bn + b->kb.bd + 1, &keys, &vals, s));
+    ORD(sort_pairs<uint64_t>(*b, k0, k1, v0, v1, n2, 2 * b->kb.bn + b->kb.bd + 1, &keys, &vals, s));
     b->keys = keys;
     pos = keys == k0 ? k1 : k0;                               // (the sort's other buffer is free again)
     hipLaunchKernelGGL(k_orders_heads, dim3(blocks(n2)), dim3(kThreads), 0, s, keys, n2, b->kb, pos);
@@ -524,7 +484,7 @@ hipError_t orders_stage(const OrdersIn& in, hipStream_t s, OrdersBuild** out, in
         hipLaunchKernelGGL(k_orders_edge_keys, dim3(blocks(b->nnz)), dim3(kThreads), 0, s, keys, b->kb, b->trip_start, b->edge_tstart, edge_min,
                            b->nnz, e0, p0);
         ORD(hipGetLastError());
-        ORD(sort_pairs<uint64_t>(b, e0, e1, p0, p1, b->nnz, 32 + b->kb.bn, &b->ekeys, &b->perm, s));
+        ORD(sort_pairs<uint64_t>(*b, e0, e1, p0, p1, b->nnz, 32 + b->kb.bn, &b->ekeys, &b->perm, s));
     }
     ORD(hipMemcpyAsync(&b->nx, b->xs + b->tn, sizeof(int), hipMemcpyDeviceToHost, s));
     ORD(hipStreamSynchronize(s));

@@ -2,11 +2,6 @@
 #include "nem_project.hpp"
 #include "nem_scan.hpp"
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include <algorithm>
-#include <vector>
-
 namespace nemk {
 
 namespace {
@@ -46,9 +41,7 @@ __global__ __launch_bounds__(kThreads) void k_project_neighbours(const int* __re
     int row = -1;
     uint32_t v = 0;
     if (valid) {
-        int lo = 0, hi = n;                                   // the row: the last r with ptr[r] <= t (ptr[r + 1] > t)
-        while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (ptr[mid] <= t) lo = mid; else hi = mid; }
-        row = lo;
+        row = last_le(ptr, n, (int)t);                        // ptr[row] <= t < ptr[row + 1]
         const int k = cls[idx[t]] & 3;
         if (k < 3) v = 1u << (kNeiShift * k);
     }
@@ -94,9 +87,7 @@ __global__ __launch_bounds__(kThreads) void k_project_genes(const int* __restric
     int org = -1;
     unsigned long long v = 0;
     if (valid) {
-        int lo = 0, hi = c;                                   // the contig: the last j with cptr[j] <= p (cptr[j + 1] > p)
-        while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (cptr[mid] <= p) lo = mid; else hi = mid; }
-        org = corg[lo];
+        org = corg[last_le(cptr, c, p)];                      // its contig's: cptr[j] <= p < cptr[j + 1]
         const int id = genes[p];
         const int fam = (repeated && repeated[id]) ? kRepeated : inv[id];
         if (gene_family) gene_family[p] = fam;
@@ -165,22 +156,6 @@ __global__ __launch_bounds__(kThreads) void k_project_copies(const uint64_t* __r
     copies[vals[i]] = starts[r + 1] - starts[r];
 }
 
-int bits_for(int count) { int b = 1; while (b < 31 && (1ll << b) < count) b++; return b; }
-int blocks(long long n) { return (int)((n + kThreads - 1) / kThreads); }
-
-struct Scratch {
-    std::vector<void*> mem;
-    ~Scratch() { for (void* p : mem) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t count)
-    {
-        void* v = nullptr;
-        const hipError_t e = hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) mem.push_back(v);
-        *p = (T*)v;
-        return e;
-    }
-};
-
 }  // namespace
 
 #define PRJ(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
@@ -235,15 +210,9 @@ hipError_t project(const MasterDev& m, const ProjectIn& in, int32_t* org_counts,
             int *rid, *starts, *partial, *copies;
             PRJ(mem.alloc(&rid, g)); PRJ(mem.alloc(&starts, (size_t)g + 1)); PRJ(mem.alloc(&partial, (size_t)g / kScanTile + 2));
             PRJ(mem.alloc(&copies, g));
-            rocprim::double_buffer<uint64_t> keys(k0, k1);
-            rocprim::double_buffer<uint32_t> vals(v0, v1);
-            size_t bytes = 0;
-            char* tmp = nullptr;
-            PRJ(rocprim::radix_sort_pairs(nullptr, bytes, keys, vals, (unsigned)g, 0u, (unsigned)(bn + bd + 1), s));
-            PRJ(mem.alloc(&tmp, bytes));
-            PRJ(rocprim::radix_sort_pairs(tmp, bytes, keys, vals, (unsigned)g, 0u, (unsigned)(bn + bd + 1), s));
-            const uint64_t* ks = keys.current();
-            const uint32_t* vs = vals.current();
+            const uint64_t* ks;
+            const uint32_t* vs;
+            PRJ(sort_pairs<uint64_t>(mem, k0, k1, v0, v1, g, bn + bd + 1, &ks, &vs, s));
             PRJ(hipMemsetAsync(copies, 0, (size_t)g * 4, s));
             hipLaunchKernelGGL(k_project_heads, dim3(blocks(g)), dim3(kThreads), 0, s, ks, g, none, rid);
             scan<int, OpSum<int>, true>(rid, rid, g, OpSum<int>(), 0, partial, (int*)nullptr, s);

@@ -1,9 +1,14 @@
 // nem_scan.hpp -- the block scans and the wave segment reduction that the units working on sorted records share
 // (nem_orders.hip: the master's build and append; nem_project.hip: a partition's projection).  256-thread blocks of 4
-// waves; a scan is three launches (tile totals, their prefixes, the tiles), in place allowed.
+// waves; a scan is three launches (tile totals, their prefixes, the tiles), in place allowed.  With them what both do
+// around rocPRIM's radix sort: the key widths, a call's scratch buffers, the sort itself, the search of a CSR's rows.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <algorithm>
 #include <cstdint>
+#include <vector>
 
 namespace nemk {
 namespace seg {
@@ -17,6 +22,50 @@ struct OpOr { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { ret
 template <class T> struct OpSum { __device__ T operator()(T a, T b) const { return a + b; } };
 
 __device__ inline int lane_id() { return threadIdx.x & 63; }
+
+// the last j in [0, count) with a[j] <= x (a non-decreasing, a[0] <= x): the row of entry x in a CSR's pointers
+__device__ inline int last_le(const int* a, int count, int x)
+{
+    int lo = 0, hi = count;
+    while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (a[mid] <= x) lo = mid; else hi = mid; }
+    return lo;
+}
+
+// the bits of a key field that holds 0 .. count - 1 (at least 1)
+static inline int bits_for(int count) { int b = 1; while (b < 31 && (1ll << b) < count) b++; return b; }
+static inline int blocks(long long n) { return (int)((n + kThreads - 1) / kThreads); }
+
+// device buffers that live as long as their owner (hidden: each unit's own, as everything here is)
+struct __attribute__((visibility("hidden"))) Scratch {
+    std::vector<void*> mem;
+    ~Scratch() { for (void* p : mem) (void)hipFree(p); }
+    template <class T> hipError_t alloc(T** p, size_t count)
+    {
+        void* v = nullptr;
+        const hipError_t e = hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) mem.push_back(v);
+        *p = (T*)v;
+        return e;
+    }
+};
+
+// (k0, v0) sorted by the keys' bits [0, end_bit) with (k1, v1) as the other halves of rocPRIM's double buffers; *k_out,
+// *v_out: the halves that hold the result; the sort's temporary storage is mem's
+template <class K> static hipError_t sort_pairs(Scratch& mem, K* k0, K* k1, uint32_t* v0, uint32_t* v1, int count, int end_bit, const K** k_out,
+                                                const uint32_t** v_out, hipStream_t s)
+{
+    rocprim::double_buffer<K> keys(k0, k1);
+    rocprim::double_buffer<uint32_t> vals(v0, v1);
+    size_t bytes = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, bytes, keys, vals, (unsigned)count, 0u, (unsigned)end_bit, s);
+    if (e != hipSuccess) return e;
+    char* tmp = nullptr;
+    if ((e = mem.alloc(&tmp, bytes)) != hipSuccess) return e;
+    if ((e = rocprim::radix_sort_pairs(tmp, bytes, keys, vals, (unsigned)count, 0u, (unsigned)end_bit, s)) != hipSuccess) return e;
+    *k_out = keys.current();
+    *v_out = vals.current();
+    return hipSuccess;
+}
 
 // ---- scans ----------------------------------------------------------------------------------------------------
 // exclusive prefix of v over the block's 256 threads (4 waves); *total (may be null): the block's total

@@ -29,28 +29,42 @@ def _popcount_rows(rows):
     return ones[np.ascontiguousarray(rows, np.uint32).view(np.uint8)].reshape(len(rows), -1).sum(axis=1)
 
 
-def check_projection_orders(genes, contig_ptr, contig_org, repeated, d, f):
-    """the rules nemgpu_master_project refuses by (the build's, without contig_circular; no gene at all is allowed)"""
+def check_orders(genes, contig_ptr, contig_org, repeated, d, f, circular=None, allow_empty=False):
+    """The gene orders as contiguous arrays, or ValueError.  circular: contig_circular [C], which the build and the append
+    need (chunks._check_orders; they also infer an f of None); allow_empty: the projection's rules
+    (check_projection_orders): no gene at all is allowed, genes + contigs stay below 2^30."""
     genes = np.ascontiguousarray(genes, np.int32)
     contig_ptr = np.ascontiguousarray(contig_ptr, np.int32)
     contig_org = np.ascontiguousarray(contig_org, np.int32)
     c = len(contig_org)
-    if genes.ndim != 1 or contig_ptr.shape != (c + 1,):
-        raise ValueError("orders: genes [G], contig_ptr [C + 1], contig_org [C]")
+    layout = "orders: genes [G], contig_ptr [C + 1], contig_org [C]"
+    if circular is not None:
+        circular = np.ascontiguousarray(circular, np.uint8)
+        layout += ", contig_circular [C]"
+    if genes.ndim != 1 or contig_ptr.shape != (c + 1,) or (circular is not None and circular.shape != (c,)):
+        raise ValueError(layout)
+    if f is None and circular is not None:
+        f = len(repeated) if repeated is not None else (int(genes.max()) + 1 if len(genes) else 1)
     if repeated is not None:
         repeated = np.ascontiguousarray(repeated, np.uint8)
         if repeated.shape != (f,):
             raise ValueError("orders: repeated [F]")
-    if f <= 0:
-        raise ValueError("orders: F must be positive")
-    if len(genes) + c >= 1 << 30:
+    if f <= 0 or (d <= 0 and not allow_empty):
+        raise ValueError("orders: F must be positive" if allow_empty else "orders: D and F must be positive")
+    if allow_empty and len(genes) + c >= 1 << 30:
         raise ValueError("orders: genes + contigs must stay below 2^30")
-    if contig_ptr[0] != 0 or contig_ptr[-1] != len(genes) or (np.diff(contig_ptr) < 0).any():
+    if (c == 0 and not allow_empty) or contig_ptr[0] != 0 or contig_ptr[-1] != len(genes) or (np.diff(contig_ptr) < 0).any():
         raise ValueError("orders: contig_ptr must run from 0 to the number of genes, monotone")
     if len(genes) and (genes.min() < 0 or genes.max() >= f):
         raise ValueError("orders: family id out of range")
     if c and (contig_org.min() < 0 or contig_org.max() >= d):
         raise ValueError("orders: contig organism out of range")
+    return genes, contig_ptr, contig_org, circular, repeated, int(d), int(f)
+
+
+def check_projection_orders(genes, contig_ptr, contig_org, repeated, d, f):
+    """the rules nemgpu_master_project refuses by (the build's, without contig_circular; no gene at all is allowed)"""
+    genes, contig_ptr, contig_org, _, repeated, _, _ = check_orders(genes, contig_ptr, contig_org, repeated, d, f, allow_empty=True)
     return genes, contig_ptr, contig_org, repeated
 
 

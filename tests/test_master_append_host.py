@@ -175,7 +175,7 @@ def test_library_checks_the_update_before_any_device_call():
     def append(genes, ptr, org, circ, d_new, f):
         arrs = [np.ascontiguousarray(genes, np.int32), np.ascontiguousarray(ptr, np.int32), np.ascontiguousarray(org, np.int32),
                 np.ascontiguousarray(circ, np.uint8)]
-        h = C.c_void_p()
+        h = C.c_void_p(1)
         rc = lib.nemgpu_master_append_orders(C.byref(h), None, d_new, f, arrs[0].ctypes.data, len(arrs[0]), arrs[1].ctypes.data,
                                              arrs[2].ctypes.data, arrs[3].ctypes.data, len(arrs[2]), None)
         assert not h.value
@@ -187,5 +187,7 @@ def test_library_checks_the_update_before_any_device_call():
                        (([0, 1, 2], [0, 3], [0], [0], -2, 3), "d_new"), (([0, 1, 2], [0, 3], [0], [0], 131072 * 32 + 1, 3), "131 072")):
         rc, msg = append(*args)
         assert rc == 3 and word in msg, (args, rc, msg)
+    rc, msg = append([0, 1, 2], [0, 3], [0], [0], 1, 0)         # (what the orders lack is refused as the build refuses it)
+    assert rc == 8 and "needed" in msg, (rc, msg)
     rc, msg = append([0, 1, 2], [0, 3], [0], [0], 1, 3)
     assert rc == 8 and "master" in msg, (rc, msg)

@@ -150,16 +150,30 @@ def test_library_checks_orders_before_any_device_call():
     build.build()
     lib = _bind_master(load_library())
 
-    def create(genes, ptr, org, circ, d, f):
+    def create(genes, ptr, org, circ, d, f, g=None, null=()):
         arrs = [np.ascontiguousarray(genes, np.int32), np.ascontiguousarray(ptr, np.int32), np.ascontiguousarray(org, np.int32),
                 np.ascontiguousarray(circ, np.uint8)]
-        h = C.c_void_p()
-        rc = lib.nemgpu_master_create_orders(C.byref(h), 0, d, f, 0, arrs[0].ctypes.data, len(arrs[0]), arrs[1].ctypes.data, arrs[2].ctypes.data,
-                                             arrs[3].ctypes.data, len(arrs[2]), None)
+        at = [None if i in null else a.ctypes.data for i, a in enumerate(arrs)]
+        h = C.c_void_p(1)
+        rc = lib.nemgpu_master_create_orders(C.byref(h), 0, d, f, 0, at[0], len(arrs[0]) if g is None else g, at[1], at[2], at[3], len(arrs[2]), None)
+        assert not h.value                                    # (refused: the handle is null, whatever it held)
         return rc, lib.nemgpu_last_error().decode()
 
-    for args, word in ((([0, 1, 3], [0, 3], [0], [0], 1, 3), "family id"), (([0, 1, 2], [0, 2, 1, 3], [0, 0, 0], [0, 0, 0], 1, 3), "monotone"),
-                       (([0, 1, 2], [0, 2], [0], [0], 1, 3), "contig_ptr"), (([0, 1, 2], [0, 3], [1], [0], 1, 3), "organism"),
+    for args, word in ((([0, 1, 3], [0, 3], [0], [0], 1, 3), "family id"), (([0, 1, -1], [0, 3], [0], [0], 1, 3), "family id"),
+                       (([0, 1, 2], [0, 2, 1, 3], [0, 0, 0], [0, 0, 0], 1, 3), "monotone"),
+                       (([0, 1, 2], [0, 2], [0], [0], 1, 3), "contig_ptr"), (([0, 1, 2], [1, 3], [0], [0], 1, 3), "contig_ptr"),
+                       (([0, 1, 2], [0, 3], [1], [0], 1, 3), "organism"), (([0, 1, 2], [0, 3], [-1], [0], 1, 3), "organism"),
                        (([0, 1, 2], [0, 3], [0], [0], 131072 * 32 + 1, 3), "131 072")):
         rc, msg = create(*args)
         assert rc == 3 and word in msg, (args, rc, msg)
+    rc, msg = create([0, 1, 2], [0, 3], [0], [0], 1, 3, g=1 << 30)     # (refused by the sizes alone: no array is read)
+    assert rc == 3 and "2^30" in msg, (rc, msg)
+    # what is missing: NEMGPU_E_FUNCARG
+    for kw in (dict(d=0), dict(f=0), dict(g=0), dict(null=(0,)), dict(null=(1,)), dict(null=(2,)), dict(null=(3,))):
+        args = dict(genes=[0, 1, 2], ptr=[0, 3], org=[0], circ=[0], d=1, f=3)
+        args.update(kw)
+        rc, msg = create(**args)
+        assert rc == 8 and "needed" in msg, (kw, rc, msg)
+    rc, msg = create([0, 1, 2], [0], [], [], 1, 3)             # (no contig)
+    assert rc == 8 and "needed" in msg, (rc, msg)
+    assert lib.nemgpu_master_create_orders(None, 0, 1, 3, 0, None, 0, None, None, None, 0, None) == 8

@@ -153,3 +153,37 @@ def test_library_refuses_a_null_master_without_a_device():
     lib = _bind_master(load_library())
     part, ptr = np.zeros(1, np.uint8), np.zeros(1, np.int32)
     assert lib.nemgpu_master_project(None, part.ctypes.data, 1, None, 0, ptr.ctypes.data, None, 0, None, None, None, None, None) == 8
+
+
+def test_the_two_rule_sets_differ_where_they_did():
+    """the projection's orders check and the build's are one function now: what only one of them refuses stays so"""
+    from pangenomenem_amd.chunks import _check_orders
+    from pangenomenem_amd.projection import check_projection_orders
+    # no gene at all: the projection takes it, with and without a contig; the build wants a contig
+    genes, ptr, org, rep = check_projection_orders([], [0], [], None, 2, 3)
+    assert (genes.dtype, ptr.dtype, org.dtype, rep) == (np.int32, np.int32, np.int32, None) and len(genes) == 0 and list(ptr) == [0]
+    assert list(check_projection_orders([], [0, 0], [1], None, 2, 3)[1]) == [0, 0]
+    with pytest.raises(ValueError, match="contig_ptr"):
+        _check_orders([], [0], [], [], None, 2, 3)
+    assert _check_orders([], [0, 0], [1], [0], None, 2, 3)[6] == 3        # (an empty contig is the build's too)
+    # the build infers f, the projection is told it; the build returns contig_circular, d and f as well
+    out = _check_orders([0, 4, 2], [0, 2, 3], [0, 1], [1, 0], None, 2, None)
+    assert len(out) == 7 and out[3].dtype == np.uint8 and out[5:] == (2, 5)
+    assert _check_orders([0, 1], [0, 2], [0], [0], [0, 0, 1, 0], 1, None)[6] == 4
+    with pytest.raises(ValueError, match="contig_circular"):
+        _check_orders([0, 1], [0, 2], [0], [0, 1], None, 1, 2)
+    with pytest.raises(ValueError, match=r"contig_org \[C\]$"):
+        check_projection_orders([0, 1], [0, 2, 2], [0], None, 1, 2)
+    # each one's words for a size that is not positive
+    with pytest.raises(ValueError, match="D and F"):
+        _check_orders([0], [0, 1], [0], [0], None, 0, 1)
+    with pytest.raises(ValueError, match="F must be positive"):
+        check_projection_orders([], [0], [], None, 2, 0)
+    # both refuse these alike
+    for bad in (dict(genes=[0, 3]), dict(genes=[-1, 0]), dict(ptr=[0, 3]), dict(ptr=[1, 2]), dict(org=[2]), dict(org=[-1]), dict(rep=[0, 0])):
+        a = dict(genes=[0, 1], ptr=[0, 2], org=[0], rep=None)
+        a.update(bad)
+        with pytest.raises(ValueError):
+            check_projection_orders(a["genes"], a["ptr"], a["org"], a["rep"], 2, 3)
+        with pytest.raises(ValueError):
+            _check_orders(a["genes"], a["ptr"], a["org"], [0], a["rep"], 2, 3)

@@ -301,6 +301,41 @@ int nemgpu_master_append_orders(nemgpu_master** out, const nemgpu_master* m, int
 int nemgpu_master_project(const nemgpu_master* m, const uint8_t* part, int f, const int32_t* genes, int g,
                           const int32_t* contig_ptr, const int32_t* contig_org, int c, const uint8_t* repeated,
                           int32_t* org_counts, int32_t* nei_counts, int32_t* gene_family, int32_t* gene_copies);
+/* The per-family TABLE of the pangenome matrix (PPanGGOLiN.write_matrix, ppanggolin.py:1400-1452: the Roary-style .csv
+   and .Rtab), computed on the device from the master and the flat orders of ALL its organisms, and the .Rtab's cell
+   block formatted there.  HOST arrays; m is only read and stays valid and unchanged; the work runs on m's stream.
+     f, genes[g], contig_ptr[c + 1], contig_org[c], repeated[f] or NULL
+                          the gene orders as nemgpu_master_project takes them (g > 0);
+     gene_len[g]          END - START of every gene, what __add_gene receives (:497, :511); any int32.
+   A gene of a repeated family is skipped, as in the build.  Per master family i (caller id order[i]):
+     nb_genes[n]          its kept genes (node["nb_genes"], :418);      nb_org[n]  the organisms with at least one;
+     len_min, len_max, len_distinct[n], len_sum[n] (int64)
+                          over the DISTINCT lengths of its kept genes (node["length"] is a set, :426-430; min, max and
+                          mean are taken over it, :1431, :1443-1445);
+     multi_ptr[n + 1], multi_org[n_multi], multi_cnt[n_multi]
+                          the (family, organism) cells whose copy count len(node[org]) (:1429) is 2 or more, in CSR
+                          over the families, the organisms increasing per family; every other cell's count is its
+                          presence bit in the master.
+   The cells derived from the orders must equal the master's presence bits, every cell, both directions (checked on the
+   device); if not -- the orders are not this master's; also a kept gene whose family the master lacks -- the call returns
+   NEMGPU_E_ARG with nemgpu_last_error's text and makes no table.  Malformed orders are refused on the host before any
+   launch by nemgpu_master_project's rules.  A master built with directed = 1 is fine: the adjacency is not read.
+   The table stays on the device until nemgpu_family_table_destroy; it does not keep m alive.
+   _rtab_size: the bytes of the text of families row0 .. row0 + rows - 1.
+   _rtab: that text into text[capacity] (HOST): per family the d copy counts in decimal joined by '\t', then '\n' -- what
+   the reference writes after column 14 of a line of the .Rtab -- and every line's end offset in line_end[rows];
+   *needed (may be NULL) = the bytes the batch takes.  capacity below that: NEMGPU_E_ARG, *needed still set, nothing
+   written.  m: the table's master. */
+typedef struct nemgpu_family_table nemgpu_family_table;
+int nemgpu_family_table_create(nemgpu_family_table** out, const nemgpu_master* m, int f, const int32_t* genes, const int32_t* gene_len,
+                               int g, const int32_t* contig_ptr, const int32_t* contig_org, int c, const uint8_t* repeated);
+int nemgpu_family_table_shape(const nemgpu_family_table* t, int* n, int* d, int* n_multi);
+int nemgpu_family_table_fetch(const nemgpu_family_table* t, int32_t* nb_genes, int32_t* nb_org, int32_t* len_min, int32_t* len_max,
+                              int32_t* len_distinct, int64_t* len_sum, int32_t* multi_ptr, int32_t* multi_org, int32_t* multi_cnt);
+int nemgpu_family_table_rtab_size(const nemgpu_family_table* t, int row0, int rows, int64_t* bytes);
+int nemgpu_family_table_rtab(nemgpu_family_table* t, const nemgpu_master* m, int row0, int rows, char* text, int64_t capacity,
+                             int64_t* needed, int64_t* line_end);
+void nemgpu_family_table_destroy(nemgpu_family_table* t);
 /* What a master holds, of whichever constructor: sizes (n families, d organisms, nnz CSR entries, n_extra pairs with
    count >= 2; any pointer may be NULL), and the arrays as nemgpu_master_create_counts takes them, read back from the
    device: xbits[n][ceil(d/32)], nei_ptr[n + 1], nei_idx[nnz], edge_bits[nnz][ceil(d/32)], extra_ptr[nnz + 1],

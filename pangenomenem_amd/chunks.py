@@ -510,6 +510,7 @@ class Master:
                             directed=directed, device=device)
         m.names, m.organism_names = [o["families"][i] for i in m.order], list(o["organisms"])
         m.id_names = list(o["families"])                      # (every caller id's name: add_annotations numbers on from them)
+        m.repeated_by_organism = {org: frozenset(repeated) for org in o["organisms"]}     # (family_table: a node keeps the genes it got)
         return m
 
     def add_orders(self, genes, contig_ptr, contig_org, contig_circular, d_new, repeated=None, f=None):
@@ -541,6 +542,8 @@ class Master:
         m = self.add_orders(o["genes"], o["contig_ptr"], o["contig_org"], o["contig_circular"], len(new_organisms), repeated=o["repeated"])
         m.id_names = list(o["families"])
         m.names, m.organism_names = [m.id_names[i] for i in m.order], list(o["organisms"])
+        if getattr(self, "repeated_by_organism", None) is not None:
+            m.repeated_by_organism = dict(self.repeated_by_organism, **{org: frozenset(repeated) for org in new_organisms})
         return m
 
     def project_orders(self, part, genes, contig_ptr, contig_org, repeated=None, f=None):
@@ -615,6 +618,31 @@ class Master:
         if len(bad):
             raise KeyError(o["families"][o["genes"][bad[0]]])
         return pj.Projection(fam, copies, nei, org, part, [col[name] for name in organisms], names, self.organism_names)
+
+    def family_table(self, annotations=None, repeated=(), *, orders=None, lengths=None, family=FAMILY):
+        """The per-family table of the pangenome matrix (PPanGGOLiN.write_matrix, ppanggolin.py:1400-1452), computed on the
+        device from this master and the gene orders of ALL its organisms (nemgpu_family_table_create;
+        matrix.family_table_arrays states what it computes).  annotations: PPanGGOLiN's, of every organism of the master
+        (they go through orders_from_annotations with this master's ids, so a master grown by add_annotations works;
+        every gene's END - START is read in the same walk); repeated: families_repeted, for a master that was not made by
+        from_annotations / add_annotations -- one that was remembers which families were repeated when each organism
+        came, as the reference's nodes keep the genes they got before a family was declared repeated.  orders=(genes, contig_ptr,
+        contig_org[, repeated[, f]]) with lengths= int32 [G] instead of annotations: flat arrays, for a master without
+        names.  Orders that are not this master's (their cells are not its presence bits) raise NemGpuError.  A directed
+        master is fine.  Returns a matrix.FamilyTable (the arrays, copies(), write_matrix(), close())."""
+        from . import matrix as mx
+        if orders is not None:
+            if annotations is not None or lengths is None:
+                raise ValueError("family_table: annotations, or orders= with lengths=")
+            return mx.FamilyTable(self, orders[0], lengths, orders[1], orders[2], orders[3] if len(orders) > 3 else None,
+                                  orders[4] if len(orders) > 4 else None)
+        if annotations is None or getattr(self, "id_names", None) is None:
+            raise ValueError("family_table: annotations and a master that carries names, or orders= with lengths=")
+        by_org = getattr(self, "repeated_by_organism", None)
+        if by_org is None:
+            by_org = {org: frozenset(repeated) for org in self.organism_names}
+        o = mx.table_orders(annotations, self.organism_names, self.id_names, by_org, family, lengths)
+        return mx.FamilyTable(self, o["genes"], o["lengths"], o["contig_ptr"], o["contig_org"], o["repeated"], repeated_names=by_org)
 
     def shape(self):
         """(n families, d organisms, nnz CSR entries, pairs with count >= 2) as the device holds them (nemgpu_master_shape)"""

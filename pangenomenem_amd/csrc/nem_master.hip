@@ -105,28 +105,6 @@ int check_extras(int d, int nnz, int wf, const uint32_t* edge_bits, const int32_
     return NEMGPU_OK;
 }
 
-// Gene orders checked on the host (no HIP call before them): the build's and the append's, or the projection's (d: the
-// master's organisms), which has no contig_circular, allows no gene at all and has refused in its own words what it needs
-int check_orders(bool projection, int d, int f, int g, int c, const int32_t* genes, const int32_t* contig_ptr, const int32_t* contig_org,
-                 const uint8_t* contig_circular)
-{
-    if (!projection) {
-        if (d <= 0 || f <= 0 || g <= 0 || c <= 0 || !genes || !contig_ptr || !contig_org || !contig_circular) {
-            set_error("nemgpu_master_create_orders: sizes, genes and contigs are needed"); return NEMGPU_E_FUNCARG;
-        }
-        if ((d + 31) / 32 > chunk_mask_words_max()) { set_error("nemgpu_master_create_orders: more than 131 072 organisms"); return NEMGPU_E_ARG; }
-    }
-    if ((long long)g + c >= (1ll << 30)) { set_error("orders: genes + contigs must stay below 2^30"); return NEMGPU_E_ARG; }
-    if (contig_ptr[0] != 0 || contig_ptr[c] != g) { set_error("orders: contig_ptr must run from 0 to the number of genes"); return NEMGPU_E_ARG; }
-    for (int j = 0; j < c; j++) {
-        if (contig_ptr[j + 1] < contig_ptr[j]) { set_error("orders: contig_ptr not monotone"); return NEMGPU_E_ARG; }
-        if (contig_org[j] < 0 || contig_org[j] >= d) { set_error("orders: contig " + std::to_string(j) + ": organism out of range"); return NEMGPU_E_ARG; }
-    }
-    for (int p = 0; p < g; p++)
-        if (genes[p] < 0 || genes[p] >= f) { set_error("orders: gene " + std::to_string(p) + ": family id out of range"); return NEMGPU_E_ARG; }
-    return NEMGPU_OK;
-}
-
 // The master of checked gene orders on the device: nemgpu_master_create_orders (old null), or nemgpu_master_append_orders'
 // old master grown by them (in.d: the grown master's organisms)
 int master_from_orders(nemgpu_master** out, const nemgpu_master* old, int device, const std::string& who, OrdersIn in)
@@ -165,6 +143,28 @@ int master_from_orders(nemgpu_master** out, const nemgpu_master* old, int device
 }
 
 }  // namespace
+
+// Gene orders checked on the host (no HIP call before them): the build's and the append's, or the projection's (d: the
+// master's organisms), which has no contig_circular, allows no gene at all and has refused in its own words what it needs
+int nemk::check_orders(bool projection, int d, int f, int g, int c, const int32_t* genes, const int32_t* contig_ptr, const int32_t* contig_org,
+                 const uint8_t* contig_circular)
+{
+    if (!projection) {
+        if (d <= 0 || f <= 0 || g <= 0 || c <= 0 || !genes || !contig_ptr || !contig_org || !contig_circular) {
+            set_error("nemgpu_master_create_orders: sizes, genes and contigs are needed"); return NEMGPU_E_FUNCARG;
+        }
+        if ((d + 31) / 32 > chunk_mask_words_max()) { set_error("nemgpu_master_create_orders: more than 131 072 organisms"); return NEMGPU_E_ARG; }
+    }
+    if ((long long)g + c >= (1ll << 30)) { set_error("orders: genes + contigs must stay below 2^30"); return NEMGPU_E_ARG; }
+    if (contig_ptr[0] != 0 || contig_ptr[c] != g) { set_error("orders: contig_ptr must run from 0 to the number of genes"); return NEMGPU_E_ARG; }
+    for (int j = 0; j < c; j++) {
+        if (contig_ptr[j + 1] < contig_ptr[j]) { set_error("orders: contig_ptr not monotone"); return NEMGPU_E_ARG; }
+        if (contig_org[j] < 0 || contig_org[j] >= d) { set_error("orders: contig " + std::to_string(j) + ": organism out of range"); return NEMGPU_E_ARG; }
+    }
+    for (int p = 0; p < g; p++)
+        if (genes[p] < 0 || genes[p] >= f) { set_error("orders: gene " + std::to_string(p) + ": family id out of range"); return NEMGPU_E_ARG; }
+    return NEMGPU_OK;
+}
 
 int nemgpu_master_create(nemgpu_master** out, int device, int n, int d, const uint32_t* xbits, const int32_t* nei_ptr,
                          const int32_t* nei_idx, const uint32_t* edge_bits)

@@ -27,4 +27,10 @@ namespace nemk {
 // the sections of a device block start on 256 bytes
 inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// Gene orders checked on the host (no HIP call before them; nem_master.hip): the build's and the append's, or the
+// projection's (d: the master's organisms), which has no contig_circular and allows no gene at all -- the family table's
+// too.  NEMGPU_OK, or the status with nemgpu_last_error's text set.
+int check_orders(bool projection, int d, int f, int g, int c, const int32_t* genes, const int32_t* contig_ptr, const int32_t* contig_org,
+                 const uint8_t* contig_circular);
+
 }  // namespace nemk

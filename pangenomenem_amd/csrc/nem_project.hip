@@ -158,6 +158,12 @@ __global__ __launch_bounds__(kThreads) void k_project_copies(const uint64_t* __r
 
 }  // namespace
 
+void launch_project_inverse(const int* order, int n, int f, int* inv, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_project_fill, dim3(blocks(f)), dim3(kThreads), 0, s, inv, f, kNoFamily);
+    hipLaunchKernelGGL(k_project_inverse, dim3(blocks(n)), dim3(kThreads), 0, s, order, n, f, inv);
+}
+
 #define PRJ(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 hipError_t project(const MasterDev& m, const ProjectIn& in, int32_t* org_counts, int32_t* nei_counts, int32_t* gene_family,
@@ -196,8 +202,7 @@ hipError_t project(const MasterDev& m, const ProjectIn& in, int32_t* org_counts,
         PRJ(hipMemcpyAsync(genes, in.genes, (size_t)g * 4, hipMemcpyHostToDevice, s));
         PRJ(hipMemcpyAsync(cptr, in.contig_ptr, ((size_t)c + 1) * 4, hipMemcpyHostToDevice, s));
         PRJ(hipMemcpyAsync(corg, in.contig_org, (size_t)c * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_project_fill, dim3(blocks(f)), dim3(kThreads), 0, s, inv, f, kNoFamily);
-        hipLaunchKernelGGL(k_project_inverse, dim3(blocks(n)), dim3(kThreads), 0, s, (const int*)order, n, f, inv);
+        launch_project_inverse(order, n, f, inv, s);
         const int bn = bits_for(n), bd = bits_for(d);
         const uint64_t none = (uint64_t)1 << (bn + bd);       // (bn + bd <= 53)
         uint64_t *k0 = nullptr, *k1 = nullptr;

@@ -42,4 +42,8 @@ constexpr int kProjectCounters = 7;   // persistent, shell, cloud, undefined, co
 hipError_t project(const MasterDev& m, const ProjectIn& in, int32_t* org_counts, int32_t* nei_counts, int32_t* gene_family,
                    int32_t* gene_copies, hipStream_t s);
 
+// step 3 alone, for the units that key genes by master family (DEVICE arrays): inv[f] = the master family of every
+// caller id, -2 where there is none; order[n] or null (the identity)
+void launch_project_inverse(const int* order, int n, int f, int* inv, hipStream_t s);
+
 }  // namespace nemk

@@ -1,5 +1,5 @@
 // nem_scan.hpp -- the block scans and the wave segment reduction that the units working on sorted records share
-// (nem_orders.hip: the master's build and append; nem_project.hip: a partition's projection).  256-thread blocks of 4
+// (nem_orders.hip: the master's build and append; nem_project.hip: a partition's projection; nem_matrix.hip: the family table).  256-thread blocks of 4
 // waves; a scan is three launches (tile totals, their prefixes, the tiles), in place allowed.  With them what both do
 // around rocPRIM's radix sort: the key widths, a call's scratch buffers, the sort itself, the search of a CSR's rows.
 #pragma once
@@ -64,6 +64,20 @@ template <class K> static hipError_t sort_pairs(Scratch& mem, K* k0, K* k1, uint
     if ((e = rocprim::radix_sort_pairs(tmp, bytes, keys, vals, (unsigned)count, 0u, (unsigned)end_bit, s)) != hipSuccess) return e;
     *k_out = keys.current();
     *v_out = vals.current();
+    return hipSuccess;
+}
+
+// keys alone, the same way: k0 sorted by its bits [0, end_bit), k1 the other half; *k_out: the half that holds the result
+template <class K> static hipError_t sort_keys(Scratch& mem, K* k0, K* k1, int count, int end_bit, const K** k_out, hipStream_t s)
+{
+    rocprim::double_buffer<K> keys(k0, k1);
+    size_t bytes = 0;
+    hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, keys, (unsigned)count, 0u, (unsigned)end_bit, s);
+    if (e != hipSuccess) return e;
+    char* tmp = nullptr;
+    if ((e = mem.alloc(&tmp, bytes)) != hipSuccess) return e;
+    if ((e = rocprim::radix_sort_keys(tmp, bytes, keys, (unsigned)count, 0u, (unsigned)end_bit, s)) != hipSuccess) return e;
+    *k_out = keys.current();
     return hipSuccess;
 }
 

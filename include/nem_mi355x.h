@@ -336,6 +336,45 @@ int nemgpu_family_table_rtab_size(const nemgpu_family_table* t, int row0, int ro
 int nemgpu_family_table_rtab(nemgpu_family_table* t, const nemgpu_master* m, int row0, int rows, char* text, int64_t capacity,
                              int64_t* needed, int64_t* line_end);
 void nemgpu_family_table_destroy(nemgpu_family_table* t);
+/* The per-edge TABLE of the pangenome graph's GEXF export (PPanGGOLiN.export_to_GEXF, ppanggolin.py:1294-1362), computed
+   on the device from the master and the flat orders of ALL its organisms, and the edges' organism <attvalue> lines
+   formatted there.  HOST arrays; m is only read and stays valid and unchanged; the work runs on m's stream.
+     f, genes[g], contig_ptr[c + 1], contig_org[c], repeated[f] or NULL
+                          the gene orders as nemgpu_family_table_create takes them (g > 0), contig_org non-decreasing:
+                          the organisms walked in column order;
+     gene_start[g], gene_end[g]   the annotation's START and END;
+     contig_size[c]       a circular contig's size (circular_contig_size), -1 for a linear contig.
+   The links are the build's (__neighborhood_computation, :485-520): a kept gene and the previous kept gene of its
+   contig, length START[gene] - END[previous]; per circular contig its first and last kept gene, length
+   (size - END[last]) + START[first]; lengths in 64 bits, one outside int32 (a gene's END - START too) is refused.  The
+   edges are the master's CSR entries with idx >= row, in CSR order: neighbors_graph.edges() of an nx.Graph.  Per edge:
+     src, dst[E]          its families;          weight[E]  the organisms that carry it;
+     len_min, len_max, len_distinct[E], len_sum[E] (int64), len_mid_lo, len_mid_hi[E]
+                          over the DISTINCT lengths of its links (data["length"] is a set, :456-459): the two middle
+                          elements of the sorted distinct lengths (equal when their number is odd) give the median;
+   per family  fam_mid_lo, fam_mid_hi[n]  the same middles over the distinct lengths END - START of its kept genes;
+   per organism  org_first_edge[d]  the first edge, in edge order, that carries it (E: none).
+   The (edge, organism, count) triples derived from the links must equal the master's edge bits and extras, every one,
+   both directions (a bits-only master: the bits alone); if not -- the orders are not this master's -- the call returns
+   NEMGPU_E_ARG with nemgpu_last_error's text and makes no table.  Malformed orders are refused on the host before any
+   launch; so is a master built with directed = 1.  The table does not keep m alive.
+   _attvalues_size: the bytes of the text of edges row0 .. row0 + rows - 1 for these attribute ids (attr_id[d] >= 0).
+   _attvalues: that text into text[capacity] (HOST): per edge, per organism on it in increasing column order, the line
+   `          <attvalue for="ID" value="COUNT" />\n` (ten spaces; ID = attr_id[organism], COUNT the pair's count), and
+   every edge's end offset in edge_end[rows]; *needed (may be NULL) = the bytes the batch takes.  capacity below that:
+   NEMGPU_E_ARG, *needed still set, nothing written.  m: the table's master. */
+typedef struct nemgpu_edge_table nemgpu_edge_table;
+int nemgpu_edge_table_create(nemgpu_edge_table** out, const nemgpu_master* m, int f, const int32_t* genes, const int32_t* gene_start,
+                             const int32_t* gene_end, int g, const int32_t* contig_ptr, const int32_t* contig_org, const int32_t* contig_size,
+                             int c, const uint8_t* repeated);
+int nemgpu_edge_table_shape(const nemgpu_edge_table* t, int* n, int* d, int* n_edges);
+int nemgpu_edge_table_fetch(const nemgpu_edge_table* t, int32_t* src, int32_t* dst, int32_t* weight, int32_t* len_min, int32_t* len_max,
+                            int32_t* len_distinct, int64_t* len_sum, int32_t* len_mid_lo, int32_t* len_mid_hi, int32_t* fam_mid_lo,
+                            int32_t* fam_mid_hi, int32_t* org_first_edge);
+int nemgpu_edge_table_attvalues_size(nemgpu_edge_table* t, const nemgpu_master* m, const int32_t* attr_id, int row0, int rows, int64_t* bytes);
+int nemgpu_edge_table_attvalues(nemgpu_edge_table* t, const nemgpu_master* m, const int32_t* attr_id, int row0, int rows, char* text,
+                                int64_t capacity, int64_t* needed, int64_t* edge_end);
+void nemgpu_edge_table_destroy(nemgpu_edge_table* t);
 /* What a master holds, of whichever constructor: sizes (n families, d organisms, nnz CSR entries, n_extra pairs with
    count >= 2; any pointer may be NULL), and the arrays as nemgpu_master_create_counts takes them, read back from the
    device: xbits[n][ceil(d/32)], nei_ptr[n + 1], nei_idx[nnz], edge_bits[nnz][ceil(d/32)], extra_ptr[nnz + 1],

@@ -644,6 +644,30 @@ class Master:
         o = mx.table_orders(annotations, self.organism_names, self.id_names, by_org, family, lengths)
         return mx.FamilyTable(self, o["genes"], o["lengths"], o["contig_ptr"], o["contig_org"], o["repeated"], repeated_names=by_org)
 
+    def edge_table(self, annotations=None, repeated=(), circular_contig_size=None, *, orders=None, starts=None, ends=None, contig_sizes=None,
+                   family=FAMILY):
+        """The per-edge table of the GEXF export (PPanGGOLiN.export_to_GEXF, ppanggolin.py:1294-1362), computed on the
+        device from this master and the gene orders of ALL its organisms (nemgpu_edge_table_create;
+        gexf.edge_table_arrays states what it computes).  annotations, repeated: as family_table takes them, the organisms
+        in column order (every gene's START and END are read in the same walk); circular_contig_size: {contig name: size},
+        as PPanGGOLiN holds it.  orders=(genes, contig_ptr, contig_org[, repeated[, f]]) with starts=, ends= int32 [G] and
+        contig_sizes= int32 [C] (-1: linear) instead: flat arrays, for a master without names.  Orders whose links are not
+        this master's edges, organisms and counts raise NemGpuError; so does a directed master.  Returns a
+        gexf.EdgeTable (the arrays, attvalues(), close())."""
+        from . import gexf
+        if orders is not None:
+            if annotations is not None or starts is None or ends is None or contig_sizes is None:
+                raise ValueError("edge_table: annotations, or orders= with starts=, ends= and contig_sizes=")
+            return gexf.EdgeTable(self, orders[0], starts, ends, orders[1], orders[2], contig_sizes, orders[3] if len(orders) > 3 else None,
+                                  orders[4] if len(orders) > 4 else None)
+        if annotations is None or getattr(self, "id_names", None) is None:
+            raise ValueError("edge_table: annotations and a master that carries names, or orders= with starts=, ends= and contig_sizes=")
+        by_org = getattr(self, "repeated_by_organism", None)
+        if by_org is None:
+            by_org = {org: frozenset(repeated) for org in self.organism_names}
+        o = gexf.gexf_orders(annotations, self.organism_names, self.id_names, by_org, circular_contig_size, family)
+        return gexf.EdgeTable(self, o["genes"], o["starts"], o["ends"], o["contig_ptr"], o["contig_org"], o["contig_sizes"], o["repeated"])
+
     def shape(self):
         """(n families, d organisms, nnz CSR entries, pairs with count >= 2) as the device holds them (nemgpu_master_shape)"""
         v = [C.c_int() for _ in range(4)]

@@ -1,0 +1,630 @@
+// nem_edges.hip -- see nem_edges.hpp.  The kernels, then the C entry points (nemgpu_edge_table_*): everything refused for
+// its arguments alone is refused on the host before the first HIP call.
+#include "nem_edges.hpp"
+
+#include <string>
+#include <vector>
+
+#include "nem_internal.hpp"
+#include "nem_master.hpp"
+#include "nem_project.hpp"
+#include "nem_scan.hpp"
+
+namespace nemk {
+
+namespace {
+
+using namespace seg;
+constexpr int kNoFamily = -2;                     // a caller id that no master family has (nem_project.hip's)
+
+__device__ inline bool fits_int32(long long v) { return v >= -2147483648ll && v <= 2147483647ll; }
+
+// the valid bits of word w of a bit row over d organisms
+__device__ inline uint32_t word_mask(int w, int d) { return (w == (d - 1) / 32 && (d & 31)) ? (1u << (d & 31)) - 1u : 0xffffffffu; }
+
+// the count of (entry t, organism o), whose bit is set: 1 + its extra
+__device__ inline int pair_count(const int* __restrict__ extra_ptr, const int* __restrict__ extra_org, const int* __restrict__ extra_add, int t, int o)
+{
+    if (!extra_ptr) return 1;
+    const int a = extra_ptr[t], b = extra_ptr[t + 1];
+    if (a == b) return 1;
+    const int x = lower_bound(extra_org, a, b, o);
+    return (x < b && extra_org[x] == o) ? 1 + extra_add[x] : 1;
+}
+
+// ---- the edges ---------------------------------------------------------------------------------------------------
+// up[t] = 1 for a CSR entry with idx >= row: an edge of nx.Graph.edges()
+__global__ __launch_bounds__(kThreads) void k_edges_up(const int* __restrict__ ptr, const int* __restrict__ idx, int n, int nnz, int* __restrict__ up)
+{
+    const int t = blockIdx.x * kThreads + threadIdx.x;
+    if (t < nnz) up[t] = idx[t] >= last_le(ptr, n, t) ? 1 : 0;
+}
+
+// every edge's ends and entry, and its key (src, dst) with its number (upx: the exclusive scan of up)
+__global__ __launch_bounds__(kThreads) void k_edges_list(const int* __restrict__ ptr, const int* __restrict__ idx, int n, int nnz,
+                                                        const int* __restrict__ up, const int* __restrict__ upx, int bn, uint64_t* __restrict__ ekey,
+                                                        uint32_t* __restrict__ eval, int* __restrict__ src, int* __restrict__ dst,
+                                                        int* __restrict__ entry)
+{
+    const int t = blockIdx.x * kThreads + threadIdx.x;
+    if (t >= nnz || !up[t]) return;
+    const int r = last_le(ptr, n, t), j = idx[t], e = upx[t];
+    src[e] = r; dst[e] = j; entry[e] = t;
+    ekey[e] = ((uint64_t)(uint32_t)r << bn) | (uint64_t)(uint32_t)j;
+    eval[e] = (uint32_t)e;
+}
+
+// the set bits of the edges' rows and the number of their extras: totals[0], totals[1]
+__global__ __launch_bounds__(kThreads) void k_edges_popcount(const uint32_t* __restrict__ bits, const int* __restrict__ up, long long words, int wf, int d,
+                                                            const int* __restrict__ extra_ptr, unsigned long long* totals)
+{
+    const long long q = (long long)blockIdx.x * kThreads + threadIdx.x;
+    int cnt = 0, xs = 0;
+    if (q < words) {
+        const int t = (int)(q / wf), w = (int)(q % wf);
+        if (up[t]) {
+            cnt = __popc(bits[q] & word_mask(w, d));
+            if (w == 0 && extra_ptr) xs = extra_ptr[t + 1] - extra_ptr[t];
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { cnt += __shfl_down(cnt, off); xs += __shfl_down(xs, off); }
+    if (lane_id() == 0 && cnt) atomicAdd(&totals[0], (unsigned long long)cnt);
+    if (lane_id() == 0 && xs) atomicAdd(&totals[1], (unsigned long long)xs);
+}
+
+// ---- the links ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void k_edges_kept(const int* __restrict__ genes, int g, const uint8_t* __restrict__ repeated, int* __restrict__ last)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p < g) last[p] = (repeated && repeated[genes[p]]) ? -1 : p;
+}
+
+// one lane per gene (last: the inclusive max-scan of k_edges_kept's): its family key (family, gene length) and, where it
+// ends a link, the link's keys (edge, organism) and (edge, length); everything else sorts behind every edge / family
+__global__ __launch_bounds__(kThreads) void k_edges_links(const int* __restrict__ genes, const int* __restrict__ gstart, const int* __restrict__ gend, int g,
+                                                         const int* __restrict__ last, const int* __restrict__ cptr, int c,
+                                                         const int* __restrict__ corg, const int* __restrict__ csize, const int* __restrict__ inv,
+                                                         int n, const uint64_t* __restrict__ ekeys, const uint32_t* __restrict__ evals, int ne, int bn,
+                                                         int bd, uint64_t* __restrict__ key_org, uint64_t* __restrict__ key_len,
+                                                         uint64_t* __restrict__ key_fam, int* flags)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= g) return;
+    uint64_t ko = (uint64_t)(uint32_t)ne << bd, kl = (uint64_t)(uint32_t)ne << 32, kf = (uint64_t)(uint32_t)n << 32;
+    int bad = 0;
+    if (last[p] == p) {
+        const int fam = inv[genes[p]];
+        if (fam == kNoFamily) {
+            bad |= kEdgesNoFamily;
+        } else {
+            const long long glen = (long long)gend[p] - (long long)gstart[p];
+            if (!fits_int32(glen)) bad |= kEdgesLength;
+            else kf = ((uint64_t)(uint32_t)fam << 32) | (uint64_t)((uint32_t)(int)glen ^ kLenBias);
+            const int j = last_le(cptr, c, p), start = cptr[j], end = cptr[j + 1];
+            const int prev = p > 0 ? last[p - 1] : -1;
+            int other = -1;
+            long long len = 0;
+            if (prev >= start) { other = prev; len = (long long)gstart[p] - (long long)gend[prev]; }                       // ppanggolin.py:513
+            else if (csize[j] >= 0) { other = last[end - 1]; len = ((long long)csize[j] - (long long)gend[other]) + (long long)gstart[p]; }   // :518-519
+            const int fb = other >= 0 ? inv[genes[other]] : kNoFamily;
+            if (other >= 0 && fb != kNoFamily) {
+                const int a = min(fam, fb), b = max(fam, fb);
+                const uint64_t key = ((uint64_t)(uint32_t)a << bn) | (uint64_t)(uint32_t)b;
+                const int at = lower_bound(ekeys, 0, ne, key);
+                if (at >= ne || ekeys[at] != key) bad |= kEdgesNoEdge;
+                else if (!fits_int32(len)) bad |= kEdgesLength;
+                else {
+                    const uint64_t e = evals[at];
+                    ko = (e << bd) | (uint64_t)(uint32_t)corg[j];
+                    kl = (e << 32) | (uint64_t)((uint32_t)(int)len ^ kLenBias);
+                }
+            }
+        }
+    }
+    if (bad) atomicOr(flags, bad);
+    key_org[p] = ko; key_len[p] = kl; key_fam[p] = kf;
+}
+
+// per sorted (edge, organism) key: head[p] = 1 where a pair starts, ehead[p] = 1 where an edge starts, multi[p] = 1 where
+// the pair's count is 2 or more; the pair must have its bit and (counts known) its count in the master
+__global__ __launch_bounds__(kThreads) void k_edges_pairs(const uint64_t* __restrict__ keys, int g, uint64_t none, int bd, const int* __restrict__ entry,
+                                                         const uint32_t* __restrict__ bits, int wf, const int* __restrict__ extra_ptr,
+                                                         const int* __restrict__ extra_org, const int* __restrict__ extra_add, int bits_only,
+                                                         int* flags, int* __restrict__ head, int* __restrict__ ehead, int* __restrict__ multi)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= g) return;
+    const uint64_t k = keys[p];
+    const bool valid = k < none;
+    const bool h = valid && (p == 0 || keys[p - 1] != k);
+    const bool eh = valid && (p == 0 || (keys[p - 1] >> bd) != (k >> bd));
+    int copies = 0;
+    if (h) {
+        const int e = (int)(k >> bd), org = (int)(k & ((1ull << bd) - 1ull));
+        const int t = entry[e];
+        copies = lower_bound(keys, p, g, k + 1) - p;
+        if (!((bits[(size_t)t * wf + (org >> 5)] >> (org & 31)) & 1u)) atomicOr(flags, (int)kEdgesNoBit);
+        else if (!bits_only && pair_count(extra_ptr, extra_org, extra_add, t, org) != copies) atomicOr(flags, (int)kEdgesCount);
+    }
+    head[p] = h ? 1 : 0;
+    ehead[p] = eh ? 1 : 0;
+    multi[p] = copies >= 2 ? 1 : 0;
+}
+
+// sstart[i] = the first sorted position of segment i (i = count: the keys that belong to one), the segment in the key's
+// bits from `shift` up
+__global__ __launch_bounds__(kThreads) void k_edges_sstart(const uint64_t* __restrict__ keys, int g, int shift, int count, int* __restrict__ sstart)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i <= count) sstart[i] = lower_bound(keys, 0, g, (uint64_t)(uint32_t)i << shift);
+}
+
+// per sorted (segment, length) key: 1 and the length where a distinct length starts
+__global__ __launch_bounds__(kThreads) void k_edges_lengths(const uint64_t* __restrict__ keys, int g, uint64_t none, int* __restrict__ dflag,
+                                                           long long* __restrict__ dval)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= g) return;
+    const uint64_t k = keys[p];
+    const bool h = k < none && (p == 0 || keys[p - 1] != k);
+    dflag[p] = h ? 1 : 0;
+    dval[p] = h ? (long long)(int)((uint32_t)k ^ kLenBias) : 0ll;
+}
+
+// per segment (an edge, or a family) what its distinct lengths give, from the scans at its ends; any output but the
+// middles may be null; rid (may be null): the scan of the pairs' heads, for the weight
+__global__ __launch_bounds__(kThreads) void k_edges_rows(int count, const int* __restrict__ sstart, const int* __restrict__ rid,
+                                                        const int* __restrict__ didx, const long long* __restrict__ dsum,
+                                                        const uint64_t* __restrict__ key_len, int* __restrict__ weight, int* __restrict__ len_min,
+                                                        int* __restrict__ len_max, int* __restrict__ len_distinct, long long* __restrict__ len_sum,
+                                                        int* __restrict__ mid_lo, int* __restrict__ mid_hi)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= count) return;
+    const int a = sstart[i], b = sstart[i + 1];
+    const int base = before(didx, a), cnt = before(didx, b) - base;
+    if (weight) weight[i] = before(rid, b) - before(rid, a);
+    if (len_distinct) len_distinct[i] = cnt;
+    if (len_sum) len_sum[i] = before(dsum, b) - before(dsum, a);
+    if (len_min) len_min[i] = b > a ? (int)((uint32_t)key_len[a] ^ kLenBias) : 0;
+    if (len_max) len_max[i] = b > a ? (int)((uint32_t)key_len[b - 1] ^ kLenBias) : 0;
+    int lo = 0, hi = 0;
+    if (cnt > 0) {
+        // the m-th distinct length (from 0) starts at the first position whose inclusive count is base + m + 1
+        const int plo = lower_bound(didx, a, b, base + (cnt - 1) / 2 + 1);
+        const int phi = lower_bound(didx, plo, b, base + cnt / 2 + 1);
+        lo = (int)((uint32_t)key_len[plo] ^ kLenBias);
+        hi = (int)((uint32_t)key_len[phi] ^ kLenBias);
+    }
+    mid_lo[i] = lo; mid_hi[i] = hi;
+}
+
+// one block per word of 32 organisms: the first edge, in edge order, that carries each
+__global__ __launch_bounds__(kThreads) void k_edges_first(const int* __restrict__ entry, int ne, const uint32_t* __restrict__ bits, int wf, int d,
+                                                         int* __restrict__ first)
+{
+    __shared__ uint32_t s_tot[kThreads / 64];
+    const int w = blockIdx.x;
+    const uint32_t full = word_mask(w, d);
+    if (threadIdx.x < 32 && w * 32 + (int)threadIdx.x < d) first[w * 32 + threadIdx.x] = ne;
+    __syncthreads();
+    uint32_t carry = 0;
+    for (int base = 0; base < ne && carry != full; base += kThreads) {
+        const int e = base + threadIdx.x;
+        const uint32_t v = e < ne ? bits[(size_t)entry[e] * wf + w] & full : 0u;
+        uint32_t all;
+        const uint32_t ex = block_exclusive(v, OpOr(), 0u, s_tot, &all);
+        uint32_t fresh = v & ~(carry | ex);
+        while (fresh) { first[w * 32 + (__ffs((int)fresh) - 1)] = e; fresh &= fresh - 1u; }
+        carry |= all;
+    }
+}
+
+// ---- the <attvalue> text -----------------------------------------------------------------------------------------
+// a line: 10 spaces, <attvalue for=", the id, " value=", the count, " />, a newline
+constexpr int kLineFixed = 39, kLineMax = kLineFixed + 20;
+constexpr int kStageWords = (64 * kLineMax + 8 + 7) / 8;      // a wave's 64 lines in LDS, at the global alignment
+
+__device__ inline int line_width(int id, int cnt) { return kLineFixed + digits_of(id) + digits_of(cnt); }
+
+// one wave per edge: the bytes of its lines
+__global__ __launch_bounds__(kThreads) void k_att_sizes(const int* __restrict__ entry, const uint32_t* __restrict__ bits, int wf, int d,
+                                                       const int* __restrict__ extra_ptr, const int* __restrict__ extra_org,
+                                                       const int* __restrict__ extra_add, const int* __restrict__ attr_id, int row0, int rows,
+                                                       long long* __restrict__ sizes)
+{
+    const int r = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6), lane = lane_id();
+    if (r >= rows) return;
+    const int t = entry[row0 + r];
+    long long sum = 0;
+    for (int w = lane; w < wf; w += 64) {
+        uint32_t v = bits[(size_t)t * wf + w] & word_mask(w, d);
+        while (v) {
+            const int o = w * 32 + __ffs((int)v) - 1;
+            v &= v - 1u;
+            sum += line_width(attr_id[o], pair_count(extra_ptr, extra_org, extra_add, t, o));
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off);
+    if (lane == 0) sizes[r] = sum;
+}
+
+__device__ inline char* put_digits(char* at, int v)
+{
+    const int nd = digits_of(v);
+    for (int q = nd - 1; q >= 0; q--) { at[q] = (char)('0' + v % 10); v /= 10; }
+    return at + nd;
+}
+
+// one wave per edge: its lines, 64 organisms at a time (everything but the lane's own line is uniform over the wave)
+__global__ __launch_bounds__(kThreads) void k_att_text(const int* __restrict__ entry, const uint32_t* __restrict__ bits, int wf, int d,
+                                                      const int* __restrict__ extra_ptr, const int* __restrict__ extra_org,
+                                                      const int* __restrict__ extra_add, const int* __restrict__ attr_id, int row0, int rows,
+                                                      const long long* __restrict__ ends, char* __restrict__ text)
+{
+    __shared__ uint64_t s_txt[kThreads / 64][kStageWords];
+    const int wv = threadIdx.x >> 6, lane = lane_id();
+    const int r = blockIdx.x * (kThreads / 64) + wv;
+    if (r >= rows) return;
+    const int t = entry[row0 + r];
+    long long at = r > 0 ? ends[r - 1] : 0ll;
+    char* stage = (char*)s_txt[wv];
+    for (int o0 = 0; o0 < d; o0 += 64) {
+        const int o = o0 + lane;
+        const bool has = o < d && ((bits[(size_t)t * wf + (o >> 5)] >> (o & 31)) & 1u);
+        if (!__ballot(has)) continue;
+        int id = 0, cnt = 0, width = 0;
+        if (has) { id = attr_id[o]; cnt = pair_count(extra_ptr, extra_org, extra_add, t, o); width = line_width(id, cnt); }
+        int inc = width;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
+        const int len = __shfl(inc, 63);
+        const int mis = (int)(at & 7);
+        if (has) {
+            char* q = stage + mis + (inc - width);
+            const char* a = "          <attvalue for=\"";
+            for (int k = 0; k < 25; k++) q[k] = a[k];
+            q = put_digits(q + 25, id);
+            const char* b = "\" value=\"";
+            for (int k = 0; k < 9; k++) q[k] = b[k];
+            q = put_digits(q + 9, cnt);
+            const char* e = "\" />\n";
+            for (int k = 0; k < 5; k++) q[k] = e[k];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        char* base = text + (at - mis);                       // 8-byte aligned: its words are the text's words
+        const int nwords = (mis + len + 7) >> 3;
+        for (int k = lane; k < nwords; k += 64) {
+            const int r0 = 8 * k - mis;                       // the word's first byte, relative to the run
+            const uint64_t word = s_txt[wv][k];
+            if (r0 >= 0 && r0 + 8 <= len) {
+                *(uint64_t*)(base + 8 * (size_t)k) = word;
+            } else {                                          // the run's first or last partial word: its own bytes only
+#pragma unroll
+                for (int b = 0; b < 8; b++)
+                    if (r0 + b >= 0 && r0 + b < len) base[8 * (size_t)k + b] = (char)(word >> (8 * b));
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the next group's layout overwrites the stage)
+        __builtin_amdgcn_wave_barrier();
+        at += len;
+    }
+}
+
+}  // namespace
+
+#define EDG(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
+
+hipError_t edge_table(const MasterDev& m, const EdgesIn& in, EdgeTableDev* t, int* mismatch, hipStream_t s)
+{
+    const int n = m.n, d = m.d, nnz = m.nnz, wf = m.wf, f = in.f, g = in.g, c = in.c;
+    *mismatch = kEdgesOk;
+    t->n = n; t->d = d; t->ne = 0;
+    Scratch mem;
+    // the edges
+    int *up, *upx, *partial, *totals;
+    unsigned long long* ones;
+    EDG(mem.alloc(&up, nnz)); EDG(mem.alloc(&upx, nnz)); EDG(mem.alloc(&partial, (size_t)std::max(nnz, g) / kScanTile + 2)); EDG(mem.alloc(&totals, 4));
+    EDG(mem.alloc(&ones, 2));
+    EDG(hipMemsetAsync(ones, 0, 16, s));
+    EDG(hipMemsetAsync(totals, 0, 16, s));
+    if (nnz > 0) hipLaunchKernelGGL(k_edges_up, dim3(blocks(nnz)), dim3(kThreads), 0, s, m.nei_ptr, m.nei_idx, n, nnz, up);
+    scan<int, OpSum<int>, false>(up, upx, nnz, OpSum<int>(), 0, partial, totals, s);
+    EDG(hipGetLastError());
+    int ne = 0;
+    EDG(hipMemcpyAsync(&ne, totals, 4, hipMemcpyDeviceToHost, s));
+    EDG(hipStreamSynchronize(s));
+    t->ne = ne;
+    EDG(dev_alloc(&t->src, ne)); EDG(dev_alloc(&t->dst, ne)); EDG(dev_alloc(&t->entry, ne));
+    const int bn = bits_for(n), bd = bits_for(d), be = bits_for(ne + 1), bn1 = bits_for(n + 1);
+    uint64_t *ek0, *ek1;
+    uint32_t *ev0, *ev1;
+    EDG(mem.alloc(&ek0, ne)); EDG(mem.alloc(&ek1, ne)); EDG(mem.alloc(&ev0, ne)); EDG(mem.alloc(&ev1, ne));
+    const uint64_t* ekeys = ek0;
+    const uint32_t* evals = ev0;
+    if (ne > 0) {
+        hipLaunchKernelGGL(k_edges_list, dim3(blocks(nnz)), dim3(kThreads), 0, s, m.nei_ptr, m.nei_idx, n, nnz, (const int*)up, (const int*)upx, bn, ek0, ev0,
+                           t->src, t->dst, t->entry);
+        const long long words = (long long)nnz * wf;
+        hipLaunchKernelGGL(k_edges_popcount, dim3(blocks(words)), dim3(kThreads), 0, s, m.edge_bits, (const int*)up, words, wf, d, m.extra_ptr, ones);
+        EDG(hipGetLastError());
+        EDG(sort_pairs<uint64_t>(mem, ek0, ek1, ev0, ev1, ne, 2 * bn, &ekeys, &evals, s));
+    }
+    // the links
+    int *inv, *order = nullptr, *genes, *gstart, *gend, *cptr, *corg, *csize, *last, *flags;
+    uint8_t* rep = nullptr;
+    EDG(mem.alloc(&inv, f)); EDG(mem.alloc(&genes, g)); EDG(mem.alloc(&gstart, g)); EDG(mem.alloc(&gend, g)); EDG(mem.alloc(&cptr, (size_t)c + 1));
+    EDG(mem.alloc(&corg, c)); EDG(mem.alloc(&csize, c)); EDG(mem.alloc(&last, g)); EDG(mem.alloc(&flags, 1));
+    if (in.order) { EDG(mem.alloc(&order, n)); EDG(hipMemcpyAsync(order, in.order, (size_t)n * 4, hipMemcpyHostToDevice, s)); }
+    if (in.repeated) { EDG(mem.alloc(&rep, f)); EDG(hipMemcpyAsync(rep, in.repeated, (size_t)f, hipMemcpyHostToDevice, s)); }
+    EDG(hipMemcpyAsync(genes, in.genes, (size_t)g * 4, hipMemcpyHostToDevice, s));
+    EDG(hipMemcpyAsync(gstart, in.gene_start, (size_t)g * 4, hipMemcpyHostToDevice, s));
+    EDG(hipMemcpyAsync(gend, in.gene_end, (size_t)g * 4, hipMemcpyHostToDevice, s));
+    EDG(hipMemcpyAsync(cptr, in.contig_ptr, ((size_t)c + 1) * 4, hipMemcpyHostToDevice, s));
+    EDG(hipMemcpyAsync(corg, in.contig_org, (size_t)c * 4, hipMemcpyHostToDevice, s));
+    EDG(hipMemcpyAsync(csize, in.contig_size, (size_t)c * 4, hipMemcpyHostToDevice, s));
+    EDG(hipMemsetAsync(flags, 0, 4, s));
+    launch_project_inverse(order, n, f, inv, s);
+    hipLaunchKernelGGL(k_edges_kept, dim3(blocks(g)), dim3(kThreads), 0, s, (const int*)genes, g, (const uint8_t*)rep, last);
+    scan<int, OpMax, true>(last, last, g, OpMax(), -1, partial, (int*)nullptr, s);
+    uint64_t *ka0, *ka1, *kb0, *kb1, *kc0, *kc1;
+    EDG(mem.alloc(&ka0, g)); EDG(mem.alloc(&ka1, g)); EDG(mem.alloc(&kb0, g)); EDG(mem.alloc(&kb1, g)); EDG(mem.alloc(&kc0, g)); EDG(mem.alloc(&kc1, g));
+    hipLaunchKernelGGL(k_edges_links, dim3(blocks(g)), dim3(kThreads), 0, s, (const int*)genes, (const int*)gstart, (const int*)gend, g, (const int*)last,
+                       (const int*)cptr, c, (const int*)corg, (const int*)csize, (const int*)inv, n, ekeys, evals, ne, bn, bd, ka0, kb0, kc0, flags);
+    EDG(hipGetLastError());
+    const uint64_t *ks_org, *ks_len, *ks_fam;
+    EDG(sort_keys<uint64_t>(mem, ka0, ka1, g, bd + be, &ks_org, s));
+    EDG(sort_keys<uint64_t>(mem, kb0, kb1, g, 32 + be, &ks_len, s));
+    EDG(sort_keys<uint64_t>(mem, kc0, kc1, g, 32 + bn1, &ks_fam, s));
+    // the (edge, organism, count) triples against the master's
+    const uint64_t none_org = (uint64_t)(uint32_t)ne << bd, none_len = (uint64_t)(uint32_t)ne << 32, none_fam = (uint64_t)(uint32_t)n << 32;
+    int *head, *ehead, *multi, *rid;
+    EDG(mem.alloc(&head, g)); EDG(mem.alloc(&ehead, g)); EDG(mem.alloc(&multi, g)); EDG(mem.alloc(&rid, g));
+    hipLaunchKernelGGL(k_edges_pairs, dim3(blocks(g)), dim3(kThreads), 0, s, ks_org, g, none_org, bd, (const int*)t->entry, m.edge_bits, wf, m.extra_ptr,
+                       m.extra_org, m.extra_add, in.bits_only ? 1 : 0, flags, head, ehead, multi);
+    scan<int, OpSum<int>, true>(head, rid, g, OpSum<int>(), 0, partial, totals + 1, s);
+    scan<int, OpSum<int>, true>(ehead, ehead, g, OpSum<int>(), 0, partial, totals + 2, s);
+    scan<int, OpSum<int>, true>(multi, multi, g, OpSum<int>(), 0, partial, totals + 3, s);
+    EDG(hipGetLastError());
+    int h_flags = 0, h_totals[4] = {0, 0, 0, 0};
+    unsigned long long h_ones[2] = {0, 0};
+    EDG(hipMemcpyAsync(&h_flags, flags, 4, hipMemcpyDeviceToHost, s));
+    EDG(hipMemcpyAsync(h_totals, totals, 16, hipMemcpyDeviceToHost, s));
+    EDG(hipMemcpyAsync(h_ones, ones, 16, hipMemcpyDeviceToHost, s));
+    EDG(hipStreamSynchronize(s));
+    if ((unsigned long long)h_totals[1] != h_ones[0] || h_totals[2] != ne) h_flags |= kEdgesMissing;
+    if (!in.bits_only && (unsigned long long)h_totals[3] != h_ones[1]) h_flags |= kEdgesCount;
+    if (h_flags) { *mismatch = h_flags; return hipSuccess; }
+    // the table's arrays
+    EDG(dev_alloc(&t->weight, ne)); EDG(dev_alloc(&t->len_min, ne)); EDG(dev_alloc(&t->len_max, ne)); EDG(dev_alloc(&t->len_distinct, ne));
+    EDG(dev_alloc(&t->len_sum, ne)); EDG(dev_alloc(&t->len_mid_lo, ne)); EDG(dev_alloc(&t->len_mid_hi, ne));
+    EDG(dev_alloc(&t->fam_mid_lo, n)); EDG(dev_alloc(&t->fam_mid_hi, n)); EDG(dev_alloc(&t->org_first_edge, d));
+    int *sstart, *dflag, *didx;
+    long long *lpartial, *dval, *dsum;
+    EDG(mem.alloc(&sstart, (size_t)std::max(ne, n) + 1)); EDG(mem.alloc(&dflag, g)); EDG(mem.alloc(&didx, g));
+    EDG(mem.alloc(&lpartial, (size_t)g / kScanTile + 2)); EDG(mem.alloc(&dval, g)); EDG(mem.alloc(&dsum, g));
+    // per edge
+    hipLaunchKernelGGL(k_edges_sstart, dim3(blocks((long long)ne + 1)), dim3(kThreads), 0, s, ks_org, g, bd, ne, sstart);
+    hipLaunchKernelGGL(k_edges_lengths, dim3(blocks(g)), dim3(kThreads), 0, s, ks_len, g, none_len, dflag, dval);
+    scan<int, OpSum<int>, true>(dflag, didx, g, OpSum<int>(), 0, partial, (int*)nullptr, s);
+    scan<long long, OpSum<long long>, true>(dval, dsum, g, OpSum<long long>(), 0ll, lpartial, (long long*)nullptr, s);
+    if (ne > 0)
+        hipLaunchKernelGGL(k_edges_rows, dim3(blocks(ne)), dim3(kThreads), 0, s, ne, (const int*)sstart, (const int*)rid, (const int*)didx,
+                           (const long long*)dsum, ks_len, t->weight, t->len_min, t->len_max, t->len_distinct, t->len_sum, t->len_mid_lo, t->len_mid_hi);
+    // per family (the kept genes' positions in the family keys; the stream orders the reuse of the scans' buffers)
+    hipLaunchKernelGGL(k_edges_sstart, dim3(blocks((long long)n + 1)), dim3(kThreads), 0, s, ks_fam, g, 32, n, sstart);
+    hipLaunchKernelGGL(k_edges_lengths, dim3(blocks(g)), dim3(kThreads), 0, s, ks_fam, g, none_fam, dflag, dval);
+    scan<int, OpSum<int>, true>(dflag, didx, g, OpSum<int>(), 0, partial, (int*)nullptr, s);
+    hipLaunchKernelGGL(k_edges_rows, dim3(blocks(n)), dim3(kThreads), 0, s, n, (const int*)sstart, (const int*)nullptr, (const int*)didx,
+                       (const long long*)nullptr, ks_fam, (int*)nullptr, (int*)nullptr, (int*)nullptr, (int*)nullptr, (long long*)nullptr, t->fam_mid_lo,
+                       t->fam_mid_hi);
+    // per organism
+    hipLaunchKernelGGL(k_edges_first, dim3(wf), dim3(kThreads), 0, s, (const int*)t->entry, ne, m.edge_bits, wf, d, t->org_first_edge);
+    EDG(hipGetLastError());
+    EDG(hipStreamSynchronize(s));
+    return hipSuccess;
+}
+
+#undef EDG
+
+void launch_att_sizes(const MasterDev& m, const EdgeTableDev& t, const int* attr_id, int row0, int rows, long long* sizes, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_att_sizes, dim3((rows + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads), 0, s, (const int*)t.entry, m.edge_bits, m.wf, m.d,
+                       m.extra_ptr, m.extra_org, m.extra_add, attr_id, row0, rows, sizes);
+}
+
+void launch_att_text(const MasterDev& m, const EdgeTableDev& t, const int* attr_id, int row0, int rows, const long long* ends, char* text,
+                     hipStream_t s)
+{
+    hipLaunchKernelGGL(k_att_text, dim3((rows + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads), 0, s, (const int*)t.entry, m.edge_bits, m.wf, m.d,
+                       m.extra_ptr, m.extra_org, m.extra_add, attr_id, row0, rows, ends, text);
+}
+
+}  // namespace nemk
+
+using namespace nemk;
+
+// An edge table on the device with the buffers of its text calls, kept for the next call
+struct nemgpu_edge_table {
+    int device = 0;
+    EdgeTableDev dev{};
+    int* attr = nullptr;                              // [d]
+    long long* ends = nullptr;                        // [ends_cap + 1]: a batch's edge ends, then its size
+    long long* partial = nullptr;
+    size_t ends_cap = 0;
+    char* text = nullptr;
+    size_t text_cap = 0;
+};
+
+namespace {
+
+void table_free(nemgpu_edge_table* t)
+{
+    EdgeTableDev& v = t->dev;
+    void* all[] = {v.src, v.dst, v.entry, v.weight, v.len_min, v.len_max, v.len_distinct, v.len_sum, v.len_mid_lo, v.len_mid_hi, v.fam_mid_lo,
+                   v.fam_mid_hi, v.org_first_edge, t->attr, t->ends, t->partial, t->text};
+    for (void* p : all) if (p) (void)hipFree(p);
+    delete t;
+}
+
+// what both text calls check and compute: the batch's edge ends on the device (t->ends) and its size
+int batch_sizes(const char* who, nemgpu_edge_table* t, const nemgpu_master* m, const int32_t* attr_id, int row0, int rows, long long* bytes)
+{
+    if (m->n != t->dev.n || m->d != t->dev.d || m->device != t->device) { set_error(std::string(who) + ": not the table's master"); return NEMGPU_E_ARG; }
+    if (row0 < 0 || rows <= 0 || (long long)row0 + rows > t->dev.ne) { set_error(std::string(who) + ": rows outside the table"); return NEMGPU_E_ARG; }
+    for (int o = 0; o < t->dev.d; o++)
+        if (attr_id[o] < 0) { set_error(std::string(who) + ": attr_id " + std::to_string(o) + " is negative"); return NEMGPU_E_ARG; }
+    HIPCHK(hipSetDevice(t->device));
+    if (!t->attr) HIPCHK(hipMalloc((void**)&t->attr, (size_t)t->dev.d * 4));
+    if (t->ends_cap < (size_t)rows) {
+        if (t->ends) (void)hipFree(t->ends);
+        if (t->partial) (void)hipFree(t->partial);
+        t->ends = nullptr; t->partial = nullptr; t->ends_cap = 0;
+        HIPCHK(hipMalloc((void**)&t->ends, ((size_t)rows + 1) * 8));
+        HIPCHK(hipMalloc((void**)&t->partial, ((size_t)rows / seg::kScanTile + 2) * 8));
+        t->ends_cap = (size_t)rows;
+    }
+    HIPCHK(hipMemcpyAsync(t->attr, attr_id, (size_t)t->dev.d * 4, hipMemcpyHostToDevice, m->stream));
+    launch_att_sizes(m->dev, t->dev, t->attr, row0, rows, t->ends, m->stream);
+    seg::scan<long long, seg::OpSum<long long>, true>(t->ends, t->ends, rows, seg::OpSum<long long>(), 0ll, t->partial, t->ends + rows, m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(bytes, t->ends + rows, 8, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return NEMGPU_OK;
+}
+
+}  // namespace
+
+int nemgpu_edge_table_create(nemgpu_edge_table** out, const nemgpu_master* m, int f, const int32_t* genes, const int32_t* gene_start,
+                             const int32_t* gene_end, int g, const int32_t* contig_ptr, const int32_t* contig_org, const int32_t* contig_size,
+                             int c, const uint8_t* repeated)
+{
+    if (!out) return NEMGPU_E_FUNCARG;
+    *out = nullptr;
+    if (!m) return NEMGPU_E_FUNCARG;
+    if (f <= 0 || g <= 0 || c <= 0 || !genes || !gene_start || !gene_end || !contig_ptr || !contig_org || !contig_size) {
+        set_error("nemgpu_edge_table_create: f > 0, the genes, their starts and ends, the contigs and their sizes are needed"); return NEMGPU_E_FUNCARG;
+    }
+    { const int r = check_orders(true, m->d, f, g, c, genes, contig_ptr, contig_org, nullptr); if (r != NEMGPU_OK) return r; }
+    for (int j = 1; j < c; j++)
+        if (contig_org[j] < contig_org[j - 1]) {
+            set_error("orders: contig " + std::to_string(j) + ": contig_org must be non-decreasing (the organisms walked in column order)");
+            return NEMGPU_E_ARG;
+        }
+    if (m->directed) {
+        set_error("nemgpu_edge_table_create: the master was built directed (edges() of a DiGraph is another walk, and the master cannot tell "
+                  "sens from antisens)");
+        return NEMGPU_E_ARG;
+    }
+    note_hip_used();
+    HIPCHK(hipSetDevice(m->device));
+    nemgpu_edge_table* t = new nemgpu_edge_table();
+    t->device = m->device;
+    const EdgesIn in{f, g, c, genes, gene_start, gene_end, contig_ptr, contig_org, contig_size, repeated, m->order.empty() ? nullptr : m->order.data(),
+                     m->bits_only};
+    int mismatch = 0;
+    const hipError_t err = edge_table(m->dev, in, &t->dev, &mismatch, m->stream);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        table_free(t);
+        set_error(std::string("nemgpu_edge_table_create: ") + hipGetErrorString(err));
+        return NEMGPU_E_DEVICE;
+    }
+    if (mismatch & kEdgesLength) {
+        table_free(t);
+        set_error("nemgpu_edge_table_create: a link's or a gene's length is outside int32");
+        return NEMGPU_E_ARG;
+    }
+    if (mismatch) {
+        table_free(t);
+        set_error(std::string("nemgpu_edge_table_create: these orders are not this master's: ") +
+                  ((mismatch & kEdgesNoFamily) ? "a kept gene's family is not in the master"
+                   : (mismatch & kEdgesNoEdge) ? "two adjacent kept genes' families are not an edge of the master"
+                   : (mismatch & kEdgesNoBit)  ? "an edge has a link in an organism where the master's edge bit is clear"
+                   : (mismatch & kEdgesCount)  ? "an (edge, organism) pair's number of links is not the master's count"
+                                               : "the master has an edge, or an edge bit, where the orders have no link"));
+        return NEMGPU_E_ARG;
+    }
+    *out = t;
+    return NEMGPU_OK;
+}
+
+int nemgpu_edge_table_shape(const nemgpu_edge_table* t, int* n, int* d, int* n_edges)
+{
+    if (!t) return NEMGPU_E_FUNCARG;
+    if (n) *n = t->dev.n;
+    if (d) *d = t->dev.d;
+    if (n_edges) *n_edges = t->dev.ne;
+    return NEMGPU_OK;
+}
+
+int nemgpu_edge_table_fetch(const nemgpu_edge_table* t, int32_t* src, int32_t* dst, int32_t* weight, int32_t* len_min, int32_t* len_max,
+                            int32_t* len_distinct, int64_t* len_sum, int32_t* len_mid_lo, int32_t* len_mid_hi, int32_t* fam_mid_lo,
+                            int32_t* fam_mid_hi, int32_t* org_first_edge)
+{
+    if (!t) return NEMGPU_E_FUNCARG;
+    HIPCHK(hipSetDevice(t->device));
+    const EdgeTableDev& v = t->dev;
+    const size_t ne = (size_t)v.ne, n = (size_t)v.n, d = (size_t)v.d;
+    if (src && ne) HIPCHK(hipMemcpy(src, v.src, ne * 4, hipMemcpyDeviceToHost));
+    if (dst && ne) HIPCHK(hipMemcpy(dst, v.dst, ne * 4, hipMemcpyDeviceToHost));
+    if (weight && ne) HIPCHK(hipMemcpy(weight, v.weight, ne * 4, hipMemcpyDeviceToHost));
+    if (len_min && ne) HIPCHK(hipMemcpy(len_min, v.len_min, ne * 4, hipMemcpyDeviceToHost));
+    if (len_max && ne) HIPCHK(hipMemcpy(len_max, v.len_max, ne * 4, hipMemcpyDeviceToHost));
+    if (len_distinct && ne) HIPCHK(hipMemcpy(len_distinct, v.len_distinct, ne * 4, hipMemcpyDeviceToHost));
+    if (len_sum && ne) HIPCHK(hipMemcpy(len_sum, v.len_sum, ne * 8, hipMemcpyDeviceToHost));
+    if (len_mid_lo && ne) HIPCHK(hipMemcpy(len_mid_lo, v.len_mid_lo, ne * 4, hipMemcpyDeviceToHost));
+    if (len_mid_hi && ne) HIPCHK(hipMemcpy(len_mid_hi, v.len_mid_hi, ne * 4, hipMemcpyDeviceToHost));
+    if (fam_mid_lo) HIPCHK(hipMemcpy(fam_mid_lo, v.fam_mid_lo, n * 4, hipMemcpyDeviceToHost));
+    if (fam_mid_hi) HIPCHK(hipMemcpy(fam_mid_hi, v.fam_mid_hi, n * 4, hipMemcpyDeviceToHost));
+    if (org_first_edge) HIPCHK(hipMemcpy(org_first_edge, v.org_first_edge, d * 4, hipMemcpyDeviceToHost));
+    return NEMGPU_OK;
+}
+
+int nemgpu_edge_table_attvalues_size(nemgpu_edge_table* t, const nemgpu_master* m, const int32_t* attr_id, int row0, int rows, int64_t* bytes)
+{
+    if (!t || !m || !attr_id || !bytes) return NEMGPU_E_FUNCARG;
+    long long size = 0;
+    const int r = batch_sizes("nemgpu_edge_table_attvalues_size", t, m, attr_id, row0, rows, &size);
+    if (r != NEMGPU_OK) return r;
+    *bytes = size;
+    return NEMGPU_OK;
+}
+
+int nemgpu_edge_table_attvalues(nemgpu_edge_table* t, const nemgpu_master* m, const int32_t* attr_id, int row0, int rows, char* text,
+                                int64_t capacity, int64_t* needed, int64_t* edge_end)
+{
+    if (!t || !m || !attr_id || !text || !edge_end) return NEMGPU_E_FUNCARG;
+    long long bytes = 0;
+    const int r = batch_sizes("nemgpu_edge_table_attvalues", t, m, attr_id, row0, rows, &bytes);
+    if (r != NEMGPU_OK) return r;
+    if (needed) *needed = bytes;
+    if (capacity < bytes) {
+        set_error("nemgpu_edge_table_attvalues: the buffer holds " + std::to_string((long long)capacity) + " bytes, the batch needs " + std::to_string(bytes));
+        return NEMGPU_E_ARG;
+    }
+    if (t->text_cap < (size_t)bytes) {
+        if (t->text) (void)hipFree(t->text);
+        t->text = nullptr; t->text_cap = 0;
+        HIPCHK(hipMalloc((void**)&t->text, a256((size_t)bytes)));
+        t->text_cap = a256((size_t)bytes);
+    }
+    launch_att_text(m->dev, t->dev, t->attr, row0, rows, t->ends, t->text, m->stream);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipMemcpyAsync(edge_end, t->ends, (size_t)rows * 8, hipMemcpyDeviceToHost, m->stream);
+    if (err == hipSuccess && bytes) err = hipMemcpyAsync(text, t->text, (size_t)bytes, hipMemcpyDeviceToHost, m->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(m->stream);
+    if (err != hipSuccess) { (void)hipGetLastError(); set_error(std::string("nemgpu_edge_table_attvalues: ") + hipGetErrorString(err)); return NEMGPU_E_DEVICE; }
+    return NEMGPU_OK;
+}
+
+void nemgpu_edge_table_destroy(nemgpu_edge_table* t)
+{
+    if (!t) return;
+    (void)hipSetDevice(t->device);
+    table_free(t);
+}

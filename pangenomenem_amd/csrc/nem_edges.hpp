@@ -1,0 +1,73 @@
+// nem_edges.hpp -- the per-edge table of the pangenome graph's GEXF export and the edges' organism <attvalue> text, from
+// the resident master.
+//
+// PPanGGOLiN.export_to_GEXF (ppanggolin.py:1294-1362) walks neighbors_graph.edges(data=True) and turns every edge's SET
+// of link lengths (`__add_link`'s `length`, :456-459) into avg / med / min / max, and every node's set of gene lengths
+// into the same; nx.write_gexf then writes per edge one <attvalue> per organism on it.  The master holds the edges, their
+// organisms and the counts, but no length.  With the master on the device and the flat orders of all its organisms:
+//   1. the EDGES are the CSR entries with idx >= row, numbered by the exclusive scan of that flag: nx.Graph.edges()'s
+//      order; their keys (src, dst) sorted once (rocPRIM's radix sort) are what a link finds its edge in;
+//   2. per kept GENE at most one link, as the build makes them (nem_orders.hpp): the previous kept gene of its contig
+//      from an inclusive max-scan, or the contig's last kept gene for the first kept gene of a circular contig; its
+//      length in 64 bits; its edge by one binary search of the sorted edge keys; two keys: (edge, organism) and
+//      (edge, length);
+//   3. both key arrays sorted: an edge's links are one segment of either, the same positions in both, found by one search
+//      per edge -- its weight, its distinct lengths and their sum are differences of inclusive scans (nem_scan.hpp) at
+//      the segment's ends, its min and max the segment's first and last key, its two middle distinct lengths one search
+//      each of the scan of the distinct flags: no per-link atomic, no walk of a row; a pair of families adjacent
+//      thousands of times costs what its links cost;
+//   4. per run of equal (edge, organism) its length is the count: the organism's bit must be set in the edge's bit row
+//      and the count must be 1 + the pair's extra (a search of the edge's extras); the number of runs must be the set
+//      bits of the edges' rows, the runs of 2 or more the edges' extras, the edges with a link all the edges: together
+//      every (edge, organism, count), both directions;
+//   5. the same segment arithmetic over (family, gene length) keys gives every family's two middle distinct lengths;
+//   6. per word of 32 organisms one block walks the edges in order with an exclusive OR-scan per tile of 256: the first
+//      edge that carries each organism (nx numbers an attribute where it first meets it).
+// The <attvalue> text (k_att_text): one wave per edge; per 64 organisms a lane per organism, the lines' offsets from a
+// wave scan of their widths, laid out in LDS at the global address's alignment and copied out in aligned 8-byte words
+// (only a run's first and last partial words by bytes); a group of 64 organisms none of which is on the edge costs one
+// load and one ballot.  gexf.edge_table_arrays / gexf.attvalues_host (Python) state the same.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "nem_chunks.hpp"
+
+namespace nemk {
+
+struct EdgesIn {                  // HOST arrays, checked by the caller
+    int f, g, c;
+    const int32_t* genes;         // [g] caller ids < f
+    const int32_t* gene_start;    // [g]
+    const int32_t* gene_end;      // [g]
+    const int32_t* contig_ptr;    // [c + 1]
+    const int32_t* contig_org;    // [c] master columns, non-decreasing
+    const int32_t* contig_size;   // [c] a circular contig's size, -1: linear
+    const uint8_t* repeated;      // [f] or null
+    const int32_t* order;         // [n] master family i = caller id order[i]; null: i
+    bool bits_only;               // the master's counts are not known: only the bits are checked
+};
+
+// the table on the device (owned by nem_edges.hip's handle)
+struct EdgeTableDev {
+    int n = 0, d = 0, ne = 0;
+    int *src = nullptr, *dst = nullptr, *entry = nullptr;     // [ne]; entry: the edge's CSR entry (its bit row, its extras)
+    int *weight = nullptr, *len_min = nullptr, *len_max = nullptr, *len_distinct = nullptr, *len_mid_lo = nullptr, *len_mid_hi = nullptr;
+    long long* len_sum = nullptr;
+    int *fam_mid_lo = nullptr, *fam_mid_hi = nullptr;         // [n]
+    int* org_first_edge = nullptr;                            // [d]
+};
+
+enum { kEdgesOk = 0, kEdgesNoFamily = 1, kEdgesNoEdge = 2, kEdgesNoBit = 4, kEdgesCount = 8, kEdgesMissing = 16, kEdgesLength = 32 };
+
+// Fills *t (its arrays allocated with hipMalloc; the caller frees them, also after a failure).  *mismatch: kEdgesOk or
+// why no table was made (then the arrays hold nothing).  The master is only read.  Waits.
+hipError_t edge_table(const MasterDev& m, const EdgesIn& in, EdgeTableDev* t, int* mismatch, hipStream_t s);
+
+// per edge row0 .. row0 + rows - 1 the bytes of its lines into sizes[rows] (DEVICE); attr_id [d] (DEVICE)
+void launch_att_sizes(const MasterDev& m, const EdgeTableDev& t, const int* attr_id, int row0, int rows, long long* sizes, hipStream_t s);
+// the lines themselves; ends[rows] (DEVICE): the inclusive scan of the sizes; text (DEVICE): ends[rows - 1] bytes
+void launch_att_text(const MasterDev& m, const EdgeTableDev& t, const int* attr_id, int row0, int rows, const long long* ends, char* text,
+                     hipStream_t s);
+
+}  // namespace nemk

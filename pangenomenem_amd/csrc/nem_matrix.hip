@@ -17,20 +17,6 @@ namespace {
 using namespace seg;
 constexpr int kNoFamily = -2;                     // a caller id that no master family has (nem_project.hip's)
 constexpr int kRepeated = -1;                     // a gene of a repeated family
-constexpr uint32_t kLenBias = 0x80000000u;        // a length as an unsigned key field: negatives sort first
-
-// the first j in [lo, hi) with a[j] >= x (hi: none)
-template <class T> __device__ inline int lower_bound(const T* a, int lo, int hi, T x)
-{
-    while (lo < hi) { const int mid = lo + (hi - lo) / 2; if (a[mid] < x) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
-__device__ inline int digits_of(int v)            // decimal digits of v >= 0
-{
-    return 1 + (v >= 10) + (v >= 100) + (v >= 1000) + (v >= 10000) + (v >= 100000) + (v >= 1000000) + (v >= 10000000) + (v >= 100000000) +
-           (v >= 1000000000);
-}
 
 // ---- the family table ------------------------------------------------------------------------------------------
 // one lane per gene: its organism (its contig's), its master family, its two keys; a gene that is not kept sorts behind
@@ -119,8 +105,6 @@ __global__ __launch_bounds__(kThreads) void k_matrix_lengths(const uint64_t* __r
     dflag[p] = h ? 1 : 0;
     dval[p] = h ? (long long)(int)((uint32_t)k ^ kLenBias) : 0ll;
 }
-
-template <class T> __device__ inline T before(const T* inclusive, int p) { return p > 0 ? inclusive[p - 1] : (T)0; }
 
 // per family its row of the table from the scans at its segment's ends; i = n closes multi_ptr and fam_xpre
 __global__ __launch_bounds__(kThreads) void k_matrix_family(int n, const int* __restrict__ fstart, const int* __restrict__ rid,
@@ -242,11 +226,6 @@ __global__ __launch_bounds__(kThreads) void k_rtab(const uint64_t* __restrict__ 
             __builtin_amdgcn_wave_barrier();
         }
     }
-}
-
-template <class T> hipError_t dev_alloc(T** p, size_t count)
-{
-    return hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 // nem_scan.hpp -- the block scans and the wave segment reduction that the units working on sorted records share
-// (nem_orders.hip: the master's build and append; nem_project.hip: a partition's projection; nem_matrix.hip: the family table).  256-thread blocks of 4
+// (nem_orders.hip: the master's build and append; nem_project.hip: a partition's projection; nem_matrix.hip: the family table; nem_edges.hip: the edge table).  256-thread blocks of 4
 // waves; a scan is three launches (tile totals, their prefixes, the tiles), in place allowed.  With them what both do
 // around rocPRIM's radix sort: the key widths, a call's scratch buffers, the sort itself, the search of a CSR's rows.
 #pragma once
@@ -31,6 +31,24 @@ __device__ inline int last_le(const int* a, int count, int x)
     return lo;
 }
 
+// the first j in [lo, hi) with a[j] >= x (hi: none)
+template <class T> __device__ inline int lower_bound(const T* a, int lo, int hi, T x)
+{
+    while (lo < hi) { const int mid = lo + (hi - lo) / 2; if (a[mid] < x) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+__device__ inline int digits_of(int v)            // decimal digits of v >= 0
+{
+    return 1 + (v >= 10) + (v >= 100) + (v >= 1000) + (v >= 10000) + (v >= 100000) + (v >= 1000000) + (v >= 10000000) + (v >= 100000000) +
+           (v >= 1000000000);
+}
+
+// the value of an inclusive scan before position p
+template <class T> __device__ inline T before(const T* inclusive, int p) { return p > 0 ? inclusive[p - 1] : (T)0; }
+
+constexpr uint32_t kLenBias = 0x80000000u;        // a length as an unsigned key field: negatives sort first
+
 // the bits of a key field that holds 0 .. count - 1 (at least 1)
 static inline int bits_for(int count) { int b = 1; while (b < 31 && (1ll << b) < count) b++; return b; }
 static inline int blocks(long long n) { return (int)((n + kThreads - 1) / kThreads); }
@@ -48,6 +66,12 @@ struct __attribute__((visibility("hidden"))) Scratch {
         return e;
     }
 };
+
+// a device array of a result that outlives the call (at least one item)
+template <class T> static hipError_t dev_alloc(T** p, size_t count)
+{
+    return hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
+}
 
 // (k0, v0) sorted by the keys' bits [0, end_bit) with (k1, v1) as the other halves of rocPRIM's double buffers; *k_out,
 // *v_out: the halves that hold the result; the sort's temporary storage is mem's

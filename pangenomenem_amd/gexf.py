@@ -1,0 +1,536 @@
+"""The pangenome graph as GEXF (PPanGGOLiN.export_to_GEXF, ppanggolin.py:1294-1362, full and ``_light``) and the series
+of the U-shaped plot (``ushaped_plot``, :1486-1523), from a resident master: no networkx graph is built or walked.
+
+``export_to_GEXF`` copies the graph, turns every node's set of gene lengths and every edge's set of link lengths
+(``__add_link``'s ``length``, :456-459) into avg / med / min / max and hands the copy to networkx's ``write_gexf``, which
+builds an ElementTree with one ``<attvalue>`` per (edge, organism).  Everything it writes is a function of the master
+(its CSR, its edge bit rows and extras, its numbering), the family table (matrix.py) and the flat gene orders of all the
+master's organisms with every gene's START and END and every circular contig's size:
+
+``edge_table_arrays`` states the per-edge table in numpy and ``attvalues_host`` the edges' organism lines;
+``nemgpu_edge_table_create`` / ``nemgpu_edge_table_attvalues`` (csrc/nem_edges.hip) compute both on the device,
+``Master.edge_table`` (chunks.py) is their Python surface; ``EdgeTable`` / ``HostEdgeTable`` hold the result;
+``write_gexf`` streams the file, byte for byte what networkx writes, and ``ushape_counts`` gives the plot's series.
+
+Where the reference's bytes are not determined -- ``"|".join(set)`` of a node's names, products and an organism's genes
+follows string hash order; the ``<meta>`` element holds the date and networkx's version -- the values are joined in walk
+order here and ``<meta>`` names this package.
+"""
+import ctypes as C
+import gzip
+import time
+
+import numpy as np
+
+from .engine import NemGpuError
+from .matrix import TEXT_BUDGET, _long_names, table_orders
+from .projection import FAMILY, START, END, PRODUCT, check_projection_orders, part_codes
+
+NAME = 5                                                      # a gene's info: TYPE, FAMILY, START, END, STRAND, NAME, PRODUCT
+EDGE_FIELDS = ("src", "dst", "weight", "len_min", "len_max", "len_distinct", "len_sum", "len_mid_lo", "len_mid_hi", "fam_mid_lo", "fam_mid_hi",
+               "org_first_edge")
+COLORS_RGB = {"accessory": (235, 55, 237), "core_exact": (255, 40, 40), "shell": (0, 216, 96), "persistent": (247, 165, 7),
+              "cloud": (121, 222, 255), "undefined": (130, 130, 130)}                             # ppanggolin.py:34 (a is 0)
+LINE_MAX = 59                                                 # an organism line of an edge: 39 bytes and two numbers of 10 digits
+HEAD = ("<?xml version='1.0' encoding='utf-8'?>\n"
+        '<gexf xmlns:viz="http://www.gexf.net/1.2draft/viz" xmlns="http://www.gexf.net/1.2draft" '
+        'xmlns:xsi="http://www.w3.org/2001/XMLSchema-instance" '
+        'xsi:schemaLocation="http://www.gexf.net/1.2draft http://www.gexf.net/1.2draft/gexf.xsd" version="1.2">\n'
+        '  <meta lastmodifieddate="%s">\n    <creator>pangenomenem_amd</creator>\n  </meta>\n'
+        '  <graph defaultedgetype="undirected" mode="static" name="">\n')
+INT32 = (-2 ** 31, 2 ** 31 - 1)
+
+
+def gexf_orders(annotations, organisms, families, repeated, circular_contig_size=None, family=FAMILY):
+    """The flat orders an edge table is made from: matrix.table_orders of ALL the organisms (a skipped gene gets the one
+    id flagged in `repeated`) with every gene's START and END in the same walk and per contig its circular size
+    (circular_contig_size: {contig name: size}, as PPanGGOLiN holds it), -1 for a linear contig.
+    Returns table_orders' dict with starts, ends, contig_sizes."""
+    o = table_orders(annotations, organisms, families, repeated, family, lengths=np.zeros(0, np.int32))
+    infos = [info for contigs in annotations.values() for annot in contigs.values() for info in annot.values()]
+    sizes = circular_contig_size or {}
+    o["starts"] = np.asarray([info[START] for info in infos], np.int64)
+    o["ends"] = np.asarray([info[END] for info in infos], np.int64)
+    o["contig_sizes"] = np.asarray([sizes.get(contig, -1) for contigs in annotations.values() for contig in contigs], np.int64)
+    for name in ("starts", "ends", "contig_sizes"):
+        if len(o[name]) and (o[name].min() < INT32[0] or o[name].max() > INT32[1]):
+            raise ValueError("gexf_orders: %s outside int32" % name)
+        o[name] = o[name].astype(np.int32)
+    return o
+
+
+def _segments(seg, val, count):
+    """over the DISTINCT (seg, val) pairs, per segment 0 .. count - 1: distinct, sum (int64), min, max and the two middle
+    elements of the sorted distinct values (0 where there is none)"""
+    out = dict(distinct=np.zeros(count, np.int32), sum=np.zeros(count, np.int64), min=np.zeros(count, np.int32), max=np.zeros(count, np.int32),
+               lo=np.zeros(count, np.int32), hi=np.zeros(count, np.int32))
+    if not len(seg):
+        return out
+    pairs = np.unique(np.stack([np.asarray(seg, np.int64), np.asarray(val, np.int64)], axis=1), axis=0)     # by segment, then value
+    s, v = pairs[:, 0], pairs[:, 1]
+    cnt = np.bincount(s, minlength=count)
+    first = np.cumsum(cnt) - cnt
+    has = cnt > 0
+    out["distinct"] = cnt.astype(np.int32)
+    np.add.at(out["sum"], s, v)
+    out["min"][has] = v[first[has]]
+    out["max"][has] = v[first[has] + cnt[has] - 1]
+    out["lo"][has] = v[first[has] + (cnt[has] - 1) // 2]
+    out["hi"][has] = v[first[has] + cnt[has] // 2]
+    return out
+
+
+def _edge_bits_bool(edge_bits, nnz, d):
+    wf = (d + 31) // 32
+    eb = np.ascontiguousarray(edge_bits, np.uint32).reshape(-1, wf)[:nnz]
+    return np.unpackbits(eb.view(np.uint8).reshape(nnz, -1), axis=1, bitorder="little")[:, :d].astype(bool)
+
+
+def master_edges(ptr, idx):
+    """nx.Graph.edges() of a master's CSR: the entries with idx >= row, in CSR order: (src, dst, entry)"""
+    ptr, idx = np.asarray(ptr, np.int64), np.asarray(idx, np.int64)
+    row = np.repeat(np.arange(len(ptr) - 1, dtype=np.int64), np.diff(ptr))
+    entry = np.flatnonzero(idx >= row)
+    return row[entry].astype(np.int32), idx[entry].astype(np.int32), entry
+
+
+def links_of_orders(fam, kept, gene_start, gene_end, contig_ptr, contig_org, contig_size):
+    """The links of __neighborhood_computation (ppanggolin.py:485-520) as arrays: per link (a, b, organism, length):
+    a kept gene and the previous kept gene of its contig, START[gene] - END[previous]; per circular contig with a kept
+    gene its first and last kept gene, (size - END[last]) + START[first].  fam: every gene's family; int64."""
+    gs, ge = np.asarray(gene_start, np.int64), np.asarray(gene_end, np.int64)
+    cid = np.repeat(np.arange(len(contig_org), dtype=np.int64), np.diff(contig_ptr))
+    kp = np.flatnonzero(kept)
+    org = np.asarray(contig_org, np.int64)
+    a, b = kp[1:], kp[:-1]
+    same = cid[a] == cid[b]
+    a, b = a[same], b[same]
+    gene = (fam[a], fam[b], org[cid[a]], gs[a] - ge[b])
+    kc = cid[kp]
+    first = kp[np.concatenate([[True], kc[1:] != kc[:-1]])] if len(kp) else kp
+    last = kp[np.concatenate([kc[1:] != kc[:-1], [True]])] if len(kp) else kp
+    size = np.asarray(contig_size, np.int64)[cid[first]]
+    ring = size >= 0
+    first, last, size = first[ring], last[ring], size[ring]
+    closing = (fam[first], fam[last], org[cid[first]], (size - ge[last]) + gs[first])
+    return tuple(np.concatenate([x, y]) for x, y in zip(gene, closing))
+
+
+def edge_table_arrays(graph, edge_bits, edge_counts, order, genes, gene_start, gene_end, contig_ptr, contig_org, contig_size, repeated=None,
+                      f=None, d=None, bits_only=False):
+    """What nemgpu_edge_table_create computes, in numpy.
+    graph (ptr, idx), edge_bits uint32 [nnz][ceil(d/32)], edge_counts (extra_ptr, extra_org, extra_count) or None, order
+    int32 [n]: the master as Master.arrays() gives it, d its organisms; the rest: the flat orders of ALL its organisms
+    (family_table_arrays' layout) with every gene's START and END and every contig's circular size or -1.
+      * the links: links_of_orders; lengths in 64 bits, one outside int32 raises ValueError;
+      * an undirected link (a, b) belongs to edge (min, max) in master numbering, a self-loop is an edge;
+      * the edges are the CSR entries with idx >= row in CSR order (E of them): src, dst;
+      * weight: the organisms on the edge; len_min, len_max, len_distinct, len_sum (int64), len_mid_lo, len_mid_hi over
+        the DISTINCT lengths of its links (the two middle elements of the sorted distinct lengths);
+      * fam_mid_lo, fam_mid_hi [n]: the same middles over the family's distinct kept-gene lengths END - START;
+      * org_first_edge [d]: the first edge that carries the organism, E if none;
+      * the (edge, organism, count) triples of the links must be the master's edge bits and extras (bits_only: the bits
+        alone): ValueError otherwise (the orders are not this master's);
+      * contig_org must be non-decreasing.
+    Returns a dict of those arrays."""
+    ptr, idx = (np.asarray(a, np.int64) for a in graph)
+    n, nnz = len(ptr) - 1, len(idx)
+    if d is None:
+        raise ValueError("edge_table_arrays: d, the master's organisms")
+    order = np.asarray(order, np.int64)
+    if f is None:
+        f = len(repeated) if repeated is not None else max(int(order.max()) + 1 if n else 1, int(np.max(genes)) + 1 if len(genes) else 1)
+    genes, contig_ptr, contig_org, repeated = check_projection_orders(genes, contig_ptr, contig_org, repeated, d, int(f))
+    if (np.diff(contig_org) < 0).any():
+        raise ValueError("edge_table_arrays: contig_org must be non-decreasing (the organisms walked in column order)")
+    gene_start, gene_end = np.ascontiguousarray(gene_start, np.int32), np.ascontiguousarray(gene_end, np.int32)
+    contig_size = np.ascontiguousarray(contig_size, np.int32)
+    if gene_start.shape != genes.shape or gene_end.shape != genes.shape or contig_size.shape != contig_org.shape:
+        raise ValueError("edge_table_arrays: gene_start [G], gene_end [G], contig_size [C]")
+    inv = np.full(int(f), -2, np.int64)
+    inside = order < f
+    inv[order[inside]] = np.flatnonzero(inside)
+    fam = inv[genes] if len(genes) else np.zeros(0, np.int64)
+    kept = np.ones(len(genes), bool) if repeated is None else repeated[genes] == 0
+    if (fam[kept] < 0).any():
+        raise ValueError("these orders are not this master's: a kept gene's family is not in the master")
+    glen = gene_end.astype(np.int64)[kept] - gene_start.astype(np.int64)[kept]
+    la, lb, lorg, llen = links_of_orders(fam, kept, gene_start, gene_end, contig_ptr, contig_org, contig_size)
+    for v in (glen, llen):
+        if len(v) and (v.min() < INT32[0] or v.max() > INT32[1]):
+            raise ValueError("a link's or a gene's length is outside int32")
+    src, dst, entry = master_edges(ptr, idx)
+    ne = len(entry)
+    ekey = src.astype(np.int64) * n + dst
+    by = np.argsort(ekey, kind="stable")
+    lkey = np.minimum(la, lb) * n + np.maximum(la, lb)
+    at = np.searchsorted(ekey[by], lkey)
+    if len(lkey) and (ne == 0 or (ekey[by][np.minimum(at, ne - 1)] != lkey).any()):
+        raise ValueError("these orders are not this master's: two adjacent kept genes' families are not an edge of the master")
+    eid = by[at] if len(lkey) else np.zeros(0, np.int64)
+    # the triples against the master's
+    pair, copies = np.unique(eid * d + lorg, return_counts=True)
+    bits = _edge_bits_bool(edge_bits, nnz, d)[entry] if ne else np.zeros((0, d), bool)
+    want = np.flatnonzero(bits.ravel())
+    if not np.array_equal(pair, want):
+        raise ValueError("these orders are not this master's: their (edge, organism) pairs are not its edge bits")
+    if not bits_only:
+        count = np.ones(len(want), np.int64)
+        if edge_counts is not None and len(edge_counts[1]):
+            xptr, xorg, xcnt = (np.asarray(a, np.int64) for a in edge_counts)
+            xe = np.repeat(np.arange(nnz, dtype=np.int64), np.diff(xptr))
+            to_edge = np.full(nnz, -1, np.int64)
+            to_edge[entry] = np.arange(ne)
+            mine = to_edge[xe] >= 0
+            xkey = to_edge[xe[mine]] * d + xorg[mine]
+            where = np.searchsorted(want, xkey)
+            if (where >= len(want)).any() or (want[np.minimum(where, len(want) - 1)] != xkey).any():
+                raise ValueError("these orders are not this master's: an extra without its edge bit")
+            count[where] = xcnt[mine]
+        if not np.array_equal(copies, count):
+            raise ValueError("these orders are not this master's: an (edge, organism) pair's number of links is not the master's count")
+    le = _segments(eid, llen, ne)
+    lf = _segments(fam[kept], glen, n)
+    first = np.where(bits.any(axis=0), bits.argmax(axis=0), ne).astype(np.int32) if ne else np.zeros(d, np.int32)
+    return dict(src=src, dst=dst, weight=bits.sum(axis=1).astype(np.int32), len_min=le["min"], len_max=le["max"], len_distinct=le["distinct"],
+                len_sum=le["sum"], len_mid_lo=le["lo"], len_mid_hi=le["hi"], fam_mid_lo=lf["lo"], fam_mid_hi=lf["hi"], org_first_edge=first)
+
+
+def attvalues_host(graph, edge_bits, edge_counts, attr_id, d, row0=0, rows=None):
+    """What nemgpu_edge_table_attvalues writes, in numpy: for edges row0 .. row0 + rows - 1 (master_edges' numbering), per
+    organism on the edge in increasing column order, the line `          <attvalue for="ID" value="COUNT" />\\n` with ID
+    = attr_id[organism] and COUNT the pair's count (1, or the master's extra count).
+    Returns (text uint8 [bytes], edge_end int64 [rows]: every edge's end offset)."""
+    ptr, idx = graph
+    _, _, entry = master_edges(ptr, idx)
+    rows = len(entry) - row0 if rows is None else rows
+    if row0 < 0 or rows <= 0 or row0 + rows > len(entry):
+        raise ValueError("attvalues_host: rows outside the table")
+    attr_id = np.asarray(attr_id, np.int64)
+    if attr_id.shape != (d,) or (attr_id < 0).any():
+        raise ValueError("attvalues_host: attr_id [d] >= 0")
+    entry = entry[row0:row0 + rows]
+    bits = _edge_bits_bool(edge_bits, len(idx), d)[entry]
+    count = bits.astype(np.int64)
+    if edge_counts is not None and len(edge_counts[1]):
+        xptr, xorg, xcnt = (np.asarray(a, np.int64) for a in edge_counts)
+        for r, t in enumerate(entry):
+            a, b = xptr[t], xptr[t + 1]
+            count[r, xorg[a:b]] = xcnt[a:b]
+    parts, ends, size = [], np.zeros(rows, np.int64), 0
+    for r in range(rows):
+        line = "".join('          <attvalue for="%d" value="%d" />\n' % (attr_id[o], count[r, o]) for o in np.flatnonzero(bits[r])).encode()
+        parts.append(line)
+        size += len(line)
+        ends[r] = size
+    return np.frombuffer(b"".join(parts), np.uint8).copy(), ends
+
+
+def _bind_edges(lib):
+    lib.nemgpu_edge_table_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.nemgpu_edge_table_shape.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
+    lib.nemgpu_edge_table_fetch.argtypes = [C.c_void_p] * 13
+    lib.nemgpu_edge_table_attvalues_size.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    lib.nemgpu_edge_table_attvalues.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                                C.c_void_p]
+    lib.nemgpu_edge_table_destroy.argtypes = [C.c_void_p]
+    lib.nemgpu_edge_table_destroy.restype = None
+    return lib
+
+
+class _Edges:
+    """what both edge tables share: EdgeTable on the device, HostEdgeTable in numpy"""
+
+    def arrays(self):
+        return {name: getattr(self, name) for name in EDGE_FIELDS}
+
+    def attribute_ids(self, first_id, organisms=True):
+        """the ids networkx gives the edge attributes when its counter stands at first_id: it numbers a title where it
+        first meets it, walking the edges in order and, inside an edge, its organisms (in column order), then the four
+        length_*.  Returns (attr_id int32 [d], 0 for an organism on no edge; the titles in id order as (id, what), what an
+        organism's column or one of the length titles)."""
+        attr_id, titles, k = np.zeros(self.d, np.int32), [], first_id
+        lengths = ("length_avg", "length_med", "length_min", "length_max")
+        if self.n_edges == 0:
+            return attr_id, titles
+        first = self.org_first_edge.astype(np.int64)
+        met = [int(o) for o in np.lexsort((np.arange(self.d), first)) if first[o] < self.n_edges] if organisms else []
+        placed = False
+        for o in met:
+            if first[o] > 0 and not placed:
+                titles += [(k + j, name) for j, name in enumerate(lengths)]
+                k, placed = k + 4, True
+            attr_id[o] = k
+            titles.append((k, o))
+            k += 1
+        if not placed:
+            titles += [(k + j, name) for j, name in enumerate(lengths)]
+        return attr_id, titles
+
+    def _batches(self, budget):
+        """(row0, rows) covering the edges, each batch's text within the budget by the widest line (one edge where an edge
+        alone is above it)"""
+        bound = np.cumsum(self.weight.astype(np.int64) * LINE_MAX)
+        row0 = 0
+        while row0 < self.n_edges:
+            base = bound[row0 - 1] if row0 else 0
+            rows = max(1, int(np.searchsorted(bound, base + budget, side="right")) - row0)
+            yield row0, rows
+            row0 += rows
+
+
+class EdgeTable(_Edges):
+    """The edge table of a master on the device (nemgpu_edge_table_create) with its arrays read back: src, dst, weight,
+    len_min, len_max, len_distinct, len_mid_lo, len_mid_hi int32 [E], len_sum int64 [E], fam_mid_lo, fam_mid_hi int32 [n],
+    org_first_edge int32 [d].  The master must stay open as long as the table writes."""
+
+    def __init__(self, master, genes, gene_start, gene_end, contig_ptr, contig_org, contig_size, repeated=None, f=None):
+        self.master, self.lib = master, _bind_edges(master.lib)
+        if f is None:
+            f = len(repeated) if repeated is not None else max(master.f, int(np.max(genes)) + 1 if len(genes) else 1)
+        genes, contig_ptr, contig_org, repeated = check_projection_orders(genes, contig_ptr, contig_org, repeated, master.d, int(f))
+        gene_start, gene_end = np.ascontiguousarray(gene_start, np.int32), np.ascontiguousarray(gene_end, np.int32)
+        contig_size = np.ascontiguousarray(contig_size, np.int32)
+        if gene_start.shape != genes.shape or gene_end.shape != genes.shape or contig_size.shape != contig_org.shape or not len(genes):
+            raise ValueError("edge table: genes [G], gene_start [G], gene_end [G], G > 0, contig_size [C]")
+        self._h = C.c_void_p()
+        rc = self.lib.nemgpu_edge_table_create(C.byref(self._h), master._h, int(f), genes.ctypes.data, gene_start.ctypes.data, gene_end.ctypes.data,
+                                               len(genes), contig_ptr.ctypes.data, contig_org.ctypes.data, contig_size.ctypes.data, len(contig_org),
+                                               repeated.ctypes.data if repeated is not None else None)
+        if rc != 0:
+            raise NemGpuError("nemgpu_edge_table_create failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+        v = [C.c_int() for _ in range(3)]
+        self.lib.nemgpu_edge_table_shape(self._h, *(C.byref(a) for a in v))
+        self.n, self.d, self.n_edges = (a.value for a in v)
+        n, d, ne = self.n, self.d, self.n_edges
+        for name, size in zip(EDGE_FIELDS, (ne,) * 9 + (n, n, d)):
+            setattr(self, name, np.zeros(size, np.int64 if name == "len_sum" else np.int32))
+        rc = self.lib.nemgpu_edge_table_fetch(self._h, *(getattr(self, name).ctypes.data if getattr(self, name).size else None for name in EDGE_FIELDS))
+        if rc != 0:
+            raise NemGpuError("nemgpu_edge_table_fetch failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+
+    def attvalues_size(self, attr_id, row0, rows):
+        attr_id = np.ascontiguousarray(attr_id, np.int32)
+        if attr_id.shape != (self.d,):
+            raise ValueError("attvalues: attr_id [d]")
+        size = C.c_int64()
+        rc = self.lib.nemgpu_edge_table_attvalues_size(self._h, self.master._h, attr_id.ctypes.data, int(row0), int(rows), C.byref(size))
+        if rc != 0:
+            raise NemGpuError("nemgpu_edge_table_attvalues_size failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+        return size.value
+
+    def attvalues(self, attr_id, row0=0, rows=None, out=None):
+        """The organism lines of edges row0 .. row0 + rows - 1, formatted on the device (nemgpu_edge_table_attvalues;
+        attvalues_host states them): (text uint8 [bytes], edge_end int64 [rows]).  out: a uint8 buffer to write into (too
+        small: NemGpuError that says the size needed, nothing written)."""
+        rows = self.n_edges - row0 if rows is None else rows
+        attr_id = np.ascontiguousarray(attr_id, np.int32)
+        if attr_id.shape != (self.d,):
+            raise ValueError("attvalues: attr_id [d]")
+        if out is None:
+            out = np.empty(max(self.attvalues_size(attr_id, row0, rows), 1), np.uint8)
+        ends, needed = np.zeros(max(rows, 1), np.int64), C.c_int64()
+        rc = self.lib.nemgpu_edge_table_attvalues(self._h, self.master._h, attr_id.ctypes.data, int(row0), int(rows), out.ctypes.data, out.size,
+                                                  C.byref(needed), ends.ctypes.data)
+        if rc != 0:
+            err = NemGpuError("nemgpu_edge_table_attvalues failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+            err.needed = needed.value
+            raise err
+        return out[:needed.value], ends[:rows]
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.nemgpu_edge_table_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HostEdgeTable(_Edges):
+    """The same table from the numpy statement (edge_table_arrays, attvalues_host): what the device is held against, and a
+    table for a caller who has the master's arrays on the host.  graph, edge_bits, edge_counts, order, d: the master's."""
+
+    def __init__(self, graph, edge_bits, edge_counts, order, genes, gene_start, gene_end, contig_ptr, contig_org, contig_size, repeated=None,
+                 f=None, d=None, bits_only=False):
+        self._master = (graph, edge_bits, edge_counts)
+        for name, a in edge_table_arrays(graph, edge_bits, edge_counts, order, genes, gene_start, gene_end, contig_ptr, contig_org, contig_size,
+                                         repeated, f, d, bits_only).items():
+            setattr(self, name, a)
+        self.n, self.d, self.n_edges = len(graph[0]) - 1, d, len(self.src)
+
+    def attvalues(self, attr_id, row0=0, rows=None):
+        return attvalues_host(*self._master, attr_id, self.d, row0, rows)
+
+    def attvalues_size(self, attr_id, row0, rows):
+        return len(self.attvalues(attr_id, row0, rows)[0])
+
+    def close(self):
+        pass
+
+
+def escape(text):
+    """XML attribute escaping as ElementTree does it (_escape_attrib)"""
+    for a, b in (("&", "&amp;"), ("<", "&lt;"), (">", "&gt;"), ('"', "&quot;"), ("\r", "&#13;"), ("\n", "&#10;"), ("\t", "&#09;")):
+        if a in text:
+            text = text.replace(a, b)
+    return text
+
+
+def _median(lo, hi, count):
+    """utils.median of the reference from the two middle elements: the element itself (an int) when the count is odd, their
+    true division when it is even; export_to_GEXF wraps it in float()"""
+    return float(int(lo)) if count % 2 else float((int(lo) + int(hi)) / 2)
+
+
+def _lengths(total, count, lo, hi, low, high):
+    """the four values (as text) of length_avg, length_med, length_min, length_max"""
+    return (str(float(int(total)) / max(int(count), 1)), str(_median(lo, hi, int(count))), str(int(low)), str(int(high)))
+
+
+def write_gexf(path, partitions, family_table, edge_table, annotations, all_node_attributes=True, all_edge_attributes=True, compressed=False,
+               budget=TEXT_BUDGET):
+    """<path>.gexf (compressed: <path>.gexf.gz through gzip) as PPanGGOLiN.export_to_GEXF and networkx's write_gexf write
+    it for a partitioned nx.Graph (ppanggolin.py:1294-1362), streamed: no networkx, no tree.  partitions: what
+    Master.partition returned, or uint8 [n]; family_table, edge_table: Master.family_table / Master.edge_table (or their
+    host forms) of the same master and annotations; annotations: the ones the tables were made from, walked in column
+    order (the genes' ids, names and products are read from them).  all_node_attributes / all_edge_attributes False: the
+    `_light` export, without the organism keys; it formats no text on the device.  An edge's organism lines are the
+    device's bytes, a slice per edge."""
+    ft, et = family_table, edge_table
+    names, orgs = ft.names, ft.organism_names
+    if names is None or orgs is None:
+        raise ValueError("write_gexf: a master that carries names (from_annotations, from_graph, add_annotations)")
+    if ft.n != et.n or ft.d != et.d:
+        raise ValueError("write_gexf: the two tables are not of one master")
+    n, d = ft.n, ft.d
+    longs = _long_names(partitions, names, n)
+    index = {name: i for i, name in enumerate(names)}
+    gene_names, products, cells = [dict() for _ in names], [dict() for _ in names], [dict() for _ in names]   # (insertion-ordered sets)
+    by_org = ft.repeated_names if isinstance(ft.repeated_names, dict) else None
+    for org, contigs in annotations.items():
+        skipped = by_org[org] if by_org is not None else ft.repeated_names
+        for annot in contigs.values():
+            for gene, info in annot.items():
+                if info[FAMILY] in skipped:
+                    continue
+                i = index[info[FAMILY]]
+                gene_names[i][info[NAME]] = None
+                products[i][info[PRODUCT]] = None
+                cells[i].setdefault(org, dict())[gene] = None
+    # the attribute ids: one counter over the nodes, then the edges, a title numbered where it is first met
+    node_ids, node_titles = {}, []
+
+    def node_id(title, kind):
+        if title not in node_ids:
+            node_ids[title] = len(node_ids)
+            node_titles.append((title, kind))
+        return node_ids[title]
+
+    tail = (("partition", "string"), ("partition_exact", "string"), ("length_avg", "double"), ("length_med", "double"), ("length_min", "long"),
+            ("length_max", "long"))
+    node_keys = []                                            # per family: the organisms before and after name and product
+    for i in range(n):
+        present = list(cells[i]) if all_node_attributes else []
+        node_id("nb_genes", "long")
+        for org in present[:1]:
+            node_id(org, "string")
+        node_id("name", "string")
+        node_id("product", "string")
+        for org in present[1:]:
+            node_id(org, "string")
+        for title, kind in tail:
+            node_id(title, kind)
+        node_keys.append(present)
+    attr_id, edge_titles = et.attribute_ids(len(node_ids), organisms=all_edge_attributes)
+    out = gzip.open(path + ".gexf.gz", "wb") if compressed else open(path + ".gexf", "wb")
+    with out:
+        w = out.write
+        w((HEAD % time.strftime("%Y-%m-%d")).encode())
+        if edge_titles:
+            w(b'    <attributes mode="static" class="edge">\n')
+            for k, what in edge_titles:
+                title, kind = (what, "double" if what in ("length_avg", "length_med") else "long") if isinstance(what, str) else (orgs[what], "long")
+                w(('      <attribute id="%d" title="%s" type="%s" />\n' % (k, escape(title), kind)).encode())
+            w(b"    </attributes>\n")
+        if node_titles:
+            w(b'    <attributes mode="static" class="node">\n')
+            for k, (title, kind) in enumerate(node_titles):
+                w(('      <attribute id="%d" title="%s" type="%s" />\n' % (k, escape(title), kind)).encode())
+            w(b"    </attributes>\n")
+        w(b"    <nodes>\n" if n else b"    <nodes />\n")
+        att = '          <attvalue for="%d" value="%s" />\n'
+        for i in range(n):
+            nb_org = int(ft.nb_org[i])
+            exact = "core_exact" if nb_org == d else "accessory"
+            color = COLORS_RGB[longs[i] if longs[i] != "undefined" else exact]
+            name = escape(names[i])
+            lines = ['      <node id="%s" label="%s">\n' % (name, name),
+                     '        <viz:color r="%d" g="%d" b="%d" a="0" />\n' % color,
+                     '        <viz:size value="%d" />\n' % nb_org,
+                     "        <attvalues>\n",
+                     att % (node_ids["nb_genes"], int(ft.nb_genes[i]))]
+            present = node_keys[i]
+            for org in present[:1]:
+                lines.append(att % (node_ids[org], escape("|".join(cells[i][org]))))
+            lines.append(att % (node_ids["name"], escape("|".join(gene_names[i]))))
+            lines.append(att % (node_ids["product"], escape("|".join(products[i]))))
+            for org in present[1:]:
+                lines.append(att % (node_ids[org], escape("|".join(cells[i][org]))))
+            values = (longs[i], exact) + _lengths(ft.len_sum[i], ft.len_distinct[i], et.fam_mid_lo[i], et.fam_mid_hi[i], ft.len_min[i], ft.len_max[i])
+            for (title, _), value in zip(tail, values):
+                lines.append(att % (node_ids[title], value))
+            lines.append("        </attvalues>\n      </node>\n")
+            w("".join(lines).encode())
+        if n:
+            w(b"    </nodes>\n")
+        ne = et.n_edges
+        w(b"    <edges>\n" if ne else b"    <edges />\n")
+        length_ids = [k for k, what in edge_titles if isinstance(what, str)]
+        escaped = [escape(name) for name in names]
+
+        def edge(e, organisms):
+            weight = str(float(int(et.weight[e])))
+            w(('      <edge source="%s" target="%s" id="%d" weight="%s">\n        <viz:thickness value="%s" />\n        <attvalues>\n'
+               % (escaped[et.src[e]], escaped[et.dst[e]], e, weight, weight)).encode())
+            if organisms is not None:
+                w(organisms)
+            values = _lengths(et.len_sum[e], et.len_distinct[e], et.len_mid_lo[e], et.len_mid_hi[e], et.len_min[e], et.len_max[e])
+            w(("".join(att % (k, value) for k, value in zip(length_ids, values)) + "        </attvalues>\n      </edge>\n").encode())
+
+        if all_edge_attributes:
+            for row0, rows in et._batches(budget):
+                text, ends = et.attvalues(attr_id, row0, rows)
+                view, start = memoryview(text), 0
+                for r in range(rows):
+                    edge(row0 + r, view[start:int(ends[r])])
+                    start = int(ends[r])
+        else:
+            for e in range(ne):
+                edge(e, None)
+        if ne:
+            w(b"    </edges>\n")
+        w(b"  </graph>\n</gexf>\n")
+
+
+def ushape_counts(partitions, family_table):
+    """The three series of ushaped_plot (ppanggolin.py:1494-1507): int64 [d][3], row k - 1 the families present in exactly
+    k organisms that are persistent / shell / cloud.  On the host, from the table's nb_org."""
+    ft = family_table
+    if isinstance(partitions, dict):
+        if ft.names is None:
+            raise ValueError("ushape_counts: this master carries no names (give the classes as uint8 [n])")
+        part = part_codes(partitions, ft.names)
+    else:
+        part = np.ascontiguousarray(partitions, np.uint8)
+    if part.shape != (ft.n,):
+        raise ValueError("ushape_counts: a class per family")
+    out = np.zeros((ft.d, 3), np.int64)
+    nb = np.asarray(ft.nb_org, np.int64)
+    use = (part < 3) & (nb >= 1) & (nb <= ft.d)
+    np.add.at(out, (nb[use] - 1, part[use].astype(np.int64)), 1)
+    return out

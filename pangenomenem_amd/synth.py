@@ -235,6 +235,37 @@ def master_pangenome_counts(n, d, seed, multi_frac=0.02, max_count=4, loops=0.01
     return x, (new_ptr, e_dst.astype(np.int32)), edge_bits, edge_counts
 
 
+def annotated_pangenome(n, d, seed, contigs_per_org=3, p_dup=0.03, p_circular=0.4):
+    """PPanGGOLiN's ``annotations`` ({organism: {contig: OrderedDict(gene -> [TYPE, FAMILY, START, END, STRAND, NAME,
+    PRODUCT])}}, ppanggolin.py:25) of the pangenome ushaped_pa_matrix(n, d, seed): every organism carries its families in
+    family order with local rearrangements and a few tandem duplicates, cut into contigs, some circular; a gene is 300 to
+    1 500 bases, the gap to the next -40 to 260 (some overlap).  What the graph build, the matrix and the GEXF export
+    read.  Returns annotations, the organisms in column order, {circular contig: size}."""
+    from collections import OrderedDict
+    x, _ = ushaped_pa_matrix(n, d, seed)
+    rng = np.random.Generator(np.random.PCG64(seed + 1))
+    ann, circular = OrderedDict(), {}
+    k = 0
+    for o in range(d):
+        org = "org%d" % o
+        have = np.flatnonzero(x[:, o])
+        have = have[np.argsort(have + rng.normal(0, 2.0, len(have)))]
+        seq = np.repeat(have, 1 + (rng.random(len(have)) < p_dup))
+        cuts = np.sort(rng.integers(0, len(seq) + 1, contigs_per_org - 1))
+        ann[org] = OrderedDict()
+        for j, (lo, hi) in enumerate(zip(np.concatenate([[0], cuts]), np.concatenate([cuts, [len(seq)]]))):
+            contig, genes, at = "%s_c%d" % (org, j), OrderedDict(), 0
+            gaps, sizes = rng.integers(-2, 14, hi - lo) * 20, rng.integers(1, 6, hi - lo) * 300
+            for fam, gap, size in zip(seq[lo:hi].tolist(), gaps.tolist(), sizes.tolist()):
+                k += 1
+                genes["g%d" % k] = ["CDS", "fam%d" % fam, at + gap, at + gap + size, "+-"[k % 2], "name%d" % fam, "product %d" % (fam % 997)]
+                at += gap + size
+            ann[org][contig] = genes
+            if rng.random() < p_circular:
+                circular[contig] = at + 500
+    return ann, list(ann), circular
+
+
 def default_init(d, low_disp=0.1):
     """PPanGGOLiN's default .m (ppanggolin.py:893-901): pi 0.33333/0.33333/rest, mu 1/0.5/0,
     eps low/0.5/low.  pi_K is computed as ReadParamFile does (float 1 - p0 - p1, nem_exe.c:1022-1034)."""

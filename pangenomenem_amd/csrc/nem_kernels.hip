@@ -30,8 +30,13 @@ namespace nemk {
 #ifdef NEM_PHASE_PROF
 __device__ unsigned long long g_phase[32];
 #define NEM_PHASE(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_phase[i] = wall_clock64(); } while (0)
+// (a stamp taken ahead of a test that may end the block, stored once the block is past it)
+#define NEM_PHASE_TAKE(t) const unsigned long long t = wall_clock64()
+#define NEM_PHASE_PUT(i, t) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_phase[i] = t; } while (0)
 #else
 #define NEM_PHASE(i) do { } while (0)
+#define NEM_PHASE_TAKE(t) do { } while (0)
+#define NEM_PHASE_PUT(i, t) do { } while (0)
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -246,13 +251,33 @@ __device__ __forceinline__ uint32_t mismatch_word(uint32_t x, const uint2 am)
     return m;
 }
 
-__device__ __forceinline__ float chain_plain(const uint4* __restrict__ xw4, int npad, int i, int D,
+// The head of a lane's matrix column: groups 0 .. 3 (clamped to the last group) of lane i, asked for by whoever knows
+// i first -- the fused density asks at block entry, beside its other first loads, and the chains take the registers
+// over.  pn / gi: the running pointer and the group it points at (see chain_ff).
+struct XwHead { uint4 x0, x1, x2, x3; const uint4* pn; int gi; };
+__device__ __forceinline__ uint4 xw_next(const uint4*& pn, int& gi, int gfull, int npad)
+{
+    const uint4 v = *pn;
+    if (gi < gfull) { pn += npad; gi++; }
+    return v;
+}
+__device__ __forceinline__ XwHead xw_head(const uint4* __restrict__ xw4, int npad, int i, int D)
+{
+    const int gfull = ((D - 1) >> 5) >> 2;
+    const uint4* pn = xw4 + i;
+    int gi = 0;
+    const uint4 x0 = xw_next(pn, gi, gfull, npad), x1 = xw_next(pn, gi, gfull, npad);
+    const uint4 x2 = xw_next(pn, gi, gfull, npad), x3 = xw_next(pn, gi, gfull, npad);
+    return XwHead{x0, x1, x2, x3, pn, gi};
+}
+
+__device__ __forceinline__ float chain_plain(const uint4* __restrict__ xw4, const XwHead& h, int npad, int i, int D,
                                     const uint2* am, double l1h, double l0)
 {
     float dk = 0.0f;
     const int wlast = (D - 1) >> 5;                      // padding organisms must not take a step here
     const int glast = wlast >> 2;
-    uint4 xn = xw4[i];
+    uint4 xn = h.x0;
     for (int g = 0; g <= glast; g++) {
         const uint4 xv = xn;
         if (g < glast) xn = xw4[(size_t)(g + 1) * npad + i];
@@ -387,7 +412,7 @@ __device__ __forceinline__ void ff_group(const uint4& xv, int g, const uint2* am
     }
 }
 
-__device__ __forceinline__ float chain_ff(const uint4* __restrict__ xw4, int npad, int i, int D,
+__device__ __forceinline__ float chain_ff(const XwHead& h, int npad, int D,
                                           const uint2* am, const uint32_t* sQ0,
                                           const uint32_t* sQ1, double l1h, double l0)
 {
@@ -400,14 +425,11 @@ __device__ __forceinline__ float chain_ff(const uint4* __restrict__ xw4, int npa
     // Every load is issued unconditionally (past the last group it simply repeats the last one) so that the
     // compiler can count outstanding loads exactly and wait for the oldest one only.  The groups are read in
     // order through ONE running pointer (a 64-bit add per load; indexing would cost three quarter-rate multiplies).
-    const uint4* pn = xw4 + i;
-    int gi = 0;                                          // group *pn points at (wave-uniform)
-    auto next = [&]() {
-        const uint4 v = *pn;
-        if (gi < gfull) { pn += npad; gi++; }
-        return v;
-    };
-    uint4 x0 = next(), x1 = next(), x2 = next(), x3 = next();
+    // The first four were asked for by the caller (xw_head).
+    const uint4* pn = h.pn;
+    int gi = h.gi;                                       // group *pn points at (wave-uniform)
+    auto next = [&]() { return xw_next(pn, gi, gfull, npad); };
+    uint4 x0 = h.x0, x1 = h.x1, x2 = h.x2, x3 = h.x3;
     int g = 0;
     for (; g + 4 <= gfull; g += 4) {
         ff_group(x0, g, am, bits, q0, q1, end, sQ0, sQ1, l1h, l0);
@@ -449,8 +471,9 @@ __device__ __forceinline__ void ff_build(uint32_t* sQ0, uint32_t* sDQ, double l1
 }
 
 // Epilogue of both density kernels: lane tid of the tile ran family perm[tile*256 + tid], which lies in the same
-// tile; the block hands its 256 results back in family order through LDS and stores them contiguously.
-__device__ __forceinline__ void density_store(const int* __restrict__ perm, int tile, int tid, int n, int npad, int k,
+// tile; the block hands its 256 results back in family order through LDS and stores them contiguously.  A caller that
+// read perm[tile*256 + tid] itself (the fused density, at block entry) passes perm = nullptr and slot = that - tile*256.
+__device__ __forceinline__ void density_store(const int* __restrict__ perm, int slot, int tile, int tid, int n, int npad, int k,
                                               float dk, uint32_t nul, double pk, float logpk,
                                               double* __restrict__ pkfki, float* __restrict__ logpkfki)
 {
@@ -459,7 +482,7 @@ __device__ __forceinline__ void density_store(const int* __restrict__ perm, int 
     float logfk; double fk;
     if (!nul) { logfk = -dk; fk = exp((double)logfk); }          // nem_mod.c:679-680
     else { logfk = -FLT_MAX; fk = 0.0; }                         // nem_mod.c:685-686
-    const int slot = perm[tile * 256 + tid] - tile * 256;
+    if (perm != nullptr) slot = perm[tile * 256 + tid] - tile * 256;
     sPk[slot] = pk * fk;                                         // nem_alg.c:2282
     sLp[slot] = logpk + logfk;                                   // nem_alg.c:2283
     __syncthreads();
@@ -515,10 +538,10 @@ __device__ __forceinline__ void density_body(const DensityArgs& a)
             const uint2 q = a.ffq[k * 256 + tid];          // (k_finish built the class's increment table)
             sQ0[tid] = q.x; sQ1[tid] = q.y;
             __syncthreads();
-            dk = chain_ff(a.xw, npad, i, a.D, sAm, sQ0, sQ1, l1h, l0);
+            dk = chain_ff(xw_head(a.xw, npad, i, a.D), npad, a.D, sAm, sQ0, sQ1, l1h, l0);
         } else {
             __syncthreads();
-            dk = chain_plain(a.xw, npad, i, a.D, sAm, l1h, l0);
+            dk = chain_plain(a.xw, XwHead{a.xw[i]}, npad, i, a.D, sAm, l1h, l0);     // (it takes group 0 from the head)
         }
     } else {
         // ---- general case (skd, s_d, hand-written .m files): per-(k,d) constants staged through LDS
@@ -553,7 +576,7 @@ __device__ __forceinline__ void density_body(const DensityArgs& a)
             }
         }
     }
-    density_store(a.perm, tile, tid, a.n, npad, k, dk, nul, a.pk[k], a.logpk[k], a.pkfki, a.logpkfki);
+    density_store(a.perm, 0, tile, tid, a.n, npad, k, dk, nul, a.pk[k], a.logpk[k], a.pkfki, a.logpkfki);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -605,16 +628,57 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
     __shared__ uint2 sAm[FD_MAXD / 32];                   // {am0, am1} per word
     __shared__ uint32_t sNz0[FD_CH / 32], sNz1[FD_CH / 32];
     __shared__ uint32_t sQ0[256], sQ1[256];
-    __shared__ unsigned long long sTot2;
-    __shared__ float sEps, sChain[2];
-    __shared__ int sGeneral;
-    if constexpr (!START) { if (a.stop != nullptr && *a.stop) return -1; }
+    __shared__ unsigned long long sTot2w[4];             // per wave: twice the class's inertia over the wave's organisms
+    __shared__ float sChain[2];
+    __shared__ int sGenW[4];                             // per wave: a centre outside {0, 1/2, 1}
     int k, tile;
     if (!density_tile(a.K, a.npad >> 8, tile, k)) return -1;
     const int tid = threadIdx.x, lane = tid & 63;
     const int i = tile * 256 + tid;                      // i < npad by construction
     const int npad = a.npad, dpad = a.dpad, D = a.D, K = a.K;
     const bool writer = (tile == 0);                     // this block publishes class k's parameters
+    NEM_PHASE_TAKE(t_entry);
+    // ---- Everything the block reads first whose address depends on nothing but the block's index, asked for together:
+    // a launch starts with cold caches, and asked for where they are used -- the stop word, then the class size, then
+    // the counts, then (behind the prologue's barriers) the matrix, then (behind the chain) the permutation -- these were
+    // five memory latencies in a row.  The counts are read whether or not the class is empty (an empty class drops them).
+    // The vector loads go first and the two scalar ones last: a wave waits for ALL of its scalar loads at once, so a
+    // kernel argument fetched behind the stop word would be waited for with it, and the vector loads behind that.
+    // (START has no stop word, class size or counts to wait for, and 22 more live registers through its prologue would
+    //  take it from 7 waves per SIMD to 5: it asks for the matrix where the chain begins, as it did)
+    XwHead xh{};
+    if constexpr (!START) xh = xw_head(a.xw, npad, i, D);
+    const int slot = a.perm[tile * 256 + tid] - tile * 256;   // (density_store)
+    constexpr int kRows = FD_MAXD / 256;                 // organisms per thread: d = tid + 256 q
+    int s1w[kRows];
+#pragma unroll
+    for (int q = 0; q < kRows; q++) {
+        s1w[q] = 0;
+        if constexpr (!START) {
+            const int d = tid + 256 * q;
+            if (d < D) s1w[q] = stat_sum(a.stats, K + k * D + d, a.stats_ranks, a.stats_rank_stride);
+        }
+    }
+    // (no branch around the stop word's load: the value would be copied where the two paths meet, and waited for there)
+    int stopw = 0, nkI = 0;
+    if constexpr (!START) {
+        stopw = *(a.stop != nullptr ? a.stop : a.stats);
+        if (a.stop == nullptr) stopw = 0;
+        nkI = stat_sum(a.stats, k, a.stats_ranks, a.stats_rank_stride);
+    }
+    // (a compiler-only fence, no instruction: without it the loads above are sunk below the stop test, to their uses)
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    if (stopw) return -1;
+    NEM_PHASE_PUT(16, t_entry);
+    NEM_PHASE(17);
+    // ---- proportion (nem_mod.c:456-465) and the class constants of ComputePkFkiM (nem_alg.c:2262-2271): they need the
+    // class size only, and run while the counts travel
+    const float nkf = (float)nkI;
+    const bool nonempty = (double)nkf > kEpsilonD;       // (START: false -- the general chain reads the given centres)
+    const float propk = START ? st->prop0[k] : (a.propor == NEMGPU_PROP_K) ? nkf / (float)a.n_total : (float)(1.0 / K);
+    if (writer && tid == 0) { a.prop[k] = propk; a.nbobs_k[k] = nkf; }
+    const double pkd = (double)propk;
+    const float logpk = (pkd > kEpsilonD) ? (float)log(pkd) : -INFINITY;
     if (tile == 0 && k == 0) {
         for (int t = tid; t < a.n_zero_flags; t += 256) a.zero_flags[t] = 0;
         for (int t = tid; t < a.n_zero_stats; t += 256) a.zero_stats[t] = 0;
@@ -628,17 +692,13 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
             a.iter_flags[FLAG_EMPTYK] = ek;
         }
     }
-    if (tid == 0) { sTot2 = 0ull; sGeneral = 0; }
-    __syncthreads();
+    NEM_PHASE(18);
 
     // ---- centres + inertia of class k from the counts (k_finish's centers_ncem_entry, per block)
-    const int nkI = START ? 0 : stat_sum(a.stats, k, a.stats_ranks, a.stats_rank_stride);
-    const float nkf = (float)nkI;
-    const bool nonempty = (double)nkf > kEpsilonD;       // (START: false -- the general chain reads the given centres)
     long long acc2 = 0;
     int general = 0;
     int differ = 0;                                      // START: a dispersion that is not the class's first, or not above EPSILON
-    for (int d = tid; d < dpad; d += 256) {              // dpad % 64 == 0: whole waves reach the ballots
+    auto centre_of = [&](const int d, const int s1_d) {  // organism d (dpad % 64 == 0: whole waves reach the ballots)
         float mu = 0.0f, in = 0.0f;
         int a0 = 0, a1 = 0;
         if (d < D) {
@@ -649,7 +709,7 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
                 differ |= (__float_as_uint(in) != __float_as_uint(st->disp0[k * D])) || !((double)in > kEpsilonD);
             } else if (nonempty) {
                 const float half = nkf / 2;
-                const int s1 = stat_sum(a.stats, K + k * D + d, a.stats_ranks, a.stats_rank_stride);
+                const int s1 = s1_d;
                 const float s0f = (float)(nkI - s1);
                 if (s0f > half) { mu = 0.0f; in = (float)s1; }
                 else if (s0f == half) { mu = 0.5f; in = 0.5f * nkf; }
@@ -670,27 +730,39 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
             sAm[w] = make_uint2((uint32_t)b0, (uint32_t)b1);
             sAm[w + 1] = make_uint2((uint32_t)(b0 >> 32), (uint32_t)(b1 >> 32));
         }
+    };
+    if constexpr (START) {
+        for (int d = tid; d < dpad; d += 256) centre_of(d, 0);
+    } else {
+#pragma unroll
+        for (int q = 0; q < kRows; q++)
+            if (tid + 256 * q < dpad) centre_of(tid + 256 * q, s1w[q]);      // (wave-uniform)
     }
-    if constexpr (!START) {
-        acc2 = wave_reduce_add_ll(acc2);
-        if (lane == 0 && acc2 != 0) atomicAdd(&sTot2, (unsigned long long)acc2);
-    }
-    if (general) sGeneral = 1;
+    // the waves' partial sums go to a slot each and every thread adds the four up: no LDS atomic, no barrier ahead of
+    // the loop to initialise its target
+    if constexpr (!START) acc2 = wave_reduce_add_ll(acc2);
+    const int gen_w = __any(general);
+    if (lane == 0) { sTot2w[tid >> 6] = (unsigned long long)acc2; sGenW[tid >> 6] = gen_w; }
     bool eps_per_d = false;                              // epsilon differs between organisms -> general chain
     if constexpr (START) eps_per_d = __syncthreads_or(differ) != 0;      // (one ballot per wave, block-uniform)
     else __syncthreads();
+    const long long tot2 = (long long)(sTot2w[0] + sTot2w[1] + sTot2w[2] + sTot2w[3]);
+    const bool any_general = (sGenW[0] | sGenW[1] | sGenW[2] | sGenW[3]) != 0;
+    NEM_PHASE(19);
 
     // ---- dispersion (InerToDispK_ / InerToDispKD with MISSING_IGNORE, nem_mod.c:1043-1073, 1152-1170)
+    // (the class's one epsilon is computed by every thread: its inputs are block-uniform)
+    float eps_u = 0.0f;
     if constexpr (START) {
-        if (tid == 0) sEps = st->disp0[k * D];
+        eps_u = st->disp0[k * D];
     } else if (a.disper == NEMGPU_DISP_K_) {
         if (nkf > 0) {
             const long long cap = 1ll << 24;
-            if ((long long)sTot2 <= cap && nkI < (1 << 24)) {                              // (block-uniform)
+            if (tot2 <= cap && nkI < (1 << 24)) {                                          // (block-uniform)
                 // the d-ordered inertia chain never rounds here (multiples of 1/2 below 2^23); the N_KD chain -- the
                 // class size added D times -- is its closed form (nem_ff.hpp: exact while N_K * D <= 2^24, then one
                 // division per binade)
-                if (tid == 0) sEps = (0.5f * (float)(long long)sTot2) / ff_repeat_add_u24((uint32_t)nkI, D);
+                eps_u = (0.5f * (float)tot2) / ff_repeat_add_u24((uint32_t)nkI, D);
             } else {
                 // the two d-ordered chains of InerToDispK_ (nem_mod.c:1054-1058), each on a wave of its own: the
                 // inertia values sixteen at a time from LDS ahead of the dependent adds, the N_KD chain from a register
@@ -711,14 +783,11 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
                     }
                 }
                 __syncthreads();
-                if (tid == 0) sEps = sChain[0] / sChain[1];
+                eps_u = sChain[0] / sChain[1];
             }
-            __syncthreads();
-            const float e = sEps;
-            if (writer) for (int d = tid; d < D; d += 256) a.disp[k * D + d] = e;
+            if (writer) for (int d = tid; d < D; d += 256) a.disp[k * D + d] = eps_u;
         } else {
             // empty class keeps whatever dispersions it had (possibly different per organism)
-            __syncthreads();
             for (int d = tid; d < D; d += 256) {
                 sVal[d] = a.disp_in[k * D + d];
                 if (writer) a.disp[k * D + d] = sVal[d];
@@ -726,7 +795,6 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
             eps_per_d = true;
         }
     } else {                                             // NEMGPU_DISP_KD
-        __syncthreads();
         for (int d = tid; d < D; d += 256) {
             float e;
             if (nonempty) e = sVal[d] / nkf;
@@ -736,17 +804,13 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
         }
         eps_per_d = true;
     }
-    // ---- proportion (nem_mod.c:456-465) and the class constants of ComputePkFkiM (nem_alg.c:2262-2271)
-    const float propk = START ? st->prop0[k] : (a.propor == NEMGPU_PROP_K) ? nkf / (float)a.n_total : (float)(1.0 / K);
-    if (writer && tid == 0) { a.prop[k] = propk; a.nbobs_k[k] = nkf; }
-    const double pkd = (double)propk;
-    const float logpk = (pkd > kEpsilonD) ? (float)log(pkd) : -INFINITY;
-    __syncthreads();
+    // (no barrier here: the uniform chain reads sAm, which the barrier behind the centres published, and its tables
+    //  behind a barrier of their own; the general chain, which alone reads the per-organism sVal, starts with one)
+    NEM_PHASE(20);
 
     float dk = 0.0f;
     uint32_t nul = 0;
-    const float eps_u = sEps;
-    bool uniform = !eps_per_d && !sGeneral && ((double)eps_u > kEpsilonD);
+    bool uniform = !eps_per_d && !any_general && ((double)eps_u > kEpsilonD);
     double l1 = 0.0, l0 = 0.0;
     if (uniform) {
         l1 = log((double)((1.0f - eps_u) / eps_u));
@@ -758,16 +822,20 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
         if (a.use_ff && l1 >= 0.0 && l0 <= 0.0) {        // block-uniform
             ff_build(sQ0, sQ1, l1, l0, tid);
             __syncthreads();
-            dk = chain_ff(a.xw, npad, i, D, sAm, sQ0, sQ1, l1h, l0);
+            NEM_PHASE(21);
+            if constexpr (START) xh = xw_head(a.xw, npad, i, D);
+            dk = chain_ff(xh, npad, D, sAm, sQ0, sQ1, l1h, l0);
         } else {
-            dk = chain_plain(a.xw, npad, i, D, sAm, l1h, l0);
+            if constexpr (START) xh = xw_head(a.xw, npad, i, D);
+            dk = chain_plain(a.xw, xh, npad, i, D, sAm, l1h, l0);
         }
+        NEM_PHASE(22);
     } else {
         // general chain: per-organism constants built chunk by chunk in LDS (table_entry's arithmetic).
-        // With every centre in {0, 1/2, 1} (sGeneral == 0; the class masks sAm are those of the new centres) an
+        // With every centre in {0, 1/2, 1} (no wave saw another; the class masks sAm are those of the new centres) an
         // organism's step is the uniform chain's, dk <- fma({2 | 0}, l1_d / 2, dk) - l0_d, with ITS two constants:
         // one 16-byte LDS read and six instructions instead of two reads, two selects and the same arithmetic.
-        const bool by_mask = nonempty && !sGeneral;          // (START: false, k_density's general chain step for step)
+        const bool by_mask = nonempty && !any_general;          // (START: false, k_density's general chain step for step)
         const float* mu_in = START ? st->center0 : a.center_in;
         for (int d0 = 0; d0 < dpad; d0 += FD_CH) {
             const int dn = min(FD_CH, dpad - d0);
@@ -830,7 +898,8 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
             }
         }
     }
-    density_store(a.perm, tile, tid, a.n, npad, k, dk, nul, pkd, logpk, a.pkfki, a.logpkfki);
+    density_store(nullptr, slot, tile, tid, a.n, npad, k, dk, nul, pkd, logpk, a.pkfki, a.logpkfki);
+    NEM_PHASE(23);
     return tile;
 }
 

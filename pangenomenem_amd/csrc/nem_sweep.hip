@@ -88,6 +88,13 @@ void launch_sweep(const SweepArgs& a0, bool ncem, hipStream_t s)
 }
 
 
+#ifdef NEM_PHASE_PROF
+extern "C" int nemgpu_debug_sweep_phases(unsigned long long* out8)
+{
+    return (int)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_sweep_phase), sizeof(unsigned long long) * 8);
+}
+#endif
+
 void sweep_dispatch_batched(int variant, dim3 grid, unsigned bdim, hipStream_t s, const void* arr, int stride, const int* gx)
 {
     sweep_dispatch<true>(variant, grid, bdim, s, nullptr, arr, stride, gx);

@@ -12,6 +12,20 @@
 
 namespace nemk {
 
+// development probe (-DNEM_PHASE_PROF, see nem_kernels.hip): the first block's first thread stamps the 100 MHz wall clock
+// at the round's phase boundaries -- one copy per translation unit; nem_sweep.hip's is the one read back
+#ifdef NEM_PHASE_PROF
+static __device__ unsigned long long g_sweep_phase[8];
+#define NEM_SWEEP_PHASE(i) do { if (bx == 0 && threadIdx.x == 0) g_sweep_phase[i] = wall_clock64(); } while (0)
+// (the entry stamp is taken ahead of the stop test and stored by a block that is past it)
+#define NEM_SWEEP_PHASE_TAKE(t) const unsigned long long t = wall_clock64()
+#define NEM_SWEEP_PHASE_PUT(i, t) do { if (bx == 0 && threadIdx.x == 0) g_sweep_phase[i] = t; } while (0)
+#else
+#define NEM_SWEEP_PHASE(i) do { } while (0)
+#define NEM_SWEEP_PHASE_TAKE(t) do { } while (0)
+#define NEM_SWEEP_PHASE_PUT(i, t) do { } while (0)
+#endif
+
 __host__ __device__ inline uint32_t mix32(uint32_t seed, uint32_t sweep, uint32_t site)
 {
     // counter-based stand-in for the reference's time-seeded random() (nem_rnd.c:40-63);
@@ -309,14 +323,76 @@ template <int KT, bool NCEM, int BS, bool LIBC = false, bool COUNT = false>
 __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, const int nblk)
 {
     static_assert(!COUNT || (NCEM && BS == 256 && !LIBC && KT > 0), "the counting round: NCEM, 256 sites per block");
+    static_assert(C_STOP == 0 && C_FOLD == 1, "one 8-byte load");
+    NEM_SWEEP_PHASE_TAKE(t_entry);
+    const int spb = (BS > 256 && a.spb > 0) ? a.spb : BS;   // sites of this block (large shards: fewer than the launch bound)
+    const int i = bx * spb + threadIdx.x;
+    const bool active = (int)threadIdx.x < spb && i < a.n_local;
+    const int gi = a.lo + (active ? i : 0);
+    const int K = KT > 0 ? KT : a.K;
+    constexpr int KA = KT > 0 ? KT : kMaxKernelK;
+    // this site's own labels, requested with everything else at the head of the block: asked for where they are
+    // used -- behind the label store, which they might alias -- they would be one more memory latency at the tail
+    int my_guess = 0, my_old = 0, my_new = 255;           // my_guess: the whole byte; my_old: the class
+    // (TIE_LIBC: the block's draw count in the guess, compared at the round's end -- asked for here, not there: a load at
+    //  the tail is a memory latency added to the block's run time)
+    int blk_cnt_guess = 0;
+    // COUNT: the block's four words of organism rows d = threadIdx.x + 256 q, requested here for the same reason: they
+    // do not depend on the labels, and the tail only ANDs them with the class masks
+    constexpr int kCntRows = COUNT ? kFusedMaxD / BS : 1;
+    uint64_t xs[kCntRows][4];
+    double pkf[NCEM ? KA : 1];                           // NCEM: the site's densities
+    int nb = 0, ne = 0;                                  // NCEM: the site's row of the graph
     int fold_hint = 0;
-    if (a.stop != nullptr) {
-        static_assert(C_STOP == 0 && C_FOLD == 1, "one 8-byte load");
-        const int2 sf = *reinterpret_cast<const int2*>(a.stop);
+    bool skip;
+    if constexpr (NCEM) {
+        // A launch starts with cold caches, so everything whose address the block knows from its index alone is asked
+        // for HERE, together, ahead of the stop word's and the previous round's tests and of the head barrier: the
+        // labels, the counting round's rows, the densities and the row's bounds used to wait for the two tests one
+        // after the other, and the last two for the barrier as well.  Each load keeps the condition that makes its
+        // address valid; a block that then leaves at the stop word or skips its sites has read a few words for nothing.
+        if (LIBC && threadIdx.x == 0 && a.tie_cnt_guess != nullptr) blk_cnt_guess = a.tie_cnt_guess[bx];
+        if (COUNT) {
+            const int w0 = 4 * bx;
+#pragma unroll
+            for (int q = 0; q < kCntRows; q++) {
+                const int d = (int)threadIdx.x + q * BS;
+#pragma unroll
+                for (int w = 0; w < 4; w++)
+                    xs[q][w] = (d < a.post_D && w0 + w < a.post_nw64) ? a.post_xt[(size_t)d * a.post_nw64 + w0 + w] : 0ull;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < KA; k++) if (k < K) pkf[k] = active ? a.pkfki[(size_t)k * a.npad + i] : 0.0;
+        if (active && a.use_nei) { nb = a.nei_ptr[i]; ne = a.nei_ptr[i + 1]; }
+        // the two control words, without a branch around either load (where two paths meet the loaded value would be
+        // copied, and waited for): a null pointer reads a word of the densities instead, and the value is dropped
+        const int* some = reinterpret_cast<const int*>(a.pkfki);
+        int2 sf = *reinterpret_cast<const int2*>(a.stop != nullptr ? a.stop : some);
+        int pc = *(a.prev_changed != nullptr ? a.prev_changed : some);
+        // (the two bytes last: the compiler masks my_old where it is loaded, and waits for it there -- behind the other
+        //  requests that wait is for all of them at once)
+        if (active) { my_guess = a.lab_guess[gi]; my_old = a.lab_old[gi] & kLabMask; }
+        if (a.stop == nullptr) sf = make_int2(0, 0);
+        if (a.prev_changed == nullptr) pc = 1;
+        // (a compiler-only fence, no instruction: without it the loads above are sunk below the tests, to their uses)
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        // (... and the previous round's word, which the leaving path does not use, would be asked for behind the stop
+        //  test: the wave waits for all of its scalar loads at once, so needing it here adds no wait of its own)
+        asm volatile("" :: "s"(pc));
         if (sf.x) return;
         fold_hint = sf.y;
+        skip = (pc == 0);                                // the previous round was already the fixed point
+    } else {
+        if (a.stop != nullptr) {
+            const int2 sf = *reinterpret_cast<const int2*>(a.stop);
+            if (sf.x) return;
+            fold_hint = sf.y;
+        }
+        skip = (a.prev_changed != nullptr && *a.prev_changed == 0);   // the previous round was already the fixed point
     }
-    bool skip = (a.prev_changed != nullptr && *a.prev_changed == 0);   // the previous round was already the fixed point
+    NEM_SWEEP_PHASE_PUT(0, t_entry);
+    NEM_SWEEP_PHASE(1);
     if (a.flags_in != nullptr) {                         // sharded: did ANY rank change a label last round?
         int any = 0;
         for (int r = 0; r < a.n_ranks; r++) any |= a.flags_in[(size_t)r * a.slot_stride];
@@ -346,36 +422,8 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     __shared__ double s_exp[NCEM ? kExpTab : 1];
     __shared__ __attribute__((aligned(16))) uint8_t s_lab[NCEM ? BS : 1];   // the block's labels while it iterates
     __shared__ uint64_t s_drew[BS / 64];                 // TIE_LIBC: per wave, which of its sites drew
-    const int spb = (BS > 256 && a.spb > 0) ? a.spb : BS;   // sites of this block (large shards: fewer than the launch bound)
-    const int i = bx * spb + threadIdx.x;
-    const bool active = (int)threadIdx.x < spb && i < a.n_local;
-    const int gi = a.lo + (active ? i : 0);
-    const int K = KT > 0 ? KT : a.K;
-    constexpr int KA = KT > 0 ? KT : kMaxKernelK;
     bool zero_density = false;
     bool changed = false;
-    // this site's own labels, requested with everything else at the head of the block: asked for where they are
-    // used -- behind the label store, which they might alias -- they would be one more memory latency at the tail
-    int my_guess = 0, my_old = 0, my_new = 255;           // my_guess: the whole byte; my_old: the class
-    if (NCEM && active) { my_guess = a.lab_guess[gi]; my_old = a.lab_old[gi] & kLabMask; }
-    // (TIE_LIBC: the block's draw count in the guess, compared at the round's end -- asked for here, not there: a load at
-    //  the tail is a memory latency added to the block's run time)
-    int blk_cnt_guess = 0;
-    if (LIBC && threadIdx.x == 0 && a.tie_cnt_guess != nullptr) blk_cnt_guess = a.tie_cnt_guess[bx];
-    // COUNT: the block's four words of organism rows d = threadIdx.x + 256 q, requested here for the same reason: they
-    // do not depend on the labels, and the tail only ANDs them with the class masks
-    constexpr int kCntRows = COUNT ? kFusedMaxD / BS : 1;
-    uint64_t xs[kCntRows][4];
-    if (COUNT) {
-        const int w0 = 4 * bx;
-#pragma unroll
-        for (int q = 0; q < kCntRows; q++) {
-            const int d = (int)threadIdx.x + q * BS;
-#pragma unroll
-            for (int w = 0; w < 4; w++)
-                xs[q][w] = (d < a.post_D && w0 + w < a.post_nw64) ? a.post_xt[(size_t)d * a.post_nw64 + w0 + w] : 0ull;
-        }
-    }
     __shared__ int s_anydrew;                            // TIE_LIBC: a site of the block drew at some local step of this launch
     if (threadIdx.x == 0) { s_nzero = 0; s_first = 0; s_chg = 0; s_mov = 0; s_anydrew = 0; }
     if (NCEM) s_lab[threadIdx.x] = (uint8_t)my_guess;
@@ -399,6 +447,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     bool blk_drew = false;
     if (LIBC) blk_drew = __syncthreads_or((my_guess & kLabDrew) != 0) != 0;
     else __syncthreads();
+    NEM_SWEEP_PHASE(2);
 
     if (NCEM) {
     // ------------------------------------------------------------------------------------------
@@ -412,16 +461,12 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     // ------------------------------------------------------------------------------------------
     constexpr bool libc = LIBC;
     const int blk_lo = a.lo + bx * spb;          // first label slot of this block
-    double pkf[KA];
-#pragma unroll
-    for (int k = 0; k < KA; k++) if (k < K) pkf[k] = active && !skip ? a.pkfki[(size_t)k * a.npad + i] : 0.0;
+    // (pkf, nb, ne: asked for at the head of the block)
     // the first four neighbours live in registers: index, weight, and the label when it cannot change in here
-    int nb = 0, ne = 0;
     int dyn[4]; float wn[4]; int fl[4];
 #pragma unroll
     for (int u = 0; u < 4; u++) { dyn[u] = -1; wn[u] = 0.0f; fl[u] = 255; }
     if (active && !skip && a.use_nei) {
-        nb = a.nei_ptr[i]; ne = a.nei_ptr[i + 1];
         int jn[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
@@ -438,6 +483,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
         }
     }
     const bool long_row = ne - nb > 4;
+    NEM_SWEEP_PHASE(3);
     int lower_draws = -1;                                // (read from s_lower, written ahead of the barrier at the block's head)
     bool tab_short = false;                              // TIE_LIBC: a draw fell outside the table: the round is void
     int cur = my_guess;                                  // this site's byte in s_lab
@@ -595,6 +641,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
         }
     }
     }
+    NEM_SWEEP_PHASE(4);
     if (__any(changed) && (threadIdx.x & 63) == 0) s_chg = 1;
     // the iteration's bookkeeping, when it rides in this round (see SweepArgs): the site's label, "moved"
     int post_lab = 255;

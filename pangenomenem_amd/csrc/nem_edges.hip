@@ -5,10 +5,7 @@
 #include <string>
 #include <vector>
 
-#include "nem_internal.hpp"
-#include "nem_master.hpp"
-#include "nem_project.hpp"
-#include "nem_scan.hpp"
+#include "nem_table.hpp"
 
 namespace nemk {
 
@@ -136,9 +133,8 @@ __global__ __launch_bounds__(kThreads) void k_edges_pairs(const uint64_t* __rest
     const int p = blockIdx.x * kThreads + threadIdx.x;
     if (p >= g) return;
     const uint64_t k = keys[p];
-    const bool valid = k < none;
-    const bool h = valid && (p == 0 || keys[p - 1] != k);
-    const bool eh = valid && (p == 0 || (keys[p - 1] >> bd) != (k >> bd));
+    const bool h = is_head(keys, p, none);
+    const bool eh = k < none && (p == 0 || (keys[p - 1] >> bd) != (k >> bd));
     int copies = 0;
     if (h) {
         const int e = (int)(k >> bd), org = (int)(k & ((1ull << bd) - 1ull));
@@ -152,52 +148,36 @@ __global__ __launch_bounds__(kThreads) void k_edges_pairs(const uint64_t* __rest
     multi[p] = copies >= 2 ? 1 : 0;
 }
 
-// sstart[i] = the first sorted position of segment i (i = count: the keys that belong to one), the segment in the key's
-// bits from `shift` up
-__global__ __launch_bounds__(kThreads) void k_edges_sstart(const uint64_t* __restrict__ keys, int g, int shift, int count, int* __restrict__ sstart)
+// the two middle distinct lengths of the segment at sorted positions [a, b) of (segment, length) keys (didx: the scan of
+// their distinct flags): the m-th distinct length (from 0) starts at the first position whose inclusive count is
+// base + m + 1; no length: zeros
+__device__ inline void middles(const uint64_t* __restrict__ key_len, const int* __restrict__ didx, int a, int b, int* lo, int* hi)
 {
-    const int i = blockIdx.x * kThreads + threadIdx.x;
-    if (i <= count) sstart[i] = lower_bound(keys, 0, g, (uint64_t)(uint32_t)i << shift);
-}
-
-// per sorted (segment, length) key: 1 and the length where a distinct length starts
-__global__ __launch_bounds__(kThreads) void k_edges_lengths(const uint64_t* __restrict__ keys, int g, uint64_t none, int* __restrict__ dflag,
-                                                           long long* __restrict__ dval)
-{
-    const int p = blockIdx.x * kThreads + threadIdx.x;
-    if (p >= g) return;
-    const uint64_t k = keys[p];
-    const bool h = k < none && (p == 0 || keys[p - 1] != k);
-    dflag[p] = h ? 1 : 0;
-    dval[p] = h ? (long long)(int)((uint32_t)k ^ kLenBias) : 0ll;
-}
-
-// per segment (an edge, or a family) what its distinct lengths give, from the scans at its ends; any output but the
-// middles may be null; rid (may be null): the scan of the pairs' heads, for the weight
-__global__ __launch_bounds__(kThreads) void k_edges_rows(int count, const int* __restrict__ sstart, const int* __restrict__ rid,
-                                                        const int* __restrict__ didx, const long long* __restrict__ dsum,
-                                                        const uint64_t* __restrict__ key_len, int* __restrict__ weight, int* __restrict__ len_min,
-                                                        int* __restrict__ len_max, int* __restrict__ len_distinct, long long* __restrict__ len_sum,
-                                                        int* __restrict__ mid_lo, int* __restrict__ mid_hi)
-{
-    const int i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= count) return;
-    const int a = sstart[i], b = sstart[i + 1];
     const int base = before(didx, a), cnt = before(didx, b) - base;
-    if (weight) weight[i] = before(rid, b) - before(rid, a);
-    if (len_distinct) len_distinct[i] = cnt;
-    if (len_sum) len_sum[i] = before(dsum, b) - before(dsum, a);
-    if (len_min) len_min[i] = b > a ? (int)((uint32_t)key_len[a] ^ kLenBias) : 0;
-    if (len_max) len_max[i] = b > a ? (int)((uint32_t)key_len[b - 1] ^ kLenBias) : 0;
-    int lo = 0, hi = 0;
-    if (cnt > 0) {
-        // the m-th distinct length (from 0) starts at the first position whose inclusive count is base + m + 1
-        const int plo = lower_bound(didx, a, b, base + (cnt - 1) / 2 + 1);
-        const int phi = lower_bound(didx, plo, b, base + cnt / 2 + 1);
-        lo = (int)((uint32_t)key_len[plo] ^ kLenBias);
-        hi = (int)((uint32_t)key_len[phi] ^ kLenBias);
-    }
-    mid_lo[i] = lo; mid_hi[i] = hi;
+    const int plo = lower_bound(didx, a, b, base + (cnt - 1) / 2 + 1);
+    const int phi = lower_bound(didx, plo, b, base + cnt / 2 + 1);
+    *lo = cnt > 0 ? (int)((uint32_t)key_len[plo] ^ kLenBias) : 0;
+    *hi = cnt > 0 ? (int)((uint32_t)key_len[phi] ^ kLenBias) : 0;
+}
+
+// per edge its row of the table from the scans at its segment's ends (rid: the scan of the pairs' heads, for the weight)
+__global__ __launch_bounds__(kThreads) void k_edges_rows(const int* __restrict__ sstart, const int* __restrict__ rid, const int* __restrict__ didx,
+                                                        const long long* __restrict__ dsum, const uint64_t* __restrict__ key_len, EdgeTableDev t)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= t.ne) return;
+    const int a = sstart[i], b = sstart[i + 1];
+    t.weight[i] = before(rid, b) - before(rid, a);
+    length_stats(key_len, didx, dsum, a, b, &t.len_distinct[i], &t.len_sum[i], &t.len_min[i], &t.len_max[i]);
+    middles(key_len, didx, a, b, &t.len_mid_lo[i], &t.len_mid_hi[i]);
+}
+
+// per family the middles of its genes' distinct lengths
+__global__ __launch_bounds__(kThreads) void k_edges_family(int n, const int* __restrict__ sstart, const int* __restrict__ didx,
+                                                          const uint64_t* __restrict__ key_fam, int* __restrict__ mid_lo, int* __restrict__ mid_hi)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) middles(key_fam, didx, sstart[i], sstart[i + 1], &mid_lo[i], &mid_hi[i]);
 }
 
 // one block per word of 32 organisms: the first edge, in edge order, that carries each
@@ -251,13 +231,6 @@ __global__ __launch_bounds__(kThreads) void k_att_sizes(const int* __restrict__ 
     if (lane == 0) sizes[r] = sum;
 }
 
-__device__ inline char* put_digits(char* at, int v)
-{
-    const int nd = digits_of(v);
-    for (int q = nd - 1; q >= 0; q--) { at[q] = (char)('0' + v % 10); v /= 10; }
-    return at + nd;
-}
-
 // one wave per edge: its lines, 64 organisms at a time (everything but the lane's own line is uniform over the wave)
 __global__ __launch_bounds__(kThreads) void k_att_text(const int* __restrict__ entry, const uint32_t* __restrict__ bits, int wf, int d,
                                                       const int* __restrict__ extra_ptr, const int* __restrict__ extra_org,
@@ -281,9 +254,8 @@ __global__ __launch_bounds__(kThreads) void k_att_text(const int* __restrict__ e
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off); if (lane >= off) inc += v; }
         const int len = __shfl(inc, 63);
-        const int mis = (int)(at & 7);
         if (has) {
-            char* q = stage + mis + (inc - width);
+            char* q = stage + (int)(at & 7) + (inc - width);
             const char* a = "          <attvalue for=\"";
             for (int k = 0; k < 25; k++) q[k] = a[k];
             q = put_digits(q + 25, id);
@@ -293,57 +265,38 @@ __global__ __launch_bounds__(kThreads) void k_att_text(const int* __restrict__ e
             const char* e = "\" />\n";
             for (int k = 0; k < 5; k++) q[k] = e[k];
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        char* base = text + (at - mis);                       // 8-byte aligned: its words are the text's words
-        const int nwords = (mis + len + 7) >> 3;
-        for (int k = lane; k < nwords; k += 64) {
-            const int r0 = 8 * k - mis;                       // the word's first byte, relative to the run
-            const uint64_t word = s_txt[wv][k];
-            if (r0 >= 0 && r0 + 8 <= len) {
-                *(uint64_t*)(base + 8 * (size_t)k) = word;
-            } else {                                          // the run's first or last partial word: its own bytes only
-#pragma unroll
-                for (int b = 0; b < 8; b++)
-                    if (r0 + b >= 0 && r0 + b < len) base[8 * (size_t)k + b] = (char)(word >> (8 * b));
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the next group's layout overwrites the stage)
-        __builtin_amdgcn_wave_barrier();
+        store_run(text, at, len, true, [&](int k, int) { return s_txt[wv][k]; });
         at += len;
     }
 }
 
 }  // namespace
 
-#define EDG(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-
 hipError_t edge_table(const MasterDev& m, const EdgesIn& in, EdgeTableDev* t, int* mismatch, hipStream_t s)
 {
-    const int n = m.n, d = m.d, nnz = m.nnz, wf = m.wf, f = in.f, g = in.g, c = in.c;
+    const int n = m.n, d = m.d, nnz = m.nnz, wf = m.wf, g = in.o.g, c = in.o.c;
     *mismatch = kEdgesOk;
     t->n = n; t->d = d; t->ne = 0;
     Scratch mem;
     // the edges
     int *up, *upx, *partial, *totals;
     unsigned long long* ones;
-    EDG(mem.alloc(&up, nnz)); EDG(mem.alloc(&upx, nnz)); EDG(mem.alloc(&partial, (size_t)std::max(nnz, g) / kScanTile + 2)); EDG(mem.alloc(&totals, 4));
-    EDG(mem.alloc(&ones, 2));
-    EDG(hipMemsetAsync(ones, 0, 16, s));
-    EDG(hipMemsetAsync(totals, 0, 16, s));
+    HIPTRY(mem.alloc(&up, nnz)); HIPTRY(mem.alloc(&upx, nnz)); HIPTRY(mem.alloc(&partial, (size_t)std::max(nnz, g) / kScanTile + 2)); HIPTRY(mem.alloc(&totals, 4));
+    HIPTRY(mem.alloc(&ones, 2));
+    HIPTRY(hipMemsetAsync(ones, 0, 16, s));
+    HIPTRY(hipMemsetAsync(totals, 0, 16, s));
     if (nnz > 0) hipLaunchKernelGGL(k_edges_up, dim3(blocks(nnz)), dim3(kThreads), 0, s, m.nei_ptr, m.nei_idx, n, nnz, up);
     scan<int, OpSum<int>, false>(up, upx, nnz, OpSum<int>(), 0, partial, totals, s);
-    EDG(hipGetLastError());
+    HIPTRY(hipGetLastError());
     int ne = 0;
-    EDG(hipMemcpyAsync(&ne, totals, 4, hipMemcpyDeviceToHost, s));
-    EDG(hipStreamSynchronize(s));
+    HIPTRY(hipMemcpyAsync(&ne, totals, 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipStreamSynchronize(s));
     t->ne = ne;
-    EDG(dev_alloc(&t->src, ne)); EDG(dev_alloc(&t->dst, ne)); EDG(dev_alloc(&t->entry, ne));
+    HIPTRY(dev_alloc(&t->src, ne)); HIPTRY(dev_alloc(&t->dst, ne)); HIPTRY(dev_alloc(&t->entry, ne));
     const int bn = bits_for(n), bd = bits_for(d), be = bits_for(ne + 1), bn1 = bits_for(n + 1);
     uint64_t *ek0, *ek1;
     uint32_t *ev0, *ev1;
-    EDG(mem.alloc(&ek0, ne)); EDG(mem.alloc(&ek1, ne)); EDG(mem.alloc(&ev0, ne)); EDG(mem.alloc(&ev1, ne));
+    HIPTRY(mem.alloc(&ek0, ne)); HIPTRY(mem.alloc(&ek1, ne)); HIPTRY(mem.alloc(&ev0, ne)); HIPTRY(mem.alloc(&ev1, ne));
     const uint64_t* ekeys = ek0;
     const uint32_t* evals = ev0;
     if (ne > 0) {
@@ -351,85 +304,73 @@ hipError_t edge_table(const MasterDev& m, const EdgesIn& in, EdgeTableDev* t, in
                            t->src, t->dst, t->entry);
         const long long words = (long long)nnz * wf;
         hipLaunchKernelGGL(k_edges_popcount, dim3(blocks(words)), dim3(kThreads), 0, s, m.edge_bits, (const int*)up, words, wf, d, m.extra_ptr, ones);
-        EDG(hipGetLastError());
-        EDG(sort_pairs<uint64_t>(mem, ek0, ek1, ev0, ev1, ne, 2 * bn, &ekeys, &evals, s));
+        HIPTRY(hipGetLastError());
+        HIPTRY(sort_pairs<uint64_t>(mem, ek0, ek1, ev0, ev1, ne, 2 * bn, &ekeys, &evals, s));
     }
     // the links
-    int *inv, *order = nullptr, *genes, *gstart, *gend, *cptr, *corg, *csize, *last, *flags;
-    uint8_t* rep = nullptr;
-    EDG(mem.alloc(&inv, f)); EDG(mem.alloc(&genes, g)); EDG(mem.alloc(&gstart, g)); EDG(mem.alloc(&gend, g)); EDG(mem.alloc(&cptr, (size_t)c + 1));
-    EDG(mem.alloc(&corg, c)); EDG(mem.alloc(&csize, c)); EDG(mem.alloc(&last, g)); EDG(mem.alloc(&flags, 1));
-    if (in.order) { EDG(mem.alloc(&order, n)); EDG(hipMemcpyAsync(order, in.order, (size_t)n * 4, hipMemcpyHostToDevice, s)); }
-    if (in.repeated) { EDG(mem.alloc(&rep, f)); EDG(hipMemcpyAsync(rep, in.repeated, (size_t)f, hipMemcpyHostToDevice, s)); }
-    EDG(hipMemcpyAsync(genes, in.genes, (size_t)g * 4, hipMemcpyHostToDevice, s));
-    EDG(hipMemcpyAsync(gstart, in.gene_start, (size_t)g * 4, hipMemcpyHostToDevice, s));
-    EDG(hipMemcpyAsync(gend, in.gene_end, (size_t)g * 4, hipMemcpyHostToDevice, s));
-    EDG(hipMemcpyAsync(cptr, in.contig_ptr, ((size_t)c + 1) * 4, hipMemcpyHostToDevice, s));
-    EDG(hipMemcpyAsync(corg, in.contig_org, (size_t)c * 4, hipMemcpyHostToDevice, s));
-    EDG(hipMemcpyAsync(csize, in.contig_size, (size_t)c * 4, hipMemcpyHostToDevice, s));
-    EDG(hipMemsetAsync(flags, 0, 4, s));
-    launch_project_inverse(order, n, f, inv, s);
-    hipLaunchKernelGGL(k_edges_kept, dim3(blocks(g)), dim3(kThreads), 0, s, (const int*)genes, g, (const uint8_t*)rep, last);
+    GeneOrdersDev o;
+    int *gstart, *gend, *csize, *last, *flags;
+    HIPTRY(mem.alloc(&gstart, g)); HIPTRY(mem.alloc(&gend, g)); HIPTRY(mem.alloc(&csize, c)); HIPTRY(mem.alloc(&last, g)); HIPTRY(mem.alloc(&flags, 1));
+    HIPTRY(hipMemcpyAsync(gstart, in.gene_start, (size_t)g * 4, hipMemcpyHostToDevice, s));
+    HIPTRY(hipMemcpyAsync(gend, in.gene_end, (size_t)g * 4, hipMemcpyHostToDevice, s));
+    HIPTRY(hipMemcpyAsync(csize, in.contig_size, (size_t)c * 4, hipMemcpyHostToDevice, s));
+    HIPTRY(hipMemsetAsync(flags, 0, 4, s));
+    HIPTRY(upload_orders(mem, in.o, n, s, &o));                   // (last: its kernels behind every copy, as before)
+    hipLaunchKernelGGL(k_edges_kept, dim3(blocks(g)), dim3(kThreads), 0, s, (const int*)o.genes, g, (const uint8_t*)o.rep, last);
     scan<int, OpMax, true>(last, last, g, OpMax(), -1, partial, (int*)nullptr, s);
     uint64_t *ka0, *ka1, *kb0, *kb1, *kc0, *kc1;
-    EDG(mem.alloc(&ka0, g)); EDG(mem.alloc(&ka1, g)); EDG(mem.alloc(&kb0, g)); EDG(mem.alloc(&kb1, g)); EDG(mem.alloc(&kc0, g)); EDG(mem.alloc(&kc1, g));
-    hipLaunchKernelGGL(k_edges_links, dim3(blocks(g)), dim3(kThreads), 0, s, (const int*)genes, (const int*)gstart, (const int*)gend, g, (const int*)last,
-                       (const int*)cptr, c, (const int*)corg, (const int*)csize, (const int*)inv, n, ekeys, evals, ne, bn, bd, ka0, kb0, kc0, flags);
-    EDG(hipGetLastError());
+    HIPTRY(mem.alloc(&ka0, g)); HIPTRY(mem.alloc(&ka1, g)); HIPTRY(mem.alloc(&kb0, g));
+    HIPTRY(mem.alloc(&kb1, g)); HIPTRY(mem.alloc(&kc0, g)); HIPTRY(mem.alloc(&kc1, g));
+    hipLaunchKernelGGL(k_edges_links, dim3(blocks(g)), dim3(kThreads), 0, s, (const int*)o.genes, (const int*)gstart, (const int*)gend, g, (const int*)last,
+                       (const int*)o.cptr, c, (const int*)o.corg, (const int*)csize, (const int*)o.inv, n, ekeys, evals, ne, bn, bd, ka0, kb0, kc0, flags);
+    HIPTRY(hipGetLastError());
     const uint64_t *ks_org, *ks_len, *ks_fam;
-    EDG(sort_keys<uint64_t>(mem, ka0, ka1, g, bd + be, &ks_org, s));
-    EDG(sort_keys<uint64_t>(mem, kb0, kb1, g, 32 + be, &ks_len, s));
-    EDG(sort_keys<uint64_t>(mem, kc0, kc1, g, 32 + bn1, &ks_fam, s));
+    HIPTRY(sort_keys<uint64_t>(mem, ka0, ka1, g, bd + be, &ks_org, s));
+    HIPTRY(sort_keys<uint64_t>(mem, kb0, kb1, g, 32 + be, &ks_len, s));
+    HIPTRY(sort_keys<uint64_t>(mem, kc0, kc1, g, 32 + bn1, &ks_fam, s));
     // the (edge, organism, count) triples against the master's
     const uint64_t none_org = (uint64_t)(uint32_t)ne << bd, none_len = (uint64_t)(uint32_t)ne << 32, none_fam = (uint64_t)(uint32_t)n << 32;
     int *head, *ehead, *multi, *rid;
-    EDG(mem.alloc(&head, g)); EDG(mem.alloc(&ehead, g)); EDG(mem.alloc(&multi, g)); EDG(mem.alloc(&rid, g));
+    HIPTRY(mem.alloc(&head, g)); HIPTRY(mem.alloc(&ehead, g)); HIPTRY(mem.alloc(&multi, g)); HIPTRY(mem.alloc(&rid, g));
     hipLaunchKernelGGL(k_edges_pairs, dim3(blocks(g)), dim3(kThreads), 0, s, ks_org, g, none_org, bd, (const int*)t->entry, m.edge_bits, wf, m.extra_ptr,
                        m.extra_org, m.extra_add, in.bits_only ? 1 : 0, flags, head, ehead, multi);
     scan<int, OpSum<int>, true>(head, rid, g, OpSum<int>(), 0, partial, totals + 1, s);
     scan<int, OpSum<int>, true>(ehead, ehead, g, OpSum<int>(), 0, partial, totals + 2, s);
     scan<int, OpSum<int>, true>(multi, multi, g, OpSum<int>(), 0, partial, totals + 3, s);
-    EDG(hipGetLastError());
+    HIPTRY(hipGetLastError());
     int h_flags = 0, h_totals[4] = {0, 0, 0, 0};
     unsigned long long h_ones[2] = {0, 0};
-    EDG(hipMemcpyAsync(&h_flags, flags, 4, hipMemcpyDeviceToHost, s));
-    EDG(hipMemcpyAsync(h_totals, totals, 16, hipMemcpyDeviceToHost, s));
-    EDG(hipMemcpyAsync(h_ones, ones, 16, hipMemcpyDeviceToHost, s));
-    EDG(hipStreamSynchronize(s));
+    HIPTRY(hipMemcpyAsync(&h_flags, flags, 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(h_totals, totals, 16, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(h_ones, ones, 16, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipStreamSynchronize(s));
     if ((unsigned long long)h_totals[1] != h_ones[0] || h_totals[2] != ne) h_flags |= kEdgesMissing;
     if (!in.bits_only && (unsigned long long)h_totals[3] != h_ones[1]) h_flags |= kEdgesCount;
     if (h_flags) { *mismatch = h_flags; return hipSuccess; }
     // the table's arrays
-    EDG(dev_alloc(&t->weight, ne)); EDG(dev_alloc(&t->len_min, ne)); EDG(dev_alloc(&t->len_max, ne)); EDG(dev_alloc(&t->len_distinct, ne));
-    EDG(dev_alloc(&t->len_sum, ne)); EDG(dev_alloc(&t->len_mid_lo, ne)); EDG(dev_alloc(&t->len_mid_hi, ne));
-    EDG(dev_alloc(&t->fam_mid_lo, n)); EDG(dev_alloc(&t->fam_mid_hi, n)); EDG(dev_alloc(&t->org_first_edge, d));
-    int *sstart, *dflag, *didx;
-    long long *lpartial, *dval, *dsum;
-    EDG(mem.alloc(&sstart, (size_t)std::max(ne, n) + 1)); EDG(mem.alloc(&dflag, g)); EDG(mem.alloc(&didx, g));
-    EDG(mem.alloc(&lpartial, (size_t)g / kScanTile + 2)); EDG(mem.alloc(&dval, g)); EDG(mem.alloc(&dsum, g));
+    HIPTRY(dev_alloc(&t->weight, ne)); HIPTRY(dev_alloc(&t->len_min, ne)); HIPTRY(dev_alloc(&t->len_max, ne)); HIPTRY(dev_alloc(&t->len_distinct, ne));
+    HIPTRY(dev_alloc(&t->len_sum, ne)); HIPTRY(dev_alloc(&t->len_mid_lo, ne)); HIPTRY(dev_alloc(&t->len_mid_hi, ne));
+    HIPTRY(dev_alloc(&t->fam_mid_lo, n)); HIPTRY(dev_alloc(&t->fam_mid_hi, n)); HIPTRY(dev_alloc(&t->org_first_edge, d));
+    int* sstart;
+    SegLengths sl;
+    HIPTRY(mem.alloc(&sstart, (size_t)std::max(ne, n) + 1)); HIPTRY(sl.alloc(mem, g));
     // per edge
-    hipLaunchKernelGGL(k_edges_sstart, dim3(blocks((long long)ne + 1)), dim3(kThreads), 0, s, ks_org, g, bd, ne, sstart);
-    hipLaunchKernelGGL(k_edges_lengths, dim3(blocks(g)), dim3(kThreads), 0, s, ks_len, g, none_len, dflag, dval);
-    scan<int, OpSum<int>, true>(dflag, didx, g, OpSum<int>(), 0, partial, (int*)nullptr, s);
-    scan<long long, OpSum<long long>, true>(dval, dsum, g, OpSum<long long>(), 0ll, lpartial, (long long*)nullptr, s);
+    hipLaunchKernelGGL(k_seg_starts<uint64_t>, dim3(blocks((long long)ne + 1)), dim3(kThreads), 0, s, ks_org, g, bd, ne, sstart);
+    sl.run(ks_len, g, none_len, true, s);
     if (ne > 0)
-        hipLaunchKernelGGL(k_edges_rows, dim3(blocks(ne)), dim3(kThreads), 0, s, ne, (const int*)sstart, (const int*)rid, (const int*)didx,
-                           (const long long*)dsum, ks_len, t->weight, t->len_min, t->len_max, t->len_distinct, t->len_sum, t->len_mid_lo, t->len_mid_hi);
+        hipLaunchKernelGGL(k_edges_rows, dim3(blocks(ne)), dim3(kThreads), 0, s, (const int*)sstart, (const int*)rid, (const int*)sl.didx,
+                           (const long long*)sl.dsum, ks_len, *t);
     // per family (the kept genes' positions in the family keys; the stream orders the reuse of the scans' buffers)
-    hipLaunchKernelGGL(k_edges_sstart, dim3(blocks((long long)n + 1)), dim3(kThreads), 0, s, ks_fam, g, 32, n, sstart);
-    hipLaunchKernelGGL(k_edges_lengths, dim3(blocks(g)), dim3(kThreads), 0, s, ks_fam, g, none_fam, dflag, dval);
-    scan<int, OpSum<int>, true>(dflag, didx, g, OpSum<int>(), 0, partial, (int*)nullptr, s);
-    hipLaunchKernelGGL(k_edges_rows, dim3(blocks(n)), dim3(kThreads), 0, s, n, (const int*)sstart, (const int*)nullptr, (const int*)didx,
-                       (const long long*)nullptr, ks_fam, (int*)nullptr, (int*)nullptr, (int*)nullptr, (int*)nullptr, (long long*)nullptr, t->fam_mid_lo,
+    hipLaunchKernelGGL(k_seg_starts<uint64_t>, dim3(blocks((long long)n + 1)), dim3(kThreads), 0, s, ks_fam, g, 32, n, sstart);
+    sl.run(ks_fam, g, none_fam, false, s);
+    hipLaunchKernelGGL(k_edges_family, dim3(blocks(n)), dim3(kThreads), 0, s, n, (const int*)sstart, (const int*)sl.didx, ks_fam, t->fam_mid_lo,
                        t->fam_mid_hi);
     // per organism
     hipLaunchKernelGGL(k_edges_first, dim3(wf), dim3(kThreads), 0, s, (const int*)t->entry, ne, m.edge_bits, wf, d, t->org_first_edge);
-    EDG(hipGetLastError());
-    EDG(hipStreamSynchronize(s));
+    HIPTRY(hipGetLastError());
+    HIPTRY(hipStreamSynchronize(s));
     return hipSuccess;
 }
-
-#undef EDG
 
 void launch_att_sizes(const MasterDev& m, const EdgeTableDev& t, const int* attr_id, int row0, int rows, long long* sizes, hipStream_t s)
 {
@@ -456,8 +397,7 @@ struct nemgpu_edge_table {
     long long* ends = nullptr;                        // [ends_cap + 1]: a batch's edge ends, then its size
     long long* partial = nullptr;
     size_t ends_cap = 0;
-    char* text = nullptr;
-    size_t text_cap = 0;
+    TableText txt;
 };
 
 namespace {
@@ -466,18 +406,17 @@ void table_free(nemgpu_edge_table* t)
 {
     EdgeTableDev& v = t->dev;
     void* all[] = {v.src, v.dst, v.entry, v.weight, v.len_min, v.len_max, v.len_distinct, v.len_sum, v.len_mid_lo, v.len_mid_hi, v.fam_mid_lo,
-                   v.fam_mid_hi, v.org_first_edge, t->attr, t->ends, t->partial, t->text};
+                   v.fam_mid_hi, v.org_first_edge, t->attr, t->ends, t->partial, t->txt.text};
     for (void* p : all) if (p) (void)hipFree(p);
     delete t;
 }
 
 // what both text calls check and compute: the batch's edge ends on the device (t->ends) and its size
-int batch_sizes(const char* who, nemgpu_edge_table* t, const nemgpu_master* m, const int32_t* attr_id, int row0, int rows, long long* bytes)
+int batch_sizes(const std::string& who, nemgpu_edge_table* t, const nemgpu_master* m, const int32_t* attr_id, int row0, int rows, int64_t* bytes)
 {
-    if (m->n != t->dev.n || m->d != t->dev.d || m->device != t->device) { set_error(std::string(who) + ": not the table's master"); return NEMGPU_E_ARG; }
-    if (row0 < 0 || rows <= 0 || (long long)row0 + rows > t->dev.ne) { set_error(std::string(who) + ": rows outside the table"); return NEMGPU_E_ARG; }
+    { const int r = check_batch(who, m, t->dev.n, t->dev.d, t->device, row0, rows, t->dev.ne); if (r != NEMGPU_OK) return r; }
     for (int o = 0; o < t->dev.d; o++)
-        if (attr_id[o] < 0) { set_error(std::string(who) + ": attr_id " + std::to_string(o) + " is negative"); return NEMGPU_E_ARG; }
+        if (attr_id[o] < 0) { set_error(who + ": attr_id " + std::to_string(o) + " is negative"); return NEMGPU_E_ARG; }
     HIPCHK(hipSetDevice(t->device));
     if (!t->attr) HIPCHK(hipMalloc((void**)&t->attr, (size_t)t->dev.d * 4));
     if (t->ends_cap < (size_t)rows) {
@@ -524,16 +463,11 @@ int nemgpu_edge_table_create(nemgpu_edge_table** out, const nemgpu_master* m, in
     HIPCHK(hipSetDevice(m->device));
     nemgpu_edge_table* t = new nemgpu_edge_table();
     t->device = m->device;
-    const EdgesIn in{f, g, c, genes, gene_start, gene_end, contig_ptr, contig_org, contig_size, repeated, m->order.empty() ? nullptr : m->order.data(),
-                     m->bits_only};
+    const EdgesIn in{{f, g, c, genes, contig_ptr, contig_org, repeated, m->order.empty() ? nullptr : m->order.data()}, gene_start, gene_end,
+                     contig_size, m->bits_only};
     int mismatch = 0;
     const hipError_t err = edge_table(m->dev, in, &t->dev, &mismatch, m->stream);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        table_free(t);
-        set_error(std::string("nemgpu_edge_table_create: ") + hipGetErrorString(err));
-        return NEMGPU_E_DEVICE;
-    }
+    if (err != hipSuccess) { table_free(t); return device_status("nemgpu_edge_table_create", err); }
     if (mismatch & kEdgesLength) {
         table_free(t);
         set_error("nemgpu_edge_table_create: a link's or a gene's length is outside int32");
@@ -588,38 +522,26 @@ int nemgpu_edge_table_fetch(const nemgpu_edge_table* t, int32_t* src, int32_t* d
 int nemgpu_edge_table_attvalues_size(nemgpu_edge_table* t, const nemgpu_master* m, const int32_t* attr_id, int row0, int rows, int64_t* bytes)
 {
     if (!t || !m || !attr_id || !bytes) return NEMGPU_E_FUNCARG;
-    long long size = 0;
+    int64_t size = 0;
     const int r = batch_sizes("nemgpu_edge_table_attvalues_size", t, m, attr_id, row0, rows, &size);
-    if (r != NEMGPU_OK) return r;
-    *bytes = size;
-    return NEMGPU_OK;
+    if (r == NEMGPU_OK) *bytes = size;
+    return r;
 }
 
 int nemgpu_edge_table_attvalues(nemgpu_edge_table* t, const nemgpu_master* m, const int32_t* attr_id, int row0, int rows, char* text,
                                 int64_t capacity, int64_t* needed, int64_t* edge_end)
 {
     if (!t || !m || !attr_id || !text || !edge_end) return NEMGPU_E_FUNCARG;
-    long long bytes = 0;
-    const int r = batch_sizes("nemgpu_edge_table_attvalues", t, m, attr_id, row0, rows, &bytes);
-    if (r != NEMGPU_OK) return r;
-    if (needed) *needed = bytes;
-    if (capacity < bytes) {
-        set_error("nemgpu_edge_table_attvalues: the buffer holds " + std::to_string((long long)capacity) + " bytes, the batch needs " + std::to_string(bytes));
-        return NEMGPU_E_ARG;
-    }
-    if (t->text_cap < (size_t)bytes) {
-        if (t->text) (void)hipFree(t->text);
-        t->text = nullptr; t->text_cap = 0;
-        HIPCHK(hipMalloc((void**)&t->text, a256((size_t)bytes)));
-        t->text_cap = a256((size_t)bytes);
-    }
-    launch_att_text(m->dev, t->dev, t->attr, row0, rows, t->ends, t->text, m->stream);
+    const std::string who = "nemgpu_edge_table_attvalues";
+    int64_t bytes = 0;
+    { const int r = batch_sizes(who, t, m, attr_id, row0, rows, &bytes); if (r != NEMGPU_OK) return r; }
+    { const int r = text_room(who, &t->txt, capacity, bytes, needed); if (r != NEMGPU_OK) return r; }
+    launch_att_text(m->dev, t->dev, t->attr, row0, rows, t->ends, t->txt.text, m->stream);
     hipError_t err = hipGetLastError();
     if (err == hipSuccess) err = hipMemcpyAsync(edge_end, t->ends, (size_t)rows * 8, hipMemcpyDeviceToHost, m->stream);
-    if (err == hipSuccess && bytes) err = hipMemcpyAsync(text, t->text, (size_t)bytes, hipMemcpyDeviceToHost, m->stream);
+    if (err == hipSuccess && bytes) err = hipMemcpyAsync(text, t->txt.text, (size_t)bytes, hipMemcpyDeviceToHost, m->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(m->stream);
-    if (err != hipSuccess) { (void)hipGetLastError(); set_error(std::string("nemgpu_edge_table_attvalues: ") + hipGetErrorString(err)); return NEMGPU_E_DEVICE; }
-    return NEMGPU_OK;
+    return device_status(who, err);
 }
 
 void nemgpu_edge_table_destroy(nemgpu_edge_table* t)

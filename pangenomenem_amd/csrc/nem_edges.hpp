@@ -32,19 +32,15 @@
 #include <cstdint>
 
 #include "nem_chunks.hpp"
+#include "nem_project.hpp"
 
 namespace nemk {
 
 struct EdgesIn {                  // HOST arrays, checked by the caller
-    int f, g, c;
-    const int32_t* genes;         // [g] caller ids < f
+    GeneOrdersIn o;               // of ALL the master's organisms, contig_org non-decreasing
     const int32_t* gene_start;    // [g]
     const int32_t* gene_end;      // [g]
-    const int32_t* contig_ptr;    // [c + 1]
-    const int32_t* contig_org;    // [c] master columns, non-decreasing
     const int32_t* contig_size;   // [c] a circular contig's size, -1: linear
-    const uint8_t* repeated;      // [f] or null
-    const int32_t* order;         // [n] master family i = caller id order[i]; null: i
     bool bits_only;               // the master's counts are not known: only the bits are checked
 };
 

@@ -278,7 +278,7 @@ int nemgpu_master_project(const nemgpu_master* m, const uint8_t* part, int f, co
     { const int r = check_orders(true, m->d, f, g, c, genes, contig_ptr, contig_org, nullptr); if (r != NEMGPU_OK) return r; }
     note_hip_used();
     HIPCHK(hipSetDevice(m->device));
-    const ProjectIn in{f, g, c, part, genes, contig_ptr, contig_org, repeated, m->order.empty() ? nullptr : m->order.data()};
+    const ProjectIn in{{f, g, c, genes, contig_ptr, contig_org, repeated, m->order.empty() ? nullptr : m->order.data()}, part};
     const hipError_t err = project(m->dev, in, org_counts, nei_counts, gene_family, gene_copies, m->stream);
     if (err != hipSuccess) { (void)hipGetLastError(); set_error(std::string("nemgpu_master_project: ") + hipGetErrorString(err)); return NEMGPU_E_DEVICE; }
     return NEMGPU_OK;

@@ -5,10 +5,7 @@
 #include <string>
 #include <vector>
 
-#include "nem_internal.hpp"
-#include "nem_master.hpp"
-#include "nem_project.hpp"
-#include "nem_scan.hpp"
+#include "nem_table.hpp"
 
 namespace nemk {
 
@@ -62,7 +59,7 @@ __global__ __launch_bounds__(kThreads) void k_matrix_cells(const uint64_t* __res
     const int p = blockIdx.x * kThreads + threadIdx.x;
     if (p >= g) return;
     const uint64_t k = keys[p];
-    const bool h = k < none && (p == 0 || keys[p - 1] != k);
+    const bool h = is_head(keys, p, none);
     int copies = 0;
     if (h) {
         const int fam = (int)(k >> bd), org = (int)(k & ((1ull << bd) - 1ull));
@@ -72,13 +69,6 @@ __global__ __launch_bounds__(kThreads) void k_matrix_cells(const uint64_t* __res
     head[p] = h ? 1 : 0;
     cnt[p] = copies;
     multi[p] = copies >= 2 ? 1 : 0;
-}
-
-// fstart[i] = the first sorted position of family i (i = n: the kept genes), the same in both sorted arrays
-__global__ __launch_bounds__(kThreads) void k_matrix_fstart(const uint64_t* __restrict__ keys, int g, int bd, int n, int* __restrict__ fstart)
-{
-    const int i = blockIdx.x * kThreads + threadIdx.x;
-    if (i <= n) fstart[i] = lower_bound(keys, 0, g, (uint64_t)(uint32_t)i << bd);
 }
 
 // the cells of 2 or more, compacted in sorted order (midx: the inclusive scan of multi): organism, count, digits - 1
@@ -92,18 +82,6 @@ __global__ __launch_bounds__(kThreads) void k_matrix_multi(const uint64_t* __res
     multi_org[t] = (int)(keys[p] & ((1ull << bd) - 1ull));
     multi_cnt[t] = cnt[p];
     multi_x[t] = digits_of(cnt[p]) - 1;
-}
-
-// per sorted (family, length) key: 1 and the length where a distinct length starts
-__global__ __launch_bounds__(kThreads) void k_matrix_lengths(const uint64_t* __restrict__ keys, int g, uint64_t none, int* __restrict__ dflag,
-                                                            long long* __restrict__ dval)
-{
-    const int p = blockIdx.x * kThreads + threadIdx.x;
-    if (p >= g) return;
-    const uint64_t k = keys[p];
-    const bool h = k < none && (p == 0 || keys[p - 1] != k);
-    dflag[p] = h ? 1 : 0;
-    dval[p] = h ? (long long)(int)((uint32_t)k ^ kLenBias) : 0ll;
 }
 
 // per family its row of the table from the scans at its segment's ends; i = n closes multi_ptr and fam_xpre
@@ -122,10 +100,7 @@ __global__ __launch_bounds__(kThreads) void k_matrix_family(int n, const int* __
     const int b = fstart[i + 1];
     t.nb_genes[i] = b - a;
     t.nb_org[i] = before(rid, b) - before(rid, a);
-    t.len_distinct[i] = before(didx, b) - before(didx, a);
-    t.len_sum[i] = before(dsum, b) - before(dsum, a);
-    t.len_min[i] = b > a ? (int)((uint32_t)key_len[a] ^ kLenBias) : 0;
-    t.len_max[i] = b > a ? (int)((uint32_t)key_len[b - 1] ^ kLenBias) : 0;
+    length_stats(key_len, didx, dsum, a, b, &t.len_distinct[i], &t.len_sum[i], &t.len_min[i], &t.len_max[i]);
 }
 
 // ---- the .Rtab cell block ---------------------------------------------------------------------------------------
@@ -173,138 +148,99 @@ __global__ __launch_bounds__(kThreads) void k_rtab(const uint64_t* __restrict__ 
         const long long start = (long long)(i - row0) * 2 * d + (fam_xpre[i] - fam_xpre[row0]) + 2ll * o0 + (multi_xpre[t0] - multi_xpre[pi]);
         const int len = 2 * ncell + (int)(multi_xpre[t1] - multi_xpre[t0]);
         const int mis = (int)(start & 7);
-        char* base = text + (start - mis);                    // 8-byte aligned: its words are the text's words
-        const int nwords = (mis + len + 7) >> 3;
         if (t0 != t1) {
-            // lay the segment out in LDS at the same alignment: per cell its position, its digits, its separator
+            // lay the segment out in LDS at the global alignment: per cell its position, its digits, its separator
             for (int cell = lane; cell < ncell; cell += 64) {
                 const int o = o0 + cell;
                 const int t = lower_bound(multi_org, t0, t1, o);
-                int pos = mis + 2 * cell + (int)(multi_xpre[t] - multi_xpre[t0]);
-                if (t < t1 && multi_org[t] == o) {
-                    int v = multi_cnt[t];
-                    const int nd = digits_of(v);
-                    for (int q = nd - 1; q >= 0; q--) { stage[pos + q] = (char)('0' + v % 10); v /= 10; }
-                    pos += nd;
-                } else {
-                    stage[pos++] = (char)('0' + (int)((bits[cell >> 6] >> (cell & 63)) & 1ull));
-                }
-                stage[pos] = (last_seg && cell == ncell - 1) ? '\n' : '\t';
+                char* q = stage + mis + 2 * cell + (int)(multi_xpre[t] - multi_xpre[t0]);
+                if (t < t1 && multi_org[t] == o) q = put_digits(q, multi_cnt[t]);
+                else *q++ = (char)('0' + (int)((bits[cell >> 6] >> (cell & 63)) & 1ull));
+                *q = (last_seg && cell == ncell - 1) ? '\n' : '\t';
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-        for (int k = lane; k < nwords; k += 64) {
-            const int r0 = 8 * k - mis;                       // the word's first byte, relative to the segment
-            uint64_t word;
-            if (t0 != t1) {
-                word = s_txt[wv][k];
-            } else {
-                // every cell is one character: the word straight from the bits (cells c0 .. c0 + 4 at the most)
-                const int c0 = max(r0, 0) >> 1, q = c0 >> 6, sh = c0 & 63;
-                const uint64_t lo = bits[min(q, kTileOrg / 64 - 1)], hi = q + 1 < kTileOrg / 64 ? bits[q + 1] : 0ull;
-                const uint64_t win = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
-                word = 0;
+        store_run(text, start, len, t0 != t1, [&](int k, int r0) {
+            if (t0 != t1) return s_txt[wv][k];
+            // every cell is one character: the word straight from the bits (cells c0 .. c0 + 4 at the most)
+            const int c0 = max(r0, 0) >> 1, q = c0 >> 6, sh = c0 & 63;
+            const uint64_t lo = bits[min(q, kTileOrg / 64 - 1)], hi = q + 1 < kTileOrg / 64 ? bits[q + 1] : 0ull;
+            const uint64_t win = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+            uint64_t word = 0;
 #pragma unroll
-                for (int b = 0; b < 8; b++) {
-                    const int r = r0 + b, cell = max(r, 0) >> 1;
-                    const int ch = (r & 1) ? ((last_seg && cell == ncell - 1) ? '\n' : '\t') : '0' + (int)((win >> (cell - c0)) & 1ull);
-                    word |= (uint64_t)(uint32_t)ch << (8 * b);
-                }
+            for (int b = 0; b < 8; b++) {
+                const int r = r0 + b, cell = max(r, 0) >> 1;
+                const int ch = (r & 1) ? ((last_seg && cell == ncell - 1) ? '\n' : '\t') : '0' + (int)((win >> (cell - c0)) & 1ull);
+                word |= (uint64_t)(uint32_t)ch << (8 * b);
             }
-            if (r0 >= 0 && r0 + 8 <= len) {
-                *(uint64_t*)(base + 8 * (size_t)k) = word;
-            } else {                                          // the segment's first or last partial word: its own bytes only
-#pragma unroll
-                for (int b = 0; b < 8; b++)
-                    if (r0 + b >= 0 && r0 + b < len) base[8 * (size_t)k + b] = (char)(word >> (8 * b));
-            }
-        }
-        if (t0 != t1) {                                       // (the next family's layout overwrites the stage)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
+            return word;
+        });
     }
 }
 
 }  // namespace
 
-#define MTX(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-
 hipError_t family_table(const MasterDev& m, const MatrixIn& in, FamilyTableDev* t, int* mismatch, hipStream_t s)
 {
-    const int n = m.n, d = m.d, f = in.f, g = in.g, c = in.c;
+    const int n = m.n, d = m.d, g = in.o.g, c = in.o.c;
     *mismatch = kMatrixOk;
     t->n = n; t->d = d; t->nm = 0;
     Scratch mem;
-    int *inv, *order = nullptr, *genes, *glen, *cptr, *corg, *flags;
-    uint8_t* rep = nullptr;
+    GeneOrdersDev o;
+    int *glen, *flags;
     unsigned long long* ones;
-    MTX(mem.alloc(&inv, f)); MTX(mem.alloc(&genes, g)); MTX(mem.alloc(&glen, g)); MTX(mem.alloc(&cptr, (size_t)c + 1)); MTX(mem.alloc(&corg, c));
-    MTX(mem.alloc(&flags, 1)); MTX(mem.alloc(&ones, 1));
-    if (in.order) { MTX(mem.alloc(&order, n)); MTX(hipMemcpyAsync(order, in.order, (size_t)n * 4, hipMemcpyHostToDevice, s)); }
-    if (in.repeated) { MTX(mem.alloc(&rep, f)); MTX(hipMemcpyAsync(rep, in.repeated, (size_t)f, hipMemcpyHostToDevice, s)); }
-    MTX(hipMemcpyAsync(genes, in.genes, (size_t)g * 4, hipMemcpyHostToDevice, s));
-    MTX(hipMemcpyAsync(glen, in.gene_len, (size_t)g * 4, hipMemcpyHostToDevice, s));
-    MTX(hipMemcpyAsync(cptr, in.contig_ptr, ((size_t)c + 1) * 4, hipMemcpyHostToDevice, s));
-    MTX(hipMemcpyAsync(corg, in.contig_org, (size_t)c * 4, hipMemcpyHostToDevice, s));
-    MTX(hipMemsetAsync(flags, 0, 4, s));
-    MTX(hipMemsetAsync(ones, 0, 8, s));
-    launch_project_inverse(order, n, f, inv, s);
+    HIPTRY(mem.alloc(&glen, g)); HIPTRY(mem.alloc(&flags, 1)); HIPTRY(mem.alloc(&ones, 1));
+    HIPTRY(hipMemcpyAsync(glen, in.gene_len, (size_t)g * 4, hipMemcpyHostToDevice, s));
+    HIPTRY(hipMemsetAsync(flags, 0, 4, s));
+    HIPTRY(hipMemsetAsync(ones, 0, 8, s));
+    HIPTRY(upload_orders(mem, in.o, n, s, &o));                   // (last: its kernels behind every copy, as before)
     const int bd = bits_for(d), bn = bits_for(n + 1);         // (the family field also holds n: not kept)
     const uint64_t none_org = (uint64_t)(uint32_t)n << bd, none_len = (uint64_t)(uint32_t)n << 32;
     uint64_t *ka0, *ka1, *kb0, *kb1;
-    MTX(mem.alloc(&ka0, g)); MTX(mem.alloc(&ka1, g)); MTX(mem.alloc(&kb0, g)); MTX(mem.alloc(&kb1, g));
-    hipLaunchKernelGGL(k_matrix_keys, dim3(blocks(g)), dim3(kThreads), 0, s, genes, glen, g, cptr, c, corg, rep, inv, n, bd, ka0, kb0, flags);
+    HIPTRY(mem.alloc(&ka0, g)); HIPTRY(mem.alloc(&ka1, g)); HIPTRY(mem.alloc(&kb0, g)); HIPTRY(mem.alloc(&kb1, g));
+    hipLaunchKernelGGL(k_matrix_keys, dim3(blocks(g)), dim3(kThreads), 0, s, o.genes, glen, g, o.cptr, c, o.corg, o.rep, o.inv, n, bd, ka0, kb0, flags);
     const long long words = (long long)d * m.nw64;
     hipLaunchKernelGGL(k_matrix_popcount, dim3(blocks(words)), dim3(kThreads), 0, s, m.xt, words, m.nw64, n, ones);
-    MTX(hipGetLastError());
+    HIPTRY(hipGetLastError());
     const uint64_t *ks_org, *ks_len;
-    MTX(sort_keys<uint64_t>(mem, ka0, ka1, g, bd + bn, &ks_org, s));
-    MTX(sort_keys<uint64_t>(mem, kb0, kb1, g, 32 + bn, &ks_len, s));
+    HIPTRY(sort_keys<uint64_t>(mem, ka0, ka1, g, bd + bn, &ks_org, s));
+    HIPTRY(sort_keys<uint64_t>(mem, kb0, kb1, g, 32 + bn, &ks_len, s));
     // the cells
     int *head, *cnt, *multi, *rid, *midx, *partial, *totals, *fstart;
-    MTX(mem.alloc(&head, g)); MTX(mem.alloc(&cnt, g)); MTX(mem.alloc(&multi, g)); MTX(mem.alloc(&rid, g)); MTX(mem.alloc(&midx, g));
-    MTX(mem.alloc(&partial, (size_t)g / kScanTile + 2)); MTX(mem.alloc(&totals, 2)); MTX(mem.alloc(&fstart, (size_t)n + 1));
+    HIPTRY(mem.alloc(&head, g)); HIPTRY(mem.alloc(&cnt, g)); HIPTRY(mem.alloc(&multi, g)); HIPTRY(mem.alloc(&rid, g)); HIPTRY(mem.alloc(&midx, g));
+    HIPTRY(mem.alloc(&partial, (size_t)g / kScanTile + 2)); HIPTRY(mem.alloc(&totals, 2)); HIPTRY(mem.alloc(&fstart, (size_t)n + 1));
     hipLaunchKernelGGL(k_matrix_cells, dim3(blocks(g)), dim3(kThreads), 0, s, ks_org, g, none_org, bd, m.xt, m.nw64, flags, head, cnt, multi);
     scan<int, OpSum<int>, true>(head, rid, g, OpSum<int>(), 0, partial, totals, s);
     scan<int, OpSum<int>, true>(multi, midx, g, OpSum<int>(), 0, partial, totals + 1, s);
-    hipLaunchKernelGGL(k_matrix_fstart, dim3(blocks((long long)n + 1)), dim3(kThreads), 0, s, ks_org, g, bd, n, fstart);
-    MTX(hipGetLastError());
+    hipLaunchKernelGGL(k_seg_starts<uint64_t>, dim3(blocks((long long)n + 1)), dim3(kThreads), 0, s, ks_org, g, bd, n, fstart);
+    HIPTRY(hipGetLastError());
     int h_flags = 0, h_totals[2] = {0, 0};
     unsigned long long h_ones = 0;
-    MTX(hipMemcpyAsync(&h_flags, flags, 4, hipMemcpyDeviceToHost, s));
-    MTX(hipMemcpyAsync(h_totals, totals, 8, hipMemcpyDeviceToHost, s));
-    MTX(hipMemcpyAsync(&h_ones, ones, 8, hipMemcpyDeviceToHost, s));
-    MTX(hipStreamSynchronize(s));
+    HIPTRY(hipMemcpyAsync(&h_flags, flags, 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(h_totals, totals, 8, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipMemcpyAsync(&h_ones, ones, 8, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipStreamSynchronize(s));
     if ((unsigned long long)h_totals[0] != h_ones) h_flags |= kMatrixCount;
     if (h_flags) { *mismatch = h_flags; return hipSuccess; }
     // the table's arrays
     const int nm = h_totals[1];
     t->nm = nm;
-    MTX(dev_alloc(&t->nb_genes, n)); MTX(dev_alloc(&t->nb_org, n)); MTX(dev_alloc(&t->len_min, n)); MTX(dev_alloc(&t->len_max, n));
-    MTX(dev_alloc(&t->len_distinct, n)); MTX(dev_alloc(&t->len_sum, n)); MTX(dev_alloc(&t->multi_ptr, (size_t)n + 1));
-    MTX(dev_alloc(&t->multi_org, nm)); MTX(dev_alloc(&t->multi_cnt, nm)); MTX(dev_alloc(&t->multi_xpre, (size_t)nm + 1));
-    MTX(dev_alloc(&t->fam_xpre, (size_t)n + 1));
-    long long *multi_x, *lpartial, *dval, *dsum;
-    int *dflag, *didx;
-    MTX(mem.alloc(&multi_x, nm)); MTX(mem.alloc(&lpartial, (size_t)g / kScanTile + 2)); MTX(mem.alloc(&dval, g)); MTX(mem.alloc(&dsum, g));
-    MTX(mem.alloc(&dflag, g)); MTX(mem.alloc(&didx, g));
+    HIPTRY(dev_alloc(&t->nb_genes, n)); HIPTRY(dev_alloc(&t->nb_org, n)); HIPTRY(dev_alloc(&t->len_min, n)); HIPTRY(dev_alloc(&t->len_max, n));
+    HIPTRY(dev_alloc(&t->len_distinct, n)); HIPTRY(dev_alloc(&t->len_sum, n)); HIPTRY(dev_alloc(&t->multi_ptr, (size_t)n + 1));
+    HIPTRY(dev_alloc(&t->multi_org, nm)); HIPTRY(dev_alloc(&t->multi_cnt, nm)); HIPTRY(dev_alloc(&t->multi_xpre, (size_t)nm + 1));
+    HIPTRY(dev_alloc(&t->fam_xpre, (size_t)n + 1));
+    long long* multi_x;
+    SegLengths sl;
+    HIPTRY(mem.alloc(&multi_x, nm)); HIPTRY(sl.alloc(mem, g));
     hipLaunchKernelGGL(k_matrix_multi, dim3(blocks(g)), dim3(kThreads), 0, s, ks_org, g, bd, (const int*)cnt, (const int*)midx, t->multi_org, t->multi_cnt, multi_x);
-    scan<long long, OpSum<long long>, false>(multi_x, t->multi_xpre, nm, OpSum<long long>(), 0ll, lpartial, t->multi_xpre + nm, s);
+    scan<long long, OpSum<long long>, false>(multi_x, t->multi_xpre, nm, OpSum<long long>(), 0ll, sl.lpartial, t->multi_xpre + nm, s);
     // the distinct lengths
-    hipLaunchKernelGGL(k_matrix_lengths, dim3(blocks(g)), dim3(kThreads), 0, s, ks_len, g, none_len, dflag, dval);
-    scan<int, OpSum<int>, true>(dflag, didx, g, OpSum<int>(), 0, partial, (int*)nullptr, s);
-    scan<long long, OpSum<long long>, true>(dval, dsum, g, OpSum<long long>(), 0ll, lpartial, (long long*)nullptr, s);
+    sl.run(ks_len, g, none_len, true, s);
     hipLaunchKernelGGL(k_matrix_family, dim3(blocks((long long)n + 1)), dim3(kThreads), 0, s, n, (const int*)fstart, (const int*)rid, (const int*)midx,
-                       (const int*)didx, (const long long*)dsum, ks_len, *t);
-    MTX(hipGetLastError());
-    MTX(hipStreamSynchronize(s));
+                       (const int*)sl.didx, (const long long*)sl.dsum, ks_len, *t);
+    HIPTRY(hipGetLastError());
+    HIPTRY(hipStreamSynchronize(s));
     return hipSuccess;
 }
-
-#undef MTX
 
 void launch_rtab(const MasterDev& m, const FamilyTableDev& t, int row0, int rows, char* text, hipStream_t s)
 {
@@ -322,8 +258,7 @@ struct nemgpu_family_table {
     int device = 0;
     FamilyTableDev dev{};
     std::vector<long long> fam_xpre;                  // [n + 1]
-    char* text = nullptr;                             // the last batch's text on the device, kept for the next
-    size_t text_cap = 0;
+    TableText txt;                                    // the last batch's text on the device, kept for the next
 };
 
 namespace {
@@ -332,7 +267,7 @@ void table_free(nemgpu_family_table* t)
 {
     FamilyTableDev& v = t->dev;
     void* all[] = {v.nb_genes, v.nb_org, v.len_min, v.len_max, v.len_distinct, v.len_sum, v.multi_ptr, v.multi_org, v.multi_cnt,
-                   v.multi_xpre, v.fam_xpre, t->text};
+                   v.multi_xpre, v.fam_xpre, t->txt.text};
     for (void* p : all) if (p) (void)hipFree(p);
     delete t;
 }
@@ -364,19 +299,14 @@ int nemgpu_family_table_create(nemgpu_family_table** out, const nemgpu_master* m
     HIPCHK(hipSetDevice(m->device));
     nemgpu_family_table* t = new nemgpu_family_table();
     t->device = m->device;
-    const MatrixIn in{f, g, c, genes, gene_len, contig_ptr, contig_org, repeated, m->order.empty() ? nullptr : m->order.data()};
+    const MatrixIn in{{f, g, c, genes, contig_ptr, contig_org, repeated, m->order.empty() ? nullptr : m->order.data()}, gene_len};
     int mismatch = 0;
     hipError_t err = family_table(m->dev, in, &t->dev, &mismatch, m->stream);
     if (err == hipSuccess && !mismatch) {
         t->fam_xpre.resize((size_t)m->n + 1);
         err = hipMemcpy(t->fam_xpre.data(), t->dev.fam_xpre, ((size_t)m->n + 1) * 8, hipMemcpyDeviceToHost);
     }
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        table_free(t);
-        set_error(std::string("nemgpu_family_table_create: ") + hipGetErrorString(err));
-        return NEMGPU_E_DEVICE;
-    }
+    if (err != hipSuccess) { table_free(t); return device_status("nemgpu_family_table_create", err); }
     if (mismatch) {
         table_free(t);
         set_error(std::string("nemgpu_family_table_create: these orders are not this master's: ") +
@@ -429,28 +359,17 @@ int nemgpu_family_table_rtab(nemgpu_family_table* t, const nemgpu_master* m, int
                              int64_t* needed, int64_t* line_end)
 {
     if (!t || !m || !text || !line_end) return NEMGPU_E_FUNCARG;
-    if (m->n != t->dev.n || m->d != t->dev.d || m->device != t->device) { set_error("nemgpu_family_table_rtab: not the table's master"); return NEMGPU_E_ARG; }
-    if (row0 < 0 || rows <= 0 || (long long)row0 + rows > t->dev.n) { set_error("nemgpu_family_table_rtab: rows outside the table"); return NEMGPU_E_ARG; }
+    const std::string who = "nemgpu_family_table_rtab";
+    { const int r = check_batch(who, m, t->dev.n, t->dev.d, t->device, row0, rows, t->dev.n); if (r != NEMGPU_OK) return r; }
     const long long bytes = batch_ends(t, row0, rows, nullptr);
-    if (needed) *needed = bytes;
-    if (capacity < bytes) {
-        set_error("nemgpu_family_table_rtab: the buffer holds " + std::to_string((long long)capacity) + " bytes, the batch needs " + std::to_string(bytes));
-        return NEMGPU_E_ARG;
-    }
-    (void)batch_ends(t, row0, rows, line_end);
     HIPCHK(hipSetDevice(t->device));
-    if (t->text_cap < (size_t)bytes) {
-        if (t->text) (void)hipFree(t->text);
-        t->text = nullptr; t->text_cap = 0;
-        HIPCHK(hipMalloc((void**)&t->text, a256((size_t)bytes)));
-        t->text_cap = a256((size_t)bytes);
-    }
-    launch_rtab(m->dev, t->dev, row0, rows, t->text, m->stream);
+    { const int r = text_room(who, &t->txt, capacity, bytes, needed); if (r != NEMGPU_OK) return r; }
+    (void)batch_ends(t, row0, rows, line_end);
+    launch_rtab(m->dev, t->dev, row0, rows, t->txt.text, m->stream);
     hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemcpyAsync(text, t->text, (size_t)bytes, hipMemcpyDeviceToHost, m->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(text, t->txt.text, (size_t)bytes, hipMemcpyDeviceToHost, m->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(m->stream);
-    if (err != hipSuccess) { (void)hipGetLastError(); set_error(std::string("nemgpu_family_table_rtab: ") + hipGetErrorString(err)); return NEMGPU_E_DEVICE; }
-    return NEMGPU_OK;
+    return device_status(who, err);
 }
 
 void nemgpu_family_table_destroy(nemgpu_family_table* t)

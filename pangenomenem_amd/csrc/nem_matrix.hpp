@@ -28,17 +28,13 @@
 #include <cstdint>
 
 #include "nem_chunks.hpp"
+#include "nem_project.hpp"
 
 namespace nemk {
 
-struct MatrixIn {                 // HOST arrays, checked by the caller
-    int f, g, c;
-    const int32_t* genes;         // [g] caller ids < f
-    const int32_t* gene_len;      // [g] END - START, any int32
-    const int32_t* contig_ptr;    // [c + 1]
-    const int32_t* contig_org;    // [c] master columns
-    const uint8_t* repeated;      // [f] or null
-    const int32_t* order;         // [n] master family i = caller id order[i]; null: i
+struct MatrixIn {
+    GeneOrdersIn o;               // of ALL the master's organisms
+    const int32_t* gene_len;      // [g] END - START, any int32 (HOST)
 };
 
 // the table on the device (owned by nem_matrix.hip's handle)

@@ -1,6 +1,5 @@
 // nem_project.hip -- see nem_project.hpp.
 #include "nem_project.hpp"
-#include "nem_scan.hpp"
 
 namespace nemk {
 
@@ -129,8 +128,7 @@ __global__ __launch_bounds__(kThreads) void k_project_heads(const uint64_t* __re
 {
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= g) return;
-    const uint64_t k = keys[i];
-    flags[i] = (k < none && (i == 0 || keys[i - 1] != k)) ? 1 : 0;
+    flags[i] = is_head(keys, i, none) ? 1 : 0;
 }
 
 // run r (rid - 1: the inclusive scan of the heads) starts at starts[r]; the last kept key closes the last run
@@ -139,10 +137,9 @@ __global__ __launch_bounds__(kThreads) void k_project_runs(const uint64_t* __res
 {
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= g) return;
-    const uint64_t k = keys[i];
-    if (k >= none) return;
+    if (keys[i] >= none) return;
     const int r = rid[i] - 1;
-    if (i == 0 || keys[i - 1] != k) starts[r] = i;
+    if (is_head(keys, i, none)) starts[r] = i;
     if (i + 1 == g || keys[i + 1] >= none) starts[r + 1] = i + 1;
 }
 
@@ -158,81 +155,81 @@ __global__ __launch_bounds__(kThreads) void k_project_copies(const uint64_t* __r
 
 }  // namespace
 
-void launch_project_inverse(const int* order, int n, int f, int* inv, hipStream_t s)
+hipError_t upload_orders(Scratch& mem, const GeneOrdersIn& in, int n, hipStream_t s, GeneOrdersDev* out)
 {
-    hipLaunchKernelGGL(k_project_fill, dim3(blocks(f)), dim3(kThreads), 0, s, inv, f, kNoFamily);
-    hipLaunchKernelGGL(k_project_inverse, dim3(blocks(n)), dim3(kThreads), 0, s, order, n, f, inv);
+    const int f = in.f, g = in.g, c = in.c;
+    int* order = nullptr;
+    out->rep = nullptr;
+    HIPTRY(mem.alloc(&out->inv, f)); HIPTRY(mem.alloc(&out->genes, g)); HIPTRY(mem.alloc(&out->cptr, (size_t)c + 1)); HIPTRY(mem.alloc(&out->corg, c));
+    if (in.order) { HIPTRY(mem.alloc(&order, n)); HIPTRY(hipMemcpyAsync(order, in.order, (size_t)n * 4, hipMemcpyHostToDevice, s)); }
+    if (in.repeated) { HIPTRY(mem.alloc(&out->rep, f)); HIPTRY(hipMemcpyAsync(out->rep, in.repeated, (size_t)f, hipMemcpyHostToDevice, s)); }
+    HIPTRY(hipMemcpyAsync(out->genes, in.genes, (size_t)g * 4, hipMemcpyHostToDevice, s));
+    HIPTRY(hipMemcpyAsync(out->cptr, in.contig_ptr, ((size_t)c + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPTRY(hipMemcpyAsync(out->corg, in.contig_org, (size_t)c * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_project_fill, dim3(blocks(f)), dim3(kThreads), 0, s, out->inv, f, kNoFamily);
+    hipLaunchKernelGGL(k_project_inverse, dim3(blocks(n)), dim3(kThreads), 0, s, (const int*)order, n, f, out->inv);
+    return hipSuccess;
 }
-
-#define PRJ(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 hipError_t project(const MasterDev& m, const ProjectIn& in, int32_t* org_counts, int32_t* nei_counts, int32_t* gene_family,
                    int32_t* gene_copies, hipStream_t s)
 {
-    const int n = m.n, d = m.d, f = in.f, g = in.g, c = in.c;
+    const int n = m.n, d = m.d, g = in.o.g, c = in.o.c;
     Scratch mem;
     // the families: class | core bit
     uint8_t* cls;
-    PRJ(mem.alloc(&cls, n));
-    PRJ(hipMemcpyAsync(cls, in.part, (size_t)n, hipMemcpyHostToDevice, s));
+    HIPTRY(mem.alloc(&cls, n));
+    HIPTRY(hipMemcpyAsync(cls, in.part, (size_t)n, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_project_family, dim3(m.nw64), dim3(kThreads), 0, s, m.xt, n, d, m.nw64, cls);
     // the neighbours' classes
     int* nei = nullptr;
     if (nei_counts) {
-        PRJ(mem.alloc(&nei, (size_t)n * 3));
-        PRJ(hipMemsetAsync(nei, 0, (size_t)n * 3 * 4, s));
+        HIPTRY(mem.alloc(&nei, (size_t)n * 3));
+        HIPTRY(hipMemsetAsync(nei, 0, (size_t)n * 3 * 4, s));
         if (m.nnz > 0)
             hipLaunchKernelGGL(k_project_neighbours, dim3(blocks(m.nnz)), dim3(kThreads), 0, s, m.nei_ptr, m.nei_idx, m.nnz, n, cls, nei);
-        PRJ(hipGetLastError());
-        PRJ(hipMemcpyAsync(nei_counts, nei, (size_t)n * 3 * 4, hipMemcpyDeviceToHost, s));
+        HIPTRY(hipGetLastError());
+        HIPTRY(hipMemcpyAsync(nei_counts, nei, (size_t)n * 3 * 4, hipMemcpyDeviceToHost, s));
     }
     // the genes
     int* oc = nullptr;
     if (org_counts) {
-        PRJ(mem.alloc(&oc, (size_t)d * kProjectCounters));
-        PRJ(hipMemsetAsync(oc, 0, (size_t)d * kProjectCounters * 4, s));
+        HIPTRY(mem.alloc(&oc, (size_t)d * kProjectCounters));
+        HIPTRY(hipMemsetAsync(oc, 0, (size_t)d * kProjectCounters * 4, s));
     }
     if (g > 0 && (org_counts || gene_family || gene_copies)) {
-        int *inv, *order = nullptr, *genes, *cptr, *corg, *gfam = nullptr;
-        uint8_t* rep = nullptr;
-        PRJ(mem.alloc(&inv, f)); PRJ(mem.alloc(&genes, g)); PRJ(mem.alloc(&cptr, (size_t)c + 1)); PRJ(mem.alloc(&corg, c));
-        if (in.order) { PRJ(mem.alloc(&order, n)); PRJ(hipMemcpyAsync(order, in.order, (size_t)n * 4, hipMemcpyHostToDevice, s)); }
-        if (in.repeated) { PRJ(mem.alloc(&rep, f)); PRJ(hipMemcpyAsync(rep, in.repeated, (size_t)f, hipMemcpyHostToDevice, s)); }
-        if (gene_family) PRJ(mem.alloc(&gfam, g));
-        PRJ(hipMemcpyAsync(genes, in.genes, (size_t)g * 4, hipMemcpyHostToDevice, s));
-        PRJ(hipMemcpyAsync(cptr, in.contig_ptr, ((size_t)c + 1) * 4, hipMemcpyHostToDevice, s));
-        PRJ(hipMemcpyAsync(corg, in.contig_org, (size_t)c * 4, hipMemcpyHostToDevice, s));
-        launch_project_inverse(order, n, f, inv, s);
+        GeneOrdersDev o;
+        int* gfam = nullptr;
+        if (gene_family) HIPTRY(mem.alloc(&gfam, g));
+        HIPTRY(upload_orders(mem, in.o, n, s, &o));
         const int bn = bits_for(n), bd = bits_for(d);
         const uint64_t none = (uint64_t)1 << (bn + bd);       // (bn + bd <= 53)
         uint64_t *k0 = nullptr, *k1 = nullptr;
         uint32_t *v0 = nullptr, *v1 = nullptr;
-        if (gene_copies) { PRJ(mem.alloc(&k0, g)); PRJ(mem.alloc(&k1, g)); PRJ(mem.alloc(&v0, g)); PRJ(mem.alloc(&v1, g)); }
-        hipLaunchKernelGGL(k_project_genes, dim3(blocks(g)), dim3(kThreads), 0, s, genes, g, cptr, c, corg, rep, inv, cls, bn, gfam, oc, k0, v0, none);
-        PRJ(hipGetLastError());
-        if (gene_family) PRJ(hipMemcpyAsync(gene_family, gfam, (size_t)g * 4, hipMemcpyDeviceToHost, s));
+        if (gene_copies) { HIPTRY(mem.alloc(&k0, g)); HIPTRY(mem.alloc(&k1, g)); HIPTRY(mem.alloc(&v0, g)); HIPTRY(mem.alloc(&v1, g)); }
+        hipLaunchKernelGGL(k_project_genes, dim3(blocks(g)), dim3(kThreads), 0, s, o.genes, g, o.cptr, c, o.corg, o.rep, o.inv, cls, bn, gfam, oc, k0, v0, none);
+        HIPTRY(hipGetLastError());
+        if (gene_family) HIPTRY(hipMemcpyAsync(gene_family, gfam, (size_t)g * 4, hipMemcpyDeviceToHost, s));
         if (gene_copies) {
             int *rid, *starts, *partial, *copies;
-            PRJ(mem.alloc(&rid, g)); PRJ(mem.alloc(&starts, (size_t)g + 1)); PRJ(mem.alloc(&partial, (size_t)g / kScanTile + 2));
-            PRJ(mem.alloc(&copies, g));
+            HIPTRY(mem.alloc(&rid, g)); HIPTRY(mem.alloc(&starts, (size_t)g + 1)); HIPTRY(mem.alloc(&partial, (size_t)g / kScanTile + 2));
+            HIPTRY(mem.alloc(&copies, g));
             const uint64_t* ks;
             const uint32_t* vs;
-            PRJ(sort_pairs<uint64_t>(mem, k0, k1, v0, v1, g, bn + bd + 1, &ks, &vs, s));
-            PRJ(hipMemsetAsync(copies, 0, (size_t)g * 4, s));
+            HIPTRY(sort_pairs<uint64_t>(mem, k0, k1, v0, v1, g, bn + bd + 1, &ks, &vs, s));
+            HIPTRY(hipMemsetAsync(copies, 0, (size_t)g * 4, s));
             hipLaunchKernelGGL(k_project_heads, dim3(blocks(g)), dim3(kThreads), 0, s, ks, g, none, rid);
             scan<int, OpSum<int>, true>(rid, rid, g, OpSum<int>(), 0, partial, (int*)nullptr, s);
             hipLaunchKernelGGL(k_project_runs, dim3(blocks(g)), dim3(kThreads), 0, s, ks, g, none, (const int*)rid, starts);
             hipLaunchKernelGGL(k_project_copies, dim3(blocks(g)), dim3(kThreads), 0, s, ks, vs, g, none, (const int*)rid, (const int*)starts, copies);
-            PRJ(hipGetLastError());
-            PRJ(hipMemcpyAsync(gene_copies, copies, (size_t)g * 4, hipMemcpyDeviceToHost, s));
+            HIPTRY(hipGetLastError());
+            HIPTRY(hipMemcpyAsync(gene_copies, copies, (size_t)g * 4, hipMemcpyDeviceToHost, s));
         }
     }
-    PRJ(hipGetLastError());
-    if (org_counts) PRJ(hipMemcpyAsync(org_counts, oc, (size_t)d * kProjectCounters * 4, hipMemcpyDeviceToHost, s));
-    PRJ(hipStreamSynchronize(s));
+    HIPTRY(hipGetLastError());
+    if (org_counts) HIPTRY(hipMemcpyAsync(org_counts, oc, (size_t)d * kProjectCounters * 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipStreamSynchronize(s));
     return hipSuccess;
 }
-
-#undef PRJ
 
 }  // namespace nemk

@@ -9,7 +9,8 @@
 //      (a lane or a wave per row would serialise it or idle on the common short rows);
 //   2. per family its class and whether it is present in all d organisms (a column count over the organism-major
 //      presence rows, once per family);
-//   3. the inverse of the master's numbering (caller id -> family, -2 where there is none);
+//   3. the orders on the device and the inverse of the master's numbering (caller id -> family, -2 where there is none):
+//      upload_orders, which the family table and the edge table call too;
 //   4. per GENE its contig's organism (a search of contig_ptr), its family, its class: the seven counters of its organism
 //      reduced inside the wave over every run of lanes of one organism (genes arrive organism by organism; an organism
 //      whose contigs are not adjacent makes several runs), one integer atomic per run and non-zero counter -- integer
@@ -22,17 +23,32 @@
 #include <cstdint>
 
 #include "nem_chunks.hpp"
+#include "nem_scan.hpp"
 
 namespace nemk {
 
-struct ProjectIn {                // HOST arrays, checked by the caller
+// the flat gene orders every reader of the master takes (the projection, the family table, the edge table)
+struct GeneOrdersIn {             // HOST arrays, checked by the caller
     int f, g, c;
-    const uint8_t* part;          // [n] classes 0 .. 3
     const int32_t* genes;         // [g] caller ids < f
     const int32_t* contig_ptr;    // [c + 1]
     const int32_t* contig_org;    // [c] master columns
     const uint8_t* repeated;      // [f] or null
     const int32_t* order;         // [n] master family i = caller id order[i]; null: i
+};
+
+// the same on the device, with step 3's inverse numbering
+struct GeneOrdersDev {
+    int *genes, *cptr, *corg, *inv;   // inv[f]: the master family of every caller id, -2 where there is none
+    uint8_t* rep;                     // [f] or null
+};
+
+// allocates them in mem, copies the orders up and fills inv (n: the master's families); g > 0
+hipError_t upload_orders(seg::Scratch& mem, const GeneOrdersIn& in, int n, hipStream_t s, GeneOrdersDev* out);
+
+struct ProjectIn {
+    GeneOrdersIn o;
+    const uint8_t* part;          // [n] classes 0 .. 3 (HOST)
 };
 
 constexpr int kProjectCounters = 7;   // persistent, shell, cloud, undefined, core_exact, accessory, pangenome
@@ -41,9 +57,5 @@ constexpr int kProjectCounters = 7;   // persistent, shell, cloud, undefined, co
 // read.  Scratch is allocated for the call and freed.  Waits.
 hipError_t project(const MasterDev& m, const ProjectIn& in, int32_t* org_counts, int32_t* nei_counts, int32_t* gene_family,
                    int32_t* gene_copies, hipStream_t s);
-
-// step 3 alone, for the units that key genes by master family (DEVICE arrays): inv[f] = the master family of every
-// caller id, -2 where there is none; order[n] or null (the identity)
-void launch_project_inverse(const int* order, int n, int f, int* inv, hipStream_t s);
 
 }  // namespace nemk

@@ -1,7 +1,10 @@
 // nem_scan.hpp -- the block scans and the wave segment reduction that the units working on sorted records share
-// (nem_orders.hip: the master's build and append; nem_project.hip: a partition's projection; nem_matrix.hip: the family table; nem_edges.hip: the edge table).  256-thread blocks of 4
-// waves; a scan is three launches (tile totals, their prefixes, the tiles), in place allowed.  With them what both do
-// around rocPRIM's radix sort: the key widths, a call's scratch buffers, the sort itself, the search of a CSR's rows.
+// (nem_orders.hip: the master's build and append; nem_project.hip: a partition's projection; nem_matrix.hip: the family
+// table; nem_edges.hip: the edge table).  256-thread blocks of 4 waves; a scan is three launches (tile totals, their
+// prefixes, the tiles), in place allowed.  With them what they do around rocPRIM's radix sort: the key widths, a call's
+// scratch buffers, the sort itself, the search of a CSR's rows.  Then what the readers of the master share beyond that:
+// the segments of sorted (segment, length) keys -- run heads, segment starts, the scans of the distinct lengths and a
+// segment's statistics from them -- and the copy of a run of text out of LDS in aligned 8-byte words.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -9,6 +12,9 @@
 #include <algorithm>
 #include <cstdint>
 #include <vector>
+
+// in a function that returns a hipError_t
+#define HIPTRY(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 namespace nemk {
 namespace seg {
@@ -195,6 +201,104 @@ template <class K, class V, class Op> __device__ inline V wave_segment(K key, V 
     const K kn = __shfl_down(key, 1);
     tail = lane == 63 || kn != key;
     return val;
+}
+
+// ---- segments of sorted keys ------------------------------------------------------------------------------------
+// a run of equal keys starts at p; the keys from `none` up belong to no run and sort behind all
+template <class K> __device__ inline bool is_head(const K* keys, int p, K none)
+{
+    const K k = keys[p];
+    return k < none && (p == 0 || keys[p - 1] != k);
+}
+
+// sstart[i] = the first sorted position of segment i (i = count: the end of the keys that belong to one), the segment in
+// the key's bits from `shift` up
+template <class K> __global__ __launch_bounds__(kThreads) void k_seg_starts(const K* __restrict__ keys, int g, int shift, int count, int* __restrict__ sstart)
+{
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i <= count) sstart[i] = lower_bound(keys, 0, g, (K)(uint32_t)i << shift);
+}
+
+// per sorted (segment, length) key, the length (biased) in its low 32 bits: 1 and the length where a distinct length starts
+template <class K> __global__ __launch_bounds__(kThreads) void k_seg_lengths(const K* __restrict__ keys, int g, K none, int* __restrict__ dflag,
+                                                                           long long* __restrict__ dval)
+{
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= g) return;
+    const bool h = is_head(keys, p, none);
+    dflag[p] = h ? 1 : 0;
+    dval[p] = h ? (long long)(int)((uint32_t)keys[p] ^ kLenBias) : 0ll;
+}
+
+// the inclusive scans of k_seg_lengths' flags and values over g sorted keys, with the buffers they are made in
+struct SegLengths {
+    int *didx = nullptr, *partial = nullptr;
+    long long *dsum = nullptr, *lpartial = nullptr;
+
+    hipError_t alloc(Scratch& mem, int g)
+    {
+        HIPTRY(mem.alloc(&didx, g)); HIPTRY(mem.alloc(&dsum, g));
+        HIPTRY(mem.alloc(&partial, (size_t)g / kScanTile + 2)); HIPTRY(mem.alloc(&lpartial, (size_t)g / kScanTile + 2));
+        return hipSuccess;
+    }
+    // sums false: didx alone (dsum then holds the values unscanned)
+    template <class K> void run(const K* keys, int g, K none, bool sums, hipStream_t s) const
+    {
+        hipLaunchKernelGGL(k_seg_lengths<K>, dim3(blocks(g)), dim3(kThreads), 0, s, keys, g, none, didx, dsum);
+        scan<int, OpSum<int>, true>(didx, didx, g, OpSum<int>(), 0, partial, (int*)nullptr, s);
+        if (sums) scan<long long, OpSum<long long>, true>(dsum, dsum, g, OpSum<long long>(), 0ll, lpartial, (long long*)nullptr, s);
+    }
+};
+
+// what the distinct lengths of the segment at sorted positions [a, b) give, from the scans at its ends and its first and
+// last key (an empty segment: zeros)
+__device__ inline void length_stats(const uint64_t* key_len, const int* didx, const long long* dsum, int a, int b, int* distinct, long long* sum,
+                                    int* min, int* max)
+{
+    *distinct = before(didx, b) - before(didx, a);
+    *sum = before(dsum, b) - before(dsum, a);
+    *min = b > a ? (int)((uint32_t)key_len[a] ^ kLenBias) : 0;
+    *max = b > a ? (int)((uint32_t)key_len[b - 1] ^ kLenBias) : 0;
+}
+
+// ---- text ---------------------------------------------------------------------------------------------------------
+__device__ inline char* put_digits(char* at, int v)      // v >= 0 in decimal at `at`; returns the end
+{
+    const int nd = digits_of(v);
+    for (int q = nd - 1; q >= 0; q--) { at[q] = (char)('0' + v % 10); v /= 10; }
+    return at + nd;
+}
+
+// the wave writes the run of `len` bytes at text + start: word_at(k, r0) gives the k-th 8-byte word of the run laid out at
+// the global address's misalignment (start & 7), r0 its first byte relative to the run; whole words go out as words, the
+// run's first and last partial words by their own bytes only.  staged (uniform over the wave): the lanes have just laid
+// the run out in LDS and word_at reads other lanes' bytes -- they wait for each other before the words are read, and
+// again before the caller's next run overwrites the stage
+template <class WordAt> __device__ inline void store_run(char* __restrict__ text, long long start, int len, bool staged, WordAt word_at)
+{
+    if (staged) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    const int mis = (int)(start & 7);
+    char* base = text + (start - mis);                        // 8-byte aligned: its words are the text's words
+    const int nwords = (mis + len + 7) >> 3;
+    for (int k = lane_id(); k < nwords; k += 64) {
+        const int r0 = 8 * k - mis;
+        const uint64_t word = word_at(k, r0);
+        if (r0 >= 0 && r0 + 8 <= len) {
+            *(uint64_t*)(base + 8 * (size_t)k) = word;
+        } else {
+#pragma unroll
+            for (int b = 0; b < 8; b++)
+                if (r0 + b >= 0 && r0 + b < len) base[8 * (size_t)k + b] = (char)(word >> (8 * b));
+        }
+    }
+    if (staged) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
 }
 
 }  // namespace seg

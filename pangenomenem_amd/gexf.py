@@ -22,8 +22,7 @@ import time
 
 import numpy as np
 
-from .engine import NemGpuError
-from .matrix import TEXT_BUDGET, _long_names, table_orders
+from .matrix import TEXT_BUDGET, DeviceTable, _long_names, table_orders
 from .projection import FAMILY, START, END, PRODUCT, check_projection_orders, part_codes
 
 NAME = 5                                                      # a gene's info: TYPE, FAMILY, START, END, STRAND, NAME, PRODUCT
@@ -280,44 +279,33 @@ class _Edges:
             row0 += rows
 
 
-class EdgeTable(_Edges):
+class EdgeTable(DeviceTable, _Edges):
     """The edge table of a master on the device (nemgpu_edge_table_create) with its arrays read back: src, dst, weight,
     len_min, len_max, len_distinct, len_mid_lo, len_mid_hi int32 [E], len_sum int64 [E], fam_mid_lo, fam_mid_hi int32 [n],
     org_first_edge int32 [d].  The master must stay open as long as the table writes."""
+    KIND, ARRAYS, COUNT = "edge_table", EDGE_FIELDS, "n_edges"
 
     def __init__(self, master, genes, gene_start, gene_end, contig_ptr, contig_org, contig_size, repeated=None, f=None):
-        self.master, self.lib = master, _bind_edges(master.lib)
-        if f is None:
-            f = len(repeated) if repeated is not None else max(master.f, int(np.max(genes)) + 1 if len(genes) else 1)
-        genes, contig_ptr, contig_org, repeated = check_projection_orders(genes, contig_ptr, contig_org, repeated, master.d, int(f))
+        self.lib = _bind_edges(master.lib)
+        f, genes, contig_ptr, contig_org, repeated = self._orders(master, genes, contig_ptr, contig_org, repeated, f)
         gene_start, gene_end = np.ascontiguousarray(gene_start, np.int32), np.ascontiguousarray(gene_end, np.int32)
         contig_size = np.ascontiguousarray(contig_size, np.int32)
         if gene_start.shape != genes.shape or gene_end.shape != genes.shape or contig_size.shape != contig_org.shape or not len(genes):
             raise ValueError("edge table: genes [G], gene_start [G], gene_end [G], G > 0, contig_size [C]")
-        self._h = C.c_void_p()
-        rc = self.lib.nemgpu_edge_table_create(C.byref(self._h), master._h, int(f), genes.ctypes.data, gene_start.ctypes.data, gene_end.ctypes.data,
-                                               len(genes), contig_ptr.ctypes.data, contig_org.ctypes.data, contig_size.ctypes.data, len(contig_org),
-                                               repeated.ctypes.data if repeated is not None else None)
-        if rc != 0:
-            raise NemGpuError("nemgpu_edge_table_create failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
-        v = [C.c_int() for _ in range(3)]
-        self.lib.nemgpu_edge_table_shape(self._h, *(C.byref(a) for a in v))
-        self.n, self.d, self.n_edges = (a.value for a in v)
-        n, d, ne = self.n, self.d, self.n_edges
-        for name, size in zip(EDGE_FIELDS, (ne,) * 9 + (n, n, d)):
-            setattr(self, name, np.zeros(size, np.int64 if name == "len_sum" else np.int32))
-        rc = self.lib.nemgpu_edge_table_fetch(self._h, *(getattr(self, name).ctypes.data if getattr(self, name).size else None for name in EDGE_FIELDS))
-        if rc != 0:
-            raise NemGpuError("nemgpu_edge_table_fetch failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+        self._create(master, f, genes, (gene_start, gene_end), contig_ptr, contig_org, (contig_size,), repeated)
 
-    def attvalues_size(self, attr_id, row0, rows):
+    def _sizes(self):
+        return (self.n_edges,) * 9 + (self.n, self.n, self.d)
+
+    def _attr_id(self, attr_id):
         attr_id = np.ascontiguousarray(attr_id, np.int32)
         if attr_id.shape != (self.d,):
             raise ValueError("attvalues: attr_id [d]")
-        size = C.c_int64()
-        rc = self.lib.nemgpu_edge_table_attvalues_size(self._h, self.master._h, attr_id.ctypes.data, int(row0), int(rows), C.byref(size))
-        if rc != 0:
-            raise NemGpuError("nemgpu_edge_table_attvalues_size failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+        return attr_id
+
+    def attvalues_size(self, attr_id, row0, rows):
+        attr_id, size = self._attr_id(attr_id), C.c_int64()
+        self._call("attvalues_size", self._h, self.master._h, attr_id.ctypes.data, int(row0), int(rows), C.byref(size))
         return size.value
 
     def attvalues(self, attr_id, row0=0, rows=None, out=None):
@@ -325,30 +313,12 @@ class EdgeTable(_Edges):
         attvalues_host states them): (text uint8 [bytes], edge_end int64 [rows]).  out: a uint8 buffer to write into (too
         small: NemGpuError that says the size needed, nothing written)."""
         rows = self.n_edges - row0 if rows is None else rows
-        attr_id = np.ascontiguousarray(attr_id, np.int32)
-        if attr_id.shape != (self.d,):
-            raise ValueError("attvalues: attr_id [d]")
+        attr_id = self._attr_id(attr_id)
         if out is None:
             out = np.empty(max(self.attvalues_size(attr_id, row0, rows), 1), np.uint8)
         ends, needed = np.zeros(max(rows, 1), np.int64), C.c_int64()
-        rc = self.lib.nemgpu_edge_table_attvalues(self._h, self.master._h, attr_id.ctypes.data, int(row0), int(rows), out.ctypes.data, out.size,
-                                                  C.byref(needed), ends.ctypes.data)
-        if rc != 0:
-            err = NemGpuError("nemgpu_edge_table_attvalues failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
-            err.needed = needed.value
-            raise err
-        return out[:needed.value], ends[:rows]
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.nemgpu_edge_table_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._text("attvalues", out, needed, self._h, self.master._h, attr_id.ctypes.data, int(row0), int(rows), out.ctypes.data, out.size,
+                          C.byref(needed), ends.ctypes.data), ends[:rows]
 
 
 class HostEdgeTable(_Edges):

@@ -262,36 +262,77 @@ class _Table:
                         start = int(ends[r])
 
 
-class FamilyTable(_Table):
+class DeviceTable:
+    """A table of a master on the device behind a C handle (nemgpu_<KIND>_create / _shape / _fetch / _destroy), its arrays
+    (ARRAYS) read back.  A subclass names KIND, ARRAYS, the attribute of its third shape number (COUNT), gives _sizes() and
+    sets self.lib (the bound library) before it calls _create().
+    The master must stay open as long as the table writes."""
+
+    def _call(self, name, *args):
+        name = "nemgpu_%s_%s" % (self.KIND, name)
+        rc = getattr(self.lib, name)(*args)
+        if rc != 0:
+            raise NemGpuError("%s failed (status %d): %s" % (name, rc, self.lib.nemgpu_last_error().decode()))
+
+    def _orders(self, master, genes, contig_ptr, contig_org, repeated, f):
+        """the orders checked, f defaulted: (f, genes, contig_ptr, contig_org, repeated)"""
+        if f is None:
+            f = len(repeated) if repeated is not None else max(master.f, int(np.max(genes)) + 1 if len(genes) else 1)
+        return (int(f),) + check_projection_orders(genes, contig_ptr, contig_org, repeated, master.d, int(f))
+
+    def _create(self, master, f, genes, per_gene, contig_ptr, contig_org, per_contig, repeated):
+        """the table made from the orders and what it adds per gene and per contig (int32 arrays), its arrays fetched"""
+        self.master, self._h = master, C.c_void_p()
+        self._call("create", C.byref(self._h), master._h, f, genes.ctypes.data, *(a.ctypes.data for a in per_gene), len(genes),
+                   contig_ptr.ctypes.data, contig_org.ctypes.data, *(a.ctypes.data for a in per_contig), len(contig_org),
+                   repeated.ctypes.data if repeated is not None else None)
+        v = [C.c_int() for _ in range(3)]
+        self._call("shape", self._h, *(C.byref(a) for a in v))
+        self.n, self.d, count = (a.value for a in v)
+        setattr(self, self.COUNT, count)
+        for name, size in zip(self.ARRAYS, self._sizes()):
+            setattr(self, name, np.zeros(size, np.int64 if name == "len_sum" else np.int32))
+        self._call("fetch", self._h, *(getattr(self, name).ctypes.data if getattr(self, name).size else None for name in self.ARRAYS))
+
+    def _text(self, name, out, needed, *args):
+        """a text call into `out`; too small: the NemGpuError carries the size needed"""
+        try:
+            self._call(name, *args)
+        except NemGpuError as err:
+            err.needed = needed.value
+            raise
+        return out[:needed.value]
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(self.lib, "nemgpu_%s_destroy" % self.KIND)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FamilyTable(DeviceTable, _Table):
     """The family table of a master on the device (nemgpu_family_table_create) with its arrays read back: nb_genes,
     nb_org, len_min, len_max, len_distinct int32 [n], len_sum int64 [n], multi_ptr int32 [n + 1], multi_org, multi_cnt.
     The master must stay open as long as the table writes."""
+    KIND, ARRAYS, COUNT = "family_table", FIELDS, "n_multi"
 
     def __init__(self, master, genes, gene_len, contig_ptr, contig_org, repeated=None, f=None, repeated_names=()):
-        self.master, self.lib = master, _bind_matrix(master.lib)
-        if f is None:
-            f = len(repeated) if repeated is not None else max(master.f, int(np.max(genes)) + 1 if len(genes) else 1)
-        genes, contig_ptr, contig_org, repeated = check_projection_orders(genes, contig_ptr, contig_org, repeated, master.d, int(f))
+        self.lib = _bind_matrix(master.lib)
+        f, genes, contig_ptr, contig_org, repeated = self._orders(master, genes, contig_ptr, contig_org, repeated, f)
         gene_len = np.ascontiguousarray(gene_len, np.int32)
         if gene_len.shape != genes.shape or not len(genes):
             raise ValueError("family table: genes [G] and gene_len [G], G > 0")
         self.repeated_names = repeated_names
         self.names, self.organism_names = getattr(master, "names", None), getattr(master, "organism_names", None)
-        self._h = C.c_void_p()
-        rc = self.lib.nemgpu_family_table_create(C.byref(self._h), master._h, int(f), genes.ctypes.data, gene_len.ctypes.data, len(genes),
-                                                 contig_ptr.ctypes.data, contig_org.ctypes.data, len(contig_org),
-                                                 repeated.ctypes.data if repeated is not None else None)
-        if rc != 0:
-            raise NemGpuError("nemgpu_family_table_create failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
-        v = [C.c_int() for _ in range(3)]
-        self.lib.nemgpu_family_table_shape(self._h, *(C.byref(a) for a in v))
-        self.n, self.d, self.n_multi = (a.value for a in v)
-        n, nm = self.n, self.n_multi
-        for name, size, dtype in zip(FIELDS, (n, n, n, n, n, n, n + 1, nm, nm), (np.int32,) * 5 + (np.int64,) + (np.int32,) * 3):
-            setattr(self, name, np.zeros(size, dtype))
-        rc = self.lib.nemgpu_family_table_fetch(self._h, *(getattr(self, name).ctypes.data if getattr(self, name).size else None for name in FIELDS))
-        if rc != 0:
-            raise NemGpuError("nemgpu_family_table_fetch failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+        self._create(master, f, genes, (gene_len,), contig_ptr, contig_org, (), repeated)
+
+    def _sizes(self):
+        return (self.n,) * 6 + (self.n + 1, self.n_multi, self.n_multi)
 
     def copies(self, i):
         """the copy count of family i in every organism (len(node[org]), 0 where it is absent): int64 [d]"""
@@ -301,9 +342,7 @@ class FamilyTable(_Table):
 
     def rtab_size(self, row0, rows):
         size = C.c_int64()
-        rc = self.lib.nemgpu_family_table_rtab_size(self._h, int(row0), int(rows), C.byref(size))
-        if rc != 0:
-            raise NemGpuError("nemgpu_family_table_rtab_size failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
+        self._call("rtab_size", self._h, int(row0), int(rows), C.byref(size))
         return size.value
 
     def rtab_cells(self, row0=0, rows=None, out=None):
@@ -314,23 +353,8 @@ class FamilyTable(_Table):
         if out is None:
             out = np.empty(self.rtab_size(row0, rows), np.uint8)
         ends, needed = np.zeros(rows, np.int64), C.c_int64()
-        rc = self.lib.nemgpu_family_table_rtab(self._h, self.master._h, int(row0), int(rows), out.ctypes.data, out.size, C.byref(needed), ends.ctypes.data)
-        if rc != 0:
-            err = NemGpuError("nemgpu_family_table_rtab failed (status %d): %s" % (rc, self.lib.nemgpu_last_error().decode()))
-            err.needed = needed.value
-            raise err
-        return out[:needed.value], ends
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.nemgpu_family_table_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._text("rtab", out, needed, self._h, self.master._h, int(row0), int(rows), out.ctypes.data, out.size, C.byref(needed),
+                          ends.ctypes.data), ends
 
 
 class HostFamilyTable(_Table):

@@ -14,6 +14,7 @@ import pytest
 from pangenomenem_amd.chunks import Master
 from pangenomenem_amd.engine import NemGpuError
 from pangenomenem_amd.gexf import attvalues_host, edge_table_arrays, ushape_counts, write_gexf
+from tests import master_shapes as ms
 from tests.append_util import build_host
 from tests.gexf_util import GEXF_FIXTURES, contigs_orders, path_contigs, same_edge_table, same_gexf_text, sizes_of
 from tests.orders_util import load, same_master
@@ -123,6 +124,29 @@ def test_a_lines_width_changes_with_the_id_and_the_count(gpu_lib):
         text, ends = t.attvalues(ids, 0, 1)
         t.close()
         assert bytes(text).decode() == "".join('          <attvalue for="%d" value="%d" />\n' % (a, b) for a, b in zip(ids, counts)) and ends.tolist() == [len(text)]
+    finally:
+        m.close()
+
+
+@pytest.mark.parametrize("size, passes", [("pass", 1), ("pass+1", 2)])
+def test_one_gene_past_a_single_pass_of_the_scans_tile_totals(gpu_lib, size, passes):
+    """the table scans one item per gene, kept or not: at SCAN_PASS + 1 genes k_scan_partials carries from its first pass
+    into a second, in the scans of the links' and of the genes' distinct lengths alike"""
+    o = dict(ms.scan_orders(size))
+    g, cptr = len(o["genes"]), o["contig_ptr"].astype(np.int64)
+    assert ms.scan_passes(g) == passes and g == ms.SCAN_PASS + passes - 1
+    assert (np.diff(o["contig_org"]) >= 0).all()
+    rng = np.random.default_rng(29)
+    length, gap = rng.integers(90, 3000, g), rng.integers(-20, 30, g)
+    upto = np.concatenate([[0], np.cumsum(gap + length)])     # (the ENDs if all the genes were one contig, from 0)
+    end = upto[1:] - np.repeat(upto[cptr[:-1]], np.diff(cptr))                        # (every contig starts over)
+    o["starts"], o["ends"] = (end - length).astype(np.int32), end.astype(np.int32)
+    o["contig_sizes"] = np.where(o["contig_circular"] != 0, upto[cptr[1:]] - upto[cptr[:-1]] + 1000, -1).astype(np.int32)
+    m = from_orders(o)
+    try:
+        assert m.d == ms.SCAN_ORGANISMS and int((o["contig_sizes"] >= 0).sum()) > 0
+        want = device_equals_statement(m, o, "scan " + size)
+        assert int(want["weight"].max()) > 1 and int(want["len_distinct"].max()) > 2
     finally:
         m.close()
 

@@ -14,6 +14,7 @@ import pytest
 from pangenomenem_amd.chunks import Master
 from pangenomenem_amd.engine import NemGpuError
 from pangenomenem_amd.matrix import family_table_arrays, rtab_cells_host
+from tests import master_shapes as ms
 from tests.matrix_util import MATRIX_FIXTURES, counts_orders, files_equal_fixture, random_counts, same_table
 from tests.orders_util import load, same_master
 from tests.projection_util import annotations_of
@@ -133,6 +134,23 @@ def test_a_family_longer_than_a_block_next_to_families_of_one_gene(gpu_lib, leng
             assert (want["len_distinct"] == want["nb_genes"]).all()
         if lengths == "negative":
             assert (want["len_max"] < 0).all() and (want["len_sum"] < 0).all()
+    finally:
+        m.close()
+
+
+@pytest.mark.parametrize("size, passes", [("pass", 1), ("pass+1", 2)])
+def test_one_gene_past_a_single_pass_of_the_scans_tile_totals(gpu_lib, size, passes):
+    """the table scans one item per gene, kept or not: at SCAN_PASS + 1 genes k_scan_partials carries from its first pass
+    into a second, in the int scans and in the int64 scan of the distinct lengths alike"""
+    o = dict(ms.scan_orders(size))
+    g = len(o["genes"])
+    assert ms.scan_passes(g) == passes and g == ms.SCAN_PASS + passes - 1
+    o["gene_len"] = np.random.default_rng(23).integers(-50, 4000, g).astype(np.int32)
+    m = from_orders(o)
+    try:
+        assert m.d == ms.SCAN_ORGANISMS
+        want = device_equals_statement(m, o, "scan " + size, batches=[(0, 1000), (1000, m.n - 1000)])
+        assert int(want["len_distinct"].max()) > 1 and len(want["multi_cnt"]) > 0
     finally:
         m.close()
 

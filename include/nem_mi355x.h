@@ -375,6 +375,42 @@ int nemgpu_edge_table_attvalues_size(nemgpu_edge_table* t, const nemgpu_master* 
 int nemgpu_edge_table_attvalues(nemgpu_edge_table* t, const nemgpu_master* m, const int32_t* attr_id, int row0, int rows, char* text,
                                 int64_t capacity, int64_t* needed, int64_t* edge_end);
 void nemgpu_edge_table_destroy(nemgpu_edge_table* t);
+/* The pangenome graph LAID OUT on the device: PPanGGOLiN.compute_layout (ppanggolin.py:1250-1292), which hands the
+   family graph to ForceAtlas2 (Jacomy et al. 2014) and puts the positions on the nodes.  The reference delegates to the
+   external package fa2 (Barnes-Hut at theta 1.2); here the repulsion is the EXACT all-pairs sum, n^2 per iteration, and
+   what is computed is stated in numpy by pangenomenem_amd/layout.py's layout_arrays: no equality with fa2 is claimed.
+   From the master (only read, and not needed after _create returns): an edge is a CSR entry with idx > row, its weight
+   the popcount of the entry's bit row; a self-loop attracts nothing; mass[i] = 1 + the entries of row i.  A bits-only
+   master is fine (the weights are popcounts); n = 0 gives an empty layout.
+     cfg     compute_layout's parameters; lin_log, adjust_sizes and strong_gravity == 0 are refused;
+     pos     the start positions, double [n][2], finite.
+   float64 throughout, IEEE division and square root, no float atomics: every term is the statement's, bit for bit, only
+   the order of the sums is the device's own (the slices of a node's j range in order, a row's entries in order, fixed
+   trees for S and T), so a result is a function of the inputs alone.  Positions, forces and the speed control's state
+   stay on the device: _run(3) then _run(2) is _run(5).  _run enqueues `iterations` iterations on the layout's stream and
+   does not wait for them; _fetch does.
+   _fetch: pos [n][2], forces [n][2] (the last iteration's), state [5] = speed, eff (the speed efficiency), S, T (the
+   last iteration's global swinging and traction), iterations done; any may be NULL.
+   Refused on the host before any launch (NEMGPU_E_ARG, nemgpu_last_error says why): the modes above, a parameter or a
+   start position that is not finite, iterations < 0, a master built with directed = 1 (a DiGraph's weight is per
+   direction, the master holds only the sum).
+   _slices: the slices a node's j range is cut into for n families (a function of n alone), the repulsion kernel's tile
+   width and the least slice length; host only. */
+typedef struct nemgpu_layout nemgpu_layout;
+typedef struct {
+    double scaling_ratio;                 /* 50000 */
+    double gravity;                       /* 1 */
+    double edge_weight_influence;         /* 1; 0: every edge counts 1; else weight ** influence */
+    double jitter_tolerance;              /* 1 */
+    int strong_gravity;                   /* 1 (0 is refused) */
+    int outbound_attraction_distribution; /* 1 */
+    int lin_log, adjust_sizes;            /* 0 (anything else is refused) */
+} nemgpu_layout_config;
+int nemgpu_layout_create(nemgpu_layout** out, const nemgpu_master* m, const nemgpu_layout_config* cfg, const double* pos);
+int nemgpu_layout_run(nemgpu_layout* l, int iterations);
+int nemgpu_layout_fetch(nemgpu_layout* l, double* pos, double* forces, double* state);
+void nemgpu_layout_destroy(nemgpu_layout* l);
+int nemgpu_layout_slices(int n, int* tile, int* slice_grain);
 /* What a master holds, of whichever constructor: sizes (n families, d organisms, nnz CSR entries, n_extra pairs with
    count >= 2; any pointer may be NULL), and the arrays as nemgpu_master_create_counts takes them, read back from the
    device: xbits[n][ceil(d/32)], nei_ptr[n + 1], nei_idx[nnz], edge_bits[nnz][ceil(d/32)], extra_ptr[nnz + 1],

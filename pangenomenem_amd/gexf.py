@@ -363,14 +363,16 @@ def _lengths(total, count, lo, hi, low, high):
 
 
 def write_gexf(path, partitions, family_table, edge_table, annotations, all_node_attributes=True, all_edge_attributes=True, compressed=False,
-               budget=TEXT_BUDGET):
+               budget=TEXT_BUDGET, positions=None):
     """<path>.gexf (compressed: <path>.gexf.gz through gzip) as PPanGGOLiN.export_to_GEXF and networkx's write_gexf write
     it for a partitioned nx.Graph (ppanggolin.py:1294-1362), streamed: no networkx, no tree.  partitions: what
     Master.partition returned, or uint8 [n]; family_table, edge_table: Master.family_table / Master.edge_table (or their
     host forms) of the same master and annotations; annotations: the ones the tables were made from, walked in column
     order (the genes' ids, names and products are read from them).  all_node_attributes / all_edge_attributes False: the
     `_light` export, without the organism keys; it formats no text on the device.  An edge's organism lines are the
-    device's bytes, a slice per edge."""
+    device's bytes, a slice per edge.  positions: float64 [n][2] in master order (Layout.positions(), layout.py): every
+    node gets the <viz:position> that compute_layout's dict makes networkx write (ppanggolin.py:1285-1292), z = 2 for a
+    persistent family, 1 for a shell one, 0 otherwise."""
     ft, et = family_table, edge_table
     names, orgs = ft.names, ft.organism_names
     if names is None or orgs is None:
@@ -379,6 +381,10 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
         raise ValueError("write_gexf: the two tables are not of one master")
     n, d = ft.n, ft.d
     longs = _long_names(partitions, names, n)
+    if positions is not None:
+        positions = np.asarray(positions, np.float64)
+        if positions.shape != (n, 2):
+            raise ValueError("write_gexf: positions float64 [n][2]")
     index = {name: i for i, name in enumerate(names)}
     gene_names, products, cells = [dict() for _ in names], [dict() for _ in names], [dict() for _ in names]   # (insertion-ordered sets)
     by_org = ft.repeated_names if isinstance(ft.repeated_names, dict) else None
@@ -441,9 +447,12 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
             name = escape(names[i])
             lines = ['      <node id="%s" label="%s">\n' % (name, name),
                      '        <viz:color r="%d" g="%d" b="%d" a="0" />\n' % color,
-                     '        <viz:size value="%d" />\n' % nb_org,
-                     "        <attvalues>\n",
-                     att % (node_ids["nb_genes"], int(ft.nb_genes[i]))]
+                     '        <viz:size value="%d" />\n' % nb_org]
+            if positions is not None:
+                lines.append('        <viz:position x="%s" y="%s" z="%d" />\n'
+                             % (str(float(positions[i, 0])), str(float(positions[i, 1])), {"persistent": 2, "shell": 1}.get(longs[i], 0)))
+            lines += ["        <attvalues>\n",
+                      att % (node_ids["nb_genes"], int(ft.nb_genes[i]))]
             present = node_keys[i]
             for org in present[:1]:
                 lines.append(att % (node_ids[org], escape("|".join(cells[i][org]))))

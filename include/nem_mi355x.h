@@ -377,7 +377,8 @@ int nemgpu_edge_table_attvalues(nemgpu_edge_table* t, const nemgpu_master* m, co
 void nemgpu_edge_table_destroy(nemgpu_edge_table* t);
 /* The pangenome graph LAID OUT on the device: PPanGGOLiN.compute_layout (ppanggolin.py:1250-1292), which hands the
    family graph to ForceAtlas2 (Jacomy et al. 2014) and puts the positions on the nodes.  The reference delegates to the
-   external package fa2 (Barnes-Hut at theta 1.2); here the repulsion is the EXACT all-pairs sum, n^2 per iteration, and
+   external package fa2 (Barnes-Hut at theta 1.2); here the repulsion is the EXACT all-pairs sum, n^2 per iteration
+   (nemgpu_layout_create_bh below: a Barnes-Hut sum), and
    what is computed is stated in numpy by pangenomenem_amd/layout.py's layout_arrays: no equality with fa2 is claimed.
    From the master (only read, and not needed after _create returns): an edge is a CSR entry with idx > row, its weight
    the popcount of the entry's bit row; a self-loop attracts nothing; mass[i] = 1 + the entries of row i.  A bits-only
@@ -411,6 +412,29 @@ int nemgpu_layout_run(nemgpu_layout* l, int iterations);
 int nemgpu_layout_fetch(nemgpu_layout* l, double* pos, double* forces, double* state);
 void nemgpu_layout_destroy(nemgpu_layout* l);
 int nemgpu_layout_slices(int n, int* tile, int* slice_grain);
+/* The same layout with the repulsion as a BARNES-HUT sum, what compute_layout asks of fa2 (barnesHutOptimize=True,
+   barnesHutTheta=1.2): O(n log n) per iteration.  The tree is this project's own, stated rule by rule in numpy by
+   pangenomenem_amd/layout_bh.py (tree_arrays, walk, layout_bh_arrays) -- a square around the bodies, 32-bit Morton keys
+   on a 2^16 grid, the bodies sorted by (key, index), a cell per run of equal key prefix under a run of more than LEAF
+   bodies, moments summed left to right, a depth-first walk that accepts an inner cell not holding the body iff
+   theta^2 d2 > size^2 -- and the device is held to it bit for bit: keys, order, cells, moments and every force; only the
+   order of S and T is the device's.  How fa2 splits its regions and sizes them could not be checked: no equality with
+   fa2 is claimed.  nemgpu_layout_create and its exact sum stay the default; this is the opt-in.
+   _create_bh: nemgpu_layout_create's arguments and theta >= 0, finite (0: every cell is opened, the exact pair set in
+   tree order).  The same handle: _run, _fetch and _destroy work on it.  Refused on the host before any HIP call
+   (NEMGPU_E_ARG, nemgpu_last_error says why): a theta that is negative or not finite, and all that _create refuses.
+   Everything is allocated here, for the statement's bound on the cells, 1 + DEPTH min(n, 4 (n / (LEAF + 1))): _run only
+   enqueues.
+   _bh_shape: DEPTH and LEAF; host only.
+   _bh_tree: the tree of the CURRENT positions, built and copied to host buffers, any of them NULL: *n_cells; box [3] = x0,
+   y0, side; keys, order [n] in sorted order (order: sorted position -> family); level, lo, hi, M, Sx, Sy with room for
+   the bound above (n_cells are written); accepted, visited [n] per family: the cells its walk accepted and the bodies
+   of the leaves it opened.  It changes no state (a run continued after it gives the same bits) and waits for the
+   layout's stream.  A layout made by nemgpu_layout_create is refused (NEMGPU_E_ARG). */
+int nemgpu_layout_create_bh(nemgpu_layout** out, const nemgpu_master* m, const nemgpu_layout_config* cfg, const double* pos, double theta);
+int nemgpu_layout_bh_shape(int* depth, int* leaf);
+int nemgpu_layout_bh_tree(nemgpu_layout* l, int* n_cells, double* box, uint32_t* keys, int32_t* order, int32_t* level, int32_t* lo, int32_t* hi,
+                          double* M, double* Sx, double* Sy, int32_t* accepted, int32_t* visited);
 /* What a master holds, of whichever constructor: sizes (n families, d organisms, nnz CSR entries, n_extra pairs with
    count >= 2; any pointer may be NULL), and the arrays as nemgpu_master_create_counts takes them, read back from the
    device: xbits[n][ceil(d/32)], nei_ptr[n + 1], nei_idx[nnz], edge_bits[nnz][ceil(d/32)], extra_ptr[nnz + 1],

@@ -668,15 +668,18 @@ class Master:
         o = gexf.gexf_orders(annotations, self.organism_names, self.id_names, by_org, circular_contig_size, family)
         return gexf.EdgeTable(self, o["genes"], o["starts"], o["ends"], o["contig_ptr"], o["contig_org"], o["contig_sizes"], o["repeated"])
 
-    def layout(self, iterations=500, pos=None, rng=None, **params):
+    def layout(self, iterations=500, pos=None, rng=None, repulsion="exact", theta=1.2, **params):
         """The family graph laid out on the device (PPanGGOLiN.compute_layout, ppanggolin.py:1250-1292; nemgpu_layout_*;
         layout.layout_arrays states what it computes: ForceAtlas2 with an exact all-pairs repulsion, n^2 per iteration).
         pos: the start positions float64 [n][2], or rng (default: the `random` module): per family in master order x =
         rng.random(), then y = rng.random(); params: compute_layout's, in layout.DEFAULTS' names.  `iterations` are
-        enqueued at once.  LinLog, adjust_sizes, strong_gravity=False and a directed master raise ValueError.  Returns a
-        layout.Layout (run(k), positions(), forces(), state(), close()); this master is only read."""
+        enqueued at once.  LinLog, adjust_sizes, strong_gravity=False and a directed master raise ValueError.
+        repulsion="barnes_hut" (compute_layout's barnesHutOptimize=True) sums the repulsion over a tree instead, n log n
+        per iteration, theta (barnesHutTheta, 1.2; >= 0 and finite, read for this repulsion alone) the opening angle:
+        layout_bh.layout_bh_arrays states it; the tree is this project's, not fa2's.  Any other repulsion: ValueError.
+        Returns a layout.Layout (run(k), positions(), forces(), state(), tree(), close()); this master is only read."""
         from . import layout as ly
-        return ly.Layout(self, pos=pos, rng=rng, **params).run(iterations)
+        return ly.Layout(self, pos=pos, rng=rng, repulsion=repulsion, theta=theta, **params).run(iterations)
 
     def shape(self):
         """(n families, d organisms, nnz CSR entries, pairs with count >= 2) as the device holds them (nemgpu_master_shape)"""

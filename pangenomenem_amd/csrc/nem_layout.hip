@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "nem_internal.hpp"
+#include "nem_layout_bh.hpp"
 #include "nem_master.hpp"
 #include "nem_table.hpp"
 
@@ -191,6 +192,12 @@ void launch_layout_iteration(const LayoutDev& l, const LayoutParams& p, hipStrea
     if (l.n <= 0) return;
     hipLaunchKernelGGL(k_layout_repulse, dim3(l.blocks, l.slices), dim3(kLayoutTile), 0, s, (const double*)l.x, (const double*)l.y,
                        (const double*)l.mass, l.n, l.slice_len, p.scaling, l.px, l.py);
+    launch_layout_rest(l, p, s);
+}
+
+void launch_layout_rest(const LayoutDev& l, const LayoutParams& p, hipStream_t s)
+{
+    if (l.n <= 0) return;
     hipLaunchKernelGGL(k_layout_forces, dim3(l.blocks), dim3(kLayoutTile), 0, s, l, p.gravity);
     hipLaunchKernelGGL(k_layout_speed, dim3(1), dim3(kLayoutTile), 0, s, l, p);
     hipLaunchKernelGGL(k_layout_move, dim3(l.blocks), dim3(kLayoutTile), 0, s, l);
@@ -200,20 +207,11 @@ void launch_layout_iteration(const LayoutDev& l, const LayoutParams& p, hipStrea
 
 using namespace nemk;
 
-// A layout on the device: its own allocation and stream; the master is read at creation only
-struct nemgpu_layout {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    char* block = nullptr;
-    LayoutDev dev{};
-    LayoutParams par{};
-    long long iterations = 0;
-};
-
 namespace {
 
 void layout_free(nemgpu_layout* l)
 {
+    if (l->bh) layout_bh_free(l->bh);
     if (l->block) (void)hipFree(l->block);
     if (l->stream) (void)hipStreamDestroy(l->stream);
     delete l;
@@ -249,12 +247,13 @@ int nemgpu_layout_slices(int n, int* tile, int* slice_grain)
     return layout_slices(n);
 }
 
-int nemgpu_layout_create(nemgpu_layout** out, const nemgpu_master* m, const nemgpu_layout_config* cfg, const double* pos)
+int nemk::layout_create(nemgpu_layout** out, const nemgpu_master* m, const nemgpu_layout_config* cfg, const double* pos, const char* name,
+                        const double* theta)
 {
     if (!out) return NEMGPU_E_FUNCARG;
     *out = nullptr;
     if (!m || !cfg) return NEMGPU_E_FUNCARG;
-    const std::string who = "nemgpu_layout_create";
+    const std::string who = name;
     if (cfg->lin_log) { set_error(who + ": the LinLog mode is not supported"); return NEMGPU_E_ARG; }
     if (cfg->adjust_sizes) { set_error(who + ": adjust_sizes (the anti-collision forces) is not supported"); return NEMGPU_E_ARG; }
     if (!cfg->strong_gravity) { set_error(who + ": only the strong gravity mode is supported"); return NEMGPU_E_ARG; }
@@ -275,7 +274,7 @@ int nemgpu_layout_create(nemgpu_layout** out, const nemgpu_master* m, const nemg
     l->device = m->device;
     LayoutDev& v = l->dev;
     v.n = n; v.nnz = nnz;
-    v.slices = layout_slices(n);
+    v.slices = theta ? 1 : layout_slices(n);                  // (the walk writes one sum per body)
     v.slice_len = n > 0 ? (n + v.slices - 1) / v.slices : 1;
     v.blocks = (n + kLayoutTile - 1) / kLayoutTile;
     const double est = 0.05 * std::sqrt((double)n);
@@ -324,10 +323,16 @@ int nemgpu_layout_create(nemgpu_layout** out, const nemgpu_master* m, const nemg
         launch_layout_setup(m->dev, v, cfg->outbound_attraction_distribution != 0, kind, pow_w.empty() ? nullptr : pow_dev, s);
         err = hipGetLastError();
     }
+    if (err == hipSuccess && theta) err = layout_bh_create(&l->bh, n, *theta, s);
     if (err == hipSuccess) err = hipStreamSynchronize(s);     // (the host vectors above go out of scope; the master may be destroyed)
     if (err != hipSuccess) { layout_free(l); return device_status(who, err); }
     *out = l;
     return NEMGPU_OK;
+}
+
+int nemgpu_layout_create(nemgpu_layout** out, const nemgpu_master* m, const nemgpu_layout_config* cfg, const double* pos)
+{
+    return layout_create(out, m, cfg, pos, "nemgpu_layout_create", nullptr);
 }
 
 int nemgpu_layout_run(nemgpu_layout* l, int iterations)
@@ -335,9 +340,17 @@ int nemgpu_layout_run(nemgpu_layout* l, int iterations)
     if (!l) return NEMGPU_E_FUNCARG;
     if (iterations < 0) { set_error("nemgpu_layout_run: iterations < 0"); return NEMGPU_E_ARG; }
     HIPCHK(hipSetDevice(l->device));
-    for (int it = 0; it < iterations; it++) launch_layout_iteration(l->dev, l->par, l->stream);
+    hipError_t err = hipSuccess;
+    for (int it = 0; it < iterations && err == hipSuccess; it++) {
+        if (l->bh) {
+            err = launch_layout_bh_repulse(l->dev, l->par, l->bh, false, l->stream);
+            if (err == hipSuccess) launch_layout_rest(l->dev, l->par, l->stream);
+        } else {
+            launch_layout_iteration(l->dev, l->par, l->stream);
+        }
+    }
     l->iterations += iterations;
-    return device_status("nemgpu_layout_run", hipGetLastError());
+    return device_status("nemgpu_layout_run", err != hipSuccess ? err : hipGetLastError());
 }
 
 int nemgpu_layout_fetch(nemgpu_layout* l, double* pos, double* forces, double* state)

@@ -1,11 +1,14 @@
 // nem_layout.hpp -- the pangenome graph laid out on the device: ForceAtlas2 (Jacomy et al. 2014) with an exact all-pairs
 // repulsion, strong gravity, the attraction as a gather over the master's CSR rows and the speed control on the device
 // (nem_layout.hip; pangenomenem_amd/layout.py's layout_arrays is the statement).  float64 throughout; no float atomics,
-// no wait of one block for another: an iteration is four plain launches in stream order.
+// no wait of one block for another: an iteration is four plain launches in stream order.  A layout made by
+// nemgpu_layout_create_bh takes step 1 from nem_layout_bh.hpp instead (a Barnes-Hut sum, one slice); steps 2 - 6 are the same
+// three launches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "../../include/nem_mi355x.h"
 #include "nem_chunks.hpp"
 
 namespace nemk {
@@ -56,7 +59,30 @@ struct LayoutParams {
 
 // masses and edge factors from the master (only read); pow_w [d + 1]: weight ** influence for influence not 0 or 1, else null
 void launch_layout_setup(const MasterDev& m, const LayoutDev& l, bool distributed, int influence_kind, const double* pow_w, hipStream_t s);
-// one iteration
+// one iteration with the exact repulsion
 void launch_layout_iteration(const LayoutDev& l, const LayoutParams& p, hipStream_t s);
+// steps 2 - 6 of one iteration, behind whichever step 1 filled l.px, l.py
+void launch_layout_rest(const LayoutDev& l, const LayoutParams& p, hipStream_t s);
+
+struct LayoutBh;                          // nem_layout_bh.hpp
+
+}  // namespace nemk
+
+// A layout on the device: its own allocation and stream; the master is read at creation only
+struct nemgpu_layout {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    char* block = nullptr;
+    nemk::LayoutDev dev{};
+    nemk::LayoutParams par{};
+    long long iterations = 0;
+    nemk::LayoutBh* bh = nullptr;         // made by nemgpu_layout_create_bh: the tree's arrays, else null
+};
+
+namespace nemk {
+
+// nemgpu_layout_create (theta null) and nemgpu_layout_create_bh (theta checked by the caller) under the name `who`
+int layout_create(nemgpu_layout** out, const nemgpu_master* m, const nemgpu_layout_config* cfg, const double* pos, const char* who,
+                  const double* theta);
 
 }  // namespace nemk

@@ -13,7 +13,8 @@ runs it on the device and is held to the statement: every term is bit-equal, onl
 device's; ``Master.layout`` (chunks.py) is the Python surface and ``Layout`` the handle; ``positions_3d`` gives ``z``.
 No equality with fa2's output is claimed, and the start stream (x then y from ``random.random()`` per node, in node order,
 what fa2 is understood to do for ``pos=None``) could not be checked against fa2: the package is not part of the reference.
-The cost grows as n^2 per iteration.
+The cost grows as n^2 per iteration.  ``repulsion="barnes_hut"`` (``layout_bh.py``: its own statement, tree and walk; this
+project's tree, not fa2's) is the opt-in that grows as n log n; ``layout_arrays`` and the default stay the exact sum.
 """
 import ctypes as C
 import math
@@ -30,6 +31,7 @@ BLOCKS_TARGET, SLICES_MAX = 1024, 64
 DEFAULTS = dict(scaling_ratio=50000.0, gravity=1.0, strong_gravity=True, outbound_attraction_distribution=True, edge_weight_influence=1.0,
                 jitter_tolerance=1.0, lin_log=False, adjust_sizes=False)
 ORDERS = ("numpy", "left", "perm", "fsum")
+REPULSIONS = ("exact", "barnes_hut")                          # Layout's repulsion=: the all-pairs sum, or layout_bh.py's tree
 
 
 def slices_of(n):
@@ -269,6 +271,9 @@ def _bind_layout(lib):
     lib.nemgpu_layout_destroy.argtypes = [C.c_void_p]
     lib.nemgpu_layout_destroy.restype = None
     lib.nemgpu_layout_slices.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.nemgpu_layout_create_bh.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(LayoutConfig), C.c_void_p, C.c_double]
+    lib.nemgpu_layout_bh_shape.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.nemgpu_layout_bh_tree.argtypes = [C.c_void_p, C.POINTER(C.c_int)] + [C.c_void_p] * 11
     return lib
 
 
@@ -279,10 +284,17 @@ def config_of(p):
 
 class Layout:
     """A layout on the device (nemgpu_layout_create): positions, forces and the speed control's state stay there between
-    run() calls.  The master is read at creation only."""
+    run() calls.  The master is read at creation only.  repulsion: "exact" (the all-pairs sum, the default) or
+    "barnes_hut" (nemgpu_layout_create_bh: layout_bh.py states the tree and the walk; theta is read for it alone)."""
 
-    def __init__(self, master, pos=None, rng=None, **params):
+    def __init__(self, master, pos=None, rng=None, repulsion="exact", theta=1.2, **params):
         p = check_params(params)
+        if repulsion not in REPULSIONS:
+            raise ValueError("layout: repulsion one of %s" % (REPULSIONS,))
+        self.repulsion = repulsion
+        if repulsion == "barnes_hut":
+            from .layout_bh import check_theta
+            self.theta = check_theta(theta)
         if getattr(master, "directed", False):
             raise ValueError("layout: a directed master (a DiGraph's weight is per direction, the master holds only the sum)")
         self.lib = _bind_layout(master.lib)
@@ -291,7 +303,10 @@ class Layout:
         self.names = getattr(master, "names", None)
         self._h = C.c_void_p()
         cfg = config_of(p)
-        self._call("create", C.byref(self._h), master._h, C.byref(cfg), start.ctypes.data if self.n else None)
+        if repulsion == "barnes_hut":
+            self._call("create_bh", C.byref(self._h), master._h, C.byref(cfg), start.ctypes.data if self.n else None, self.theta)
+        else:
+            self._call("create", C.byref(self._h), master._h, C.byref(cfg), start.ctypes.data if self.n else None)
 
     def _call(self, name, *args):
         rc = getattr(self.lib, "nemgpu_layout_" + name)(*args)
@@ -325,6 +340,28 @@ class Layout:
         v = np.zeros(5, np.float64)
         self._fetch(state=v)
         return dict(speed=float(v[0]), eff=float(v[1]), S=float(v[2]), T=float(v[3]), iterations=int(v[4]))
+
+    def tree(self):
+        """The Barnes-Hut tree of the current positions as the device builds it (nemgpu_layout_bh_tree): what
+        layout_bh.tree_arrays returns, and accepted, visited int64 [n] (the walk's counters per family).  It changes no
+        state.  A layout with the exact repulsion has no tree: NemGpuError."""
+        from . import layout_bh as bh
+        n, cap = self.n, bh.cell_bound(self.n)
+        cells, box = C.c_int(), np.zeros(3, np.float64)
+        skey, order = np.zeros(n, np.uint32), np.zeros(n, np.int32)
+        level, lo, hi = (np.zeros(cap, np.int32) for _ in range(3))
+        M, Sx, Sy = (np.zeros(cap, np.float64) for _ in range(3))
+        accepted, visited = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._call("bh_tree", self._h, C.byref(cells), *(a.ctypes.data if a.size else None for a in (box, skey, order, level, lo, hi, M, Sx, Sy, accepted, visited)))
+        nc = cells.value
+        order = order.astype(np.int64)
+        key = np.zeros(n, np.uint32)
+        key[order] = skey
+        level, lo, hi = (a[:nc].astype(np.int64) for a in (level, lo, hi))
+        child, rope = bh.links(skey, level, lo, hi) if nc else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+        return dict(n=n, x0=float(box[0]), y0=float(box[1]), side=float(box[2]), key=key, order=order, cells=nc, level=level, lo=lo, hi=hi, M=M[:nc].copy(),
+                    Sx=Sx[:nc].copy(), Sy=Sy[:nc].copy(), child=child, rope=rope, bound=cap, accepted=accepted.astype(np.int64),
+                    visited=visited.astype(np.int64))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

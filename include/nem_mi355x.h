@@ -468,6 +468,34 @@ typedef struct {
 int nemgpu_solve_chunks(nemgpu_master* m, nemgpu_chunk* chunks, int count, int k, const float* prop, const float* center_k,
                         const float* disp_k, const nemgpu_config* cfg, int workers, int group);
 
+/* ---- The sub-problem of a selection of families (partition_shell) ------------------------------------------------
+   partition_shell (ppanggolin.py:1175-1248, the CLI's -ss) solves the NEM problem of the shell families alone:
+   `__write_nem_input_files(dir, organisms, init, filter_by_partition="shell")` keeps the nodes whose partition is
+   "shell" (:844), in node order, and runs INIT_RANDOM (50 starts) or a parameter file on them.
+   nemgpu_master_subproblem forms that problem on the device from the resident master and hands back an ENGINE of
+   n x dc and k classes that holds it: organisms[dc] are the columns (distinct indices of the master's organisms),
+   select_bytes[n_master] the selection (non-zero: selected; packed to bits on the device).  A family is kept iff it is
+   selected and present in one of the organisms; families_out[n] (room for n_master; may be NULL) lists the kept
+   families' master indices, *n and *nnz the problem's sizes.  edge_rule:
+     0, induced:   an edge is kept iff its coverage over the organisms is positive and both ends are kept (the writer's
+                   evident intent: what it writes, unfiltered, for neighbors_graph.subgraph(shell));
+     1, reference: the writer as written.  Its test at :859 is inverted: a neighbour that IS shell is skipped, one that
+                   is NOT reaches index_fam[neighbor] without an entry (KeyError).  No edge is kept; when a kept family
+                   has an entry of positive coverage to a family that is not selected, *outside_entry is the smallest
+                   such CSR entry of the master, NO engine is made (*engine stays NULL) and the call returns NEMGPU_OK:
+                   the caller raises the KeyError naming nei_idx[*outside_entry].  Else *outside_entry is -1.
+   The formed bit rows also come back into the engine's host rows, so that nemgpu_run_random (which draws its centres
+   from them), nemgpu_set_params + nemgpu_run and nemgpu_get_results work on the engine as on any other; the caller
+   configures it, runs it and destroys it (nemgpu_destroy).  The master is only read.
+   NEMGPU_E_ARG, before any launch: an organism out of range or given twice, k <= 0 or k > 32, a selection without a
+   family, a master built directed (nx.all_neighbors of a DiGraph is not its row).  NEMGPU_E_ARG after phase 1: no
+   selected family is present in the organisms.
+   nemgpu_subproblem_fetch reads the formed problem back (HOST buffers; any may be NULL): xbits[n][ceil(dc/32)],
+   ptr[n + 1], idx[nnz], w[nnz]. */
+int nemgpu_master_subproblem(nemgpu_master* m, const int32_t* organisms, int dc, const uint8_t* select_bytes, int edge_rule, int k,
+                             nemgpu_engine** engine, int32_t* families_out, int* n, int* nnz, int* outside_entry);
+int nemgpu_subproblem_fetch(nemgpu_engine* e, uint32_t* xbits, int32_t* ptr, int32_t* idx, float* w);
+
 /* ---- The vote of partition()'s loop over the samples ----------------------------------------------------------
    partition() (ppanggolin.py:1015-1105) counts, per family of the pangenome, the P/S/C/U votes of the samples' runs
    (run_partitioning, :1886-1980: P/S/C if the class with the most non-zero centres is class 0 and the one with the

@@ -681,6 +681,33 @@ class Master:
         from . import layout as ly
         return ly.Layout(self, pos=pos, rng=rng, repulsion=repulsion, theta=theta, **params).run(iterations)
 
+    def partition_shell(self, partitions=None, Q="auto", mean_shell=None, beta=0.5, free_dispersion=False, exclusity_th=0.1,
+                        init_using_qual=None, edges="induced", seed=None, subpart_name="subpartition_shell", *, select=None,
+                        annotations=None, repeated=(), low_disp=0.1):
+        """PPanGGOLiN.partition_shell (ppanggolin.py:1175-1248, the CLI's -ss) on this master: the NEM problem of the shell
+        families and all organisms is formed on the device (nemgpu_master_subproblem; shell.form_subproblem_host states
+        it), run there and labelled as the reference labels it (shell.shell_labels).  partitions: what Master.partition
+        returned ({family: 'P' | 'S' | 'C' | 'U'}); or select= bool [n] for a master without names.
+        Q: "auto" (without init_using_qual: projection.shell_q_auto of mean_shell = Projection.means()[1], or of the
+        projection this call runs itself when given annotations= [and repeated=]; with a dict: len + 1; with a list: 3) or
+        an int; 1 or less is the reference's error (ValueError), more than 32 is refused.
+        edges: "induced" (default) keeps the edges between shell families -- the writer's evident intent.  "reference" is
+        the writer as written: its test at :859 is inverted (a neighbour that IS shell is skipped, one that is NOT has no
+        index), so it raises KeyError naming a non-shell neighbour as soon as a shell family has one, and runs on an
+        empty graph when the shell is closed under adjacency; on a real pangenome it cannot return.
+        init_using_qual: None (INIT_RANDOM, 50 starts), a dict {group: set(organisms)} or a list (positive, negative):
+        shell.shell_init_params' parameter file (ValueError where nem() refuses it), set_params + run.
+        seed: None is time(), as the reference seeds; it is the starts' stream and the tie stream (one random() stream, as
+        in nem()).  The numbers in the labels and in .parameters went through the `.mf`'s print formats ("%5.3g",
+        "%10g", "%10.3g"), as the reference reads them.  A run that emptied a class raises KeyError('U'), as the
+        reference does.  Not here: the untangled graph, metadata= (the CLI's -ss 0 builds its dict from a metadata
+        file; the dict itself is supported).  A directed master raises NemGpuError.  This master is only read.
+        Returns a shell.ShellSubpartition: Q, parameters {label: ([organisms], mean eps, proportion)}, organisms
+        {organism: {labels}}, families {label: [families]}, node_attribute {family: label | its partition's long name}."""
+        from . import shell
+        return shell.partition_shell(self, partitions, Q, mean_shell, beta, free_dispersion, exclusity_th, init_using_qual, edges, seed,
+                                     subpart_name, select, annotations, repeated, low_disp)
+
     def shape(self):
         """(n families, d organisms, nnz CSR entries, pairs with count >= 2) as the device holds them (nemgpu_master_shape)"""
         v = [C.c_int() for _ in range(4)]

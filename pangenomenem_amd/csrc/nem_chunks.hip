@@ -3,6 +3,7 @@
 // of partition()'s voting loop, ppanggolin.py:1045-1086).  Integer / bit work only; gfx950, wave64.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 
 #include "nem_chunks.hpp"
@@ -65,9 +66,19 @@ __global__ __launch_bounds__(256) void k_chunk_mask(const ChunkPlan* __restrict_
     __syncthreads();
     for (int w = threadIdx.x; w < wf; w += 256) p.mask[w] = s_mask[w];
     if (threadIdx.x < 2) p.counts[threadIdx.x] = 0;
+    if (threadIdx.x == 2 && p.outside) *p.outside = INT_MAX;
+}
+
+// one byte per family -> the selection's bit set: a wave packs 64 families into a word with one ballot
+__global__ __launch_bounds__(256) void k_select_pack(const uint8_t* __restrict__ bytes, int n, int nw64, uint64_t* __restrict__ bits)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const uint64_t word = __ballot(i < n && bytes[i] != 0);
+    if ((threadIdx.x & 63) == 0 && (i >> 6) < nw64) bits[i >> 6] = word;
 }
 
 // families present in at least one sampled organism (ppanggolin.py:849: `if not organisms.isdisjoint(node_organisms)`)
+// and, with a selection, selected (:844)
 __global__ __launch_bounds__(256) void k_chunk_keep(const ChunkPlan* __restrict__ plans, const uint64_t* __restrict__ xt, int nw64)
 {
     const ChunkPlan p = plans[blockIdx.y];
@@ -75,7 +86,7 @@ __global__ __launch_bounds__(256) void k_chunk_keep(const ChunkPlan* __restrict_
     if (g >= nw64) return;
     uint64_t acc = 0;
     for (int t = 0; t < p.dc; t++) acc |= xt[(size_t)p.organisms[t] * nw64 + g];
-    p.keep[g] = acc;
+    p.keep[g] = p.select ? acc & p.select[g] : acc;
 }
 
 // the kept families numbered in the master's order (index_fam, ppanggolin.py:851): list[j] = master index, map[i] = j | -1
@@ -149,10 +160,20 @@ __global__ __launch_bounds__(256) void k_chunk_cov(const ChunkPlan* __restrict__
 }
 
 // an edge of the chunk's graph: carried by a sampled organism (`if coverage == 0: continue`, ppanggolin.py:877), between
-// two kept families (always so when the edge sets agree with the matrix; an edge to a dropped family is dropped too)
+// two kept families (always so when the edge sets agree with the matrix; an edge to a dropped family is dropped too).
+// kEdgeReference keeps none (nem_chunks.hpp).
 __device__ __forceinline__ bool chunk_edge(const ChunkPlan& p, const int* __restrict__ nei_idx, int e)
 {
-    return p.cov[e] != 0 && p.map[nei_idx[e]] >= 0;
+    return p.edge_rule == kEdgeInduced && p.cov[e] != 0 && p.map[nei_idx[e]] >= 0;
+}
+
+// kEdgeReference: the smallest CSR entry of row i that the writer has no index for (coverage > 0, neighbour not selected)
+__device__ __forceinline__ void chunk_outside(const ChunkPlan& p, const int* __restrict__ nei_ptr, const int* __restrict__ nei_idx, int i)
+{
+    for (int e = nei_ptr[i]; e < nei_ptr[i + 1]; e++) {
+        const int b = nei_idx[e];
+        if (p.cov[e] != 0 && !((p.select[b >> 6] >> (b & 63)) & 1ull)) { atomicMin(p.outside, e); return; }
+    }
 }
 
 // row pointers of the chunk's graph over the kept families
@@ -168,6 +189,7 @@ __global__ __launch_bounds__(1024) void k_chunk_ptr(const ChunkPlan* __restrict_
         if (j < nc) {
             const int i = p.list[j];
             for (int e = nei_ptr[i]; e < nei_ptr[i + 1]; e++) deg += chunk_edge(p, nei_idx, e) ? 1 : 0;
+            if (p.edge_rule == kEdgeReference && p.outside && p.select) chunk_outside(p, nei_ptr, nei_idx, i);
         }
         int total = 0;
         const int off = block_scan_1024(deg, &total);
@@ -250,6 +272,11 @@ __global__ __launch_bounds__(256) void k_chunk_graph(ChunkPlan p, ChunkFill f, c
 void launch_master_transpose(const uint32_t* xf, int n, int wf, int d, int nw64, uint64_t* xt, hipStream_t s)
 {
     hipLaunchKernelGGL(k_master_transpose, dim3(nw64, wf), dim3(64), 0, s, xf, n, wf, d, nw64, xt);
+}
+
+void launch_select_pack(const uint8_t* bytes, int n, int nw64, uint64_t* bits, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_select_pack, dim3((nw64 * 64 + 255) / 256), dim3(256), 0, s, bytes, n, nw64, bits);
 }
 
 void launch_chunk_plan(const MasterDev& m, const ChunkPlan* plans_dev, int count, int max_dc, hipStream_t s)

@@ -13,6 +13,15 @@
 // problem is FORMED there: no matrix, no graph crosses PCIe per chunk.  The coverage of edge e in a sample is
 // popc(edge_bits[e] & mask) + sum over e's extras in the sample of (count - 1); a master without extras (every count 1)
 // is the bits alone.
+//
+// A plan may also carry a SELECTION of the master's families and an edge rule: the sub-problem of
+// `__write_nem_input_files(..., filter_by_partition="shell")` (ppanggolin.py:844 and :859, what partition_shell solves).
+// A family is then kept iff it is selected and present in a sampled organism; the numbering stays the master's order.
+//   * kEdgeInduced: an edge is kept iff its coverage is positive and both ends are kept (the induced subgraph, the
+//     writer's evident intent);
+//   * kEdgeReference: the writer as written.  Its test at :859 is inverted -- a neighbour that IS selected is skipped --
+//     so no edge is ever kept, and a neighbour of positive coverage that is NOT selected has no index (its KeyError):
+//     phase 1 reports the smallest CSR entry of a kept family that has one.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -42,7 +51,12 @@ struct ChunkPlan {
     uint32_t* cov;                // [nnz]    coverage of every directed master edge in the sample
     int* ptr;                     // [n + 1]  CSR row pointers of the chunk's graph (kept rows)
     int* counts;                  // [2]      {kept families, kept directed edges}
+    const uint64_t* select = nullptr;   // [nw64] the selected families as a bit set; null: every family
+    int edge_rule = 0;            // kEdgeInduced | kEdgeReference
+    int* outside = nullptr;       // [1] kEdgeReference: the smallest CSR entry (kept family -> unselected family, coverage
+                                  //     > 0), INT_MAX: none; null: not asked for
 };
+constexpr int kEdgeInduced = 0, kEdgeReference = 1;
 // ... and phase 2 (the engine's own buffers, filled in place)
 struct ChunkFill {
     int nc, dc, wfc, npad;        // kept families, organisms of the sample, words per bit row, families padded to 256
@@ -56,6 +70,8 @@ void launch_master_transpose(const uint32_t* xf, int n, int wf, int d, int nw64,
 void launch_chunk_plan(const MasterDev& m, const ChunkPlan* plans_dev, int count, int max_dc, hipStream_t s);
 // phase 2 for one chunk
 void launch_chunk_fill(const MasterDev& m, const ChunkPlan& plan, const ChunkFill& fill, hipStream_t s);
+// a selection given as one byte per family (non-zero: selected) packed to the bit set a plan takes, [nw64] words
+void launch_select_pack(const uint8_t* bytes, int n, int nw64, uint64_t* bits, hipStream_t s);
 int chunk_mask_words_max();
 
 }  // namespace nemk

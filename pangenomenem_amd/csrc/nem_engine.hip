@@ -10,6 +10,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <climits>
 #include <atomic>
 #include <cfloat>
 #include <chrono>
@@ -3704,6 +3705,112 @@ int nemgpu_solve_chunks(nemgpu_master* M, nemgpu_chunk* chunks, int count, int k
                         const float* disp_k, const nemgpu_config* cfg, int workers, int group)
 {
     return solve_chunks_impl(M, chunks, count, k, prop, center_k, disp_k, cfg, workers, group, nullptr);
+}
+
+// ============================================================================================
+// The sub-problem of a selection of families (`__write_nem_input_files(..., filter_by_partition="shell")`,
+// ppanggolin.py:844 and :859: what partition_shell solves), formed on the device into an engine that random starts can
+// run on: the formed bit rows also come back into the engine's host rows, where nemgpu_run_random draws its centres.
+// ============================================================================================
+int nemgpu_master_subproblem(nemgpu_master* M, const int32_t* organisms, int dc, const uint8_t* select_bytes, int edge_rule, int k,
+                             nemgpu_engine** engine, int32_t* families_out, int* n_out, int* nnz_out, int* outside_entry)
+{
+    if (!M || !organisms || !select_bytes || !engine || !n_out || !nnz_out) return NEMGPU_E_FUNCARG;
+    *engine = nullptr; *n_out = 0; *nnz_out = 0;
+    if (outside_entry) *outside_entry = -1;
+    // ---- everything that can be refused without a launch
+    if (M->directed) {
+        set_error("nemgpu_master_subproblem: the master was built directed (nx.all_neighbors of a DiGraph lists a family that is both "
+                  "predecessor and successor twice, its row holds it once)");
+        return NEMGPU_E_ARG;
+    }
+    if (k <= 0 || k > kMaxKernelK) { set_error("nemgpu_master_subproblem: 1 .. 32 classes"); return NEMGPU_E_ARG; }
+    if (edge_rule != nemk::kEdgeInduced && edge_rule != nemk::kEdgeReference) { set_error("nemgpu_master_subproblem: edge_rule is 0 (induced) or 1 (reference)"); return NEMGPU_E_ARG; }
+    if (dc <= 0 || dc > M->d) { set_error("nemgpu_master_subproblem: 1 .. d organisms are needed"); return NEMGPU_E_ARG; }
+    {
+        std::vector<char> seen((size_t)M->d, 0);
+        for (int t = 0; t < dc; t++) {
+            const int o = organisms[t];
+            if (o < 0 || o >= M->d) { set_error("nemgpu_master_subproblem: organism index out of range"); return NEMGPU_E_ARG; }
+            if (seen[(size_t)o]) { set_error("nemgpu_master_subproblem: organism " + std::to_string(o) + " is given twice"); return NEMGPU_E_ARG; }
+            seen[(size_t)o] = 1;
+        }
+    }
+    const int n = M->n, nw64 = M->nw64, wf = M->wf, nnz = M->nnz;
+    if (std::all_of(select_bytes, select_bytes + n, [](uint8_t b) { return b == 0; })) {
+        set_error("nemgpu_master_subproblem: the selection keeps no family"); return NEMGPU_E_ARG;
+    }
+    HIPCHK(hipSetDevice(M->device));
+    // ---- phase 1 of one plan: the selection packed to bits, then which families, which edges, how many of each
+    const size_t b_plan = a256(sizeof(nemk::ChunkPlan)), b_org = a256((size_t)dc * 4), b_cnt = 256, b_sel = a256((size_t)n),
+                 b_keep = a256((size_t)nw64 * 8), b_mask = a256((size_t)wf * 4), b_list = a256((size_t)n * 4),
+                 b_cov = a256((size_t)std::max(nnz, 1) * 4), b_ptr = a256(((size_t)n + 1) * 4);
+    char* slab = nullptr;
+    if (hipMalloc(&slab, b_plan + b_org + b_cnt + b_sel + 2 * b_keep + b_mask + 2 * b_list + b_cov + b_ptr) != hipSuccess) {
+        (void)hipGetLastError(); set_error("nemgpu_master_subproblem: device memory for the plan"); return NEMGPU_E_MEMORY;
+    }
+    // (the fill kernels read the plan's arrays on the engine's stream: the slab goes once both streams are idle)
+    struct SlabFree { char* p; hipStream_t a; hipStream_t b; ~SlabFree() { (void)hipStreamSynchronize(a); if (b) (void)hipStreamSynchronize(b); (void)hipFree(p); } } slab_free{slab, M->stream, nullptr};
+    nemk::ChunkPlan plan;
+    char* b = slab + b_plan;
+    plan.organisms = (const int*)b; b += b_org; plan.dc = dc;
+    plan.counts = (int*)b; plan.outside = plan.counts + 2; b += b_cnt;
+    uint8_t* sel_bytes_dev = (uint8_t*)b; b += b_sel;
+    uint64_t* sel_bits = (uint64_t*)b; b += b_keep;
+    plan.select = sel_bits; plan.edge_rule = edge_rule;
+    plan.keep = (uint64_t*)b; b += b_keep;
+    plan.mask = (uint32_t*)b; b += b_mask;
+    plan.list = (int*)b; b += b_list;
+    plan.map = (int*)b; b += b_list;
+    plan.cov = (uint32_t*)b; b += b_cov;
+    plan.ptr = (int*)b;
+    HIPCHK(hipMemcpyAsync(slab, &plan, sizeof(plan), hipMemcpyHostToDevice, M->stream));
+    HIPCHK(hipMemcpyAsync(slab + b_plan, organisms, (size_t)dc * 4, hipMemcpyHostToDevice, M->stream));
+    HIPCHK(hipMemcpyAsync(sel_bytes_dev, select_bytes, (size_t)n, hipMemcpyHostToDevice, M->stream));
+    nemk::launch_select_pack(sel_bytes_dev, n, nw64, sel_bits, M->stream);
+    nemk::launch_chunk_plan(M->dev, reinterpret_cast<const nemk::ChunkPlan*>(slab), 1, dc, M->stream);
+    HIPCHK(hipGetLastError());
+    int counts[3] = {0, 0, 0};
+    HIPCHK(hipMemcpyAsync(counts, plan.counts, sizeof(counts), hipMemcpyDeviceToHost, M->stream));
+    HIPCHK(hipStreamSynchronize(M->stream));
+    *n_out = counts[0]; *nnz_out = counts[1];
+    if (edge_rule == nemk::kEdgeReference && counts[2] != INT_MAX) {          // the writer's KeyError: no problem is formed
+        if (outside_entry) *outside_entry = counts[2];
+        return NEMGPU_OK;
+    }
+    if (counts[0] <= 0) { set_error("nemgpu_master_subproblem: the selection keeps no family (none is present in these organisms)"); return NEMGPU_E_ARG; }
+    // ---- phase 2: the engine, its buffers filled in place, its rows brought back for the random starts
+    nemgpu_engine* e = nullptr;
+    int r = nemgpu_create(&e, counts[0], dc, k, 0, counts[0], M->device, nullptr);
+    if (r != NEMGPU_OK) return r;
+    slab_free.b = e->stream;
+    r = adopt_chunk(e, M, plan, counts[1]);
+    hipError_t err = hipSuccess;
+    if (r == NEMGPU_OK) {
+        const size_t words = (size_t)e->n * e->wf;
+        uint32_t* rows = host_bits_reserve(e, words);
+        err = hipMemcpyAsync(rows, e->xf_stage, words * 4, hipMemcpyDeviceToHost, e->stream);
+        if (err == hipSuccess && families_out) err = hipMemcpyAsync(families_out, plan.list, (size_t)counts[0] * 4, hipMemcpyDeviceToHost, e->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+    }
+    if (r == NEMGPU_OK && err != hipSuccess) { (void)hipGetLastError(); set_error(std::string("nemgpu_master_subproblem: ") + hipGetErrorString(err)); r = NEMGPU_E_DEVICE; }
+    if (r != NEMGPU_OK) { slab_free.b = nullptr; (void)hipStreamSynchronize(e->stream); nemgpu_destroy(e); return r; }
+    *engine = e;
+    return NEMGPU_OK;
+}
+
+// the problem an engine holds as nemgpu_master_subproblem formed it: bit rows [n][ceil(d/32)], ptr [n + 1], idx and w [nnz]
+int nemgpu_subproblem_fetch(nemgpu_engine* e, uint32_t* xbits, int32_t* ptr, int32_t* idx, float* w)
+{
+    if (!e) return NEMGPU_E_FUNCARG;
+    if (!e->have_matrix || e->host_bits_words != (size_t)e->n * e->wf || !e->nei_ptr) { set_error("nemgpu_subproblem_fetch: not an engine of nemgpu_master_subproblem"); return NEMGPU_E_FUNCARG; }
+    HIPCHK(hipSetDevice(e->device));
+    if (xbits) memcpy(xbits, e->host_bits, e->host_bits_words * 4);
+    if (ptr) HIPCHK(hipMemcpyAsync(ptr, e->nei_ptr, ((size_t)e->n + 1) * 4, hipMemcpyDeviceToHost, e->stream));
+    if (idx && e->nnz > 0) HIPCHK(hipMemcpyAsync(idx, e->nei_idx, (size_t)e->nnz * 4, hipMemcpyDeviceToHost, e->stream));
+    if (w && e->nnz > 0) HIPCHK(hipMemcpyAsync(w, e->nei_w, (size_t)e->nnz * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return NEMGPU_OK;
 }
 
 // ============================================================================================

@@ -363,7 +363,7 @@ def _lengths(total, count, lo, hi, low, high):
 
 
 def write_gexf(path, partitions, family_table, edge_table, annotations, all_node_attributes=True, all_edge_attributes=True, compressed=False,
-               budget=TEXT_BUDGET, positions=None):
+               budget=TEXT_BUDGET, positions=None, subpartition=None):
     """<path>.gexf (compressed: <path>.gexf.gz through gzip) as PPanGGOLiN.export_to_GEXF and networkx's write_gexf write
     it for a partitioned nx.Graph (ppanggolin.py:1294-1362), streamed: no networkx, no tree.  partitions: what
     Master.partition returned, or uint8 [n]; family_table, edge_table: Master.family_table / Master.edge_table (or their
@@ -372,7 +372,9 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
     `_light` export, without the organism keys; it formats no text on the device.  An edge's organism lines are the
     device's bytes, a slice per edge.  positions: float64 [n][2] in master order (Layout.positions(), layout.py): every
     node gets the <viz:position> that compute_layout's dict makes networkx write (ppanggolin.py:1285-1292), z = 2 for a
-    persistent family, 1 for a shell one, 0 otherwise."""
+    persistent family, 1 for a shell one, 0 otherwise.  subpartition: (name, {family: value}) -- the node attribute that
+    partition_shell sets on every node (ppanggolin.py:1243-1247; Master.partition_shell's .subpart_name and
+    .node_attribute): one more string attribute, where the node's data holds it, behind partition_exact."""
     ft, et = family_table, edge_table
     names, orgs = ft.names, ft.organism_names
     if names is None or orgs is None:
@@ -409,6 +411,8 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
 
     tail = (("partition", "string"), ("partition_exact", "string"), ("length_avg", "double"), ("length_med", "double"), ("length_min", "long"),
             ("length_max", "long"))
+    if subpartition is not None:
+        tail = tail[:2] + ((subpartition[0], "string"),) + tail[2:]
     node_keys = []                                            # per family: the organisms before and after name and product
     for i in range(n):
         present = list(cells[i]) if all_node_attributes else []
@@ -460,7 +464,7 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
             lines.append(att % (node_ids["product"], escape("|".join(products[i]))))
             for org in present[1:]:
                 lines.append(att % (node_ids[org], escape("|".join(cells[i][org]))))
-            values = (longs[i], exact) + _lengths(ft.len_sum[i], ft.len_distinct[i], et.fam_mid_lo[i], et.fam_mid_hi[i], ft.len_min[i], ft.len_max[i])
+            values = (longs[i], exact) + (() if subpartition is None else (escape(subpartition[1][names[i]]),)) + _lengths(ft.len_sum[i], ft.len_distinct[i], et.fam_mid_lo[i], et.fam_mid_hi[i], ft.len_min[i], ft.len_max[i])
             for (title, _), value in zip(tail, values):
                 lines.append(att % (node_ids[title], value))
             lines.append("        </attvalues>\n      </node>\n")

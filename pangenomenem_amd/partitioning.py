@@ -15,10 +15,11 @@ from .engine import NemEngine
 
 
 def run_partitioning_arrays(x, nei, beta, free_dispersion=False, Q=3, init="param_file_default", names=None,
-                            low_disp=0.1, params=None, rng_seed=1, device=0):
+                            low_disp=0.1, params=None, rng_seed=1, device=0, tie="hash"):
     """x uint8 [families, organisms]; nei = CSR (ptr, idx, w) or None; names = family identifiers (default
     fam1..famN).  init: "param_file_default" (PPanGGOLiN's default .m, ppanggolin.py:893-901), "param_file" (give
     params = (prop, center, disp)) or "random" (init_mode INIT_RANDOM, 50 starts, ppanggolin.py:1207).
+    tie: the tie rule ("libc" with init="random": the starts and the ties draw from one random() stream, as in nem()).
     Returns ({family: 'P'|'S'|'C'|'U' or class index}, {k: (mu bool list, epsilon list, proportion)})."""
     x = np.ascontiguousarray(x, np.uint8)
     n, d = x.shape
@@ -28,7 +29,7 @@ def run_partitioning_arrays(x, nei, beta, free_dispersion=False, Q=3, init="para
         eng.set_matrix(x)
         eng.set_graph(nei)
         eng.configure(algo="ncem", beta=beta, disper="skd" if free_dispersion else "sk_", propor="pk", cvtest="clas",
-                      cvthres=1e-8, it_max=100, seed=rng_seed)
+                      cvthres=1e-8, it_max=100, tie=tie, seed=rng_seed)
         if init.startswith("param_file"):
             if init == "param_file_default":
                 if Q != 3:

@@ -30,7 +30,7 @@ SLICE_GRAIN = 64                                              # kLayoutSliceGrai
 BLOCKS_TARGET, SLICES_MAX = 1024, 64
 DEFAULTS = dict(scaling_ratio=50000.0, gravity=1.0, strong_gravity=True, outbound_attraction_distribution=True, edge_weight_influence=1.0,
                 jitter_tolerance=1.0, lin_log=False, adjust_sizes=False)
-ORDERS = ("numpy", "left", "perm", "fsum")
+ORDERS = ("numpy", "left", "perm", "fsum", "extended")
 REPULSIONS = ("exact", "barnes_hut")                          # Layout's repulsion=: the all-pairs sum, or layout_bh.py's tree
 
 
@@ -120,8 +120,14 @@ def _ordered_sum(terms, order, perm):
     return np.cumsum(terms, axis=1)[:, -1]                    # (accumulate is strictly left to right)
 
 
+def extended_type():
+    """np.longdouble where it carries at least 64 significant bits (x87's extended format, or wider), else None: the
+    "extended" order then takes math.fsum per row"""
+    return np.longdouble if np.finfo(np.longdouble).nmant >= 63 else None
+
+
 def _total(values, order):
-    if order == "fsum":
+    if order in ("fsum", "extended"):
         return math.fsum(values.tolist())
     if order == "numpy":
         return float(values.sum())
@@ -153,7 +159,7 @@ def speed_control(n, S, T, speed, eff, jitter_tolerance):
 
 
 def layout_arrays(graph, edge_bits, d, iterations=500, pos=None, rng=None, order="numpy", perm=None, attraction="gather", old=None,
-                  speed=1.0, eff=1.0, **params):
+                  speed=1.0, eff=1.0, block_rows=None, **params):
     """What nemgpu_layout_create / _run compute, in numpy, float64.
     graph (ptr, idx), edge_bits uint32 [nnz][ceil(d/32)], d: the master as Master.arrays() gives it (a symmetric CSR);
     pos / rng: start_positions; params: compute_layout's (DEFAULTS).  State: old = 0 (the previous forces), speed = 1,
@@ -170,15 +176,22 @@ def layout_arrays(graph, edge_bits, d, iterations=500, pos=None, rng=None, order
       6. p_i += f_i * speed / (1 + sqrt(speed * mass_i * sw_i)), old = f.
     order: how the sums of steps 1 - 4 are taken: "numpy" (np.sum), "left" (j ascending, then gravity, then the row's
     entries), "perm" (the repulsion's j in the order perm, int [n]), "fsum" (math.fsum over all of a component's terms:
-    the exactly rounded sum, the yardstick).
+    the exactly rounded sum, the yardstick), "extended" (the yardstick for a large n: the same float64 terms accumulated
+    in np.longdouble, 64 significant bits, and rounded once -- within n 2^-64 B of the exact sum before that rounding, B
+    the bound below; S and T by math.fsum; where np.longdouble is no wider than float64, math.fsum per row).
+    block_rows: None, or the rows of the [n][n] arrays of step 1 that are held at a time (memory O(block_rows * n)
+    instead of O(n * n)): a row's sum is taken along that row alone, so every returned bit is the unblocked form's.
     Returns a dict: pos [n][2], forces [n][2], speed, eff, S, T of the last iteration, iterations, bound [n][2] (per node
     and component the sum of the absolute values of the last iteration's terms of steps 1 - 3), old [n][2], moved (the
-    last iteration's T != 0), comparisons (per iteration speed_control's list, [] where T == 0)."""
+    last iteration's T != 0), comparisons (per iteration speed_control's list, [] where T == 0), wide (order="extended":
+    the last iteration's forces before their one rounding, np.longdouble [n][2]; else, and for iterations=0, None)."""
     p = check_params(params)
     if order not in ORDERS or attraction not in ("gather", "scatter"):
         raise ValueError("layout_arrays: order one of %s, attraction gather or scatter" % (ORDERS,))
     if iterations < 0:
         raise ValueError("layout_arrays: iterations < 0")
+    if block_rows is not None and (int(block_rows) != block_rows or block_rows < 1):
+        raise ValueError("layout_arrays: block_rows is None or a whole number >= 1")
     g = layout_graph(graph, edge_bits, d)
     n, mass = g["n"], g["mass"]
     if order == "perm":
@@ -198,33 +211,52 @@ def layout_arrays(graph, edge_bits, d, iterations=500, pos=None, rng=None, order
     up = ei < ej                                              # (the edges: the scatter form walks them)
     sm = p["scaling_ratio"] * mass
     forces, bound = np.zeros((n, 2)), np.zeros((n, 2))
+    by_row = order == "fsum" or (order == "extended" and extended_type() is None)
+    wide = np.zeros((n, 2), extended_type()) if order == "extended" and not by_row else None
+    entries = [None, None]                                    # per component: step 3's (node, term) of every entry
     S = T = 0.0
     moved, comparisons = False, []
     for _ in range(iterations):
-        dx =xy[:, 0][:, None] - xy[:, 0][None, :]
-        dy = xy[:, 1][:, None] - xy[:, 1][None, :]
-        d2 = dx * dx + dy * dy
-        with np.errstate(divide="ignore", invalid="ignore"):
-            coef = (sm[:, None] * mass[None, :]) / d2
-        coef[~(d2 > 0.0)] = 0.0
         grav = (p["gravity"] * mass)[:, None] * xy
-        for c, delta in ((0, dx), (1, dy)):
-            rep = delta * coef                                # [n][n]
+        for c in (0, 1):
             if attraction == "gather":
                 at_node, at_term = ei, (xy[ei, c] - xy[ej, c]) * fac
             else:
                 t = (xy[ei[up], c] - xy[ej[up], c]) * fac[up]
                 at_node, at_term = np.concatenate([ei[up], ej[up]]), np.concatenate([t, -t])
-            if order == "fsum":
+            entries[c] = (at_node, at_term)
+            if by_row:
                 rows = [[] for _ in range(n)]
                 for node, term in zip(at_node.tolist(), at_term.tolist()):
                     rows[node].append(term)
-                forces[:, c] = [math.fsum(rep[i].tolist() + [-grav[i, c]] + rows[i]) for i in range(n)]
-            else:
-                f = _ordered_sum(rep, order, perm) - grav[:, c]
+                entries[c] += (rows,)
+        for r0 in range(0, n, block_rows or max(n, 1)):
+            r1 = min(n, r0 + (block_rows or n))
+            dx = xy[r0:r1, 0][:, None] - xy[:, 0][None, :]    # [rows][n]
+            dy = xy[r0:r1, 1][:, None] - xy[:, 1][None, :]
+            d2 = dx * dx + dy * dy
+            with np.errstate(divide="ignore", invalid="ignore"):
+                coef = (sm[r0:r1, None] * mass[None, :]) / d2
+            coef[~(d2 > 0.0)] = 0.0
+            for c, delta in ((0, dx), (1, dy)):
+                rep = delta * coef
+                if by_row:
+                    rows = entries[c][2]
+                    forces[r0:r1, c] = [math.fsum(rep[i - r0].tolist() + [-grav[i, c]] + rows[i]) for i in range(r0, r1)]
+                elif order == "extended":
+                    wide[r0:r1, c] = rep.sum(axis=1, dtype=wide.dtype)
+                else:
+                    forces[r0:r1, c] = _ordered_sum(rep, order, perm)
+                bound[r0:r1, c] = np.abs(rep).sum(axis=1)
+        for c in (0, 1):
+            at_node, at_term = entries[c][:2]
+            if not by_row:
+                f = (wide[:, c] if order == "extended" else forces[:, c]) - grav[:, c]
                 np.add.at(f, at_node, at_term)                # (unbuffered: the entries in order)
-                forces[:, c] = f
-            b = np.abs(rep).sum(axis=1) + np.abs(grav[:, c])
+                forces[:, c] = f                              # (the extended sum: rounded here, once)
+                if order == "extended":
+                    wide[:, c] = f
+            b = bound[:, c] + np.abs(grav[:, c])
             np.add.at(b, at_node, np.abs(at_term))
             bound[:, c] = b
         sx, sy = old[:, 0] - forces[:, 0], old[:, 1] - forces[:, 1]
@@ -240,7 +272,7 @@ def layout_arrays(graph, edge_bits, d, iterations=500, pos=None, rng=None, order
         xy = xy + forces * speed / (1.0 + np.sqrt(speed * mass * sw))[:, None]
         old = forces.copy()
     return dict(pos=xy, forces=forces.copy(), speed=speed, eff=eff, S=S, T=T, iterations=iterations, bound=bound, old=old, moved=moved,
-                comparisons=comparisons)
+                comparisons=comparisons, wide=wide if iterations else None)
 
 
 def positions_3d(partitions, names, pos):

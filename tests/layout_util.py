@@ -80,18 +80,24 @@ def check_margins(made, old_is_zero, what):
         assert abs(left - right) > MARGIN * max(abs(left), abs(right)), (what, name, left, right)
 
 
-def step_tolerances(n, mass, want, prev_old, prev_speed):
+def step_tolerances(n, mass, want, prev_old, prev_speed, order="fsum"):
     """For one iteration from identical inputs: the statement `want` (order="fsum": every sum exactly rounded) against
     any device order.  Every term is bit-equal; a sum of m terms taken in any order is within (m - 1) u of sum |terms|,
     the fsum one within u: a component has at most 2 n - 1 terms (n - 1 pairs, gravity, at most n - 1 entries), so
-      forces  E = 2 n u B;
+      forces  E = 2 n u B; for a statement in order="extended" (layout_arrays: the terms accumulated in 64 significant
+              bits, off the exact sum by at most n 2^-64 B before the one rounding) that error of the yardstick is added:
+              E = 2 n u B + n 2^-64 B;
       sw, tr  (the norm of old -/+ f) inherit |E| and a few roundings: dsw = |E| + 8 u sw;
       S, T    2 n u S for the order, sum mass dsw for the terms;
       speed   exact where the step is half the speed; where it is target - speed, the relative error of jt eff T / S;
       pos     f speed / (1 + sqrt(speed mass sw)) with all of the above.
     Returns a dict of absolute tolerances."""
     f = want["forces"]
+    if order not in ("fsum", "extended"):
+        raise ValueError("step_tolerances: the statement in order fsum or extended")
     E = 2.0 * n * U * want["bound"]
+    if order == "extended":
+        E = E + n * 2.0 ** -64 * want["bound"]
     En = np.sqrt(E[:, 0] ** 2 + E[:, 1] ** 2)
     sw = np.sqrt(((prev_old - f) ** 2).sum(axis=1))
     tr = np.sqrt(((prev_old + f) ** 2).sum(axis=1))
@@ -115,5 +121,5 @@ def step_tolerances(n, mass, want, prev_old, prev_speed):
     return out
 
 
-def statement_step(graph, eb, d, pos, old, speed, eff, **params):
-    return layout_arrays(graph, eb, d, iterations=1, pos=pos, old=old, speed=speed, eff=eff, order="fsum", **params)
+def statement_step(graph, eb, d, pos, old, speed, eff, order="fsum", block_rows=None, **params):
+    return layout_arrays(graph, eb, d, iterations=1, pos=pos, old=old, speed=speed, eff=eff, order=order, block_rows=block_rows, **params)

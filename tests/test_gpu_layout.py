@@ -8,7 +8,16 @@ B the statement's sum of the terms' absolute values; S, T, the speed and the pos
 steps: the growth of a rounding difference is chaotic, so the yardstick is measured, from the statement alone.  The
 shapes are the smallest at which a kernel takes another path: one family to three, one below / at / one above the tile
 and the first slice boundary, several slices, bit rows that cross a word, an isolated family, masters grown and bits-only,
-a coincident pair."""
+a coincident pair -- and the tile loop of k_layout_repulse, which below 8 193 families never makes a second trip (a slice
+of the j range is at most 64 there).  Those sizes are held to the row-blocked statement in extended precision
+(layout_arrays: order="extended", block_rows=), whose own error n 2^-64 B is added to the force bound; the path each
+reaches, and the wall time of its test on an MI355X host (the statement on one core is nearly all of it):
+  n  8 192   32 slices of 256: one full tile per slice                                1.6 s
+  n  8 193   32 slices of 257: a second trip of the tile loop, a tile of one j         1.4 s
+  n 12 500   21 slices of 596: two full tiles and one of 84                            3.3 s
+  n  8 193   the exact path against the theta 0 walk over all 8 193 bodies per lane    0.7 s
+Above 65 536 families the exact path's only further path is the stride of k_layout_speed over more than 256 blocks; the
+launches it sits in are shared with the Barnes-Hut path, and tests/test_gpu_layout_bh.py runs them at 65 793."""
 import ctypes as C
 
 import numpy as np
@@ -20,7 +29,7 @@ from pangenomenem_amd.chunks import Master
 from pangenomenem_amd.gexf import write_gexf
 from pangenomenem_amd.layout import SLICE_GRAIN, TILE, layout_arrays, layout_graph, slices_of
 from tests.gexf_util import contigs_orders, host_tables, path_contigs, same_gexf_text, sizes_of
-from tests.layout_util import (LAYOUT_FIXTURES, arrays_of, base_record, branches, check_margins, positions_in_master_order,
+from tests.layout_util import (LAYOUT_FIXTURES, U, arrays_of, base_record, branches, check_margins, positions_in_master_order,
                                ring_with_chords, statement_step, step_tolerances)
 from tests.orders_util import load, same_master
 from tests.projection_util import annotations_of
@@ -39,9 +48,10 @@ def from_orders(o, **kw):
     return Master.from_orders(o["genes"], o["contig_ptr"], o["contig_org"], o["contig_circular"], o["d"], repeated=o["repeated"], **kw)
 
 
-def held_to_the_statement(m, pos, what, steps=2, **params):
-    """`steps` single iterations on the device from pos, each against one iteration of the statement (fsum order) from
-    the device's own state before it: the first from old = 0, the next from the old the first left"""
+def held_to_the_statement(m, pos, what, steps=2, order="fsum", block_rows=None, **params):
+    """`steps` single iterations on the device from pos, each against one iteration of the statement (fsum order; for a
+    large n order="extended" in blocks of block_rows rows, its own error added to the force bound) from the device's own
+    state before it: the first from old = 0, the next from the old the first left"""
     _, graph, eb, _, _ = m.arrays()
     n = m.n
     mass = layout_graph(graph, eb, m.d)["mass"]
@@ -52,10 +62,10 @@ def held_to_the_statement(m, pos, what, steps=2, **params):
         assert lay.state() == dict(speed=1.0, eff=1.0, S=0.0, T=0.0, iterations=0)
         old, speed, eff = np.zeros((n, 2)), 1.0, 1.0
         for step in range(steps):
-            want = statement_step(graph, eb, m.d, pos, old, speed, eff, **params)
+            want = statement_step(graph, eb, m.d, pos, old, speed, eff, order=order, block_rows=block_rows, **params)
             if want["moved"]:
                 check_margins(want["comparisons"][0], not old.any(), "%s step %d" % (what, step))
-            tol = step_tolerances(n, mass, want, old, speed)
+            tol = step_tolerances(n, mass, want, old, speed, order=order)
             lay.run(1)
             got_pos, got_f, st = lay.positions(), lay.forces(), lay.state()
             worst = float(np.max(np.abs(got_f - want["forces"]) / np.maximum(tol["forces"], 1e-300))) if n else 0.0
@@ -123,6 +133,62 @@ def test_around_the_tile_and_the_first_slice_boundary(gpu_lib, n, d):
         held_to_the_statement(m, start(n, n + d, coincident=True), "n %d d %d" % (n, d))
     finally:
         m.close()
+
+
+TILED = {8192: (32, 256, 1), 8193: (32, 257, 2), 12500: (21, 596, 3)}         # n: slices, slice_len, tiles per slice
+TILED_D = 9
+
+
+def tiled_master(n):
+    return counts_master(n, TILED_D, 9000 + n)
+
+
+def tiled_start(n):
+    return start(n, n + TILED_D, coincident=True)
+
+
+@pytest.mark.parametrize("n", sorted(TILED))
+def test_the_tile_loop_of_a_slice(gpu_lib, n):
+    """k_layout_repulse's loop over the LDS tiles of one slice: at 8192 a slice is one full tile of 256 j's, at 8193 the
+    loop makes its second trip (a tile of one j, behind the barrier that guards the reload), at 12500 two full tiles and
+    one of 84.  Two steps from a start with a coincident pair, a master with self-loops and counts above 1, against the
+    row-blocked statement in extended precision: the force bound is 2 n u B + n 2^-64 B, about 1e-8 of one pair term
+    (tests/test_layout_host.py shows that it rejects a dropped tile and a wrong term)."""
+    slices, length, tiles = TILED[n]
+    assert (slices_of(n), -(-n // slices_of(n)), -(-length // TILE)) == (slices, length, tiles)
+    m = tiled_master(n)
+    try:
+        _, (ptr, idx), eb, counts, _ = m.arrays()
+        g = layout_graph((ptr, idx), eb, TILED_D)
+        assert (g["col"] == g["row"]).any() and len(counts[1]) > 0
+        held_to_the_statement(m, tiled_start(n), "n %d" % n, order="extended", block_rows=256)
+    finally:
+        m.close()
+
+
+def test_the_two_device_orders_past_one_tile(gpu_lib):
+    """n = 8193: the exact path (32 slices of 257, two tiles each) against the Barnes-Hut walk at theta 0, which opens every
+    cell and so sums the same 8192 pair terms per family in the tree's order: each within n u B of the exact sum, so
+    within 2 n u B of each other (tests/test_gpu_layout_bh.py does this below one tile)"""
+    n = 8193
+    m = tiled_master(n)
+    try:
+        _, graph, eb, _, _ = m.arrays()
+        pos = tiled_start(n)
+        a, b = m.layout(1, pos=pos, theta=0.0, repulsion="barnes_hut"), m.layout(1, pos=pos)
+        try:
+            fa, fb = a.forces(), b.forces()
+            walked = a.tree()["visited"]
+        finally:
+            a.close()
+            b.close()
+    finally:
+        m.close()
+    B = layout_arrays(graph, eb, TILED_D, iterations=1, pos=pos, order="left", block_rows=256)["bound"]
+    worst = float((np.abs(fa - fb) / (2.0 * n * U * B)).max())
+    print("n %d: theta 0 against the exact path at %.3f of the bound" % (n, worst))
+    assert (np.abs(fa - fb) <= 2.0 * n * U * B).all()
+    assert np.isfinite(fa).all() and fa.any() and not np.array_equal(fa, fb)       # (two orders of 8192 terms)
 
 
 def test_an_isolated_family_a_grown_master_and_a_bits_only_one(gpu_lib):

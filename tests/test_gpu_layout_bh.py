@@ -6,7 +6,19 @@ The tree is the statement's bit for bit -- keys, order, cells, moments -- and so
 the statement's order, and k_layout_forces adds gravity and the row's entries behind it as layout_bh_arrays does.  Only S
 and T are summed in the device's own trees, so they, the speed and the positions are held as tests/layout_util.py's
 step_tolerances holds the exact path, with the force term of the bound set to zero.  The inputs are
-tests/layout_bh_util.py's: the smallest at which a kernel takes another path."""
+tests/layout_bh_util.py's: the smallest at which a kernel takes another path.
+
+Its LARGE cases are the sizes at which the large-n paths begin -- the passes of the scan that numbers the cells over
+17 n flags (524 288 per pass), the stride of k_bh_box and k_layout_speed over more than 256 blocks of bodies, rocPRIM's
+radix sort at tens of thousands of pairs with equal keys -- at theta 1.2 only (theta 0 is n^2 per lane, and minutes of the
+statement's walk).  The path each reaches, and the wall times on an MI355X host of its tree test / its two steps (the
+statement on one core is nearly all of both):
+  clustered30840   1 scan pass (8 flags below the second), 121 blocks, a tree down to level 16       0.6 s / 0.7 s
+  clustered30841   2 scan passes: the carry's first n; four level-16 cells behind the boundary      0.6 s / 0.6 s
+  clustered32768   2 scan passes, the second level 16 alone (753 cells), 128 blocks                  0.7 s / 0.7 s
+  uniform65793     3 scan passes, the first boundary inside level 7 (1 700 cells behind), 258 blocks 0.3 s / 0.4 s
+  clustered65793   3 scan passes with cells in each, 258 blocks, level-16 leaves of hundreds         1.5 s / 1.7 s
+  clustered65793   three steps and two against five, the tree after them                            0.1 s"""
 import ctypes as C
 
 import numpy as np
@@ -18,7 +30,7 @@ from pangenomenem_amd.engine import NemGpuError
 from pangenomenem_amd.gexf import write_gexf
 from pangenomenem_amd.layout_bh import cell_bound, layout_bh_arrays, tree_arrays
 from tests.gexf_util import contigs_orders, path_contigs, sizes_of
-from tests.layout_bh_util import DEVICE_CASES, case, check_tree, same_tree, statement_tree
+from tests.layout_bh_util import DEVICE_CASES, LARGE_CASES, case, check_large, check_tree, same_tree, statement_step, statement_tree
 from tests.layout_util import LAYOUT_FIXTURES, U, base_record, branches, check_margins, ring_with_chords, step_tolerances
 from tests.orders_util import load
 from tests.projection_util import annotations_of
@@ -48,9 +60,7 @@ def test_the_tree_is_the_statements_bit_for_bit(gpu_lib, name):
     check_tree(got, c["mass"], name)
 
 
-@pytest.mark.parametrize("theta", [1.2, 0.0])
-@pytest.mark.parametrize("name", DEVICE_CASES)
-def test_one_step_and_two(gpu_lib, name, theta):
+def steps_against_the_statement(name, theta, steps=2):
     """each step against one iteration of the statement from the device's own state before it: forces and counters equal,
     S, T, speed and positions within the bound that the order of S and T alone leaves"""
     c = case(name)
@@ -59,7 +69,7 @@ def test_one_step_and_two(gpu_lib, name, theta):
     try:
         lay = m.layout(0, pos=c["pos"], theta=theta, **BH)
         pos, old, speed, eff = np.array(c["pos"]), np.zeros((n, 2)), 1.0, 1.0
-        for step in range(2):
+        for step in range(steps):
             want = layout_bh_arrays(c["graph"], c["eb"], c["d"], iterations=1, pos=pos, old=old, speed=speed, eff=eff, theta=theta, order="fsum")
             if want["moved"]:
                 check_margins(want["comparisons"][0], not old.any(), "%s step %d" % (name, step))
@@ -82,6 +92,41 @@ def test_one_step_and_two(gpu_lib, name, theta):
         lay.close()
     finally:
         m.close()
+
+
+@pytest.mark.parametrize("theta", [1.2, 0.0])
+@pytest.mark.parametrize("name", DEVICE_CASES)
+def test_one_step_and_two(gpu_lib, name, theta):
+    steps_against_the_statement(name, theta)
+
+
+@pytest.mark.parametrize("name", LARGE_CASES)
+def test_the_tree_at_the_sizes_where_the_scan_carries_and_the_blocks_are_strided(gpu_lib, name):
+    """tests/layout_bh_util.py's LARGE: the cell numbering's scan in one pass, in two from the first n that needs them, in
+    two with the second all of level DEPTH, in three; 258 blocks of bodies for k_bh_box's stride; a radix sort of 30 000
+    and 65 000 pairs with thousands of equal keys.  Keys, order, cells, links, moments, the box and the walk's counters
+    at theta 1.2 are the statement's bit for bit (check_large: the cells behind the pass boundaries are there)."""
+    check_large(name)
+    c = case(name)
+    m = master_of(c)
+    try:
+        lay = m.layout(0, pos=c["pos"], **BH)
+        got = lay.tree()
+        lay.close()
+    finally:
+        m.close()
+    same_tree(got, statement_tree(name), name)
+    check_tree(got, c["mass"], name)
+    want = statement_step(name, 1.2)
+    assert np.array_equal(got["accepted"], want["accepted"]) and np.array_equal(got["visited"], want["visited"]), name
+    assert got["accepted"].any() and got["visited"].any()
+
+
+@pytest.mark.parametrize("name", LARGE_CASES)
+def test_two_steps_at_the_large_sizes(gpu_lib, name):
+    """test_one_step_and_two's body at theta 1.2 (theta 0 is n^2 per lane and minutes of the statement's walk here): the
+    65 793 cases run k_layout_forces in 258 blocks and k_layout_speed's stride over their sums, which the exact path shares"""
+    steps_against_the_statement(name, 1.2)
 
 
 @pytest.mark.parametrize("name", ["n256", "n257", "n1500"])
@@ -152,6 +197,29 @@ def test_runs_repeat_bit_for_bit_and_a_tree_in_between_changes_nothing(gpu_lib):
         finally:
             for lay in (whole, again, parts):
                 lay.close()
+    finally:
+        m.close()
+
+
+def test_runs_repeat_bit_for_bit_at_65793_clustered(gpu_lib):
+    """three scan passes, 258 blocks, a tree down to level DEPTH: three steps then two are five, bit for bit, and the
+    device's tree after them is the statement's tree of the device's positions"""
+    c = case("clustered65793")
+    m = master_of(c)
+    try:
+        whole, parts = m.layout(5, pos=c["pos"], **BH), m.layout(3, pos=c["pos"], **BH)
+        try:
+            parts.positions()                                 # (a fetch between the two runs)
+            parts.run(2)
+            a, p = whole.positions(), parts.positions()
+            assert np.array_equal(a, p) and not np.array_equal(a, c["pos"]) and np.isfinite(a).all()
+            assert np.array_equal(whole.forces(), parts.forces()) and whole.state() == parts.state() and whole.state()["iterations"] == 5
+            after = whole.tree()
+            same_tree(after, tree_arrays(a, c["mass"]), "after five steps")
+            check_tree(after, c["mass"], "after five steps")
+        finally:
+            whole.close()
+            parts.close()
     finally:
         m.close()
 

@@ -14,7 +14,7 @@ from pangenomenem_amd import layout_bh as bh
 from pangenomenem_amd.engine import load_library
 from pangenomenem_amd.layout import layout_arrays
 from pangenomenem_amd.layout_bh import DEPTH, LEAF, layout_bh_arrays, tree_arrays, walk
-from tests.layout_bh_util import CASES, case, check_tree, statement_step, statement_tree
+from tests.layout_bh_util import CASES, LARGE_CASES, case, check_large, check_tree, large_properties, statement_step, statement_tree
 from tests.layout_util import U, ring_with_chords
 
 
@@ -37,6 +37,39 @@ def test_tree_invariants(name):
     if name in ("horizontal", "vertical"):
         keep = 0x55555555 if name == "horizontal" else 0xAAAAAAAA
         assert not (t["key"] & np.uint32(0xFFFFFFFF ^ keep)).any()
+
+
+@pytest.mark.parametrize("name", LARGE_CASES)
+def test_the_large_inputs_are_what_they_claim(name):
+    """the scan's passes over the 17 n flags, cells behind every pass boundary, for the clustered ones a tree down to
+    level DEPTH with a leaf of hundreds there, the bound on the cells -- and the invariants every tree is held to
+    (check_tree is linear in n: it runs at every size here)"""
+    check_large(name)
+    p = large_properties(name)
+    print("%s: %d scan passes over %d flags (they begin in levels %s), cells per pass %s, deepest level %d, its largest leaf %d, %d cells of at most %d, %d blocks"
+          % (name, p["passes"], (DEPTH + 1) * p["n"], p["level_of_pass"], p["cells_in_pass"], p["deepest"], p["deep_leaf"], p["cells"], p["bound"], p["blocks"]))
+    check_tree(statement_tree(name), case(name)["mass"], name)
+
+
+def test_check_tree_sees_a_wrong_cell_a_wrong_moment_and_a_wrong_order():
+    t, mass = statement_tree("n1500"), case("n1500")["mass"]
+    check_tree(t, mass, "as it is")
+    inner = int(np.nonzero((t["level"] == 3) & (t["child"] >= 0))[0][0])
+    spoiled = []
+    for key, at, by in (("hi", inner, -1), ("lo", t["cells"] - 1, 1), ("M", inner, 1.0), ("level", t["cells"] - 1, -1)):
+        a = t[key].copy()
+        a[at] += by
+        spoiled.append(dict(t, **{key: a}))
+    spoiled += [dict(t, level=t["level"][:-1], lo=t["lo"][:-1], hi=t["hi"][:-1], child=t["child"][:-1], cells=t["cells"] - 1)]
+    for k, bad in enumerate(spoiled):
+        with pytest.raises(AssertionError):
+            check_tree(bad, mass, "spoiled %d" % k)
+    t, mass = statement_tree("bucket"), case("bucket")["mass"]               # (bodies in one grid cell: their indices ascend)
+    same = np.nonzero(np.diff(t["key"][t["order"]].astype(np.int64)) == 0)[0]
+    swapped = t["order"].copy()
+    swapped[[same[0], same[0] + 1]] = swapped[[same[0] + 1, same[0]]]
+    with pytest.raises(AssertionError, match="equal keys"):
+        check_tree(dict(t, order=swapped), mass, "two equal keys out of order")
 
 
 @pytest.mark.parametrize("theta", [1.2, 0.5, 0.0])

@@ -9,10 +9,11 @@ import numpy as np
 import pytest
 
 from pangenomenem_amd import layout as ly
+from pangenomenem_amd import synth
 from pangenomenem_amd.engine import load_library
 from pangenomenem_amd.gexf import write_gexf
 from tests.gexf_util import host_tables, same_gexf_text
-from tests.layout_util import LAYOUT_FIXTURES, arrays_of, base_record, positions_in_master_order, ring_with_chords
+from tests.layout_util import LAYOUT_FIXTURES, U, arrays_of, base_record, positions_in_master_order, ring_with_chords, step_tolerances
 from tests.orders_util import load
 
 
@@ -190,6 +191,9 @@ def test_what_is_refused():
         one(graph, eb, 3, pos[:4])
     with pytest.raises(ValueError, match="permutation"):
         one(graph, eb, 3, pos, order="perm", perm=[0, 1, 2, 3, 3])
+    for rows in (0, -1, 2.5):
+        with pytest.raises(ValueError, match="block_rows"):
+            one(graph, eb, 3, pos, block_rows=rows)
     assert one(graph, eb, 3, pos, iterations=0)["pos"].tolist() == pos.tolist()
     empty = ly.layout_arrays((np.zeros(1, np.int32), np.zeros(0, np.int32)), np.zeros((0, 1), np.uint32), 3, iterations=2)
     assert empty["pos"].shape == (0, 2) and empty["iterations"] == 2
@@ -203,3 +207,159 @@ def test_the_slices_are_the_librarys():
         assert lib.nemgpu_layout_slices(n, C.byref(tile), C.byref(grain)) == ly.slices_of(n), n
     assert (tile.value, grain.value) == (ly.TILE, ly.SLICE_GRAIN)
     assert ly.slices_of(ly.SLICE_GRAIN) == 1 and ly.slices_of(ly.SLICE_GRAIN + 1) == 2 and ly.slices_of(1500) > 8
+
+
+SAME_KEYS = ("pos", "forces", "bound", "old")
+
+
+@pytest.mark.parametrize("n", [300, 700])
+def test_the_row_blocked_form_is_the_unblocked_one_bit_for_bit(n):
+    """block_rows= changes what is held at a time, not one bit: a block size of one row, one that does not divide n, one
+    that does, n itself and one above n; two iterations from a start with a coincident pair, a master with self-loops.
+    The exactly rounded order is blocked too (one iteration: it is the slow one)."""
+    d = 9
+    _, graph, eb, _ = synth.master_pangenome_counts(n, d, n, loops=0.05, multi_frac=0.1)
+    pos = np.random.default_rng(n).random((n, 2))
+    pos[n // 2] = pos[0]
+    perm = np.random.default_rng(1).permutation(n)
+    assert n % 11 and n % 100 == 0
+    for order, iterations, blocks in (("left", 2, (1, 11, 100, n, n + 5)), ("numpy", 2, (1, 11, 100, n, n + 5)), ("perm", 2, (1, 11, 100, n, n + 5)),
+                                      ("extended", 2, (11, 100, n + 5)), ("fsum", 1, (11, n + 5))):
+        whole = one(graph, eb, d, pos, order=order, perm=perm, iterations=iterations)
+        for rows in blocks:
+            cut = one(graph, eb, d, pos, order=order, perm=perm, iterations=iterations, block_rows=rows)
+            for k in SAME_KEYS:
+                assert np.array_equal(whole[k], cut[k]), (order, rows, k)
+            assert [whole[k] for k in ("S", "T", "speed", "eff", "moved", "comparisons")] == [cut[k] for k in ("S", "T", "speed", "eff", "moved", "comparisons")]
+            assert (cut["wide"] is None) == (order != "extended" or ly.extended_type() is None)
+
+
+@pytest.mark.parametrize("n", [300, 700])
+def test_the_extended_order_is_within_its_bound_of_the_exactly_rounded_one(n):
+    """The float64 terms accumulated in 64 significant bits are within n 2^-64 B of the exact sum s (at most 2 n - 1 terms,
+    summed pairwise: the bound has room).  The fsum order gives fl(s), itself within u |s| of s, so the unrounded
+    extended sum ("wide") is held to n 2^-64 B + u |fl(s)| of it, and the rounded one is fl(s) or a neighbour of it.
+    Where np.longdouble is no wider than float64 the order IS fsum per row."""
+    d = 9
+    _, graph, eb, _ = synth.master_pangenome_counts(n, d, n, loops=0.05, multi_frac=0.1)
+    pos = np.random.default_rng(n).random((n, 2))
+    pos[n // 2] = pos[0]
+    exact = one(graph, eb, d, pos, order="fsum")
+    wide = one(graph, eb, d, pos, order="extended", block_rows=64)
+    if ly.extended_type() is None:
+        assert np.array_equal(wide["forces"], exact["forces"]) and wide["wide"] is None
+        return
+    assert np.finfo(np.longdouble).nmant >= 63 and wide["wide"].dtype == np.longdouble
+    B = exact["bound"]
+    assert np.array_equal(wide["bound"], B)
+    off = np.abs(wide["wide"] - exact["forces"].astype(np.longdouble))
+    room = (n * 2.0 ** -64) * B + U * np.abs(exact["forces"])
+    print("n %d: the extended sums are at most %.3g of n 2^-64 B + u |f| off the exactly rounded ones; %d of %d rounded ones differ"
+          % (n, float((off / room).max()), int((wide["forces"] != exact["forces"]).sum()), 2 * n))
+    assert (off <= room).all()
+    assert np.array_equal(wide["forces"], wide["wide"].astype(np.float64))
+    assert (np.abs(wide["forces"] - exact["forces"]) <= np.spacing(np.abs(exact["forces"]))).all()
+    assert (wide["S"], wide["T"]) != (0.0, 0.0) and abs(wide["S"] - exact["S"]) <= step_tolerances(n, ly.layout_graph(graph, eb, d)["mass"], exact, np.zeros((n, 2)), 1.0)["S"]
+
+
+def test_without_a_wide_longdouble_the_extended_order_is_fsum_per_row(monkeypatch):
+    """where np.longdouble has fewer than 64 significant bits (extended_type() is None) order="extended" sums every row
+    with math.fsum: the exactly rounded order, bit for bit"""
+    n, d = 90, 9
+    _, graph, eb = ring_with_chords(n, d, 3)
+    pos = np.random.default_rng(2).random((n, 2))
+    assert ly.extended_type() in (None, np.longdouble) and (ly.extended_type() is None) == (np.finfo(np.longdouble).nmant < 63)
+    monkeypatch.setattr(ly, "extended_type", lambda: None)
+    exact = one(graph, eb, d, pos, order="fsum", iterations=2)
+    narrow = one(graph, eb, d, pos, order="extended", iterations=2, block_rows=32)
+    assert narrow["wide"] is None
+    for k in SAME_KEYS:
+        assert np.array_equal(exact[k], narrow[k]), k
+    assert (exact["S"], exact["T"], exact["speed"], exact["eff"]) == (narrow["S"], narrow["T"], narrow["speed"], narrow["eff"])
+
+
+def slice_len(n):
+    return -(-n // ly.slices_of(n))
+
+
+def test_the_slice_arithmetic_the_large_shapes_rest_on():
+    """k_layout_repulse walks a slice of the j range in tiles of TILE: 8192 is the largest n whose slice is one full tile,
+    8193 the smallest with a second trip of the tile loop (a tile of one j), 12500 has two full tiles and one of 84; and
+    no slice is empty (its block would still be launched: j0 = j1 = n), at any n below 2^20"""
+    import ctypes as C
+    lib = ly._bind_layout(load_library())
+    for n, slices, length in ((8192, 32, 256), (8193, 32, 257), (12500, 21, 596)):
+        assert (ly.slices_of(n), slice_len(n)) == (slices, length) and lib.nemgpu_layout_slices(n, None, None) == slices, n
+    assert 596 == 2 * ly.TILE + 84
+    first = next(n for n in range(1, 2 ** 20) if slice_len(n) > ly.TILE)
+    assert first == 8193
+    for n in range(1, 2 ** 20):
+        s = ly.slices_of(n)
+        assert (s - 1) * (-(-n // s)) < n, n                  # (the last slice starts below n)
+
+
+def repulsion_rows(xy, mass, scaling, rows, keep=None, scale=None):
+    """step 1 of layout_arrays for the rows `rows` alone, j ascending (order="left"), over the j's `keep` (all: None);
+    scale: {(row, j): factor} multiplies single pair terms.  Returns float64 [len(rows)][2]."""
+    out = np.zeros((len(rows), 2))
+    for at, i in enumerate(rows):
+        dx, dy = xy[i, 0] - xy[:, 0], xy[i, 1] - xy[:, 1]
+        d2 = dx * dx + dy * dy
+        with np.errstate(divide="ignore", invalid="ignore"):
+            coef = ((scaling * mass[i]) * mass) / d2
+        coef[~(d2 > 0.0)] = 0.0
+        for c, delta in ((0, dx), (1, dy)):
+            terms = delta * coef
+            for (row, j), factor in (scale or {}).items():
+                if row == i:
+                    terms[j] *= factor
+            if keep is not None:
+                terms = terms[keep]
+            out[at, c] = np.cumsum(terms)[-1]
+    return out
+
+
+def test_the_force_bound_at_8193_rejects_a_wrong_pair_term_and_a_dropped_second_tile():
+    """What tests/test_gpu_layout.py's comparison at n = 8193 can see, shown on the CPU: the yardstick is the row-blocked
+    statement in extended precision, the bound step_tolerances' 2 n u B + n 2^-64 B.  A correct kernel in another order
+    (the blocked statement, j ascending) lies inside it at every family.  Made wrong, it does not:
+      one pair term of one row off by 2^-20 of itself, or missing;
+      the j's behind the first TILE of one slice left out (slice_len - TILE = 1 of them at 8193: what a kernel that
+      never makes the tile loop's second trip computes) -- at every family looked at, 300 of them."""
+    n, d = 8193, 9
+    _, graph, eb, _ = synth.master_pangenome_counts(n, d, 9000 + n, loops=0.05, multi_frac=0.1)
+    g = ly.layout_graph(graph, eb, d)
+    mass = g["mass"]
+    pos = np.random.default_rng(n + 9).random((n, 2))
+    pos[n // 2] = pos[0]
+    want = one(graph, eb, d, pos, order="extended", block_rows=256)
+    tol = step_tolerances(n, mass, want, np.zeros((n, 2)), 1.0, order="extended")["forces"]
+    left = one(graph, eb, d, pos, order="left", block_rows=256)["forces"]
+    inside = lambda f, rows: (np.abs(f - want["forces"][rows]) <= tol[rows]).all(axis=1)
+    everyone = np.arange(n)
+    worst = float((np.abs(left - want["forces"]) / tol).max())
+    print("n %d: another order is at %.3g of the bound; the bound is %.3g of B; one pair term is about %.3g of B"
+          % (n, worst, float((tol / want["bound"]).max()), 1.0 / n))
+    assert inside(left, everyone).all()
+    scaling = ly.DEFAULTS["scaling_ratio"]
+    # the rows looked at: the first, the last, those around the slice's own j's, and a spread of others
+    length, s = slice_len(n), 17
+    gone = np.arange(s * length + ly.TILE, min(n, (s + 1) * length))
+    assert length == ly.TILE + 1 and gone.tolist() == [s * length + ly.TILE]
+    rows = np.unique(np.concatenate([[0, 1, n - 2, n - 1], np.arange(gone[0] - 3, gone[0] + 4), np.random.default_rng(5).integers(0, n, 300)]))
+    rows = rows[(rows != gone[0]) & ~((pos[rows] == pos[gone[0]]).all(axis=1))]      # (its own term and a coincident pair's are 0 anyway)
+    assert len(rows) >= 300
+    full = repulsion_rows(pos, mass, scaling, rows)
+    keep = np.setdiff1d(everyone, gone)
+    dropped = left[rows] + (repulsion_rows(pos, mass, scaling, rows, keep=keep) - full)
+    assert inside(left[rows] + (repulsion_rows(pos, mass, scaling, rows) - full), rows).all()      # (the method itself adds nothing)
+    assert not inside(dropped, rows).any(), "a dropped second tile passes the bound at %d of %d families" % (int(inside(dropped, rows).sum()), len(rows))
+    # one pair term of one row: the middle-sized term of that row
+    i = int(rows[len(rows) // 2])
+    dx, dy = pos[i] - pos[n - 7]
+    assert dx != 0.0 and dy != 0.0
+    k = int(np.nonzero(rows == i)[0][0])
+    for factor in (1.0 + 2.0 ** -20, 0.0):
+        wrong = left[rows] + (repulsion_rows(pos, mass, scaling, rows, scale={(i, n - 7): factor}) - full)
+        verdict = inside(wrong, rows)
+        assert not verdict[k] and verdict.sum() == len(rows) - 1, (factor, i)

@@ -374,6 +374,33 @@ int nemgpu_edge_table_fetch(const nemgpu_edge_table* t, int32_t* src, int32_t* d
 int nemgpu_edge_table_attvalues_size(nemgpu_edge_table* t, const nemgpu_master* m, const int32_t* attr_id, int row0, int rows, int64_t* bytes);
 int nemgpu_edge_table_attvalues(nemgpu_edge_table* t, const nemgpu_master* m, const int32_t* attr_id, int row0, int rows, char* text,
                                 int64_t capacity, int64_t* needed, int64_t* edge_end);
+/* The organisms' METADATA on the edges (export_to_GEXF's metadata=, ppanggolin.py:1339-1354): per edge and attribute the
+   sorted set of the values of the organisms that carry the edge, joined by `|`.  The caller ranks every attribute's
+   distinct values in sorted order and escapes them; the device ORs one-hot(rank) over an edge's organisms and writes
+   the values present in increasing rank.
+   _metadata: gives the table its metadata, uploaded once and kept until the next _metadata call or _destroy.  HOST:
+     n_attr > 0;  attr_id[n_attr] >= 0   the attributes' ids, in the order their lines are written;
+     value_rank[n_attr][d]   every organism's value as its rank in [0, n_values[a]);
+     n_values[n_attr]        the attribute's distinct values, 1 .. 65536 (an edge's mask of one attribute is built in
+                             8 KiB of LDS per wave);
+     value_ptr[V + 1], value_text   V = the sum of n_values: the bytes of value (a, rank) are value_text[value_ptr[v]
+                             .. value_ptr[v + 1]) with v = n_values[0] + .. + n_values[a - 1] + rank; value_ptr starts at 0
+                             and ascends (an empty value is a value); value_ptr[V] + V <= 2^30.  A single value's length
+                             has no bound of its own: no value is staged.
+   Anything outside that is refused with NEMGPU_E_ARG before any launch, and the table keeps the metadata it had.
+   _metamasks: for edges row0 .. row0 + rows - 1 the present-value bit masks into masks[rows][W] (HOST), W = the sum over
+   the attributes of ceil(n_values[a] / 32): an edge's words are the attributes' one after the other, bit (rank & 31) of
+   word (rank >> 5) set where an organism of the edge has that value.
+   _metavalues_size / _metavalues: as _attvalues_size / _attvalues, the same contract (*needed always set, a capacity
+   below it NEMGPU_E_ARG and nothing written): per edge, per attribute in order, the line
+   `          <attvalue for="ID" value="V1|V2|..." />\n`.  m is only read; the work runs on m's stream, its scratch is
+   allocated for the call and freed.  Without metadata these three return NEMGPU_E_ARG. */
+int nemgpu_edge_table_metadata(nemgpu_edge_table* t, int n_attr, const int32_t* attr_id, const int32_t* value_rank, const int32_t* n_values,
+                               const int64_t* value_ptr, const char* value_text);
+int nemgpu_edge_table_metamasks(nemgpu_edge_table* t, const nemgpu_master* m, int row0, int rows, uint32_t* masks);
+int nemgpu_edge_table_metavalues_size(nemgpu_edge_table* t, const nemgpu_master* m, int row0, int rows, int64_t* bytes);
+int nemgpu_edge_table_metavalues(nemgpu_edge_table* t, const nemgpu_master* m, int row0, int rows, char* text, int64_t capacity, int64_t* needed,
+                                 int64_t* edge_end);
 void nemgpu_edge_table_destroy(nemgpu_edge_table* t);
 /* The pangenome graph LAID OUT on the device: PPanGGOLiN.compute_layout (ppanggolin.py:1250-1292), which hands the
    family graph to ForceAtlas2 (Jacomy et al. 2014) and puts the positions on the nodes.  The reference delegates to the

@@ -653,7 +653,7 @@ class Master:
         as PPanGGOLiN holds it.  orders=(genes, contig_ptr, contig_org[, repeated[, f]]) with starts=, ends= int32 [G] and
         contig_sizes= int32 [C] (-1: linear) instead: flat arrays, for a master without names.  Orders whose links are not
         this master's edges, organisms and counts raise NemGpuError; so does a directed master.  Returns a
-        gexf.EdgeTable (the arrays, attvalues(), close())."""
+        gexf.EdgeTable (the arrays, attvalues(), set_metadata() / metavalues(), close())."""
         from . import gexf
         if orders is not None:
             if annotations is not None or starts is None or ends is None or contig_sizes is None:
@@ -700,8 +700,8 @@ class Master:
         seed: None is time(), as the reference seeds; it is the starts' stream and the tie stream (one random() stream, as
         in nem()).  The numbers in the labels and in .parameters went through the `.mf`'s print formats ("%5.3g",
         "%10g", "%10.3g"), as the reference reads them.  A run that emptied a class raises KeyError('U'), as the
-        reference does.  Not here: the untangled graph, metadata= (the CLI's -ss 0 builds its dict from a metadata
-        file; the dict itself is supported).  A directed master raises NemGpuError.  This master is only read.
+        reference does.  Not here: the untangled graph.  The CLI's -ss 0 builds its dict from the metadata file:
+        gexf.shell_init_from_metadata(gexf.read_metadata(file, organisms)).  A directed master raises NemGpuError.  This master is only read.
         Returns a shell.ShellSubpartition: Q, parameters {label: ([organisms], mean eps, proportion)}, organisms
         {organism: {labels}}, families {label: [families]}, node_attribute {family: label | its partition's long name}."""
         from . import shell

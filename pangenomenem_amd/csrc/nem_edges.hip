@@ -398,9 +398,17 @@ struct nemgpu_edge_table {
     long long* partial = nullptr;
     size_t ends_cap = 0;
     TableText txt;
+    EdgeMetaDev meta{};                               // nemgpu_edge_table_metadata's; n_attr 0: none
 };
 
 namespace {
+
+void meta_free(EdgeMetaDev* v)
+{
+    void* all[] = {v->attr_id, v->n_values, v->rank, v->mask_off, v->val_base, v->val_ptr, v->blob};
+    for (void* p : all) if (p) (void)hipFree(p);
+    *v = EdgeMetaDev{};
+}
 
 void table_free(nemgpu_edge_table* t)
 {
@@ -408,7 +416,21 @@ void table_free(nemgpu_edge_table* t)
     void* all[] = {v.src, v.dst, v.entry, v.weight, v.len_min, v.len_max, v.len_distinct, v.len_sum, v.len_mid_lo, v.len_mid_hi, v.fam_mid_lo,
                    v.fam_mid_hi, v.org_first_edge, t->attr, t->ends, t->partial, t->txt.text};
     for (void* p : all) if (p) (void)hipFree(p);
+    meta_free(&t->meta);
     delete t;
+}
+
+// room for a batch's edge ends and their scan's tile totals
+int ends_room(nemgpu_edge_table* t, int rows)
+{
+    if (t->ends_cap >= (size_t)rows) return NEMGPU_OK;
+    if (t->ends) (void)hipFree(t->ends);
+    if (t->partial) (void)hipFree(t->partial);
+    t->ends = nullptr; t->partial = nullptr; t->ends_cap = 0;
+    HIPCHK(hipMalloc((void**)&t->ends, ((size_t)rows + 1) * 8));
+    HIPCHK(hipMalloc((void**)&t->partial, ((size_t)rows / seg::kScanTile + 2) * 8));
+    t->ends_cap = (size_t)rows;
+    return NEMGPU_OK;
 }
 
 // what both text calls check and compute: the batch's edge ends on the device (t->ends) and its size
@@ -419,14 +441,7 @@ int batch_sizes(const std::string& who, nemgpu_edge_table* t, const nemgpu_maste
         if (attr_id[o] < 0) { set_error(who + ": attr_id " + std::to_string(o) + " is negative"); return NEMGPU_E_ARG; }
     HIPCHK(hipSetDevice(t->device));
     if (!t->attr) HIPCHK(hipMalloc((void**)&t->attr, (size_t)t->dev.d * 4));
-    if (t->ends_cap < (size_t)rows) {
-        if (t->ends) (void)hipFree(t->ends);
-        if (t->partial) (void)hipFree(t->partial);
-        t->ends = nullptr; t->partial = nullptr; t->ends_cap = 0;
-        HIPCHK(hipMalloc((void**)&t->ends, ((size_t)rows + 1) * 8));
-        HIPCHK(hipMalloc((void**)&t->partial, ((size_t)rows / seg::kScanTile + 2) * 8));
-        t->ends_cap = (size_t)rows;
-    }
+    { const int r = ends_room(t, rows); if (r != NEMGPU_OK) return r; }
     HIPCHK(hipMemcpyAsync(t->attr, attr_id, (size_t)t->dev.d * 4, hipMemcpyHostToDevice, m->stream));
     launch_att_sizes(m->dev, t->dev, t->attr, row0, rows, t->ends, m->stream);
     seg::scan<long long, seg::OpSum<long long>, true>(t->ends, t->ends, rows, seg::OpSum<long long>(), 0ll, t->partial, t->ends + rows, m->stream);
@@ -434,6 +449,32 @@ int batch_sizes(const std::string& who, nemgpu_edge_table* t, const nemgpu_maste
     HIPCHK(hipMemcpyAsync(bytes, t->ends + rows, 8, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     return NEMGPU_OK;
+}
+
+// what the metadata calls check and compute: the batch's present-value masks (*masks, mem's), from them its edge ends
+// on the device (t->ends) and its size
+int meta_batch(const std::string& who, nemgpu_edge_table* t, const nemgpu_master* m, int row0, int rows, seg::Scratch& mem, uint32_t** masks,
+               int64_t* bytes)
+{
+    { const int r = check_batch(who, m, t->dev.n, t->dev.d, t->device, row0, rows, t->dev.ne); if (r != NEMGPU_OK) return r; }
+    if (!t->meta.n_attr) { set_error(who + ": the table has no metadata (nemgpu_edge_table_metadata)"); return NEMGPU_E_ARG; }
+    HIPCHK(hipSetDevice(t->device));
+    { const int r = ends_room(t, rows); if (r != NEMGPU_OK) return r; }
+    HIPCHK(mem.alloc(masks, (size_t)rows * t->meta.mask_words));
+    launch_meta_masks(m->dev, t->dev, t->meta, row0, rows, *masks, m->stream);
+    if (!bytes) return NEMGPU_OK;
+    launch_meta_sizes(t->meta, rows, *masks, t->ends, m->stream);
+    seg::scan<long long, seg::OpSum<long long>, true>(t->ends, t->ends, rows, seg::OpSum<long long>(), 0ll, t->partial, t->ends + rows, m->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(bytes, t->ends + rows, 8, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return NEMGPU_OK;
+}
+
+template <class T> hipError_t upload(T** dev, const T* host, size_t count)
+{
+    HIPTRY(seg::dev_alloc(dev, count));
+    return count ? hipMemcpy(*dev, host, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
 }
 
 }  // namespace
@@ -537,6 +578,107 @@ int nemgpu_edge_table_attvalues(nemgpu_edge_table* t, const nemgpu_master* m, co
     { const int r = batch_sizes(who, t, m, attr_id, row0, rows, &bytes); if (r != NEMGPU_OK) return r; }
     { const int r = text_room(who, &t->txt, capacity, bytes, needed); if (r != NEMGPU_OK) return r; }
     launch_att_text(m->dev, t->dev, t->attr, row0, rows, t->ends, t->txt.text, m->stream);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipMemcpyAsync(edge_end, t->ends, (size_t)rows * 8, hipMemcpyDeviceToHost, m->stream);
+    if (err == hipSuccess && bytes) err = hipMemcpyAsync(text, t->txt.text, (size_t)bytes, hipMemcpyDeviceToHost, m->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(m->stream);
+    return device_status(who, err);
+}
+
+int nemgpu_edge_table_metadata(nemgpu_edge_table* t, int n_attr, const int32_t* attr_id, const int32_t* value_rank, const int32_t* n_values,
+                               const int64_t* value_ptr, const char* value_text)
+{
+    if (!t || !attr_id || !value_rank || !n_values || !value_ptr) return NEMGPU_E_FUNCARG;
+    const std::string who = "nemgpu_edge_table_metadata";
+    const int d = t->dev.d;
+    if (n_attr <= 0) { set_error(who + ": n_attr > 0"); return NEMGPU_E_ARG; }
+    std::vector<int> mask_off((size_t)n_attr + 1, 0), val_base((size_t)n_attr, 0);
+    long long values = 0, words = 0;
+    for (int a = 0; a < n_attr; a++) {
+        if (attr_id[a] < 0) { set_error(who + ": attr_id " + std::to_string(a) + " is negative"); return NEMGPU_E_ARG; }
+        if (n_values[a] < 1 || n_values[a] > kMetaValuesMax) {
+            set_error(who + ": attribute " + std::to_string(a) + " has " + std::to_string(n_values[a]) + " values, 1 .. " +
+                      std::to_string(kMetaValuesMax) + " are held");
+            return NEMGPU_E_ARG;
+        }
+        for (int o = 0; o < d; o++) {
+            const int v = value_rank[(size_t)a * d + o];
+            if (v < 0 || v >= n_values[a]) {
+                set_error(who + ": attribute " + std::to_string(a) + ", organism " + std::to_string(o) + ": rank " + std::to_string(v) + " outside its " +
+                          std::to_string(n_values[a]) + " values");
+                return NEMGPU_E_ARG;
+            }
+        }
+        val_base[a] = (int)values;
+        values += n_values[a];
+        words += (n_values[a] + 31) / 32;
+        if (values > kMetaTextMax) { set_error(who + ": too many values"); return NEMGPU_E_ARG; }
+        mask_off[(size_t)a + 1] = (int)words;
+    }
+    if (value_ptr[0] != 0) { set_error(who + ": value_ptr must start at 0"); return NEMGPU_E_ARG; }
+    for (long long v = 0; v < values; v++)
+        if (value_ptr[v + 1] < value_ptr[v]) { set_error(who + ": value_ptr must ascend (value " + std::to_string(v) + ")"); return NEMGPU_E_ARG; }
+    const long long bytes = value_ptr[values];
+    if (bytes + values > kMetaTextMax) {
+        set_error(who + ": the values take " + std::to_string(bytes) + " bytes, with their number at most " + std::to_string(kMetaTextMax));
+        return NEMGPU_E_ARG;
+    }
+    if (bytes && !value_text) return NEMGPU_E_FUNCARG;
+    std::vector<int> ptr((size_t)values + 1);
+    for (long long v = 0; v <= values; v++) ptr[(size_t)v] = (int)value_ptr[v];
+    note_hip_used();
+    HIPCHK(hipSetDevice(t->device));
+    meta_free(&t->meta);
+    EdgeMetaDev v;
+    v.mask_words = (int)words;
+    hipError_t err = upload(&v.attr_id, (const int*)attr_id, (size_t)n_attr);
+    if (err == hipSuccess) err = upload(&v.n_values, (const int*)n_values, (size_t)n_attr);
+    if (err == hipSuccess) err = upload(&v.rank, (const int*)value_rank, (size_t)n_attr * d);
+    if (err == hipSuccess) err = upload(&v.mask_off, (const int*)mask_off.data(), mask_off.size());
+    if (err == hipSuccess) err = upload(&v.val_base, (const int*)val_base.data(), val_base.size());
+    if (err == hipSuccess) err = upload(&v.val_ptr, (const int*)ptr.data(), ptr.size());
+    if (err == hipSuccess) err = upload(&v.blob, value_text, (size_t)bytes);
+    if (err != hipSuccess) { meta_free(&v); return device_status(who, err); }
+    v.n_attr = n_attr;
+    t->meta = v;
+    return NEMGPU_OK;
+}
+
+int nemgpu_edge_table_metamasks(nemgpu_edge_table* t, const nemgpu_master* m, int row0, int rows, uint32_t* masks)
+{
+    if (!t || !m || !masks) return NEMGPU_E_FUNCARG;
+    const std::string who = "nemgpu_edge_table_metamasks";
+    seg::Scratch mem;
+    uint32_t* dev = nullptr;
+    { const int r = meta_batch(who, t, m, row0, rows, mem, &dev, nullptr); if (r != NEMGPU_OK) return r; }
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipMemcpyAsync(masks, dev, (size_t)rows * t->meta.mask_words * 4, hipMemcpyDeviceToHost, m->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(m->stream);
+    return device_status(who, err);
+}
+
+int nemgpu_edge_table_metavalues_size(nemgpu_edge_table* t, const nemgpu_master* m, int row0, int rows, int64_t* bytes)
+{
+    if (!t || !m || !bytes) return NEMGPU_E_FUNCARG;
+    seg::Scratch mem;
+    uint32_t* masks = nullptr;
+    int64_t size = 0;
+    const int r = meta_batch("nemgpu_edge_table_metavalues_size", t, m, row0, rows, mem, &masks, &size);
+    if (r == NEMGPU_OK) *bytes = size;
+    return r;
+}
+
+int nemgpu_edge_table_metavalues(nemgpu_edge_table* t, const nemgpu_master* m, int row0, int rows, char* text, int64_t capacity, int64_t* needed,
+                                 int64_t* edge_end)
+{
+    if (!t || !m || !text || !edge_end) return NEMGPU_E_FUNCARG;
+    const std::string who = "nemgpu_edge_table_metavalues";
+    seg::Scratch mem;
+    uint32_t* masks = nullptr;
+    int64_t bytes = 0;
+    { const int r = meta_batch(who, t, m, row0, rows, mem, &masks, &bytes); if (r != NEMGPU_OK) return r; }
+    { const int r = text_room(who, &t->txt, capacity, bytes, needed); if (r != NEMGPU_OK) return r; }
+    launch_meta_text(t->meta, rows, masks, t->ends, t->txt.text, m->stream);
     hipError_t err = hipGetLastError();
     if (err == hipSuccess) err = hipMemcpyAsync(edge_end, t->ends, (size_t)rows * 8, hipMemcpyDeviceToHost, m->stream);
     if (err == hipSuccess && bytes) err = hipMemcpyAsync(text, t->txt.text, (size_t)bytes, hipMemcpyDeviceToHost, m->stream);

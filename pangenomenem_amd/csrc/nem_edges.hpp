@@ -27,6 +27,21 @@
 // wave scan of their widths, laid out in LDS at the global address's alignment and copied out in aligned 8-byte words
 // (only a run's first and last partial words by bytes); a group of 64 organisms none of which is on the edge costs one
 // load and one ballot.  gexf.edge_table_arrays / gexf.attvalues_host (Python) state the same.
+//
+// The METADATA lines (nem_edge_meta.hip; export_to_GEXF's metadata=, :1339-1354): per edge and attribute the sorted set
+// of the values of the edge's organisms.  The host ranks every attribute's distinct values in sorted order, so the set
+// is a bit mask over the ranks and "sorted" is "increasing bit":
+//   k_meta_masks   one wave per edge; per attribute the mask is zeroed in the wave's LDS, the edge's bit row is read 64
+//                  organisms at a time as k_att_text reads it and every set organism ORs one-hot(rank) into LDS (an LDS
+//                  atomic; no global atomic), then the words go out to masks[rows][mask_words];
+//   k_meta_sizes / k_meta_text   one wave per edge, both read those masks and take a line's width from
+//                  meta_line_width; the text pass puts a line's tail at its start + width - 5, so an edge's bytes stay
+//                  in [edge_end[e - 1], edge_end[e]).  A value's bytes are copied by the wave, a lane per byte, straight
+//                  from the blob: nothing of a value is staged, so a value's length has no bound of its own.
+// Bounds (refused on the host before any launch): an attribute has 1 .. kMetaValuesMax distinct values -- its mask is
+// kMetaValuesMax / 32 words = 8 KiB of LDS per wave, 32 KiB per block of 4 waves; the blob's bytes plus the number of
+// values is at most kMetaTextMax, so a line's width fits an int.  gexf.edge_metadata_arrays / gexf.metavalues_host
+// (Python) state the same.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -65,5 +80,27 @@ void launch_att_sizes(const MasterDev& m, const EdgeTableDev& t, const int* attr
 // the lines themselves; ends[rows] (DEVICE): the inclusive scan of the sizes; text (DEVICE): ends[rows - 1] bytes
 void launch_att_text(const MasterDev& m, const EdgeTableDev& t, const int* attr_id, int row0, int rows, const long long* ends, char* text,
                      hipStream_t s);
+
+// ---- the metadata lines (nem_edge_meta.hip) -------------------------------------------------------------------
+constexpr int kMetaValuesMax = 65536;             // distinct values of one attribute: the wave's mask in LDS
+constexpr long long kMetaTextMax = 1ll << 30;     // the values' bytes + the number of values
+
+// a table's metadata on the device (owned by nem_edges.hip's handle)
+struct EdgeMetaDev {
+    int n_attr = 0, mask_words = 0;               // mask_words: an edge's masks, the attributes' one after the other
+    int *attr_id = nullptr, *n_values = nullptr;  // [n_attr]
+    int* rank = nullptr;                          // [n_attr][d]: the organism's value as its rank among the attribute's
+    int* mask_off = nullptr;                      // [n_attr + 1]: the attribute's first word in an edge's masks
+    int* val_base = nullptr;                      // [n_attr]: the attribute's first value in val_ptr
+    int* val_ptr = nullptr;                       // [values + 1]: a value's bytes in blob
+    char* blob = nullptr;
+};
+
+// per edge row0 .. row0 + rows - 1 the present-value masks into masks[rows][mask_words] (DEVICE)
+void launch_meta_masks(const MasterDev& m, const EdgeTableDev& t, const EdgeMetaDev& meta, int row0, int rows, uint32_t* masks, hipStream_t s);
+// from those masks: per edge the bytes of its lines into sizes[rows] (DEVICE)
+void launch_meta_sizes(const EdgeMetaDev& meta, int rows, const uint32_t* masks, long long* sizes, hipStream_t s);
+// the lines themselves; ends[rows] (DEVICE): the inclusive scan of the sizes; text (DEVICE): ends[rows - 1] bytes
+void launch_meta_text(const EdgeMetaDev& meta, int rows, const uint32_t* masks, const long long* ends, char* text, hipStream_t s);
 
 }  // namespace nemk

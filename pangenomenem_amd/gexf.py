@@ -12,12 +12,19 @@ master's organisms with every gene's START and END and every circular contig's s
 ``Master.edge_table`` (chunks.py) is their Python surface; ``EdgeTable`` / ``HostEdgeTable`` hold the result;
 ``write_gexf`` streams the file, byte for byte what networkx writes, and ``ushape_counts`` gives the plot's series.
 
+``export_to_GEXF(metadata=)`` (:1339-1354) gives every edge, per metadata attribute, the sorted set of the values of the
+organisms that carry it: ``read_metadata`` is the CLI's parse of the ``-mt`` file, ``rank_metadata`` ranks and escapes
+the values on the host, ``edge_metadata_arrays`` states the edges' present-value masks and ``metavalues_host`` their
+lines; ``nemgpu_edge_table_metadata`` / ``_metamasks`` / ``_metavalues`` (csrc/nem_edge_meta.hip) compute both on the
+device; ``shell_init_from_metadata`` turns the same dict into ``partition_shell``'s ``init_using_qual``.
+
 Where the reference's bytes are not determined -- ``"|".join(set)`` of a node's names, products and an organism's genes
 follows string hash order; the ``<meta>`` element holds the date and networkx's version -- the values are joined in walk
 order here and ``<meta>`` names this package.
 """
 import ctypes as C
 import gzip
+import os
 import time
 
 import numpy as np
@@ -31,6 +38,9 @@ EDGE_FIELDS = ("src", "dst", "weight", "len_min", "len_max", "len_distinct", "le
 COLORS_RGB = {"accessory": (235, 55, 237), "core_exact": (255, 40, 40), "shell": (0, 216, 96), "persistent": (247, 165, 7),
               "cloud": (121, 222, 255), "undefined": (130, 130, 130)}                             # ppanggolin.py:34 (a is 0)
 LINE_MAX = 59                                                 # an organism line of an edge: 39 bytes and two numbers of 10 digits
+LINE_FIXED = 39                                               # an <attvalue> line without its id and its value
+LENGTH_TITLES = ("length_avg", "length_med", "length_min", "length_max")
+META_VALUES_MAX = 65536                                       # distinct values of one attribute the device holds (nem_edges.hpp)
 HEAD = ("<?xml version='1.0' encoding='utf-8'?>\n"
         '<gexf xmlns:viz="http://www.gexf.net/1.2draft/viz" xmlns="http://www.gexf.net/1.2draft" '
         'xmlns:xsi="http://www.w3.org/2001/XMLSchema-instance" '
@@ -225,6 +235,159 @@ def attvalues_host(graph, edge_bits, edge_counts, attr_id, d, row0=0, rows=None)
     return np.frombuffer(b"".join(parts), np.uint8).copy(), ends
 
 
+def read_metadata(file, organisms):
+    """The CLI's parse of its -mt METADATA_FILE (command_line.py:439-447, 487): tab-separated, the first line the attribute
+    names, line i + 1 the values of the i-th organism of `organisms` (pan.organisms), every element stripped; zip() cuts
+    a line at the header's length and the lines at the organisms' number, as there.  file: a path or an iterable of
+    lines.  Returns {organism: {attribute: value}}, both ordered: what write_gexf(metadata=) takes."""
+    lines = open(file, encoding="utf-8") if isinstance(file, (str, bytes, os.PathLike)) else file
+    try:
+        names, rows = [], []
+        for num, line in enumerate(lines):
+            elements = [el.strip() for el in line.split("\t")]
+            if num == 0:
+                names = elements
+            else:
+                rows.append(dict(zip(names, elements)))
+    finally:
+        if lines is not file:
+            lines.close()
+    return dict(zip(list(organisms), rows))
+
+
+def shell_init_from_metadata(metadata, attribute=None):
+    """{value: set(organisms)} of one metadata column -- the first one (the -ss help text: "use the first column of
+    metadata"), or `attribute` -- ready for Master.partition_shell(init_using_qual=).  The reference's own lines
+    (command_line.py:494-497) use an organism's whole dict as the key and raise TypeError; this follows the help text."""
+    init = {}
+    for org, values in metadata.items():
+        if attribute is None and not values:
+            raise ValueError("shell_init_from_metadata: organism %r has no metadata" % (org,))
+        key = next(iter(values)) if attribute is None else attribute
+        if key not in values:
+            raise ValueError("shell_init_from_metadata: organism %r has no attribute %r" % (org, key))
+        init.setdefault(values[key], set()).add(org)
+    return init
+
+
+def rank_metadata(metadata, organisms, reserved=()):
+    """export_to_GEXF's metadata ({organism: ordered {attribute: str}}) as the arrays the edge tables take, made on the
+    host: per attribute its distinct values sorted as Python sorts str (code points: the order of their UTF-8 bytes too),
+    every organism's value as its rank among them, and the values escaped as ElementTree escapes them, in one blob.
+    ValueError: an organism of `organisms` without an entry; a value that is not a str; organisms whose attribute names or
+    their order differ (the CLI's zip over one header row cannot make that); an attribute named like an organism or one
+    of `reserved`; more than META_VALUES_MAX distinct values.
+    Returns a dict: titles [n_attr], value_rank int32 [n_attr][d], n_values int32 [n_attr], value_ptr int64 [V + 1],
+    value_text uint8 [bytes]."""
+    organisms = list(organisms)
+    for org in organisms:
+        if org not in metadata:
+            raise ValueError("metadata: organism %r is missing" % (org,))
+    titles = list(metadata[organisms[0]]) if organisms else []
+    taken = set(organisms) | set(reserved)
+    for title in titles:
+        if not isinstance(title, str) or title in taken:
+            raise ValueError("metadata: attribute %r is named like an organism or another edge attribute" % (title,))
+    for org in organisms:
+        if list(metadata[org]) != titles:
+            raise ValueError("metadata: organism %r has attributes %r, %r has %r" % (org, list(metadata[org]), organisms[0], titles))
+        for title, value in metadata[org].items():
+            if not isinstance(value, str):
+                raise ValueError("metadata: %r of organism %r is %r, not a str" % (title, org, value))
+    rank = np.zeros((len(titles), len(organisms)), np.int32)
+    n_values, ptr, blob = [], [0], []
+    for a, title in enumerate(titles):
+        values = sorted(set(metadata[org][title] for org in organisms))
+        if len(values) > META_VALUES_MAX:
+            raise ValueError("metadata: attribute %r has %d distinct values, %d are held" % (title, len(values), META_VALUES_MAX))
+        at = {value: k for k, value in enumerate(values)}
+        rank[a] = [at[metadata[org][title]] for org in organisms]
+        n_values.append(len(values))
+        for value in values:
+            blob.append(escape(value).encode("utf-8"))
+            ptr.append(ptr[-1] + len(blob[-1]))
+    return dict(titles=titles, value_rank=rank, n_values=np.asarray(n_values, np.int32), value_ptr=np.asarray(ptr, np.int64),
+                value_text=np.frombuffer(b"".join(blob), np.uint8).copy())
+
+
+def _check_ranks(value_rank, n_values):
+    if (n_values < 1).any() or (n_values > META_VALUES_MAX).any():
+        raise ValueError("metadata: an attribute has 1 .. %d values" % META_VALUES_MAX)
+    if (value_rank < 0).any() or (value_rank >= n_values[:, None]).any():
+        raise ValueError("metadata: a rank outside its attribute's values")
+
+
+def _check_metadata(attr_id, value_rank, n_values, value_ptr, value_text, d):
+    """the arrays nemgpu_edge_table_metadata takes, checked as it checks them: (attr_id, value_rank, n_values, value_ptr,
+    value_text) contiguous in its types"""
+    attr_id, n_values = np.ascontiguousarray(attr_id, np.int32), np.ascontiguousarray(n_values, np.int32)
+    value_rank, value_ptr = np.ascontiguousarray(value_rank, np.int32), np.ascontiguousarray(value_ptr, np.int64)
+    value_text = np.ascontiguousarray(value_text, np.uint8)
+    n_attr = len(attr_id)
+    if n_attr < 1 or attr_id.ndim != 1 or n_values.shape != (n_attr,) or value_rank.shape != (n_attr, d):
+        raise ValueError("metadata: attr_id [n_attr], n_attr > 0, value_rank [n_attr][d], n_values [n_attr]")
+    if (attr_id < 0).any():
+        raise ValueError("metadata: an attr_id is negative")
+    _check_ranks(value_rank, n_values)
+    if value_ptr.shape != (int(n_values.sum()) + 1,) or value_ptr[0] != 0 or (np.diff(value_ptr) < 0).any() or value_ptr[-1] != len(value_text):
+        raise ValueError("metadata: value_ptr [values + 1] from 0, ascending, to the bytes of value_text")
+    return attr_id, value_rank, n_values, value_ptr, value_text
+
+
+def _present_values(graph, edge_bits, value_rank, n_values, d, row0, rows, who):
+    """per attribute bool [rows][n_values[a]]: the values of the organisms on each edge"""
+    ptr, idx = graph
+    _, _, entry = master_edges(ptr, idx)
+    rows = len(entry) - row0 if rows is None else rows
+    if row0 < 0 or rows <= 0 or row0 + rows > len(entry):
+        raise ValueError(who + ": rows outside the table")
+    bits = _edge_bits_bool(edge_bits, len(idx), d)[entry[row0:row0 + rows]]
+    edge, org = np.nonzero(bits)
+    out = []
+    for rank, count in zip(np.asarray(value_rank, np.int64), n_values):
+        present = np.zeros((rows, int(count)), bool)
+        present[edge, rank[org]] = True
+        out.append(present)
+    return out
+
+
+def edge_metadata_arrays(graph, edge_bits, value_rank, n_values, d, row0=0, rows=None):
+    """What nemgpu_edge_table_metamasks computes, in numpy: for edges row0 .. row0 + rows - 1 (master_edges' numbering)
+    and every attribute the set of the values of the organisms on the edge, as a bit mask over the values' ranks:
+    uint32 [rows][W], W the sum of ceil(n_values[a] / 32), an edge's words the attributes' one after the other, bit
+    (rank & 31) of word (rank >> 5).  value_rank int32 [n_attr][d], n_values int32 [n_attr] (rank_metadata)."""
+    value_rank, n_values = np.asarray(value_rank, np.int64), np.asarray(n_values, np.int64)
+    if value_rank.shape != (len(n_values), d) or not len(n_values):
+        raise ValueError("edge_metadata_arrays: value_rank [n_attr][d], n_values [n_attr], n_attr > 0")
+    _check_ranks(value_rank, n_values)
+    words = []
+    for present in _present_values(graph, edge_bits, value_rank, n_values, d, row0, rows, "edge_metadata_arrays"):
+        padded = np.zeros((present.shape[0], (present.shape[1] + 31) // 32 * 32), np.uint8)
+        padded[:, :present.shape[1]] = present
+        words.append(np.packbits(padded, axis=1, bitorder="little").view("<u4"))
+    return np.ascontiguousarray(np.concatenate(words, axis=1), np.uint32)
+
+
+def metavalues_host(graph, edge_bits, attr_id, value_rank, n_values, value_ptr, value_text, d, row0=0, rows=None):
+    """What nemgpu_edge_table_metavalues writes, in numpy: for edges row0 .. row0 + rows - 1, per attribute in order, the
+    line `          <attvalue for="ID" value="V1|V2|..." />\n` with ID = attr_id[a] and the values present on the edge
+    (edge_metadata_arrays) in increasing rank, their bytes value_text[value_ptr[v] : value_ptr[v + 1]].
+    Returns (text uint8 [bytes], edge_end int64 [rows]: every edge's end offset)."""
+    attr_id, value_rank, n_values, value_ptr, value_text = _check_metadata(attr_id, value_rank, n_values, value_ptr, value_text, d)
+    present = _present_values(graph, edge_bits, value_rank, n_values, d, row0, rows, "metavalues_host")
+    blob, base = value_text.tobytes(), np.concatenate([[0], np.cumsum(n_values)])
+    values = [[blob[value_ptr[base[a] + k]:value_ptr[base[a] + k + 1]] for k in range(n_values[a])] for a in range(len(attr_id))]
+    rows = present[0].shape[0]
+    parts, ends, size = [], np.zeros(rows, np.int64), 0
+    for r in range(rows):
+        for a, mine in enumerate(present):
+            line = b'          <attvalue for="%d" value="' % attr_id[a] + b"|".join(values[a][k] for k in np.flatnonzero(mine[r])) + b'" />\n'
+            parts.append(line)
+            size += len(line)
+        ends[r] = size
+    return np.frombuffer(b"".join(parts), np.uint8).copy(), ends
+
+
 def _bind_edges(lib):
     lib.nemgpu_edge_table_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -233,6 +396,10 @@ def _bind_edges(lib):
     lib.nemgpu_edge_table_attvalues_size.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]
     lib.nemgpu_edge_table_attvalues.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
                                                 C.c_void_p]
+    lib.nemgpu_edge_table_metadata.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+    lib.nemgpu_edge_table_metamasks.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.nemgpu_edge_table_metavalues_size.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    lib.nemgpu_edge_table_metavalues.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]
     lib.nemgpu_edge_table_destroy.argtypes = [C.c_void_p]
     lib.nemgpu_edge_table_destroy.restype = None
     return lib
@@ -244,13 +411,14 @@ class _Edges:
     def arrays(self):
         return {name: getattr(self, name) for name in EDGE_FIELDS}
 
-    def attribute_ids(self, first_id, organisms=True):
+    def attribute_ids(self, first_id, organisms=True, n_attr=0):
         """the ids networkx gives the edge attributes when its counter stands at first_id: it numbers a title where it
         first meets it, walking the edges in order and, inside an edge, its organisms (in column order), then the four
-        length_*.  Returns (attr_id int32 [d], 0 for an organism on no edge; the titles in id order as (id, what), what an
-        organism's column or one of the length titles)."""
+        length_*, then the n_attr metadata attributes (every edge has an organism, so edge 0 has them all).  Returns
+        (attr_id int32 [d], 0 for an organism on no edge; the titles in id order as (id, what), what an organism's column,
+        one of the length titles or ("metadata", j))."""
         attr_id, titles, k = np.zeros(self.d, np.int32), [], first_id
-        lengths = ("length_avg", "length_med", "length_min", "length_max")
+        behind = list(LENGTH_TITLES) + [("metadata", j) for j in range(n_attr)]
         if self.n_edges == 0:
             return attr_id, titles
         first = self.org_first_edge.astype(np.int64)
@@ -258,19 +426,37 @@ class _Edges:
         placed = False
         for o in met:
             if first[o] > 0 and not placed:
-                titles += [(k + j, name) for j, name in enumerate(lengths)]
-                k, placed = k + 4, True
+                titles += [(k + j, what) for j, what in enumerate(behind)]
+                k, placed = k + len(behind), True
             attr_id[o] = k
             titles.append((k, o))
             k += 1
         if not placed:
-            titles += [(k + j, name) for j, name in enumerate(lengths)]
+            titles += [(k + j, what) for j, what in enumerate(behind)]
         return attr_id, titles
 
-    def _batches(self, budget):
+    def _hold_metadata(self, held):
+        """_check_metadata's arrays, for the metavalues calls and for _batches"""
+        self._metadata = held
+        self._metadata_longest = int(np.diff(held[3]).max(initial=0))
+
+    def _metadata_bound(self):
+        """per edge, above the bytes a metavalues call takes for it on the device: every attribute's line with its widest
+        id and as many of its longest value as the edge can have, and the edge's masks"""
+        _, _, n_values, _, _ = self._metadata
+        weight = self.weight.astype(np.int64)
+        bound = np.full(self.n_edges, 4 * int(((n_values.astype(np.int64) + 31) // 32).sum()), np.int64)
+        for count in n_values:
+            bound += LINE_FIXED + 10 + np.minimum(weight, int(count)) * (self._metadata_longest + 1)
+        return bound
+
+    def _batches(self, budget, organisms=True, metadata=False):
         """(row0, rows) covering the edges, each batch's text within the budget by the widest line (one edge where an edge
-        alone is above it)"""
-        bound = np.cumsum(self.weight.astype(np.int64) * LINE_MAX)
+        alone is above it): the organism lines (organisms) and the metadata lines (metadata: set_metadata's) together"""
+        bound = self.weight.astype(np.int64) * LINE_MAX if organisms else np.zeros(self.n_edges, np.int64)
+        if metadata:
+            bound = bound + self._metadata_bound()
+        bound = np.cumsum(bound)
         row0 = 0
         while row0 < self.n_edges:
             base = bound[row0 - 1] if row0 else 0
@@ -321,6 +507,39 @@ class EdgeTable(DeviceTable, _Edges):
                           C.byref(needed), ends.ctypes.data), ends[:rows]
 
 
+    def set_metadata(self, attr_id, value_rank, n_values, value_ptr, value_text):
+        """The metadata the next metavalues calls format (rank_metadata's arrays; attr_id [n_attr]: the attributes' ids),
+        uploaded once (nemgpu_edge_table_metadata) and kept until the next call or close().  Outside its bounds: ValueError
+        here, NemGpuError from the library; the table then keeps the metadata it had."""
+        held = _check_metadata(attr_id, value_rank, n_values, value_ptr, value_text, self.d)
+        self._call("metadata", self._h, len(held[0]), *(a.ctypes.data for a in held))
+        self._hold_metadata(held)
+
+    def metamasks(self, row0=0, rows=None):
+        """The present-value masks of edges row0 .. row0 + rows - 1 from the device (nemgpu_edge_table_metamasks;
+        edge_metadata_arrays states them): uint32 [rows][W]."""
+        rows = self.n_edges - row0 if rows is None else rows
+        words = int(((self._metadata[2].astype(np.int64) + 31) // 32).sum())
+        out = np.zeros((max(rows, 1), words), np.uint32)
+        self._call("metamasks", self._h, self.master._h, int(row0), int(rows), out.ctypes.data)
+        return out[:rows]
+
+    def metavalues_size(self, row0, rows):
+        size = C.c_int64()
+        self._call("metavalues_size", self._h, self.master._h, int(row0), int(rows), C.byref(size))
+        return size.value
+
+    def metavalues(self, row0=0, rows=None, out=None):
+        """The metadata lines of edges row0 .. row0 + rows - 1, formatted on the device (nemgpu_edge_table_metavalues;
+        metavalues_host states them): (text uint8 [bytes], edge_end int64 [rows]).  out: as attvalues'."""
+        rows = self.n_edges - row0 if rows is None else rows
+        if out is None:
+            out = np.empty(max(self.metavalues_size(row0, rows), 1), np.uint8)
+        ends, needed = np.zeros(max(rows, 1), np.int64), C.c_int64()
+        return self._text("metavalues", out, needed, self._h, self.master._h, int(row0), int(rows), out.ctypes.data, out.size, C.byref(needed),
+                          ends.ctypes.data), ends[:rows]
+
+
 class HostEdgeTable(_Edges):
     """The same table from the numpy statement (edge_table_arrays, attvalues_host): what the device is held against, and a
     table for a caller who has the master's arrays on the host.  graph, edge_bits, edge_counts, order, d: the master's."""
@@ -338,6 +557,18 @@ class HostEdgeTable(_Edges):
 
     def attvalues_size(self, attr_id, row0, rows):
         return len(self.attvalues(attr_id, row0, rows)[0])
+
+    def set_metadata(self, attr_id, value_rank, n_values, value_ptr, value_text):
+        self._hold_metadata(_check_metadata(attr_id, value_rank, n_values, value_ptr, value_text, self.d))
+
+    def metamasks(self, row0=0, rows=None):
+        return edge_metadata_arrays(*self._master[:2], self._metadata[1], self._metadata[2], self.d, row0, rows)
+
+    def metavalues(self, row0=0, rows=None):
+        return metavalues_host(*self._master[:2], *self._metadata, self.d, row0, rows)
+
+    def metavalues_size(self, row0, rows):
+        return len(self.metavalues(row0, rows)[0])
 
     def close(self):
         pass
@@ -363,7 +594,7 @@ def _lengths(total, count, lo, hi, low, high):
 
 
 def write_gexf(path, partitions, family_table, edge_table, annotations, all_node_attributes=True, all_edge_attributes=True, compressed=False,
-               budget=TEXT_BUDGET, positions=None, subpartition=None):
+               budget=TEXT_BUDGET, positions=None, subpartition=None, metadata=None):
     """<path>.gexf (compressed: <path>.gexf.gz through gzip) as PPanGGOLiN.export_to_GEXF and networkx's write_gexf write
     it for a partitioned nx.Graph (ppanggolin.py:1294-1362), streamed: no networkx, no tree.  partitions: what
     Master.partition returned, or uint8 [n]; family_table, edge_table: Master.family_table / Master.edge_table (or their
@@ -374,7 +605,15 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
     node gets the <viz:position> that compute_layout's dict makes networkx write (ppanggolin.py:1285-1292), z = 2 for a
     persistent family, 1 for a shell one, 0 otherwise.  subpartition: (name, {family: value}) -- the node attribute that
     partition_shell sets on every node (ppanggolin.py:1243-1247; Master.partition_shell's .subpart_name and
-    .node_attribute): one more string attribute, where the node's data holds it, behind partition_exact."""
+    .node_attribute): one more string attribute, where the node's data holds it, behind partition_exact.
+    metadata: export_to_GEXF's metadata= (:1339-1354; read_metadata makes it from the CLI's file): {organism name:
+    ordered {attribute: str}} with an entry per organism of the master.  Every edge gets, per attribute, one string
+    attribute behind length_max whose value is "|".join(sorted(set of the values of the edge's organisms)) -- in the full
+    and in the light export, which then formats these lines (and still no organism lines) on the device.  The ranking,
+    the escaping and the values' blob are made on the host (rank_metadata), the sets and the lines on the device, a
+    slice per edge.  ValueError: a missing organism; a value that is not a str; organisms whose attribute names or their
+    order differ (the CLI's zip over one header row cannot produce that); an attribute named like an organism, like
+    weight or like a length_* title.  An empty metadata (or one without attributes) is none, as in the reference."""
     ft, et = family_table, edge_table
     names, orgs = ft.names, ft.organism_names
     if names is None or orgs is None:
@@ -426,7 +665,13 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
         for title, kind in tail:
             node_id(title, kind)
         node_keys.append(present)
-    attr_id, edge_titles = et.attribute_ids(len(node_ids), organisms=all_edge_attributes)
+    meta = rank_metadata(metadata, orgs, ("weight",) + LENGTH_TITLES) if metadata else None
+    if meta is not None and not (meta["titles"] and et.n_edges):
+        meta = None
+    attr_id, edge_titles = et.attribute_ids(len(node_ids), organisms=all_edge_attributes, n_attr=len(meta["titles"]) if meta else 0)
+    if meta is not None:
+        et.set_metadata([k for k, what in edge_titles if isinstance(what, tuple)], meta["value_rank"], meta["n_values"], meta["value_ptr"],
+                        meta["value_text"])
     out = gzip.open(path + ".gexf.gz", "wb") if compressed else open(path + ".gexf", "wb")
     with out:
         w = out.write
@@ -434,7 +679,10 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
         if edge_titles:
             w(b'    <attributes mode="static" class="edge">\n')
             for k, what in edge_titles:
-                title, kind = (what, "double" if what in ("length_avg", "length_med") else "long") if isinstance(what, str) else (orgs[what], "long")
+                if isinstance(what, tuple):
+                    title, kind = meta["titles"][what[1]], "string"
+                else:
+                    title, kind = (what, "double" if what in ("length_avg", "length_med") else "long") if isinstance(what, str) else (orgs[what], "long")
                 w(('      <attribute id="%d" title="%s" type="%s" />\n' % (k, escape(title), kind)).encode())
             w(b"    </attributes>\n")
         if node_titles:
@@ -476,22 +724,26 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
         length_ids = [k for k, what in edge_titles if isinstance(what, str)]
         escaped = [escape(name) for name in names]
 
-        def edge(e, organisms):
+        def edge(e, organisms, values_of_metadata=b""):
             weight = str(float(int(et.weight[e])))
             w(('      <edge source="%s" target="%s" id="%d" weight="%s">\n        <viz:thickness value="%s" />\n        <attvalues>\n'
                % (escaped[et.src[e]], escaped[et.dst[e]], e, weight, weight)).encode())
             if organisms is not None:
                 w(organisms)
             values = _lengths(et.len_sum[e], et.len_distinct[e], et.len_mid_lo[e], et.len_mid_hi[e], et.len_min[e], et.len_max[e])
-            w(("".join(att % (k, value) for k, value in zip(length_ids, values)) + "        </attvalues>\n      </edge>\n").encode())
+            w(b"".join(("".join(att % (k, value) for k, value in zip(length_ids, values)).encode(), values_of_metadata,
+                        b"        </attvalues>\n      </edge>\n")))
 
-        if all_edge_attributes:
-            for row0, rows in et._batches(budget):
-                text, ends = et.attvalues(attr_id, row0, rows)
-                view, start = memoryview(text), 0
+        def slices(text, ends):
+            view = memoryview(text)
+            return [view[int(ends[r - 1]) if r else 0:int(ends[r])] for r in range(len(ends))]
+
+        if all_edge_attributes or meta is not None:
+            for row0, rows in et._batches(budget, organisms=all_edge_attributes, metadata=meta is not None):
+                organisms = slices(*et.attvalues(attr_id, row0, rows)) if all_edge_attributes else [None] * rows
+                behind = slices(*et.metavalues(row0, rows)) if meta is not None else [b""] * rows
                 for r in range(rows):
-                    edge(row0 + r, view[start:int(ends[r])])
-                    start = int(ends[r])
+                    edge(row0 + r, organisms[r], behind[r])
         else:
             for e in range(ne):
                 edge(e, None)

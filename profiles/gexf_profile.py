@@ -3,7 +3,9 @@
 reference (--reference: the real __neighborhood_computation builds the graph, the real export_to_GEXF writes it; needs
 the reference tree and networkx, as the generators under tests/golden/ do) or from the resident master (--device:
 Master.from_annotations, family_table, edge_table, write_gexf; needs the GPU).  Both label a family persistent above
-0.9 d organisms, cloud below 0.1 d, shell between.  Prints one JSON line.
+0.9 d organisms, cloud below 0.1 d, shell between.  --metadata: three metadata attributes of 2, 20 and 200 distinct
+values (export_to_GEXF's metadata=, write_gexf's metadata=) -- the exports are timed with and, on the device, also
+without them, and the device's metadata lines of all the edges on their own.  Prints one JSON line.
 
     python profiles/gexf_profile.py --n 2000 --d 200 --seed 11 --device --runs 3
 """
@@ -24,6 +26,11 @@ def label(nb_org, d):
     return "P" if nb_org > 0.9 * d else "C" if nb_org < 0.1 * d else "S"
 
 
+def metadata_of(orgs):
+    """{organism: {attribute: value}}: 2, 20 and 200 distinct values (as far as there are organisms)"""
+    return {org: {"clade": "clade%d" % (i % 2), "country": "country %d" % (i % 20), "isolate": "isolate-%03d" % (i % 200)} for i, org in enumerate(orgs)}
+
+
 def timed(fn, runs):
     out = []
     for _ in range(runs):
@@ -33,7 +40,7 @@ def timed(fn, runs):
     return out
 
 
-def reference(ann, orgs, circular, runs, tmp):
+def reference(ann, orgs, circular, runs, tmp, metadata=False):
     sys.path.insert(0, os.path.join(HERE, "..", "tests", "golden"))
     from make_orders import RESERVED, reference_class
     PPanGGOLiN = reference_class()
@@ -59,15 +66,16 @@ def reference(ann, orgs, circular, runs, tmp):
         data["partition_exact"] = "core_exact" if nb == len(orgs) else "accessory"
         data["viz"] = dict(color=module.COLORS_RGB[data["partition"]], size=nb)
     obj.is_partitionned = True
-    full = timed(lambda: obj.export_to_GEXF(tmp + "/ref"), runs)
-    light = timed(lambda: obj.export_to_GEXF(tmp + "/ref_light", all_node_attributes=False, all_edge_attributes=False), runs)
-    return dict(who="reference", families=g.number_of_nodes(), edges=g.number_of_edges(), graph_build_s=build, export_full_s=full, export_light_s=light,
+    meta = metadata_of(orgs) if metadata else None
+    full = timed(lambda: obj.export_to_GEXF(tmp + "/ref", False, meta), runs)
+    light = timed(lambda: obj.export_to_GEXF(tmp + "/ref_light", False, meta, all_node_attributes=False, all_edge_attributes=False), runs)
+    return dict(who="reference", metadata=bool(metadata), families=g.number_of_nodes(), edges=g.number_of_edges(), graph_build_s=build, export_full_s=full, export_light_s=light,
                 full_bytes=os.path.getsize(tmp + "/ref.gexf"), light_bytes=os.path.getsize(tmp + "/ref_light.gexf"))
 
 
-def device(ann, orgs, circular, runs, tmp):
+def device(ann, orgs, circular, runs, tmp, metadata=False):
     from pangenomenem_amd.chunks import Master
-    from pangenomenem_amd.gexf import gexf_orders, write_gexf
+    from pangenomenem_amd.gexf import LENGTH_TITLES, gexf_orders, rank_metadata, write_gexf
     m = Master.from_annotations(ann, orgs, list(circular))
     ft = m.family_table(ann)
     labels = {name: label(int(nb), len(orgs)) for name, nb in zip(m.names, ft.nb_org)}
@@ -95,6 +103,20 @@ def device(ann, orgs, circular, runs, tmp):
     out = dict(who="device", families=m.n, edges=et.n_edges, edge_table_from_annotations_s=table, edge_table_from_flat_orders_s=flat,
                attvalue_text_bytes=text_bytes, attvalue_text_s=lines, write_full_s=full, write_light_s=light,
                full_bytes=os.path.getsize(tmp + "/dev.gexf"), light_bytes=os.path.getsize(tmp + "/dev_light.gexf"))
+    if metadata:
+        meta = metadata_of(orgs)
+        write_gexf(tmp + "/dev_meta", labels, ft, et, ann, metadata=meta)             # (warm-up: the three kernels' code)
+        out["write_full_metadata_s"] = timed(lambda: write_gexf(tmp + "/dev_meta", labels, ft, et, ann, metadata=meta), runs)
+        out["write_light_metadata_s"] = timed(lambda: write_gexf(tmp + "/dev_meta_light", labels, ft, et, ann, all_node_attributes=False,
+                                                                 all_edge_attributes=False, metadata=meta), runs)
+        out["write_full_again_s"] = timed(lambda: write_gexf(tmp + "/dev", labels, ft, et, ann), runs)          # (alternated with the above)
+        out["write_light_again_s"] = timed(lambda: write_gexf(tmp + "/dev_light", labels, ft, et, ann, all_node_attributes=False,
+                                                              all_edge_attributes=False), runs)
+        out["rank_metadata_s"] = timed(lambda: rank_metadata(meta, orgs, ("weight",) + LENGTH_TITLES), runs)
+        out["metavalue_text_bytes"] = len(et.metavalues()[0])
+        out["metavalue_text_s"] = timed(lambda: et.metavalues(), runs)                # (one call, all edges; the text comes down)
+        out["metamasks_s"] = timed(lambda: et.metamasks(), runs)
+        out.update(full_metadata_bytes=os.path.getsize(tmp + "/dev_meta.gexf"), light_metadata_bytes=os.path.getsize(tmp + "/dev_meta_light.gexf"))
     et.close()
     ft.close()
     m.close()
@@ -109,13 +131,14 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--reference", action="store_true")
     ap.add_argument("--device", action="store_true")
+    ap.add_argument("--metadata", action="store_true")
     args = ap.parse_args()
     ann, orgs, circular = annotated_pangenome(args.n, args.d, args.seed)
     genes = sum(len(annot) for contigs in ann.values() for annot in contigs.values())
     tmp = tempfile.mkdtemp()
     for who, fn in (("reference", reference), ("device", device)):
         if getattr(args, who):
-            res = fn(ann, orgs, circular, args.runs, tmp)
+            res = fn(ann, orgs, circular, args.runs, tmp, args.metadata)
             res.update(n=args.n, d=args.d, seed=args.seed, genes=genes, date=time.strftime("%Y-%m-%d"))
             print(json.dumps(res), flush=True)
     shutil.rmtree(tmp)

@@ -817,7 +817,8 @@ int nemgpu_set_graph_policy(nemgpu_engine* e, int capture_on_first);
 int nemgpu_graph_counters(const nemgpu_engine* e, int out[4]);
 /* how the last nemgpu_run_random went (RandNemAlgo, nem_alg.c:1574-1742, starts in lock step): out = {lock-step rounds,
    starts that stood in them, starts run alone on the engine's own path, starts thrown away and redone because a start
-   before them drew tie-breaks behind its initial sweeps (TIE_LIBC: one random() stream for all starts)} */
+   before them drew tie-breaks behind its initial sweeps (TIE_LIBC: one random() stream for all starts)}.  A logged
+   call whose lock-step round lost that bet hands nothing over and runs every start again, alone: {0, 0, n, n}. */
 int nemgpu_random_start_counters(const nemgpu_engine* e, int out[4]);
 
 /* Re-target the engine to another HIP stream (e.g. the capturing stream of a torch.cuda.graph). */

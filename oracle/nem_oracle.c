@@ -374,10 +374,28 @@ int orc_converged(int n, int k, const float* c_nk, const float* cold_nk, float t
 }
 
 /* ----------------------------------------------------------------- loop */
+/* the trace (nem_oracle.h): off unless orc_set_trace was given a function */
+static orc_trace_fn g_trace = NULL;
+static void* g_trace_user = NULL;
+static int g_trace_start = 0;                                      /* the start orc_run_random is at */
+void orc_set_trace(orc_trace_fn fn, void* user) { g_trace = fn; g_trace_user = user; }
+
+static void trace_emit(int kind, int iter, int emptyk, const float* cb, const float* ca, const orc_state* s, const float* nbobs_k)
+{
+    orc_trace_event ev;
+    memset(&ev, 0, sizeof ev);
+    ev.kind = kind; ev.start = g_trace_start; ev.iter = iter; ev.emptyk = emptyk;
+    ev.crit_before = cb; ev.crit_after = ca;
+    if (kind == ORC_EV_LINE) { ev.prop = s->prop_k; ev.center = s->center_kd; ev.disp = s->disp_kd; }
+    ev.nbobs_k = nbobs_k;
+    g_trace(&ev, g_trace_user);
+}
+
 static int run_from_params(const orc_problem* p, orc_state* s, int reseed);
 
 int orc_run(const orc_problem* p, orc_state* s)
 {
+    g_trace_start = 0;
     return run_from_params(p, s, 1);
 }
 
@@ -423,6 +441,8 @@ int orc_run_random(const orc_problem* p, orc_state* s, int n_starts, unsigned se
             }
             for (j = 0; j < d; j++) s->center_kd[h * d + j] = (float)p->x[(size_t)ipt * d + j];       /* :1457 */
         }
+        g_trace_start = irandom;
+        if (g_trace) trace_emit(ORC_EV_START, 0, 0, NULL, NULL, s, NULL);   /* "Random initialization %d :", :1632-1636 */
         err = run_from_params(p, s, 0);
         if (err == ORC_STS_OK) {
             nbsucc++;
@@ -443,6 +463,7 @@ int orc_run_random(const orc_problem* p, orc_state* s, int n_starts, unsigned se
         s->iters = best_iters; s->converged = best_conv;
     }
     if (best_start) *best_start = best;
+    g_trace_start = 0;
     free(dispsam); free(bestc);
     return err;
 }
@@ -455,6 +476,7 @@ static int run_from_params(const orc_problem* p, orc_state* s, int reseed)
     unsigned sweep = 0;
     size_t nk = (size_t)n * k;
     float* cold = (float*)malloc(sizeof(float) * nk);
+    float tcb[6], tca[6];                                          /* the trace's criteria (never s->crit) */
     double t0;
 
     if (!s->pkfki_nk) { s->pkfki_nk = (double*)malloc(sizeof(double) * nk); own_pk = 1; }
@@ -469,9 +491,15 @@ static int run_from_params(const orc_problem* p, orc_state* s, int reseed)
     orc_density(n, d, k, p->x, s->prop_k, s->center_kd, s->disp_kd, s->pkfki_nk, s->logpkfki_nk);
     s->n_zero_density += orc_sweep(n, k, p->nei_ptr, p->nei_idx, p->nei_w, 0.0f, s->pkfki_nk, ncem,
                                    p->tie_rule, p->tie_seed, sweep++, s->c_nk);
+    if (g_trace)                                                   /* WriteLogCrit before the beta sweep, :2361 */
+        orc_crit(n, k, p->nei_ptr, p->nei_idx, p->nei_w, p->beta, s->c_nk, s->pkfki_nk, s->logpkfki_nk, tcb);
     s->n_zero_density += orc_sweep(n, k, p->nei_ptr, p->nei_idx, p->nei_w, p->beta, s->pkfki_nk, ncem,
                                    p->tie_rule, p->tie_seed, sweep++, s->c_nk);
     draw_log("init", 0);
+    if (g_trace) {                                                 /* ... and behind it, :2398; WriteLogClasses */
+        orc_crit(n, k, p->nei_ptr, p->nei_idx, p->nei_w, p->beta, s->c_nk, s->pkfki_nk, s->logpkfki_nk, tca);
+        trace_emit(ORC_EV_LINE, 0, 0, tcb, tca, s, NULL);
+    }
 
     /* NemAlgo (nem_alg.c:1789-1840) */
     {
@@ -489,9 +517,15 @@ static int run_from_params(const orc_problem* p, orc_state* s, int reseed)
                             s->disp_kd, s->nbobs_k, s->nbobs_kd, s->iner_kd, &s->emptyk);
         if (err == ORC_STS_OK) {                                   /* :1815-1829 */
             orc_density(n, d, k, p->x, s->prop_k, s->center_kd, s->disp_kd, s->pkfki_nk, s->logpkfki_nk);
+            if (g_trace)                                           /* :2361: cold on the new densities */
+                orc_crit(n, k, p->nei_ptr, p->nei_idx, p->nei_w, p->beta, cold, s->pkfki_nk, s->logpkfki_nk, tcb);
             s->n_zero_density += orc_sweep(n, k, p->nei_ptr, p->nei_idx, p->nei_w, p->beta, s->pkfki_nk,
                                            ncem, p->tie_rule, p->tie_seed, sweep++, s->c_nk);
             draw_log("iter", iter);
+            if (g_trace) {                                         /* :2398 */
+                orc_crit(n, k, p->nei_ptr, p->nei_idx, p->nei_w, p->beta, s->c_nk, s->pkfki_nk, s->logpkfki_nk, tca);
+                trace_emit(ORC_EV_LINE, iter, 0, tcb, tca, s, s->nbobs_k);
+            }
             if (p->cvtest == ORC_CV_CLAS) converged = orc_converged(n, k, s->c_nk, cold, p->cvthres);
             else if (p->cvtest == ORC_CV_CRIT || p->cvtest == ORC_CV_CRIT_LOGGED) {     /* nem_alg.c:2090-2105 */
                 float curcrit, critdif;
@@ -501,7 +535,8 @@ static int run_from_params(const orc_problem* p, orc_state* s, int reseed)
                 else critdif = FLT_MAX;                            /* MAXFLOAT */
                 converged = (critdif < p->cvthres);
             }
-        }
+        } else if (g_trace)                                        /* "Class %d empty at iteration %d", :1835-1837 */
+            trace_emit(ORC_EV_EMPTY, iter, s->emptyk, NULL, NULL, s, s->nbobs_k);
     }
     iter = iter - 1;                                               /* :1842 */
     g_loop_seconds = now_s() - t0;

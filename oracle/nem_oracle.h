@@ -116,6 +116,28 @@ int orc_run(const orc_problem* p, orc_state* s);
    criterion M, final EstimPara on the best partition.  best_start: 0-based index or -1. */
 int orc_run_random(const orc_problem* p, orc_state* s, int n_starts, unsigned seed, int* best_start);
 
+/* The per-iteration trace of orc_run / orc_run_random: the events nemgpu_log_event (include/nem_mi355x.h) documents,
+   in the reference's order (WriteLogCrit at nem_alg.c:2361 and :2398, WriteLogClasses, RandNemAlgo :1632-1636).
+     ORC_EV_START  orc_run_random, before each start's line 0: `start`
+     ORC_EV_LINE   iter 0: crit_before = the criteria of the blind (beta = 0) sweep's partition, crit_after = of the beta
+                   sweep's partition, both on the initial densities; the initial parameters; nbobs_k NULL.
+                   iter t: crit_before = orc_crit of the partition the E-step sweep started from on the NEW densities,
+                   crit_after = orc_crit of the partition it left; the parameters and nbobs_k of this iteration's M-step.
+     ORC_EV_EMPTY  the iteration whose M-step emptied class `emptyk` (1..K); nbobs_k as that orc_mstep left it.
+   The pointers are valid during the call only.  fn = NULL (the default) turns the trace off: nothing extra is computed. */
+enum { ORC_EV_START = 0, ORC_EV_LINE = 1, ORC_EV_EMPTY = 2 };
+typedef struct {
+    int kind, start, iter, emptyk;
+    const float* crit_before;    /* 6: D G U M L Z */
+    const float* crit_after;
+    const float* prop;           /* k */
+    const float* center;         /* k*d */
+    const float* disp;           /* k*d */
+    const float* nbobs_k;        /* k or NULL */
+} orc_trace_event;
+typedef void (*orc_trace_fn)(const orc_trace_event* ev, void* user);
+void orc_set_trace(orc_trace_fn fn, void* user);
+
 /* seconds of wall time spent in the EM iteration loop of the last orc_run (bench only) */
 double orc_last_loop_seconds(void);
 

@@ -68,6 +68,24 @@ class _State(C.Structure):
                 ("emptyk", C.c_int), ("n_zero_density", C.c_int)]
 
 
+class _TraceEvent(C.Structure):
+    _fields_ = [("kind", C.c_int), ("start", C.c_int), ("iter", C.c_int), ("emptyk", C.c_int),
+                ("crit_before", C.POINTER(C.c_float)), ("crit_after", C.POINTER(C.c_float)),
+                ("prop", C.POINTER(C.c_float)), ("center", C.POINTER(C.c_float)), ("disp", C.POINTER(C.c_float)),
+                ("nbobs_k", C.POINTER(C.c_float))]
+
+
+_TRACE_FN = C.CFUNCTYPE(None, C.POINTER(_TraceEvent), C.c_void_p)
+EVENT_KINDS = ("start", "line", "empty")
+
+
+def _copy(ptr, shape):
+    """A pointer of an event (valid during the callback only) as an array of its own; None for NULL."""
+    if not ptr:
+        return None
+    return np.ctypeslib.as_array(ptr, shape=(int(np.prod(shape)),)).reshape(shape).copy()
+
+
 class Oracle:
     """The plain-C restatement (oracle/nem_oracle.c)."""
 
@@ -78,6 +96,45 @@ class Oracle:
         self.lib.orc_last_loop_seconds.restype = C.c_double
         self.lib.orc_mix32.restype = C.c_uint
         self.lib.orc_mix32.argtypes = [C.c_uint, C.c_uint, C.c_uint]
+        self.lib.orc_tie_draws.restype = C.c_long
+        self.lib.orc_set_trace.restype = None
+        self.lib.orc_set_trace.argtypes = [_TRACE_FN, C.c_void_p]
+
+    def _traced(self, k, d, call):
+        """call() with the trace on: (what call returned, the events as dicts with arrays of their own, the tie
+        draws made meanwhile).  The trace is off again afterwards, whatever happened."""
+        events = []
+        draws = self.lib.orc_tie_draws()
+
+        def on_event(evp, _user):
+            ev = evp.contents
+            # draws: the random() draws the sweeps have made when the event is emitted, counted from the call's begin
+            events.append(dict(kind=EVENT_KINDS[ev.kind], start=ev.start, iter=ev.iter, emptyk=ev.emptyk,
+                               draws=int(self.lib.orc_tie_draws() - draws),
+                               crit_before=_copy(ev.crit_before, (6,)), crit_after=_copy(ev.crit_after, (6,)),
+                               prop=_copy(ev.prop, (k,)), center=_copy(ev.center, (k, d)), disp=_copy(ev.disp, (k, d)),
+                               nbobs_k=_copy(ev.nbobs_k, (k,))))
+
+        fn = _TRACE_FN(on_event)
+        self.lib.orc_set_trace(fn, None)
+        try:
+            out = call()
+        finally:
+            self.lib.orc_set_trace(_TRACE_FN(), None)
+        return out, events, int(self.lib.orc_tie_draws() - draws)
+
+    def trace_run(self, x, nei, k, prop, center, disp, **cfg):
+        """run() with the per-iteration trace (orc_set_trace): (result, events).  result["tie_draws"]: the random()
+        draws the run's sweeps made (tie="libc")."""
+        out, events, draws = self._traced(k, x.shape[1], lambda: self.run(x, nei, k, prop, center, disp, **cfg))
+        out["tie_draws"] = draws
+        return out, events
+
+    def trace_run_random(self, x, nei, k, **cfg):
+        """run_random() with the per-iteration trace: (result, events), a "start" event before each start's line 0."""
+        out, events, draws = self._traced(k, x.shape[1], lambda: self.run_random(x, nei, k, **cfg))
+        out["tie_draws"] = draws
+        return out, events
 
     def mix32(self, seed, sweep, site):
         return int(self.lib.orc_mix32(seed, sweep, site))

@@ -3113,7 +3113,7 @@ int nemgpu_run_logged(nemgpu_engine* e, nemgpu_result* res, nemgpu_log_fn fn, vo
     auto lap = [&](const char* what) { if (prof) { const auto now = std::chrono::steady_clock::now(); fprintf(stderr, "[logged run] %s: %.0f us\n", what, std::chrono::duration<double, std::micro>(now - lapt).count()); lapt = now; } };
     // ---- line 0: the start (reset, the two initial sweeps), both criteria, the parameters
     if ((r = iterate_logged_impl(e, 1, false, &r1, cb, ca, prop.data(), center.data(), disp.data(), nb.data()))) return r;
-    emit_line(0, cb, ca, prop.data(), center.data(), disp.data(), nb.data());
+    emit_line(0, cb, ca, prop.data(), center.data(), disp.data(), nullptr);   // (no EstimPara yet: no sizes, as the header says)
     lap("line 0 (start, two criteria)");
     static const bool batched_on = !(getenv("NEM_MI355X_LOG_BATCHED") && getenv("NEM_MI355X_LOG_BATCHED")[0] == '0');
     const bool batched = batched_on && e->ncem() && !crit_test(e) && e->lo == 0 && e->hi == e->n_total && e->parent == nullptr;
@@ -4204,6 +4204,7 @@ static int run_random_impl(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu
     if (!e->have_matrix || e->host_bits_words == 0) { set_error("the matrix must be set first"); return NEMGPU_E_FUNCARG; }
     HIPCHK(hipSetDevice(e->device));
     { const int fr = flush_reset(e); if (fr) return fr; }
+    int voided = 0;                                                // starts of a logged lock-step round that was thrown away whole
     {
         // the starts are independent EM runs on ONE matrix: by default they run in lock step, every launch serving all
         // of them (NEM_MI355X_BATCH_STARTS=0: one after the other on this engine)
@@ -4218,6 +4219,7 @@ static int run_random_impl(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu
         if (fn && lock_ok && n_starts <= 64 && !(gl && gl[0] == '0')) {
             const int rr = run_random_lockstep(e, n_starts, seed, res, best_start, fn, user);
             if (rr != kStartsNotInLockStep) return rr;
+            voided = n_starts;
         }
     }
     int r;
@@ -4261,7 +4263,8 @@ static int run_random_impl(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu
     int nbsucc = 0, best = -1, last_status = NEMGPU_OK;
     float best_crit[6] = {0, 0, 0, 0, 0, 0};
     nemgpu_result best_res{};
-    e->rs_rounds = e->rs_lockstep = e->rs_redone = e->rs_two_waits = 0; e->rs_alone = n_starts;   // (one after the other)
+    e->rs_rounds = e->rs_lockstep = e->rs_two_waits = 0; e->rs_alone = n_starts;   // (one after the other)
+    e->rs_redone = voided;                                         // (... after a round that lost its bet: the counters must tell)
     for (int s = 0; s < n_starts; s++) {
         // MakeRandomPara
         for (int h = 0; h < k; h++) for (int j = 0; j < d; j++) disp[(size_t)h * d + j] = dispsam[j] / k;      // :1400

@@ -49,6 +49,17 @@ class Problem(C.Structure):
                 ("result", Result), ("rc", C.c_int)]
 
 
+class LogEvent(C.Structure):
+    """nemgpu_log_event (include/nem_mi355x.h): the pointers are host arrays that die with the callback."""
+    _fields_ = [("kind", C.c_int), ("start", C.c_int), ("iter", C.c_int), ("emptyk", C.c_int),
+                ("crit_before", C.POINTER(C.c_float)), ("crit_after", C.POINTER(C.c_float)),
+                ("prop", C.POINTER(C.c_float)), ("center", C.POINTER(C.c_float)), ("disp", C.POINTER(C.c_float)),
+                ("nbobs_k", C.POINTER(C.c_float))]
+
+
+LOG_FN = C.CFUNCTYPE(None, C.POINTER(LogEvent), C.c_void_p)
+LOG_KINDS = ("start", "line", "empty")                    # NEMGPU_LOG_START, _LINE, _EMPTY
+
 _lib = None
 
 
@@ -75,6 +86,9 @@ def load_library():
     lib.nemgpu_run.argtypes = [vp, C.POINTER(Result)]
     lib.nemgpu_run_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(Result)]
     lib.nemgpu_run_random.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(Result), ip]
+    lib.nemgpu_run_logged.argtypes = [vp, C.POINTER(Result), LOG_FN, vp]
+    lib.nemgpu_run_random_logged.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(Result), ip, LOG_FN, vp]
+    lib.nemgpu_iterate_logged.argtypes = [vp, C.c_int, C.POINTER(Result), fp, fp, vp, vp, vp, vp]
     lib.nemgpu_glibc_random.argtypes = [C.c_uint32, C.c_int, vp]
     lib.nemgpu_init_partition.argtypes = [vp]
     lib.nemgpu_iterate.argtypes = [vp, C.c_int, C.POINTER(Result)]
@@ -253,6 +267,81 @@ class NemEngine:
         out.update(self.results())
         out["best_start"] = best.value
         return out
+
+    def _log_collector(self):
+        """(callback, events): the callback copies every array of an event (its pointers are valid during the call
+        only) into a dict appended to `events`; an exception in it is kept in events.error and raised by the caller."""
+        k, d = self.k, self.d
+
+        class Events(list):
+            error = None
+
+        events = Events()
+
+        def copy(ptr, shape):
+            if not ptr:
+                return None
+            return np.ctypeslib.as_array(ptr, shape=(int(np.prod(shape)),)).reshape(shape).copy()
+
+        def on_event(evp, _user):
+            try:
+                ev = evp.contents
+                events.append(dict(kind=LOG_KINDS[ev.kind], start=ev.start, iter=ev.iter, emptyk=ev.emptyk,
+                                   crit_before=copy(ev.crit_before, (6,)), crit_after=copy(ev.crit_after, (6,)),
+                                   prop=copy(ev.prop, (k,)), center=copy(ev.center, (k, d)), disp=copy(ev.disp, (k, d)),
+                                   nbobs_k=copy(ev.nbobs_k, (k,))))
+            except Exception as exc:                      # (must not unwind through the C caller)
+                events.error = events.error or exc
+
+        return LOG_FN(on_event), events
+
+    def run_logged(self):
+        """nemgpu_run_logged: the INIT_PARAM_FILE run with the reference's per-iteration log as events.  Returns
+        (result, events); result["crit"][0] is NaN where the header says the caller has to ask for the criteria."""
+        r = Result()
+        fn, events = self._log_collector()
+        self._chk(self.lib.nemgpu_run_logged(self._h, C.byref(r), fn, None))
+        if events.error is not None:
+            raise events.error
+        out = self._result(r)
+        out.update(self.results())
+        return out, list(events)
+
+    def run_random_logged(self, n_starts=50, rng_seed=1):
+        """nemgpu_run_random_logged: run_random with every start's log events.  Returns (result, events)."""
+        r = Result()
+        best = C.c_int(-1)
+        fn, events = self._log_collector()
+        self._chk(self.lib.nemgpu_run_random_logged(self._h, int(n_starts), C.c_uint32(rng_seed), C.byref(r),
+                                                    C.byref(best), fn, None))
+        if events.error is not None:
+            raise events.error
+        out = self._result(r)
+        out.update(self.results())
+        out["best_start"] = best.value
+        return out, list(events)
+
+    def iterate_logged(self, with_init):
+        """nemgpu_iterate_logged: the start (with_init) or one EM iteration with what its log line needs.  Returns
+        (result, events) with the one event the step amounts to, as run_logged hands it over: a line (iter = the
+        iterations so far; no sizes at the start), or `empty` when the M-step emptied a class."""
+        r = Result()
+        cb, ca = (C.c_float * 6)(), (C.c_float * 6)()
+        prop = np.zeros(self.k, np.float32)
+        center = np.zeros((self.k, self.d), np.float32)
+        disp = np.zeros((self.k, self.d), np.float32)
+        nk = np.zeros(self.k, np.float32)
+        self._chk(self.lib.nemgpu_iterate_logged(self._h, int(bool(with_init)), C.byref(r), cb, ca, _vp(prop),
+                                                 _vp(center), _vp(disp), _vp(nk)))
+        out = self._result(r)
+        if r.status == STATUS_W_EMPTYCLASS:
+            ev = dict(kind="empty", start=0, iter=r.iters, emptyk=r.emptyk, crit_before=None, crit_after=None,
+                      prop=None, center=None, disp=None, nbobs_k=None)
+        else:
+            ev = dict(kind="line", start=0, iter=r.iters, emptyk=0, crit_before=np.array(list(cb), np.float32),
+                      crit_after=np.array(list(ca), np.float32), prop=prop, center=center, disp=disp,
+                      nbobs_k=None if with_init else nk)
+        return out, [ev]
 
     def init_partition(self):
         self._chk(self.lib.nemgpu_init_partition(self._h))

@@ -247,6 +247,9 @@ struct nemgpu_engine {
         return d <= kFusedMaxD && (cfg.disper == NEMGPU_DISP_KD || cfg.disper == NEMGPU_DISP_K_);
     }
     bool use_ff() const { return ff_mode < 0 ? d >= 256 : ff_mode != 0; }
+    // the fused density kernels walk the fast-forwarded chain lane by lane and cross binades in batches (chain_ff_batched);
+    // NEM_MI355X_FF_BATCH=0: word by word, as every other density kernel does
+    bool ff_batch = true;
     // a kernel's FLAG_FAULT seen on the host (cleared, device word included, by the next reset / restart);
     // fault_inject: NEM_MI355X_FAULT_INJECT=fuzzy_pc makes one producer of k_mstep_fuzzy_pc skip a hand-over (tests)
     bool fault_seen = false; int fault_inject = 0;
@@ -705,7 +708,7 @@ FinishArgs finish_args(nemgpu_engine* e, int mode, const int* stats)
     t.reset_ctrl = nullptr; t.reset_ctrl_words = 0; t.reset_sweep_next = nullptr;
     t.prev_center = nullptr; t.prev_disp = nullptr;
     t.zero_stats = nullptr; t.n_zero_stats = 0;
-    t.use_ff = e->use_ff() ? 1 : 0;
+    t.use_ff = !e->use_ff() ? FF_OFF : e->ff_batch ? FF_BATCHED : FF_WORD;
     t.perm = e->perm;
     t.ffq = e->ffq;
     return t;
@@ -2588,6 +2591,7 @@ int nemgpu_create(nemgpu_engine** out, int n_total, int d, int k, int site_lo, i
     e->rounds_iter = std::min(e->rounds_iter, e->round_batch);
     if (const char* g = getenv("NEM_MI355X_FAULT_INJECT")) e->fault_inject = !strcmp(g, "fuzzy_pc") ? 1 : 0;
     if (const char* g = getenv("NEM_MI355X_FF")) e->ff_mode = (g[0] == '0') ? 0 : (g[0] == '1') ? 1 : -1;   // 0 plain chain, 1 always
+    if (const char* g = getenv("NEM_MI355X_FF_BATCH")) e->ff_batch = (g[0] != '0');   // 0: the word-synchronous chain everywhere
     if (const char* g = getenv("NEM_MI355X_SORT")) e->use_sort = (g[0] != '0');       // 0: E1 lanes in family order
     if (hip_stream) { e->stream = (hipStream_t)hip_stream; e->own_stream = false; }
     else {
@@ -4370,7 +4374,7 @@ static int make_clone(nemgpu_engine* p, nemgpu_engine** out, char* slab, size_t 
     c->cfg = p->cfg; c->have_matrix = true; c->have_params = true; c->has_graph = p->has_graph;
     c->xw = p->xw; c->xws = p->xws; c->perm = p->perm; c->xt = p->xt; c->use_sort = p->use_sort;
     c->nei_ptr = p->nei_ptr; c->nei_idx = p->nei_idx; c->nei_w = p->nei_w; c->nnz = p->nnz;
-    c->use_graphs = p->use_graphs; c->ff_mode = p->ff_mode; c->round_batch = p->round_batch; c->rounds_iter = p->rounds_iter;
+    c->use_graphs = p->use_graphs; c->ff_mode = p->ff_mode; c->ff_batch = p->ff_batch; c->round_batch = p->round_batch; c->rounds_iter = p->rounds_iter;
     c->parent = p; c->carve_all = true;
     c->chunks.push_back({slab, slab_bytes, 0, false});
     c->shared_chunk = 0;
@@ -4485,7 +4489,7 @@ static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, ne
     int width = (e->libc() && !(fa && fa[0] == '0') && fn == nullptr) ? 1 : group;   // (a logged run bets from the first start on: a lost bet sends the whole call to the sequential form)
     int voided_in_a_row = 0, clean_run = 0; bool alone_for_good = false;
     if ((r = ensure_clones(e, group))) return r;
-    for (nemgpu_engine* c : e->clones) { c->cfg = e->cfg; c->stream = e->stream; c->round_batch = e->round_batch; c->ff_mode = e->ff_mode; }
+    for (nemgpu_engine* c : e->clones) { c->cfg = e->cfg; c->stream = e->stream; c->round_batch = e->round_batch; c->ff_mode = e->ff_mode; c->ff_batch = e->ff_batch; }
 
     e->rs_rounds = e->rs_lockstep = e->rs_alone = e->rs_redone = e->rs_two_waits = 0;
     // (random starts tie by the hundreds in their initial sweeps: the draw window is sized for that from the first start on,

@@ -33,7 +33,15 @@ __device__ unsigned long long g_phase[32];
 // (a stamp taken ahead of a test that may end the block, stored once the block is past it)
 #define NEM_PHASE_TAKE(t) const unsigned long long t = wall_clock64()
 #define NEM_PHASE_PUT(i, t) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_phase[i] = t; } while (0)
+// the fast-forwarded chain of block 0, per wave (4 each): the clock at the end of the last launch's chain, then -- summed
+// over the launches -- the trips of chain_ff_batched and the crossing passes of either chain (nemgpu_debug_ff_waves)
+__device__ unsigned long long g_ff_wave[12];
+#define NEM_FF_WAVE_ADD(slot, v) do { if (blockIdx.x == 0 && (int)__lane_id() == __ffsll((unsigned long long)__ballot(1)) - 1) \
+        atomicAdd(&g_ff_wave[4 * (slot) + (threadIdx.x >> 6)], (unsigned long long)(v)); } while (0)
+#define NEM_FF_WAVE_END() do { if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) g_ff_wave[threadIdx.x >> 6] = wall_clock64(); } while (0)
 #else
+#define NEM_FF_WAVE_ADD(slot, v) do { } while (0)
+#define NEM_FF_WAVE_END() do { } while (0)
 #define NEM_PHASE(i) do { } while (0)
 #define NEM_PHASE_TAKE(t) do { } while (0)
 #define NEM_PHASE_PUT(i, t) do { } while (0)
@@ -366,6 +374,7 @@ __device__ __forceinline__ void ff_word(uint32_t& bits, uint32_t& q0, uint32_t& 
         uint32_t mm = m;
         int rem = nb;
         for (;;) {
+            NEM_FF_WAVE_ADD(2, 1);
             // organisms of this word that still fit in the binade: binary search over j, the pattern after the j
             // matching ones (at = bits + j * q0) carried along, so that a probe costs a shift-add and ONE multiply
             uint32_t j = 0, at = bits;
@@ -455,6 +464,132 @@ __device__ __forceinline__ float chain_ff(const XwHead& h, int npad, int D,
         const int nb = (w < wlast) ? 32 : (D - (wlast << 5));
         if (nb < 32) m &= (1u << nb) - 1u;
         ff_word(bits, q0, q1, end, m, nb, sQ0, sQ1, l1h, l0);
+    }
+    return __uint_as_float(bits);
+}
+
+// chain_ff with the lanes decoupled from the wave's word (33 .. kFusedMaxD organisms).  In chain_ff a wave runs the
+// crossing branch of ff_word whenever ANY of its lanes leaves its binade in the current word -- at dispersions of a few
+// per cent almost every word, with a handful of lanes in it.  Here every lane walks its own row: a lane whose next word
+// (or the rest of a partly consumed one) fits its binade takes it, a lane that would cross waits, and the wave runs ONE
+// crossing pass -- ff_word's search, exact step and table reload -- for all waiting lanes once kFFBatchT of them wait or
+// nobody can advance.  Every lane performs the operations of chain_ff on the same values in the same order; only which
+// lanes share a pass changes, so the result is the same bits.
+// sRow: the block's MISMATCH words, [word][lane of the block], three rows more than there are words (the walk asks for the
+// second word after the lane's own without clamping, and a lane through its row stands one past it; what comes from
+// beyond the row's end is dropped).  A lane reads and writes its own
+// column only (no barrier), and lanes at different words still hit different banks.  The class masks are applied where
+// the row is stored, with wave-uniform reads, so that a trip reads one word.  am must be clear for organisms >= D (the
+// fused density's centre_of clears them): the last word needs no masking then.
+// A trip is one decision step -- candidate, two ballots, the pass if it is due -- and kFFBatchSteps - 1 plain steps in
+// which lanes that fit advance and the others idle: the wave-level bookkeeping is scalar work on the one wave's issue
+// path, and most trips decide nothing.  16 and 3 are the measured optimum at 20 000 x 500 (flat from 8 to 24 waiting
+// lanes; 2 and 4 steps cost 0.4 us more per EM iteration, 1 step loses the whole gain).  The first word is stepped
+// (kFFPlainSteps = 32 organisms).
+#ifndef NEM_FF_BATCH_T
+#define NEM_FF_BATCH_T 16
+#endif
+#ifndef NEM_FF_BATCH_STEPS
+#define NEM_FF_BATCH_STEPS 3
+#endif
+constexpr int kFFBatchT = NEM_FF_BATCH_T;              // waiting lanes that trigger a crossing pass
+constexpr int kFFBatchSteps = NEM_FF_BATCH_STEPS;      // lane steps per wave decision
+constexpr int kFFRowWords = kFusedMaxD / 32 + 3;
+static_assert(kFFPlainSteps == 32, "chain_ff_batched steps the whole first word");
+
+__device__ __forceinline__ float chain_ff_batched(const XwHead& h, int npad, int D, uint32_t* sRow, const uint2* am,
+                                                  const uint32_t* sQ0, const uint32_t* sDQ, double l1h, double l0)
+{
+    const int tid = threadIdx.x;
+    const int wlast = (D - 1) >> 5;                      // 1 .. 31
+    const int glast = wlast >> 2;
+    // ---- the row goes to LDS as it arrives: the head's groups, then the rest (at most four more), asked for together
+    uint32_t* row = sRow + tid;
+    auto put = [&](const int g, const uint4& v) {        // (am[w] beyond the last word: never used)
+        row[(4 * g + 0) * 256] = mismatch_word(v.x, am[4 * g + 0]); row[(4 * g + 1) * 256] = mismatch_word(v.y, am[4 * g + 1]);
+        row[(4 * g + 2) * 256] = mismatch_word(v.z, am[4 * g + 2]); row[(4 * g + 3) * 256] = mismatch_word(v.w, am[4 * g + 3]);
+    };
+    uint4 y0 = h.x0, y1 = h.x0, y2 = h.x0, y3 = h.x0;
+    {
+        const uint4* p = h.pn;                           // group 4 where there is one (xw_head)
+        if (glast >= 4) y0 = *p;
+        if (glast >= 5) y1 = p[npad];
+        if (glast >= 6) y2 = p[2 * (size_t)npad];
+        if (glast >= 7) y3 = p[3 * (size_t)npad];
+    }
+    // ---- word 0: stepped
+    uint32_t bits, q0, dq, end;
+    {
+        const uint32_t m = mismatch_word(h.x0.x, am[0]);
+        float dk0 = 0.0f;
+#pragma unroll
+        for (int b = 0; b < 32; b++) dk0 = bern_step(dk0, m, b, l1h, l0);
+        bits = __float_as_uint(dk0);
+        ff_load(sQ0, sDQ, bits, q0, dq, end);
+    }
+    put(0, h.x0);
+    if (glast >= 1) put(1, h.x1);
+    if (glast >= 2) put(2, h.x2);
+    if (glast >= 3) put(3, h.x3);
+    if (glast >= 4) put(4, y0);
+    if (glast >= 5) put(5, y1);
+    if (glast >= 6) put(6, y2);
+    if (glast >= 7) put(7, y3);
+    // ---- the walk.  w: the lane's word; mm / rem: the mismatch bits and the organisms of it not yet taken; mn, mn2: the
+    // two words after it, asked for two steps ahead of their use (an LDS read takes about as long as a step)
+    const uint32_t nlast = (uint32_t)(D - (wlast << 5)); // organisms of the last word, 1 .. 32
+    int w = 1;
+    uint32_t mm = row[256];
+    uint32_t rem = (wlast == 1) ? nlast : 32u;
+    uint32_t mn = row[2 * 256], mn2 = row[3 * 256];
+    auto advance = [&](const bool take) {
+        w += take ? 1 : 0;
+        mm = take ? mn : mm;
+        mn = take ? mn2 : mn;
+        rem = take ? ((w == wlast) ? nlast : 32u) : rem;
+        mn2 = row[(w + 2) * 256];                        // (w + 2 <= wlast + 3 < kFFRowWords: a lane through its row takes nothing)
+    };
+    for (;;) {
+        const bool active = w <= wlast;
+        const uint32_t cand = ff_cand(mm, dq, mad24(rem, q0, bits));
+        const bool fits = active && cand < end;
+        const uint64_t bact = __builtin_amdgcn_ballot_w64(active);
+        if (bact == 0) break;                            // every lane is through its row
+        const uint64_t ba = __builtin_amdgcn_ballot_w64(fits);
+        NEM_FF_WAVE_ADD(1, 1);
+        bits = fits ? cand : bits;
+        bool take = fits;
+        if (__popcll(bact & ~ba) >= kFFBatchT || ba == 0) {      // (wave-uniform)
+            NEM_FF_WAVE_ADD(2, 1);
+            if (active && !fits) {
+                // ff_word's crossing step: the organisms of the word that still fit (f(t) >= f(rem) >= end for t >= rem:
+                // never accepted), the boundary organism with the reference's arithmetic, the new binade's increments
+                uint32_t j = 0, at = bits;
+#pragma unroll
+                for (int sh = 4; sh >= 0; sh--) {
+                    const uint32_t t = j + (1u << sh);
+                    const uint32_t at_t = at + (q0 << sh);
+                    const bool ok = ff_probe(mm, t, dq, at_t) < end;
+                    j = ok ? t : j;
+                    at = ok ? at_t : at;
+                }
+                bits = ff_probe(mm, j, dq, at);
+                bits = ff_exact_step(bits, mm, j, l1h, l0);
+                ff_load(sQ0, sDQ, bits, q0, dq, end);
+                rem -= j + 1u;                           // (j < rem)
+                mm = (mm >> j) >> 1;
+                take = (rem == 0u);                      // else: the rest of the word is the next step's candidate
+            }
+        }
+        advance(take);
+#pragma unroll
+        for (int s = 1; s < kFFBatchSteps; s++) {
+            const uint32_t c2 = ff_cand(mm, dq, mad24(rem, q0, bits));
+            const bool f2 = (w <= wlast) && c2 < end;
+            NEM_FF_WAVE_ADD(1, 1);
+            bits = f2 ? c2 : bits;
+            advance(f2);
+        }
     }
     return __uint_as_float(bits);
 }
@@ -619,13 +754,15 @@ struct StartArgs {
 };
 
 // returns the family tile the block worked on, -1 when it had nothing to do
-template <bool START = false>
+// ROW: the instance may be launched with the LDS rows of chain_ff_batched as its dynamic shared memory (ff_row_bytes:
+// FF_BATCHED in a.use_ff says that it was); without ROW, FF_BATCHED is read as FF_WORD (the lock-step batches)
+template <bool START = false, bool ROW = true>
 __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, const StartArgs* st = nullptr)
 {
     __shared__ __align__(16) float sVal[FD_MAXD];        // inertia per organism, later epsilon per organism
     __shared__ double2 sT[FD_CH];
     __shared__ double sL[FD_CH];
-    __shared__ uint2 sAm[FD_MAXD / 32];                   // {am0, am1} per word
+    __shared__ uint2 sAm[FD_MAXD / 32];                   // {am0, am1} per word (clear for organisms >= D)
     __shared__ uint32_t sNz0[FD_CH / 32], sNz1[FD_CH / 32];
     __shared__ uint32_t sQ0[256], sQ1[256];
     __shared__ unsigned long long sTot2w[4];             // per wave: twice the class's inertia over the wave's organisms
@@ -824,7 +961,16 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
             __syncthreads();
             NEM_PHASE(21);
             if constexpr (START) xh = xw_head(a.xw, npad, i, D);
-            dk = chain_ff(xh, npad, D, sAm, sQ0, sQ1, l1h, l0);
+            bool walked = false;
+            if constexpr (ROW) {
+                extern __shared__ uint32_t sRow[];               // the block's mismatch words, [word][lane] (ff_row_bytes)
+                if (a.use_ff == FF_BATCHED) {                    // block-uniform
+                    dk = chain_ff_batched(xh, npad, D, sRow, sAm, sQ0, sQ1, l1h, l0);
+                    walked = true;
+                }
+            }
+            if (!walked) dk = chain_ff(xh, npad, D, sAm, sQ0, sQ1, l1h, l0);
+            NEM_FF_WAVE_END();
         } else {
             if constexpr (START) xh = xw_head(a.xw, npad, i, D);
             dk = chain_plain(a.xw, xh, npad, i, D, sAm, l1h, l0);
@@ -2216,8 +2362,12 @@ __global__ __launch_bounds__(1024) void k_finish_b(const void* arr, int stride, 
 __global__ __launch_bounds__(256) void k_density(DensityArgs a) { density_body(a); }
 __global__ __launch_bounds__(256) void k_density_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(DensityArgs) density_body(a); }
 __global__ __launch_bounds__(256) void k_density_fused(FusedDensityArgs a) { (void)density_fused_body(a); }
-__global__ __launch_bounds__(256) void k_density_fused_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FusedDensityArgs) (void)density_fused_body(a); }
+__global__ __launch_bounds__(256) void k_density_fused_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FusedDensityArgs) (void)density_fused_body<false, false>(a); }
 __global__ __launch_bounds__(256) void k_density_start(FusedDensityArgs a, StartArgs st) { (void)density_fused_body<true>(a, &st); }
+// the two without chain_ff_batched, for the grids that do not take it (fused_density_args): the walk's registers cost
+// these kernels two waves per SIMD, which a grid that fills the device several times over would pay for nothing
+__global__ __launch_bounds__(256) void k_density_fused_word(FusedDensityArgs a) { (void)density_fused_body<false, false>(a); }
+__global__ __launch_bounds__(256) void k_density_start_word(FusedDensityArgs a, StartArgs st) { (void)density_fused_body<true, false>(a, &st); }
 // (k_sweep / k_sweep_b: nem_sweep.hip)
 // One relaxation round (blocks [0, nsweep)) and the M-step counts of the partition it verifies (the other blocks: its
 // class masks were made by the round before) side by side in ONE launch -- the sharded iteration's second half, where
@@ -2401,6 +2551,22 @@ void launch_density(const FinishArgs& t, const uint32_t* xw, int n, int npad, do
     hipLaunchKernelGGL(k_density, grid, dim3(256), 0, s, a);
 }
 
+static int density_blocks(int npad, int K) { return ((npad / 256 + 7) / 8) * 8 * K; }
+
+// compute units of the current device (asked once per device)
+static int compute_units()
+{
+    static int cus[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    if (cus[dev] == 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 0;
+        cus[dev] = v;
+    }
+    return cus[dev];
+}
+
 static FusedDensityArgs fused_density_args(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki,
                                            float* logpkfki, int* zero_flags, int n_zero_flags)
 {
@@ -2414,7 +2580,19 @@ static FusedDensityArgs fused_density_args(const FinishArgs& t, const uint32_t* 
     a.pkfki = pkfki; a.logpkfki = logpkfki; a.zero_flags = zero_flags; a.n_zero_flags = n_zero_flags; a.stop = t.stop;
     a.zero_stats = t.zero_stats; a.n_zero_stats = t.zero_stats != nullptr ? t.n_zero_stats : 0;
     a.use_ff = t.use_ff; a.perm = t.perm;
+    // the lane-by-lane walk where it pays: more than one word, and a grid that is resident at once with the walk's LDS
+    // rows (three blocks per compute unit).  It shortens the slowest wave of a block, which is what a launch of a few
+    // blocks per compute unit waits for; a grid that fills the device several times over is bound by the sum of its
+    // waves' work and by how many of them are resident, and there the rows cost more than the passes save
+    // (200 000 x 1 000: 5 % slower with the walk, 400 000 x 300: 13 %).
+    if (a.use_ff == FF_BATCHED && !(t.D > 32 && density_blocks(npad, t.K) <= 3 * compute_units())) a.use_ff = FF_WORD;
     return a;
+}
+
+// dynamic shared memory of a fused density launch: the rows of chain_ff_batched
+static size_t ff_row_bytes(const FusedDensityArgs& a)
+{
+    return a.use_ff == FF_BATCHED ? sizeof(uint32_t) * kFFRowWords * 256 : 0;
 }
 
 void launch_density_fused(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
@@ -2423,7 +2601,8 @@ void launch_density_fused(const FinishArgs& t, const uint32_t* xw, int n, int np
     const FusedDensityArgs a = fused_density_args(t, xw, n, npad, pkfki, logpkfki, zero_flags, n_zero_flags);
     const dim3 grid(((npad / 256 + 7) / 8) * 8 * t.K);
     if (record_op(OP_DENSITY_FUSED, 0, grid, 256, a)) return;
-    hipLaunchKernelGGL(k_density_fused, grid, dim3(256), 0, s, a);
+    if (a.use_ff == FF_BATCHED) hipLaunchKernelGGL(k_density_fused, grid, dim3(256), ff_row_bytes(a), s, a);
+    else hipLaunchKernelGGL(k_density_fused_word, grid, dim3(256), 0, s, a);
 }
 
 void launch_density_start(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
@@ -2434,7 +2613,8 @@ void launch_density_start(const FinishArgs& t, const uint32_t* xw, int n, int np
     st.prop0 = t.reset_prop; st.center0 = t.reset_center; st.disp0 = t.reset_disp;
     st.ctrl = t.reset_ctrl; st.ctrl_words = t.reset_ctrl_words; st.sweep_next = t.reset_sweep_next;
     const dim3 grid(((npad / 256 + 7) / 8) * 8 * t.K);
-    hipLaunchKernelGGL(k_density_start, grid, dim3(256), 0, s, a, st);
+    if (a.use_ff == FF_BATCHED) hipLaunchKernelGGL(k_density_start, grid, dim3(256), ff_row_bytes(a), s, a, st);
+    else hipLaunchKernelGGL(k_density_start_word, grid, dim3(256), 0, s, a, st);
 }
 
 bool density_verify_supported(int n_local, int K, int tie_rule)
@@ -2449,7 +2629,7 @@ void launch_density_verify(const FinishArgs& t, const uint32_t* xw, int n, int n
     const int nd = ((npad / 256 + 7) / 8) * 8 * t.K;
     const int ns = (sw.n_local + 255) / 256;
     const dim3 grid(nd + ns);
-#define NEM_DV(KT_) case KT_: hipLaunchKernelGGL((k_density_verify<KT_>), grid, dim3(256), 0, s, a, sw, nd); break;
+#define NEM_DV(KT_) case KT_: hipLaunchKernelGGL((k_density_verify<KT_>), grid, dim3(256), ff_row_bytes(a), s, a, sw, nd); break;
     switch (sw.K) { NEM_DV(1) NEM_DV(2) NEM_DV(3) NEM_DV(4) NEM_DV(5) NEM_DV(6) NEM_DV(7) NEM_DV(8) NEM_DV(9) NEM_DV(10) default: break; }
 #undef NEM_DV
 }
@@ -2599,6 +2779,10 @@ void launch_calib_read(const uint32_t* buf, size_t words, uint32_t* sink, hipStr
 extern "C" int nemgpu_debug_phases(unsigned long long* out32)
 {
     return (int)hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_phase), sizeof(unsigned long long) * 32);
+}
+extern "C" int nemgpu_debug_ff_waves(unsigned long long* out12)
+{
+    return (int)hipMemcpyFromSymbol(out12, HIP_SYMBOL(g_ff_wave), sizeof(unsigned long long) * 12);
 }
 #endif
 

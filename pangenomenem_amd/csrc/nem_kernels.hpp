@@ -169,7 +169,7 @@ struct FinishArgs {
     const float* reset_prop; const float* reset_center; const float* reset_disp;
     int* reset_ctrl; int reset_ctrl_words; int* reset_sweep_next;
     const int* perm;               // density kernels: lane i of the (sorted) matrix copy is family perm[i]
-    int use_ff;                    // density kernels: fast-forward the uniform chain inside float binades (nem_ff.hpp)
+    int use_ff;                    // density kernels: fast-forward the uniform chain inside float binades (nem_ff.hpp), an FFMode
     uint2* ffq;                    // [K][256] (q0, q1 - q0): the fast-forward increments per class, built next to the tables
     // fused density (mode 1): where an empty class keeps its centre and dispersions from (nullptr: center / disp)
     const float* prev_center; const float* prev_disp;
@@ -181,6 +181,10 @@ void launch_density(const FinishArgs& t, const uint32_t* xw, int n, int npad, do
                     int* zero_flags, int n_zero_flags, hipStream_t s);
 // NCEM, sk_/skd, D <= kFusedMaxD: parameter update from t.stats folded into the density kernel (no k_finish)
 constexpr int kFusedMaxD = 1024;   // beyond this the per-block parameter derivation costs more than a k_finish launch
+// FinishArgs::use_ff.  FF_BATCHED: the fused density kernels (33 .. kFusedMaxD organisms, a grid the device holds at
+// once) let every lane walk its own row and cross binades in batches (chain_ff_batched); every other kernel and shape
+// reads it as FF_WORD.
+enum FFMode { FF_OFF = 0, FF_WORD = 1, FF_BATCHED = 2 };
 void launch_density_fused(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
                           int* zero_flags, int n_zero_flags, hipStream_t s);
 // the start of a run in ONE launch (k_density_start): the restart head (t.reset_*: initial parameters into t.prop / center /

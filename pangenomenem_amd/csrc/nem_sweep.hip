@@ -93,6 +93,11 @@ extern "C" int nemgpu_debug_sweep_phases(unsigned long long* out8)
 {
     return (int)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_sweep_phase), sizeof(unsigned long long) * 8);
 }
+// (the counting instance's stamps: the same eight phases)
+extern "C" int nemgpu_debug_sweep_phases_count(unsigned long long* out8)
+{
+    return (int)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_sweep_phase), sizeof(unsigned long long) * 8, sizeof(unsigned long long) * 8);
+}
 #endif
 
 void sweep_dispatch_batched(int variant, dim3 grid, unsigned bdim, hipStream_t s, const void* arr, int stride, const int* gx)

@@ -13,13 +13,15 @@
 namespace nemk {
 
 // development probe (-DNEM_PHASE_PROF, see nem_kernels.hip): the first block's first thread stamps the 100 MHz wall clock
-// at the round's phase boundaries -- one copy per translation unit; nem_sweep.hip's is the one read back
+// at the round's phase boundaries -- one copy per translation unit; nem_sweep.hip's is the one read back.  Slots 0-7: the
+// head (0-4) and the tail (5: behind the tail barrier, 6: flags published, 7: the last count add issued); slots 8-15: the
+// same eight of the counting instance, which a cycle's last plain round would otherwise overwrite
 #ifdef NEM_PHASE_PROF
-static __device__ unsigned long long g_sweep_phase[8];
-#define NEM_SWEEP_PHASE(i) do { if (bx == 0 && threadIdx.x == 0) g_sweep_phase[i] = wall_clock64(); } while (0)
+static __device__ unsigned long long g_sweep_phase[16];
+#define NEM_SWEEP_PHASE(i) do { if (bx == 0 && threadIdx.x == 0) g_sweep_phase[(COUNT ? 8 : 0) + (i)] = wall_clock64(); } while (0)
 // (the entry stamp is taken ahead of the stop test and stored by a block that is past it)
 #define NEM_SWEEP_PHASE_TAKE(t) const unsigned long long t = wall_clock64()
-#define NEM_SWEEP_PHASE_PUT(i, t) do { if (bx == 0 && threadIdx.x == 0) g_sweep_phase[i] = t; } while (0)
+#define NEM_SWEEP_PHASE_PUT(i, t) do { if (bx == 0 && threadIdx.x == 0) g_sweep_phase[(COUNT ? 8 : 0) + (i)] = t; } while (0)
 #else
 #define NEM_SWEEP_PHASE(i) do { } while (0)
 #define NEM_SWEEP_PHASE_TAKE(t) do { } while (0)
@@ -409,7 +411,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     // "a label changed" / "a label moved": per block, then ONE device-scope atomic -- behind a device-scope look at the
     // flag -- instead of one per wave behind a plain load (which another XCD's L2 answers with a stale 0 long after the
     // flag was set: at 200 000 x 5 000, where every wave has something to report, a round's 3 136 same-address atomics
-    // were 10-40 us of its 24-52)
+    // were 10-40 us of its 24-52).  A launch of at most kNoLookBlocks blocks skips the look, see the round's tail.
     __shared__ int s_chg, s_mov;
     // NCEM: the MRF factor exp(beta * context) takes few distinct arguments -- the context of a class is a sum of edge
     // weights, small integers in PPanGGOLiN's graphs (numbers of organisms sharing an adjacency): the block fills a table
@@ -665,6 +667,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
         atomicMax(&s_first, a.n_total - (gi + (int)__ffsll((long long)zmask) - 1));   // lanes are consecutive sites
     }
     __syncthreads();
+    NEM_SWEEP_PHASE(5);
     // One same-address atomic per block is what a round costs when every site reports (all densities underflow at
     // D = 5000: 196 blocks x ~45 ns, 12 of a round's 26 us at 200 000 x 5 000).  Once the loop control has seen
     // such a sweep (ctrl[C_FOLD], set by ctrl_logic, read with the stop word) the tally rides on the last-block
@@ -674,11 +677,20 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
         if (!fold) atomicAdd(&a.flags[FLAG_NZERO], s_nzero);
         if (a.flags[FLAG_FIRSTZERO] < s_first) atomicMax(&a.flags[FLAG_FIRSTZERO], s_first);   // first site = n_total - max
     }
+    // "changed" and "moved": the look that thins same-address atomics out on grids of thousands of waves (see s_chg) is a
+    // device-scope round trip per flag on thread 0, and in the counting round the whole block's adds wait for both at the
+    // barrier below.  The blocks of a small grid reach the look within its own latency of each other, most see 0 and send
+    // the atomic anyway: up to kNoLookBlocks blocks (`nblk`, the round's own) the no-return atomic goes straight out, and
+    // thread 0 waits for nothing.  Larger grids keep the look.
+    constexpr int kNoLookBlocks = 128;
     if (threadIdx.x == 0) {
-        if (s_chg && __hip_atomic_load(&a.flags[FLAG_CHANGED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) atomicOr(&a.flags[FLAG_CHANGED], 1);
-        if (NCEM && a.post_on && s_mov && __hip_atomic_load(&a.post_flags[FLAG_MOVED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
+        const bool look = nblk > kNoLookBlocks;
+        if (s_chg && !(look && __hip_atomic_load(&a.flags[FLAG_CHANGED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))
+            atomicOr(&a.flags[FLAG_CHANGED], 1);
+        if (NCEM && a.post_on && s_mov && !(look && __hip_atomic_load(&a.post_flags[FLAG_MOVED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))
             atomicOr(&a.post_flags[FLAG_MOVED], 1);
     }
+    NEM_SWEEP_PHASE(6);
     __shared__ uint64_t s_cmask[COUNT ? KA : 1][4];      // COUNT: the block's class masks, [class][wave]
     if (NCEM && a.post_on) {                             // k_labels_post's work, see SweepArgs
         const int wave = i >> 6;
@@ -722,6 +734,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
             if (v != 0) atomicAdd(&st[k], v);
         }
     }
+    NEM_SWEEP_PHASE(7);
     const bool post_ctrl = NCEM && a.post_on && a.post_ctrl.ctrl != nullptr;
     if (a.publish_byte != nullptr || post_ctrl || fold) {
         int* ticket = a.publish_byte != nullptr ? a.publish_ticket : (post_ctrl ? a.post_ctrl.ticket : a.fold_ticket);

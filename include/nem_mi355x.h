@@ -462,6 +462,37 @@ int nemgpu_layout_create_bh(nemgpu_layout** out, const nemgpu_master* m, const n
 int nemgpu_layout_bh_shape(int* depth, int* leaf);
 int nemgpu_layout_bh_tree(nemgpu_layout* l, int* n_cells, double* box, uint32_t* keys, int32_t* order, int32_t* level, int32_t* lo, int32_t* hi,
                           double* M, double* Sx, double* Sy, int32_t* accepted, int32_t* visited);
+/* The organisms CLUSTERED for the presence/absence plot: what the R script of PPanGGOLiN's CLI computes with
+   hclust(dist(t(binary_matrix), method = "binary")) (command_line.py:57, :79) and the raster it draws (:84-101), from the
+   master's presence bits; pangenomenem_amd/tileplot.py states every step in numpy.  m is only read (its presence rows;
+   the adjacency is not: a bits-only master and one built with directed = 1 are fine) and MUST OUTLIVE the handle, which
+   reads its rows again in _cells; the work runs on m's stream.
+   _create: the distances of all pairs of organisms, resident until _destroy as the full symmetric square double [d][d]
+     (8 d^2 bytes): with A, B the family sets of organisms i, j, inter = |A & B|, uni = |A| + |B| - inter,
+     dist = (double)(uni - inter) / uni, 0 where uni == 0 (R_dist_binary; both empty: 0; the diagonal is 0).  Exact
+     integer counts and one IEEE division: no tolerance.  d <= 32768 (_tile_info's max_organisms); more is refused
+     before any allocation.
+   _distances: rows i0 .. i0 + rows - 1 of the square into out[rows][d] (HOST).
+   _run: R's hclust(method = "complete") as Murtagh's nearest-neighbour algorithm (hclust.f; tileplot.
+     hclust_complete_host is the statement, ties included: every minimum is found with a strict <, the lowest index
+     wins): merge s joins the clusters of organisms i2[s] < j2[s] (the merged cluster goes on under i2[s], j2[s] is
+     retired) at height[s]; d - 1 merges (HOST arrays of d - 1; d == 1: nothing is written, they may be NULL).
+     The merges run on a copy (another 8 d^2 bytes, for the call): _distances gives the same rows afterwards.  The loop
+     runs on the device without a host round trip per merge.
+   _cells: the raster's rows row0 .. row0 + rows - 1 into out[rows][d] (HOST, uint8 0 / 1): cell (r, c) = family
+     fam_order[row0 + r] present in organism org_order[c].  fam_order[n] and org_order[d] are permutations.
+   _tile_info: the distance kernel's tile (organisms per side), the 64-bit words of a row it stages per step, and the
+     most organisms _create takes; host only; any may be NULL.
+   NEMGPU_E_ARG before any launch (nemgpu_last_error says why): a NULL pointer, rows out of range (rows <= 0 too), an
+   order that is not a permutation, d above the limit. */
+typedef struct nemgpu_orgclust nemgpu_orgclust;
+int nemgpu_orgclust_create(nemgpu_orgclust** out, const nemgpu_master* m);
+int nemgpu_orgclust_shape(const nemgpu_orgclust* h, int* n, int* d);
+int nemgpu_orgclust_distances(const nemgpu_orgclust* h, int i0, int rows, double* out);
+int nemgpu_orgclust_run(nemgpu_orgclust* h, int32_t* i2, int32_t* j2, double* height);
+int nemgpu_orgclust_cells(nemgpu_orgclust* h, const int32_t* fam_order, const int32_t* org_order, int row0, int rows, uint8_t* out);
+void nemgpu_orgclust_destroy(nemgpu_orgclust* h);
+int nemgpu_orgdist_tile_info(int* tile, int* chunk_words, int* max_organisms);
 /* What a master holds, of whichever constructor: sizes (n families, d organisms, nnz CSR entries, n_extra pairs with
    count >= 2; any pointer may be NULL), and the arrays as nemgpu_master_create_counts takes them, read back from the
    device: xbits[n][ceil(d/32)], nei_ptr[n + 1], nei_idx[nnz], edge_bits[nnz][ceil(d/32)], extra_ptr[nnz + 1],

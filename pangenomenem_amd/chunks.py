@@ -708,6 +708,25 @@ class Master:
         return shell.partition_shell(self, partitions, Q, mean_shell, beta, free_dispersion, exclusity_th, init_using_qual, edges, seed,
                                      subpart_name, select, annotations, repeated, low_disp)
 
+    def organism_clustering(self):
+        """The organisms clustered on the device for the CLI's presence/absence plot (the R script's
+        hclust(dist(t(binary_matrix), method="binary")), command_line.py:79; nemgpu_orgclust_*): the Jaccard distances of
+        all pairs over this master's presence bits (tileplot.organism_distances_host states them) and R's complete
+        linkage on them (tileplot.hclust_complete_host).  At most 32 768 organisms (NemGpuError above).  A bits-only
+        master and a directed one are fine: the adjacency is not read.  This master is only read and must stay open as
+        long as the result.  Returns a tileplot.OrganismClustering: distances(i0, rows), merge, height, order, labels,
+        close()."""
+        from . import tileplot
+        return tileplot.OrganismClustering(self)
+
+    def tile_plot(self, partitions):
+        """What the presence/absence plot draws (command_line.py:75-101): the organisms in the clustering's leaf order,
+        the families in tileplot.family_plot_order, the raster gathered on the device in batches.  partitions: what
+        Master.partition returned, or uint8 [n] (P 0, S 1, C 2, U 3).  Returns a tileplot.TilePlot: organism_order,
+        organism_labels, family_order, cells(row0, rows), close()."""
+        from . import tileplot
+        return tileplot.TilePlot(self, partitions)
+
     def shape(self):
         """(n families, d organisms, nnz CSR entries, pairs with count >= 2) as the device holds them (nemgpu_master_shape)"""
         v = [C.c_int() for _ in range(4)]

@@ -833,6 +833,14 @@ int nemgpu_chain_device(const double* x, long long n, float init, int device, fl
 float nemgpu_halfsum_host(const float* x, int n, int mode, int* stepped);
 int nemgpu_halfsum_device(const float* x, int n, int waves, int device, float* out);
 int nemgpu_halfsum_profile(const float* x, int n, int waves, int device, double us[5]);
+/* An NCEM round takes a site's label from the unnormalised row cinum[k] = pkf[k] * exp(beta ctx[k]) where the row's
+   maximum is clear, and normalises only the other rows (pangenomenem_amd/csrc/nem_map.hpp; NEM_MI355X_MAP_MARGIN=0:
+   every row).  Test hooks, out[i] = {the normalised row's first maximum, the later entries equal to it as floats, the
+   unnormalised row's first maximum, 1 if the row is clear}: nemgpu_map_margin_host -- rows cinum[n][K], K <= 32, on
+   the CPU (no GPU needed); nemgpu_map_margin_device -- rows as a round has them (pkf[n][K], ctx[n][K]; use_nei = 0:
+   cinum = pkf), K <= 8, with the device's arithmetic. */
+int nemgpu_map_margin_host(const double* cinum, int n, int K, int* out);
+int nemgpu_map_margin_device(const double* pkf, const float* ctx, int n, int K, float beta, int use_nei, int device, int* out);
 
 /* nemgpu_destroy parks an engine's stream, first 16 MB of device memory and pinned control block (up to 16 sets
    per process) for the next nemgpu_create on the same device -- a nem() call creates and destroys an engine, and

@@ -31,6 +31,7 @@
 #include "nem_ff.hpp"
 #include "nem_chain.hpp"
 #include "nem_halfsum.hpp"
+#include "nem_map.hpp"
 #include "nem_rng.hpp"
 #include "nem_kernels.hpp"
 #include "nem_chunks.hpp"
@@ -250,6 +251,9 @@ struct nemgpu_engine {
     // the fused density kernels walk the fast-forwarded chain lane by lane and cross binades in batches (chain_ff_batched);
     // NEM_MI355X_FF_BATCH=0: word by word, as every other density kernel does
     bool ff_batch = true;
+    // an NCEM round takes a site's label from the unnormalised row where the maximum is clear (nem_map.hpp);
+    // NEM_MI355X_MAP_MARGIN=0: every row is normalised
+    bool map_margin = true;
     // a kernel's FLAG_FAULT seen on the host (cleared, device word included, by the next reset / restart);
     // fault_inject: NEM_MI355X_FAULT_INJECT=fuzzy_pc makes one producer of k_mstep_fuzzy_pc skip a hand-over (tests)
     bool fault_seen = false; int fault_inject = 0;
@@ -889,7 +893,7 @@ int sweep_setup(nemgpu_engine* e, float beta, SweepCtx& c, bool id_by_value)
     a.nei_ptr = e->nei_ptr; a.nei_idx = e->nei_idx; a.nei_w = e->nei_w;
     a.beta = beta;
     a.pkfki = e->pkfki;
-    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.sweep_id = e->sweep_counter++;
+    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.map_full = e->map_margin ? 0 : 1; a.sweep_id = e->sweep_counter++;
     a.sweep_id_ptr = (e->stop_ptr != nullptr && !id_by_value) ? e->sweep_next : nullptr;   // pipelined loop: the device keeps count
     if (e->libc()) {
         if (e->stop_ptr == nullptr) { int r = ensure_draw_window(e, e->draws, draw_need(e)); if (r) return r; }
@@ -1077,7 +1081,7 @@ int host_rounds_ctx(nemgpu_engine* e, SweepCtx& sc, uint32_t sweep_id, int launc
     SweepArgs& a = sc.a;
     a.n_local = e->n; a.lo = e->lo; a.n_total = e->n_total; a.K = e->k; a.npad = e->npad; a.use_nei = sc.use_nei ? 1 : 0;
     a.nei_ptr = e->nei_ptr; a.nei_idx = e->nei_idx; a.nei_w = e->nei_w; a.beta = e->cfg.beta; a.pkfki = e->pkfki;
-    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.sweep_id = sweep_id; a.sweep_id_ptr = nullptr;
+    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.map_full = e->map_margin ? 0 : 1; a.sweep_id = sweep_id; a.sweep_id_ptr = nullptr;
     sc.r = launched; sc.checked = launched;               // (the enqueued rounds all changed something)
     if (e->libc()) {
         for (int q = 0; q < launched; q++) if (e->h_round(q)[FLAG_NTIES] & (1 << 30)) e->tie_heavy = true;
@@ -2592,6 +2596,7 @@ int nemgpu_create(nemgpu_engine** out, int n_total, int d, int k, int site_lo, i
     if (const char* g = getenv("NEM_MI355X_FAULT_INJECT")) e->fault_inject = !strcmp(g, "fuzzy_pc") ? 1 : 0;
     if (const char* g = getenv("NEM_MI355X_FF")) e->ff_mode = (g[0] == '0') ? 0 : (g[0] == '1') ? 1 : -1;   // 0 plain chain, 1 always
     if (const char* g = getenv("NEM_MI355X_FF_BATCH")) e->ff_batch = (g[0] != '0');   // 0: the word-synchronous chain everywhere
+    if (const char* g = getenv("NEM_MI355X_MAP_MARGIN")) e->map_margin = (g[0] != '0');   // 0: every NCEM row normalised
     if (const char* g = getenv("NEM_MI355X_SORT")) e->use_sort = (g[0] != '0');       // 0: E1 lanes in family order
     if (hip_stream) { e->stream = (hipStream_t)hip_stream; e->own_stream = false; }
     else {
@@ -4374,7 +4379,7 @@ static int make_clone(nemgpu_engine* p, nemgpu_engine** out, char* slab, size_t 
     c->cfg = p->cfg; c->have_matrix = true; c->have_params = true; c->has_graph = p->has_graph;
     c->xw = p->xw; c->xws = p->xws; c->perm = p->perm; c->xt = p->xt; c->use_sort = p->use_sort;
     c->nei_ptr = p->nei_ptr; c->nei_idx = p->nei_idx; c->nei_w = p->nei_w; c->nnz = p->nnz;
-    c->use_graphs = p->use_graphs; c->ff_mode = p->ff_mode; c->ff_batch = p->ff_batch; c->round_batch = p->round_batch; c->rounds_iter = p->rounds_iter;
+    c->use_graphs = p->use_graphs; c->ff_mode = p->ff_mode; c->ff_batch = p->ff_batch; c->map_margin = p->map_margin; c->round_batch = p->round_batch; c->rounds_iter = p->rounds_iter;
     c->parent = p; c->carve_all = true;
     c->chunks.push_back({slab, slab_bytes, 0, false});
     c->shared_chunk = 0;
@@ -4489,7 +4494,7 @@ static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, ne
     int width = (e->libc() && !(fa && fa[0] == '0') && fn == nullptr) ? 1 : group;   // (a logged run bets from the first start on: a lost bet sends the whole call to the sequential form)
     int voided_in_a_row = 0, clean_run = 0; bool alone_for_good = false;
     if ((r = ensure_clones(e, group))) return r;
-    for (nemgpu_engine* c : e->clones) { c->cfg = e->cfg; c->stream = e->stream; c->round_batch = e->round_batch; c->ff_mode = e->ff_mode; c->ff_batch = e->ff_batch; }
+    for (nemgpu_engine* c : e->clones) { c->cfg = e->cfg; c->stream = e->stream; c->round_batch = e->round_batch; c->ff_mode = e->ff_mode; c->ff_batch = e->ff_batch; c->map_margin = e->map_margin; }
 
     e->rs_rounds = e->rs_lockstep = e->rs_alone = e->rs_redone = e->rs_two_waits = 0;
     // (random starts tie by the hundreds in their initial sweeps: the draw window is sized for that from the first start on,
@@ -4819,7 +4824,7 @@ void shard_sweep_args(nemgpu_engine* e, SweepArgs& a, float beta, int sweep_id)
     a.use_nei = (e->has_graph && beta != 0.0f) ? 1 : 0;
     a.nei_ptr = e->nei_ptr; a.nei_idx = e->nei_idx; a.nei_w = e->nei_w;
     a.beta = beta; a.pkfki = e->pkfki;
-    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed;
+    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.map_full = e->map_margin ? 0 : 1;
     a.sweep_id = sweep_id >= 0 ? (uint32_t)sweep_id : 0u;
     a.sweep_id_ptr = sweep_id >= 0 ? nullptr : e->sweep_next;     // -1: the device keeps count (pipelined loop)
     a.stop = e->stop_ptr;
@@ -5063,7 +5068,7 @@ int nemgpu_shard_fuzzy_round(nemgpu_engine* e, float beta, int sweep_id, int rou
     a.use_nei = (e->has_graph && beta != 0.0f) ? 1 : 0;
     a.nei_ptr = e->nei_ptr; a.nei_idx = e->nei_idx; a.nei_w = e->nei_w;
     a.beta = beta; a.pkfki = e->pkfki;
-    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.sweep_id = (uint32_t)sweep_id;
+    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.map_full = e->map_margin ? 0 : 1; a.sweep_id = (uint32_t)sweep_id;
     a.c_old = c_old_dev; a.c_guess = c_guess_dev; a.c_out = c_out_dev;
     a.flags = e->round_flags(slot);
     a.fold_ticket = e->sweep_next + 32;
@@ -5915,6 +5920,42 @@ extern "C" int nemgpu_halfsum_device(const float* x, int n, int waves, int devic
     HIPCHK(hipMemcpyAsync(out, dout, sizeof(float), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     (void)hipStreamDestroy(st); (void)hipFree(dx); (void)hipFree(dout);
+    return NEMGPU_OK;
+}
+
+// ---- test hooks for the NCEM label from the unnormalised row (nem_map.hpp) ----
+// n rows cinum[n][K] (K <= 32): out[i] = {the normalised row's first maximum, the later entries equal to it as floats,
+// the unnormalised row's first maximum, whether the row is clear}.  No GPU needed.
+extern "C" int nemgpu_map_margin_host(const double* cinum, int n, int K, int* out)
+{
+    if (cinum == nullptr || out == nullptr || n < 0 || K < 1 || K > nemk::kMaxKernelK) { set_error("nemgpu_map_margin_host: bad argument"); return NEMGPU_E_FUNCARG; }
+    for (int i = 0; i < n; i++) {
+        int* o = out + 4 * (size_t)i;
+        o[3] = nemk::map_row_host(cinum + (size_t)i * K, K, &o[0], &o[1], &o[2]) ? 1 : 0;
+    }
+    return NEMGPU_OK;
+}
+
+// the same four per row from the device's arithmetic, rows given as a round has them: densities pkf[n][K] and class
+// contexts ctx[n][K], cinum = pkf * exp(beta * ctx) when use_nei (else pkf); K <= 8
+extern "C" int nemgpu_map_margin_device(const double* pkf, const float* ctx, int n, int K, float beta, int use_nei, int device, int* out)
+{
+    if (pkf == nullptr || ctx == nullptr || out == nullptr || n <= 0 || K < 1 || K > 8) { set_error("nemgpu_map_margin_device: bad argument"); return NEMGPU_E_FUNCARG; }
+    HIPCHK(hipSetDevice(device));
+    const size_t m = (size_t)n * K;
+    double* dp = nullptr; float* dc = nullptr; int* dout = nullptr;
+    HIPCHK(hipMalloc(&dp, m * sizeof(double)));
+    HIPCHK(hipMalloc(&dc, m * sizeof(float)));
+    HIPCHK(hipMalloc(&dout, (size_t)n * 4 * sizeof(int)));
+    hipStream_t st;
+    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIPCHK(hipMemcpyAsync(dp, pkf, m * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dc, ctx, m * sizeof(float), hipMemcpyHostToDevice, st));
+    nemk::launch_map_margin_debug(dp, dc, n, K, beta, use_nei, dout, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    (void)hipStreamDestroy(st); (void)hipFree(dp); (void)hipFree(dc); (void)hipFree(dout);
     return NEMGPU_OK;
 }
 

@@ -2374,8 +2374,9 @@ __global__ __launch_bounds__(256) void k_density_start_word(FusedDensityArgs a, 
 // the counts are taken from round 0's labels while round 1, the verifying round, runs.  The two do not depend on each
 // other; as two launches the second waited for the first.  (The round's last-block ticket -- it publishes the rank's
 // flag bytes -- is among the round's blocks only.)
+// (K = 2: the round stands at 81 registers, one step past six waves per SIMD -- held to 80, nothing spills)
 template <int KT, int R>
-__global__ __launch_bounds__(256) void k_sweep_counts(SweepArgs s, CountsArgs c, int nsweep)
+__global__ __launch_bounds__(256, KT == 2 ? 6 : 1) void k_sweep_counts(SweepArgs s, CountsArgs c, int nsweep)
 {
     if ((int)blockIdx.x < nsweep) { sweep_body<KT, true, 256, false>(s, blockIdx.x, nsweep); return; }   // (the sharded path has no TIE_LIBC)
     mstep_counts_body<R>(c.K, c.D, c.nw64, c.xt, c.mask, c.stats, c.stop, CtrlArgs{}, (int)blockIdx.x - nsweep, (int)gridDim.x - nsweep);

@@ -102,6 +102,9 @@ struct SweepArgs {
     // (k_mstep_counts' {N_k, S1[k][d]}) added into post_stats, zeroed by an earlier launch -- every block its 256
     // families' share, from the organism-major bit rows post_xt ([post_D][post_nw64]).  nullptr: no counting.
     int* post_stats; const uint64_t* post_xt; int post_D;
+    // NCEM: a site's label comes from the unnormalised row where its maximum is clear (nem_map.hpp); nonzero: every row
+    // is normalised, as the reference does (NEM_MI355X_MAP_MARGIN=0)
+    int map_full;
 };
 // argument blocks of the kernels whose launch wrappers take scalars (the batched launches need them as structs)
 struct LabelsPostArgs { int n_local, lo, K, nw64; const uint8_t* lab_new; const uint8_t* lab_old; uint64_t* mask; int* flags;
@@ -213,6 +216,7 @@ void launch_mstep_fuzzy(int n, int npad, int K, int D, const uint32_t* xw, const
 void launch_conv_fuzzy(size_t m, const float* c, const float* cold, float thres, int* flags, const int* stop,
                        const CtrlArgs* ctrl, hipStream_t s);
 void launch_chain_debug(const double* x, long long n, float init, float* out, hipStream_t s);
+bool launch_map_margin_debug(const double* pkf, const float* ctx, int n, int K, float beta, int use_nei, int* out, hipStream_t s);   // K <= 8; out[n][4]
 bool launch_halfsum_debug(const float* x, int n, int waves, float* out, hipStream_t s, long long* stamps = nullptr);   // n <= 8192, waves 1 | 16; out[2], stamps[6] when timing
 void launch_calib_read(const uint32_t* buf, size_t words, uint32_t* sink, hipStream_t s);
 void launch_onehot(int n, int K, const uint8_t* lab, float* c, hipStream_t s);

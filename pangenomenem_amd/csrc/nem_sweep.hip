@@ -88,6 +88,39 @@ void launch_sweep(const SweepArgs& a0, bool ncem, hipStream_t s)
 }
 
 
+// test hook: n given rows (pkf[n][K] densities, ctx[n][K] class contexts) through the two ways an NCEM round has to a
+// label -- out[i] = {the normalised row's first maximum, the later entries equal to it, the unnormalised row's first
+// maximum, whether the row is clear (nem_map.hpp)} -- with the device's own exp, divisions and conversions
+constexpr int kMapDebugK = 8;
+__global__ __launch_bounds__(256) void k_map_margin_debug(SweepArgs a, const float* ctx_rows, int4* out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_local) return;
+    const int K = a.K;
+    double pkf[kMapDebugK], cinum[kMapDebugK];
+    float ctx[kMapDebugK], cf[kMapDebugK];
+#pragma unroll
+    for (int k = 0; k < kMapDebugK; k++) {
+        pkf[k] = k < K ? a.pkfki[(size_t)i * K + k] : 0.0;
+        ctx[k] = k < K ? ctx_rows[(size_t)i * K + k] : 0.0f;
+    }
+    const double cum = local_cinum<kMapDebugK>(a, K, pkf, ctx, cinum);
+    int k_clear;
+    const bool clear = map_clear_row<kMapDebugK>(cinum, K, cum, k_clear);
+    map_normalise<kMapDebugK>(cinum, K, cum, cf);
+    int nequal = 0;
+    const int k_full = map_full<kMapDebugK>(cf, K, nequal);
+    out[i] = make_int4(k_full, nequal, k_clear, clear ? 1 : 0);
+}
+bool launch_map_margin_debug(const double* pkf, const float* ctx, int n, int K, float beta, int use_nei, int* out, hipStream_t s)
+{
+    if (n <= 0 || K < 1 || K > kMapDebugK) return false;
+    SweepArgs a{};
+    a.n_local = n; a.K = K; a.pkfki = pkf; a.beta = beta; a.use_nei = use_nei ? 1 : 0;
+    hipLaunchKernelGGL(k_map_margin_debug, dim3((n + 255) / 256), dim3(256), 0, s, a, ctx, reinterpret_cast<int4*>(out));
+    return true;
+}
+
 #ifdef NEM_PHASE_PROF
 extern "C" int nemgpu_debug_sweep_phases(unsigned long long* out8)
 {

@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "nem_kernels.hpp"
+#include "nem_map.hpp"
 
 namespace nemk {
 
@@ -249,17 +250,47 @@ __device__ inline bool last_block_ticket(int* ticket, int nblocks, int tally = 0
 // solution, bit for bit.  Round r reads guess_r and writes out_r; rounds after the first
 // unchanged one exit immediately (prev_changed == 0).
 // ------------------------------------------------------------------------------------------
-// One site's row: ComputeLocalProba (nem_alg.c:2576-2613) from the class contexts.  cf = the normalised row;
-// returns true when the site hit the "density = 0" branch.
+// One site's row: ComputeLocalProba (nem_alg.c:2576-2613) from the class contexts.  local_cinum: the unnormalised row
+// and its sum; local_proba: cf = the normalised row, returns true when the site hit the "density = 0" branch.
 template <int KA>
-__device__ __forceinline__ bool local_proba(const SweepArgs& a, int K, const double* pkf, const float* ctx, float* cf,
-                                            const double* exp_tab = nullptr, int exp_tab_len = 0)
+__device__ __forceinline__ double local_cinum(const SweepArgs& a, int K, const double* pkf, const float* ctx, double* cinum,
+                                              const double* exp_tab = nullptr, int exp_tab_len = 0)
 {
-    double cinum[KA];
     double cum = 0.0;
     // (exp_tab[m] = exp((double)beta * (double)(float)m) from the same device exp: a context that is such an integer
     //  takes its factor from the table, every other one runs exp -- decided for the whole row, so that a row costs
     //  either K table reads or K calls)
+    bool tab = exp_tab != nullptr;
+    int mi[KA];
+    if (tab) {
+#pragma unroll
+        for (int k = 0; k < KA; k++) {
+            if (k < K) {
+                const float c = ctx[k];
+                mi[k] = (int)c;
+                tab = tab && c >= 0.0f && c < (float)exp_tab_len && (float)mi[k] == c;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KA; k++) {
+        if (k < K) {                                     // nem_alg.c:2581-2584
+            double v = pkf[k];
+            if (a.use_nei) v = v * (tab ? exp_tab[mi[k]] : exp((double)a.beta * (double)ctx[k]));
+            cinum[k] = v;
+            cum = cum + v;
+        }
+    }
+    return cum;
+}
+template <int KA>
+__device__ __forceinline__ bool local_proba(const SweepArgs& a, int K, const double* pkf, const float* ctx, float* cf,
+                                            const double* exp_tab = nullptr, int exp_tab_len = 0)
+{
+    // (local_cinum's loops in its own text, as it was before there was a local_cinum: the fuzzy instances and the NCEM
+    //  ones that do not take the label shortcut then compile to what they were, register for register)
+    double cinum[KA];
+    double cum = 0.0;
     bool tab = exp_tab != nullptr;
     int mi[KA];
     if (tab) {
@@ -462,6 +493,9 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     // rounds: label changes run down the path inside one launch instead of one launch per hop.
     // ------------------------------------------------------------------------------------------
     constexpr bool libc = LIBC;
+    // (the label shortcut of nem_map.hpp: in the instances for K <= 7 -- from K = 8 on, and in the instance for any K,
+    //  the decision's registers on top of the row's cost a wave per SIMD or spill)
+    constexpr bool kMapShort = KT >= 1 && KT <= 7;
     const int blk_lo = a.lo + bx * spb;          // first label slot of this block
     // (pkf, nb, ne: asked for at the head of the block)
     // the first four neighbours live in registers: index, weight, and the label when it cannot change in here
@@ -535,13 +569,24 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
                     for (int k = 0; k < KA; k++)
                         if (k < K) ctx[k] = ctx[k] + ((l == k) ? wt : -0.0f);
                 }
+                // a row whose maximum is clear has its label without the normalised row (nem_map.hpp); the lanes of
+                // a wave that are not sure branch together, around all the divisions
                 float cf[KA];
-                zero_density = local_proba<KA>(a, K, pkf, ctx, cf, s_exp, kExpTab);
+                int kmax = 0;
+                bool clear = false;
+                if constexpr (kMapShort) {
+                    double cinum[KA];
+                    const double cum = local_cinum<KA>(a, K, pkf, ctx, cinum, s_exp, kExpTab);
+                    zero_density = !(cum > 0);
+                    clear = !a.map_full && map_clear_row<KA>(cinum, K, cum, kmax);
+                    if (!clear) map_normalise<KA>(cinum, K, cum, cf);
+                } else zero_density = local_proba<KA>(a, K, pkf, ctx, cf, s_exp, kExpTab);
+                int drew = 0;
+                if (!clear) {                            // every other row: the reference's arithmetic, as it was
                 // ComputeMAP, nem_alg.c:603-640
-                int kmax = 0; float ukmax = cf[0];
+                kmax = 0; float ukmax = cf[0];
 #pragma unroll
                 for (int k = 1; k < KA; k++) if (k < K && cf[k] > ukmax) { ukmax = cf[k]; kmax = k; }
-                int drew = 0;
                 if (a.tie_rule != NEMGPU_TIE_FIRST) {
                     int nequal = 0;
 #pragma unroll
@@ -573,6 +618,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
                         kmax = chosen;
                     }
                 }
+                }                                        // (!clear)
                 nxt = kmax | drew;
                 seen_drew = drew_lt; seen_wave_draws = below_in_block;
             }

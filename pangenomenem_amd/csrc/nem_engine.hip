@@ -1023,7 +1023,7 @@ int read_iter_flags(nemgpu_engine* e)
 int reset_device(nemgpu_engine* e);
 int reset_state(nemgpu_engine* e, bool lazy = false);
 int flush_reset(nemgpu_engine* e);
-int criteria_enqueue(nemgpu_engine* e, int buf);
+int criteria_enqueue(nemgpu_engine* e, int buf, bool second = false);
 void fill_result(nemgpu_engine* e, nemgpu_result* res);
 
 // ComputePartitionFromPara(Needinit = 1), nem_alg.c:1967-1981
@@ -1899,6 +1899,52 @@ int zip_reserve(nemgpu_engine* lead, size_t bytes)
     return NEMGPU_OK;
 }
 
+// may two members' recorded sequences go out as one?  (launch for launch the same kernel, variant, block, grid height)
+bool same_sequence(const Recorder& a, const Recorder& b)
+{
+    bool same = a.ops.size() == b.ops.size();
+    for (size_t t = 0; same && t < a.ops.size(); t++) same = same_launch(a.ops[t], b.ops[t]);
+    return same;
+}
+
+// One position of a zipped sequence in an argument slab: from `args_off` on the B members' argument blocks, `stride`
+// bytes apart (a block's size rounded up to 16), behind them (gx_off) their grid widths, rounded up to 16 bytes.
+struct ZipPos { int kind, variant, B, stride; size_t args_off, gx_off; unsigned max_gx, gy, block; };
+
+// Lays out the sequences of `groups` (each a list of members, indices into recs, whose sequences same_sequence holds
+// alike) in `slab`, position after position and group after group; *out: the positions.  Returns the size.
+// slab == nullptr: nothing is written and the same size and positions come out -- what a caller reserves by.
+size_t zip_pack(char* slab, const Recorder* recs, const std::vector<std::vector<int>>& groups, std::vector<ZipPos>* out)
+{
+    size_t off = 0;
+    if (out) out->clear();
+    for (const std::vector<int>& g : groups) {
+        const int B = (int)g.size();
+        for (size_t t = 0; t < recs[g[0]].ops.size(); t++) {
+            const OpRecord& o0 = recs[g[0]].ops[t];
+            const int stride = (o0.nbytes + 15) & ~15;
+            ZipPos L{o0.kind, o0.variant, B, stride, off, off + (size_t)B * stride, 0, o0.gy, o0.block};
+            for (int b = 0; b < B; b++) {
+                const OpRecord& o = recs[g[b]].ops[t];
+                L.max_gx = std::max(L.max_gx, o.gx);
+                if (slab == nullptr) continue;
+                memcpy(slab + L.args_off + (size_t)b * stride, o.args, (size_t)o0.nbytes);
+                reinterpret_cast<int*>(slab + L.gx_off)[b] = (int)o.gx;
+            }
+            if (out) out->push_back(L);
+            off = L.gx_off + (((size_t)B * sizeof(int) + 15) & ~(size_t)15);
+        }
+    }
+    return off;
+}
+
+// ... and its launch, the slab being at `dev` on the device
+void zip_issue(const ZipPos& L, const char* dev, hipStream_t s)
+{
+    launch_zipped(L.kind, L.variant, L.B, dev + L.args_off, L.stride, reinterpret_cast<const int*>(dev + L.gx_off), L.max_gx, L.gy,
+                  L.block, s);
+}
+
 // issue the recorded sequences of `members` (indices into recs / E) on the lead's stream; flags_words > 0: behind them,
 // one copy of every member's flag block to the host (gathered on the device first)
 int zip_and_launch(nemgpu_engine* lead, const std::vector<Recorder>& recs, const std::vector<int>& members, size_t flags_words)
@@ -1910,50 +1956,25 @@ int zip_and_launch(nemgpu_engine* lead, const std::vector<Recorder>& recs, const
     for (int m : members) {
         bool placed = false;
         for (auto& g : groups) {
-            const std::vector<OpRecord>& a = recs[g[0]].ops; const std::vector<OpRecord>& b = recs[m].ops;
-            bool same = a.size() == b.size();
-            for (size_t t = 0; same && t < a.size(); t++)
-                same = a[t].kind == b[t].kind && a[t].variant == b[t].variant && a[t].block == b[t].block && a[t].gy == b[t].gy &&
-                       a[t].nbytes == b[t].nbytes;
-            if (same) { g.push_back(m); placed = true; break; }
+            if (same_sequence(recs[g[0]], recs[m])) { g.push_back(m); placed = true; break; }
         }
         if (!placed) groups.push_back({m});
     }
-    size_t total = 0;
-    for (const auto& g : groups)
-        for (const OpRecord& o : recs[g[0]].ops) total += ((size_t)((o.nbytes + 15) & ~15) + 16) * g.size() + 64;
-    int r = zip_reserve(lead, total);
+    int r = zip_reserve(lead, zip_pack(nullptr, recs.data(), groups, nullptr));
     if (r) return r;
-    struct Launch { int kind, variant, B, stride; size_t args_off, gx_off; unsigned max_gx, gy, block; };
-    std::vector<Launch> launches;
-    size_t off = 0;
+    std::vector<ZipPos> launches;
+    const size_t off = zip_pack(z->zip_host, recs.data(), groups, &launches);
     std::vector<uint64_t> desc;                                   // everything a captured sequence depends on
-    for (const auto& g : groups) {
-        const int B = (int)g.size();
-        for (size_t t = 0; t < recs[g[0]].ops.size(); t++) {
-            const OpRecord& o0 = recs[g[0]].ops[t];
-            const int stride = (o0.nbytes + 15) & ~15;
-            Launch L{o0.kind, o0.variant, B, stride, off, 0, 0, o0.gy, o0.block};
-            for (int b = 0; b < B; b++) memcpy(z->zip_host + off + (size_t)b * stride, recs[g[b]].ops[t].args, (size_t)o0.nbytes);
-            off += (size_t)B * stride;
-            L.gx_off = off;
-            int* gx = reinterpret_cast<int*>(z->zip_host + off);
-            for (int b = 0; b < B; b++) { gx[b] = (int)recs[g[b]].ops[t].gx; L.max_gx = std::max(L.max_gx, recs[g[b]].ops[t].gx); }
-            off += ((size_t)B * sizeof(int) + 15) & ~(size_t)15;
-            launches.push_back(L);
-            for (uint64_t v : {(uint64_t)L.kind, (uint64_t)L.variant, (uint64_t)B, (uint64_t)stride, (uint64_t)L.max_gx, (uint64_t)L.gy,
-                               (uint64_t)L.block, (uint64_t)L.args_off, (uint64_t)L.gx_off}) desc.push_back(v);
-        }
-    }
+    for (const ZipPos& L : launches)
+        for (uint64_t v : {(uint64_t)L.kind, (uint64_t)L.variant, (uint64_t)L.B, (uint64_t)L.stride, (uint64_t)L.max_gx, (uint64_t)L.gy,
+                           (uint64_t)L.block, (uint64_t)L.args_off, (uint64_t)L.gx_off}) desc.push_back(v);
     desc.push_back(flags_words);
     if (off == 0 && flags_words == 0) return NEMGPU_OK;
     if (off) HIPCHK(hipMemcpyAsync(z->zip_dev, z->zip_host, off, hipMemcpyHostToDevice, lead->stream));
     // The launches themselves depend only on the shape (kernels, grids, slab offsets), not on the argument blocks'
     // content: a shape seen before is replayed from its captured graph
     auto issue = [&]() -> int {
-        for (const Launch& L : launches)
-            launch_zipped(L.kind, L.variant, L.B, z->zip_dev + L.args_off, L.stride, reinterpret_cast<const int*>(z->zip_dev + L.gx_off),
-                          L.max_gx, L.gy, L.block, lead->stream);
+        for (const ZipPos& L : launches) zip_issue(L, z->zip_dev, lead->stream);
         if (flags_words)
             HIPCHK(hipMemcpyAsync(z->zip_flags_host, z->zip_flags_dev, flags_words * sizeof(int), hipMemcpyDeviceToHost, lead->stream));
         return NEMGPU_OK;
@@ -2345,22 +2366,23 @@ int ensure_crit_buffers(nemgpu_engine* e)
     return NEMGPU_OK;
 }
 
-const float* float_partition(nemgpu_engine* e, int buf)
-{
-    if (!e->ncem()) return e->cbuf[buf];
-    launch_onehot(e->n_total, e->k, e->lab[buf], e->c_onehot, e->stream);
-    return e->c_onehot;
-}
-
-// ComputeCrit on the partition in buffer `buf` (default: the current one) with the current densities: the launches
-int criteria_enqueue(nemgpu_engine* e, int buf = -1)
+// ComputeCrit on the partition in buffer `buf` (default: the current one) with the current densities: the launches.
+// second: the evaluation writes the crit2_* set of buffers (criteria_pair_enqueue has made them)
+int criteria_enqueue(nemgpu_engine* e, int buf = -1, bool second)
 {
     int r;
     if (e->lo != 0 || e->hi != e->n_total) { set_error("criteria need the whole partition on one engine"); return NEMGPU_E_FUNCARG; }
     if ((r = ensure_crit_buffers(e))) return r;
-    const float* c = float_partition(e, buf < 0 ? e->cur : buf);
+    if (buf < 0) buf = e->cur;
+    const float* c = e->cbuf[buf];
+    if (e->ncem()) {
+        float* onehot = second ? e->c_onehot2 : e->c_onehot;
+        launch_onehot(e->n_total, e->k, e->lab[buf], onehot, e->stream);
+        c = onehot;
+    }
     launch_criteria(e->n, e->k, e->npad, e->nei_ptr, e->nei_idx, e->nei_w, e->has_graph ? 1 : 0, e->cfg.beta, c,
-                    e->pkfki, e->logpkfki, e->crit_dik, e->crit_gik, e->crit_lfi, e->crit_lzi, e->crit6_dev,
+                    e->pkfki, e->logpkfki, second ? e->crit2_dik : e->crit_dik, second ? e->crit2_gik : e->crit_gik,
+                    second ? e->crit2_lfi : e->crit_lfi, second ? e->crit2_lzi : e->crit_lzi, second ? e->crit2_6 : e->crit6_dev,
                     e->ncem() ? 1 : 0, e->stream);
     if (!current_recorder()) HIPCHK(hipGetLastError());
     return NEMGPU_OK;
@@ -2368,10 +2390,10 @@ int criteria_enqueue(nemgpu_engine* e, int buf = -1)
 // The criteria of TWO partitions of the engine (label / membership buffers buf_a and buf_b) in the same launches --
 // problem = blockIdx.z, through the kernels' batched twins: the i-ordered reductions are four lone blocks each and
 // take as long for two partitions as for one.  Results: crit6_dev (buf_a), crit2_6 (buf_b).
+constexpr size_t kCritPairBytes = 2048;                // crit_pair_dev: the two evaluations' records, packed (under 1 KB)
 int criteria_pair_enqueue(nemgpu_engine* e, int buf_a, int buf_b)
 {
     int r;
-    if (e->lo != 0 || e->hi != e->n_total) { set_error("criteria need the whole partition on one engine"); return NEMGPU_E_FUNCARG; }
     if ((r = ensure_crit_buffers(e))) return r;
     const size_t nk = (size_t)e->n * e->k;
     if (!e->crit2_dik) {
@@ -2382,40 +2404,28 @@ int criteria_pair_enqueue(nemgpu_engine* e, int buf_a, int buf_b)
         if ((r = dev_alloc(&e->crit2_lzi, (size_t)e->n))) return r;
         if ((r = dev_alloc(&e->crit2_6, 16))) return r;
         if (e->ncem()) { if ((r = dev_alloc(&e->c_onehot2, (size_t)e->n_total * e->k))) return r; }
-        if ((r = dev_alloc(&e->crit_pair_dev, 2048))) return r;
+        if ((r = dev_alloc(&e->crit_pair_dev, kCritPairBytes))) return r;
     }
-    // argument blocks: [2 x OnehotArgs | gx] [2 x CritArgs | gx terms | gx reduce | gx final]
-    constexpr int so = (sizeof(OnehotArgs) + 15) & ~15, sc = (sizeof(CritArgs) + 15) & ~15;
-    static_assert(2 * so + 16 + 2 * sc + 48 <= 2048, "argument slab of the paired criteria");
-    char* st = stage(e, 2048);
-    if (!st) { set_error("no staging memory for the paired criteria"); return NEMGPU_E_DEVICE; }
-    memset(st, 0, 2048);
-    const int o_oh = 0, o_ohgx = 2 * so, o_cr = o_ohgx + 16, o_gxt = o_cr + 2 * sc, o_gxr = o_gxt + 16, o_gxf = o_gxr + 16;
-    const float* cpart[2];
+    // the two evaluations as each would run alone, recorded; their launches are alike position by position
+    Recorder recs[2];
     const int bufs[2] = {buf_a, buf_b};
-    float* onehots[2] = {e->c_onehot, e->c_onehot2};
-    const unsigned g_oh = (unsigned)(((size_t)e->n_total * e->k + 255) / 256), g_t = (unsigned)((e->n + 255) / 256);
     for (int p = 0; p < 2; p++) {
-        if (e->ncem()) {
-            OnehotArgs oa{e->n_total, e->k, e->lab[bufs[p]], onehots[p]};
-            memcpy(st + o_oh + p * so, &oa, sizeof oa);
-            cpart[p] = onehots[p];
-        } else cpart[p] = e->cbuf[bufs[p]];
-        CritArgs ca{e->n, e->k, e->npad, e->nei_ptr, e->nei_idx, e->nei_w, e->has_graph ? 1 : 0, e->cfg.beta, cpart[p], e->pkfki, e->logpkfki,
-                    p ? e->crit2_dik : e->crit_dik, p ? e->crit2_gik : e->crit_gik, p ? e->crit2_lfi : e->crit_lfi,
-                    p ? e->crit2_lzi : e->crit_lzi, p ? e->crit2_6 : e->crit6_dev, e->ncem() ? 1 : 0};
-        memcpy(st + o_cr + p * sc, &ca, sizeof ca);
-        reinterpret_cast<int*>(st + o_ohgx)[p] = (int)g_oh;
-        reinterpret_cast<int*>(st + o_gxt)[p] = (int)g_t;
-        reinterpret_cast<int*>(st + o_gxr)[p] = 4;
-        reinterpret_cast<int*>(st + o_gxf)[p] = 1;
+        recs[p].ops.reserve(4);                            // (one-hot, terms, reduce, final)
+        set_recorder(&recs[p]);
+        r = criteria_enqueue(e, bufs[p], p == 1);
+        set_recorder(nullptr);
+        if (r) return r;
     }
-    HIPCHK(hipMemcpyAsync(e->crit_pair_dev, st, 2048, hipMemcpyHostToDevice, e->stream));
-    const char* dv = e->crit_pair_dev;
-    if (e->ncem()) launch_zipped(OP_ONEHOT, 0, 2, dv + o_oh, so, reinterpret_cast<const int*>(dv + o_ohgx), g_oh, 1, 256, e->stream);
-    launch_zipped(OP_CRIT_TERMS, 0, 2, dv + o_cr, sc, reinterpret_cast<const int*>(dv + o_gxt), g_t, 1, 256, e->stream);
-    launch_zipped(OP_CRIT_REDUCE, 0, 2, dv + o_cr, sc, reinterpret_cast<const int*>(dv + o_gxr), 4, 1, (unsigned)kCritReduceThreads, e->stream);
-    launch_zipped(OP_CRIT_FINAL, 0, 2, dv + o_cr, sc, reinterpret_cast<const int*>(dv + o_gxf), 1, 1, 1, e->stream);
+    if (!same_sequence(recs[0], recs[1])) { set_error("the paired criteria's launches differ"); return NEMGPU_E_INTERNAL; }
+    const std::vector<std::vector<int>> both{{0, 1}};
+    if (zip_pack(nullptr, recs, both, nullptr) > kCritPairBytes) { set_error("argument slab of the paired criteria"); return NEMGPU_E_INTERNAL; }
+    char* st = stage(e, kCritPairBytes);
+    if (!st) { set_error("no staging memory for the paired criteria"); return NEMGPU_E_DEVICE; }
+    memset(st, 0, kCritPairBytes);
+    std::vector<ZipPos> pos;
+    zip_pack(st, recs, both, &pos);
+    HIPCHK(hipMemcpyAsync(e->crit_pair_dev, st, kCritPairBytes, hipMemcpyHostToDevice, e->stream));
+    for (const ZipPos& L : pos) zip_issue(L, e->crit_pair_dev, e->stream);
     HIPCHK(hipGetLastError());
     return NEMGPU_OK;
 }
@@ -5663,29 +5673,19 @@ int nemgpu_profile_density_many(nemgpu_engine** engines, int count, int reps, do
         set_recorder(nullptr);
         if (r) return r;
         if (recs[m].ops.size() != 1) { set_error("profile_density_many: one density launch per engine expected"); return NEMGPU_E_INTERNAL; }
-        const OpRecord& o = recs[m].ops[0]; const OpRecord& o0 = recs[0].ops[0];
-        if (o.kind != o0.kind || o.variant != o0.variant || o.block != o0.block || o.gy != o0.gy || o.nbytes != o0.nbytes) {
-            set_error("profile_density_many: the engines' density launches differ in shape"); return NEMGPU_E_FUNCARG;
-        }
+        if (!same_sequence(recs[m], recs[0])) { set_error("profile_density_many: the engines' density launches differ in shape"); return NEMGPU_E_FUNCARG; }
         bytes += (double)e->n * e->wf * 4.0 + (double)e->k * e->d * 24.0 + (double)e->n * e->k * 12.0;
     }
-    const OpRecord& o0 = recs[0].ops[0];
-    const int stride = (o0.nbytes + 15) & ~15;
-    const size_t gx_off = (size_t)count * stride, total = gx_off + (((size_t)count * sizeof(int) + 15) & ~(size_t)15);
+    std::vector<std::vector<int>> all(1);
+    for (int m = 0; m < count; m++) all[0].push_back(m);
+    const size_t total = zip_pack(nullptr, recs.data(), all, nullptr);
     if ((r = zip_reserve(lead, total))) return r;
     nemgpu_engine::ZipContext* z = zip_context(lead);
-    unsigned max_gx = 0;
-    for (int m = 0; m < count; m++) {
-        memcpy(z->zip_host + (size_t)m * stride, recs[m].ops[0].args, (size_t)o0.nbytes);
-        reinterpret_cast<int*>(z->zip_host + gx_off)[m] = (int)recs[m].ops[0].gx;
-        max_gx = std::max(max_gx, recs[m].ops[0].gx);
-    }
+    std::vector<ZipPos> pos;
+    zip_pack(z->zip_host, recs.data(), all, &pos);
     HIPCHK(hipMemcpyAsync(z->zip_dev, z->zip_host, total, hipMemcpyHostToDevice, lead->stream));
     if (!lead->ev0) { HIPCHK(hipEventCreate(&lead->ev0)); HIPCHK(hipEventCreate(&lead->ev1)); }
-    auto once = [&]() {
-        launch_zipped(o0.kind, o0.variant, count, z->zip_dev, stride, reinterpret_cast<const int*>(z->zip_dev + gx_off), max_gx, o0.gy,
-                      o0.block, lead->stream);
-    };
+    auto once = [&]() { zip_issue(pos[0], z->zip_dev, lead->stream); };
     once();                                                    // (warm)
     HIPCHK(hipEventRecord(lead->ev0, lead->stream));
     for (int i = 0; i < reps; i++) once();

@@ -11,6 +11,7 @@
 // denormals preserved.  Where a sum is order-independent (NCEM: c in {0,1} => integer
 // counts < 2^24) it is computed with popcounts over bit-packed rows instead.
 #include <hip/hip_runtime.h>
+#include <cstdio>
 #include <cstdlib>
 #include <algorithm>
 #include <cfloat>
@@ -2136,7 +2137,6 @@ __device__ __forceinline__ void crit_terms_body(int n, int K, int npad, const in
 // reference's conditional adds (nem_alg.c:2727-2736) bit for bit.
 // ------------------------------------------------------------------------------------------
 constexpr int CH_T = 1024, CH_C = 4, CH_W = CH_T * CH_C;
-static_assert(CH_T == kCritReduceThreads, "launchers outside this file use kCritReduceThreads");
 
 struct ChainShared {
     double x[CH_W];
@@ -2348,21 +2348,59 @@ bool launch_halfsum_debug(const float* x, int n, int waves, float* out, hipStrea
     return true;
 }
 
-// ------------------------------------------------------------------------------------------
-// launch wrappers
-// ------------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------------
-// Kernels = the bodies above, twice: once with the argument block as a kernel parameter (one problem), once with an
-// array of argument blocks in device memory and the problem in blockIdx.z (B problems per launch).
-// ------------------------------------------------------------------------------------------
-// (NEM_B_HEAD: nem_kernels.hpp)
+__device__ __forceinline__ void fill_body(const FillArgs& a)
+{
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < a.words; t += 256) a.ptr[t] = a.value;   // (one block)
+}
+__device__ __forceinline__ void copy_body(const CopyArgs& a, int bx, int nblk)
+{
+    for (int t = bx * 256 + (int)threadIdx.x; t < a.words; t += nblk * 256) a.dst[t] = a.src[t];    // (one block per 4096 words, at most 64)
+}
 
-__global__ __launch_bounds__(1024) void k_finish(FinishArgs a) { finish_body(a, gridDim.x); }
-__global__ __launch_bounds__(1024) void k_finish_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FinishArgs) finish_body(a, nblk); }
-__global__ __launch_bounds__(256) void k_density(DensityArgs a) { density_body(a); }
-__global__ __launch_bounds__(256) void k_density_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(DensityArgs) density_body(a); }
+// ------------------------------------------------------------------------------------------
+// Kernels = the bodies above.  The recordable ones (nem_kernels.hpp) are this list: kind, kernel, launch bounds
+// (NEM_NO_BOUNDS: the compiler is left to itself), argument block, and the body's call in terms of the argument block
+// `a`, blockIdx.x and `nblk`, the problem's own grid width.  Each entry becomes the kernel with the argument block as
+// its parameter (one problem), its twin k_X_b with an array of argument blocks in device memory and the problem in
+// blockIdx.z (B problems per launch; NEM_B_HEAD: nem_kernels.hpp), the kind OP_X and OP_X's case in launch_zipped.
+// ------------------------------------------------------------------------------------------
+#define NEM_NO_BOUNDS
+#define NEM_OPS(OP)                                                                                                                   \
+    OP(FINISH,       k_finish,           __launch_bounds__(1024),            FinishArgs,     finish_body(a, nblk))                    \
+    OP(DENSITY,      k_density,          __launch_bounds__(256),             DensityArgs,    density_body(a))                         \
+    OP(CTRL,         k_ctrl,             NEM_NO_BOUNDS,                      CtrlArgs,       ctrl_logic(a))                           \
+    OP(LABELS_POST,  k_labels_post,      NEM_NO_BOUNDS,                      LabelsPostArgs,                                          \
+       labels_post_body(a.n_local, a.lo, a.K, a.nw64, a.lab_new, a.lab_old, a.mask, a.flags, a.stop, a.ca, nblk))                     \
+    OP(FUZZY_PC,     k_mstep_fuzzy_pc,   __launch_bounds__(64 * kPcWaves),   FuzzyArgs,      mstep_fuzzy_pc_body(a))                  \
+    OP(FUZZY_MED2,   k_mstep_fuzzy_med2, __launch_bounds__(64),              FuzzyArgs,      mstep_fuzzy_med2_body(a))                \
+    OP(FUZZY_T,      k_transpose_c,      NEM_NO_BOUNDS,                      FuzzyArgs,                                               \
+       transpose_c_body(a.n, a.ctpad, a.K, a.c, a.ct, a.stop))                                                                        \
+    OP(CONV_FUZZY,   k_conv_fuzzy,       NEM_NO_BOUNDS,                      ConvFuzzyArgs,                                           \
+       conv_fuzzy_body(a.m, a.c, a.cold, a.thres, a.flags, a.stop, a.ca, nblk))                                                       \
+    OP(ONEHOT,       k_onehot,           NEM_NO_BOUNDS,                      OnehotArgs,     onehot_body(a.n, a.K, a.lab, a.c))       \
+    OP(CRIT_TERMS,   k_crit_terms,       __launch_bounds__(256),             CritArgs,                                                \
+       crit_terms_body(a.n, a.K, a.npad, a.nei_ptr, a.nei_idx, a.nei_w, a.use_nei, a.beta, a.c, a.pkfki, a.logpkfki, a.dik, a.gik,    \
+                       a.lfi, a.lzi, a.hard))                                                                                         \
+    /* (crit6 has room for the four partial results behind the six criteria) */                                                       \
+    OP(CRIT_REDUCE,  k_crit_reduce,      __launch_bounds__(CH_T),            CritArgs,                                                \
+       crit_reduce_body(a.n, a.hard ? 1 : a.K, a.dik, a.gik, a.lfi, a.lzi, a.crit6 + 6))                                              \
+    OP(CRIT_FINAL,   k_crit_final,       NEM_NO_BOUNDS,                      CritArgs,       crit_final_body(a.beta, a.crit6 + 6, a.crit6)) \
+    OP(FILL,         k_fill,             NEM_NO_BOUNDS,                      FillArgs,       fill_body(a))                            \
+    OP(COPY,         k_copy_words,       NEM_NO_BOUNDS,                      CopyArgs,       copy_body(a, blockIdx.x, nblk))          \
+    OP(LAYOUT_WORDS, k_layout_words,     __launch_bounds__(256),             LayoutArgs,     layout_words_body(a, blockIdx.x))        \
+    OP(LAYOUT_BITS,  k_layout_bits,      __launch_bounds__(256),             LayoutArgs,     layout_bits_body(a, blockIdx.x))
+
+#define NEM_OP_KIND(ID, KERNEL, BOUNDS, ARGS, BODY) OP_##ID,
+enum { OP_LISTED_FIRST = OP_LISTED - 1, NEM_OPS(NEM_OP_KIND) };
+#define NEM_OP_KERNELS(ID, KERNEL, BOUNDS, ARGS, BODY)                                                             \
+    __global__ BOUNDS void KERNEL(ARGS a) { const int nblk = gridDim.x; (void)nblk; BODY; }                        \
+    __global__ BOUNDS void KERNEL##_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(ARGS) BODY; }
+NEM_OPS(NEM_OP_KERNELS)
+#undef NEM_OP_KIND
+#undef NEM_OP_KERNELS
+
+// ... and the others, which no batch records
 __global__ __launch_bounds__(256) void k_density_fused(FusedDensityArgs a) { (void)density_fused_body(a); }
-__global__ __launch_bounds__(256) void k_density_fused_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FusedDensityArgs) (void)density_fused_body<false, false>(a); }
 __global__ __launch_bounds__(256) void k_density_start(FusedDensityArgs a, StartArgs st) { (void)density_fused_body<true>(a, &st); }
 // the two without chain_ff_batched, for the grids that do not take it (fused_density_args): the walk's registers cost
 // these kernels two waves per SIMD, which a grid that fills the device several times over would pay for nothing
@@ -2396,17 +2434,7 @@ __global__ __launch_bounds__(256) void k_density_verify(FusedDensityArgs d, Swee
     sweep_body<KT, true, 256, false>(s, (int)blockIdx.x - nd, (int)gridDim.x - nd);
 }
 
-__global__ void k_ctrl(CtrlArgs a) { ctrl_logic(a); }
-__global__ void k_ctrl_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(CtrlArgs) ctrl_logic(a); }
-__global__ void k_labels_post(LabelsPostArgs a)
-{
-    labels_post_body(a.n_local, a.lo, a.K, a.nw64, a.lab_new, a.lab_old, a.mask, a.flags, a.stop, a.ca, gridDim.x);
-}
-__global__ void k_labels_post_b(const void* arr, int stride, const int* gx)
-{
-    NEM_B_HEAD(LabelsPostArgs)
-    labels_post_body(a.n_local, a.lo, a.K, a.nw64, a.lab_new, a.lab_old, a.mask, a.flags, a.stop, a.ca, nblk);
-}
+// the M-step counts: a template, so a pair by hand (kind OP_COUNTS, variant R)
 template <int R>
 __global__ __launch_bounds__(256) void k_mstep_counts(CountsArgs a)
 {
@@ -2418,60 +2446,6 @@ __global__ __launch_bounds__(256) void k_mstep_counts_b(const void* arr, int str
     NEM_B_HEAD(CountsArgs)
     mstep_counts_body<R>(a.K, a.D, a.nw64, a.xt, a.mask, a.stats, a.stop, a.prev_ctrl, blockIdx.x, nblk);
 }
-__global__ __launch_bounds__(64 * kPcWaves) void k_mstep_fuzzy_pc(FuzzyArgs a) { mstep_fuzzy_pc_body(a); }
-__global__ __launch_bounds__(64 * kPcWaves) void k_mstep_fuzzy_pc_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FuzzyArgs) mstep_fuzzy_pc_body(a); }
-__global__ __launch_bounds__(64) void k_mstep_fuzzy_med2(FuzzyArgs a) { mstep_fuzzy_med2_body(a); }
-__global__ __launch_bounds__(64) void k_mstep_fuzzy_med2_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FuzzyArgs) mstep_fuzzy_med2_body(a); }
-__global__ void k_transpose_c(FuzzyArgs a) { transpose_c_body(a.n, a.ctpad, a.K, a.c, a.ct, a.stop); }
-__global__ void k_transpose_c_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FuzzyArgs) transpose_c_body(a.n, a.ctpad, a.K, a.c, a.ct, a.stop); }
-__global__ void k_conv_fuzzy(ConvFuzzyArgs a) { conv_fuzzy_body(a.m, a.c, a.cold, a.thres, a.flags, a.stop, a.ca, gridDim.x); }
-__global__ void k_conv_fuzzy_b(const void* arr, int stride, const int* gx)
-{
-    NEM_B_HEAD(ConvFuzzyArgs)
-    conv_fuzzy_body(a.m, a.c, a.cold, a.thres, a.flags, a.stop, a.ca, nblk);
-}
-__global__ void k_onehot(OnehotArgs a) { onehot_body(a.n, a.K, a.lab, a.c); }
-__global__ void k_onehot_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(OnehotArgs) onehot_body(a.n, a.K, a.lab, a.c); }
-__global__ __launch_bounds__(256) void k_crit_terms(CritArgs a)
-{
-    crit_terms_body(a.n, a.K, a.npad, a.nei_ptr, a.nei_idx, a.nei_w, a.use_nei, a.beta, a.c, a.pkfki, a.logpkfki, a.dik, a.gik,
-                    a.lfi, a.lzi, a.hard);
-}
-__global__ __launch_bounds__(256) void k_crit_terms_b(const void* arr, int stride, const int* gx)
-{
-    NEM_B_HEAD(CritArgs)
-    crit_terms_body(a.n, a.K, a.npad, a.nei_ptr, a.nei_idx, a.nei_w, a.use_nei, a.beta, a.c, a.pkfki, a.logpkfki, a.dik, a.gik,
-                    a.lfi, a.lzi, a.hard);
-}
-// (crit6 has room for the four partial results behind the six criteria)
-__global__ __launch_bounds__(CH_T) void k_crit_reduce(CritArgs a)
-{
-    crit_reduce_body(a.n, a.hard ? 1 : a.K, a.dik, a.gik, a.lfi, a.lzi, a.crit6 + 6);
-}
-__global__ __launch_bounds__(CH_T) void k_crit_reduce_b(const void* arr, int stride, const int* gx)
-{
-    NEM_B_HEAD(CritArgs)
-    crit_reduce_body(a.n, a.hard ? 1 : a.K, a.dik, a.gik, a.lfi, a.lzi, a.crit6 + 6);
-}
-__global__ void k_crit_final(CritArgs a) { crit_final_body(a.beta, a.crit6 + 6, a.crit6); }
-__global__ void k_crit_final_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(CritArgs) crit_final_body(a.beta, a.crit6 + 6, a.crit6); }
-__device__ __forceinline__ void fill_body(const FillArgs& a)
-{
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < a.words; t += 256) a.ptr[t] = a.value;   // (one block)
-}
-__global__ void k_fill(FillArgs a) { fill_body(a); }
-__global__ void k_fill_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(FillArgs) fill_body(a); }
-
-__device__ __forceinline__ void copy_body(const CopyArgs& a, int bx, int nblk)
-{
-    for (int t = bx * 256 + (int)threadIdx.x; t < a.words; t += nblk * 256) a.dst[t] = a.src[t];    // (one block per 4096 words, at most 64)
-}
-__global__ __launch_bounds__(256) void k_layout_words(LayoutArgs a) { layout_words_body(a, blockIdx.x); }
-__global__ __launch_bounds__(256) void k_layout_words_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(LayoutArgs) layout_words_body(a, blockIdx.x); }
-__global__ __launch_bounds__(256) void k_layout_bits(LayoutArgs a) { layout_bits_body(a, blockIdx.x); }
-__global__ __launch_bounds__(256) void k_layout_bits_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(LayoutArgs) layout_bits_body(a, blockIdx.x); }
-__global__ void k_copy_words(CopyArgs a) { copy_body(a, blockIdx.x, gridDim.x); }
-__global__ void k_copy_words_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(CopyArgs) copy_body(a, blockIdx.x, nblk); }
 
 // ---- the recorder ----
 static thread_local Recorder* g_recorder = nullptr;
@@ -2480,15 +2454,12 @@ Recorder* current_recorder() { return g_recorder; }
 
 void launch_ctrl(const CtrlArgs& a, hipStream_t s)
 {
-    if (record_op(OP_CTRL, 0, dim3(1), 1, a)) return;
-    hipLaunchKernelGGL(k_ctrl, dim3(1), dim3(1), 0, s, a);
+    issue(OP_CTRL, 0, k_ctrl, dim3(1), 1, a, s);
 }
 
 void launch_fill(int* ptr, int words, int value, hipStream_t s)
 {
-    FillArgs a{ptr, words, value};
-    if (record_op(OP_FILL, 0, dim3(1), 256, a)) return;
-    hipLaunchKernelGGL(k_fill, dim3(1), dim3(256), 0, s, a);
+    issue(OP_FILL, 0, k_fill, dim3(1), 256, FillArgs{ptr, words, value}, s);
 }
 
 __global__ __launch_bounds__(256) void k_copy_segments(CopySegsArgs a)
@@ -2512,10 +2483,8 @@ void launch_copy_segments(const CopySegsArgs& a, hipStream_t s)
 
 void launch_copy_words(const int* src, int* dst, int words, hipStream_t s)
 {
-    CopyArgs a{src, dst, words};
     const dim3 grid((unsigned)std::max(1, std::min(64, (words + 4095) / 4096)));   // (a fuzzy member's memberships: n x k words)
-    if (record_op(OP_COPY, 0, grid, 256, a)) return;
-    hipLaunchKernelGGL(k_copy_words, grid, dim3(256), 0, s, a);
+    issue(OP_COPY, 0, k_copy_words, grid, 256, CopyArgs{src, dst, words}, s);
 }
 
 // the device layouts of an uploaded matrix (recordable: nemgpu_solve_many leaves them to the group's run, one launch each
@@ -2525,18 +2494,18 @@ void launch_layout(const uint32_t* xf, int n, int wf, int W, int npad, int d, in
 {
     const LayoutArgs a{xf, perm, n, wf, W, npad, d, nw64, xw, xws, xt};
     const dim3 gw((npad + 255) / 256, ((W + 3) / 4) * 4), gb((nw64 * 64 + 255) / 256, W);
-    if (!record_op(OP_LAYOUT_WORDS, 0, gw, 256, a)) hipLaunchKernelGGL(k_layout_words, gw, dim3(256), 0, s, a);
-    if (!record_op(OP_LAYOUT_BITS, 0, gb, 256, a)) hipLaunchKernelGGL(k_layout_bits, gb, dim3(256), 0, s, a);
+    issue(OP_LAYOUT_WORDS, 0, k_layout_words, gw, 256, a, s);
+    issue(OP_LAYOUT_BITS, 0, k_layout_bits, gb, 256, a, s);
 }
 
 void launch_finish(const FinishArgs& a, hipStream_t s)
 {
     // tables only (mode 0) and the models whose dispersion is per class (sk_, skd): one block per class
     const bool separable = a.mode == 0 || a.disper == NEMGPU_DISP_K_ || a.disper == NEMGPU_DISP_KD;
-    const dim3 grid(separable ? a.K : 1);
-    if (record_op(OP_FINISH, separable ? 1 : 0, grid, 1024, a)) return;
-    hipLaunchKernelGGL(k_finish, grid, dim3(1024), 0, s, a);
+    issue(OP_FINISH, separable ? 1 : 0, k_finish, dim3(separable ? a.K : 1), 1024, a, s);
 }
+
+static int density_blocks(int npad, int K) { return ((npad / 256 + 7) / 8) * 8 * K; }
 
 void launch_density(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
                     int* zero_flags, int n_zero_flags, hipStream_t s)
@@ -2547,12 +2516,8 @@ void launch_density(const FinishArgs& t, const uint32_t* xw, int n, int npad, do
     a.uni = t.uni; a.nonuni = t.nonuni; a.pk = t.pk; a.logpk = t.logpk;
     a.pkfki = pkfki; a.logpkfki = logpkfki; a.zero_flags = zero_flags; a.n_zero_flags = n_zero_flags;
     a.stop = t.stop; a.use_ff = t.use_ff; a.perm = t.perm; a.ffq = t.ffq;
-    const dim3 grid(((npad / 256 + 7) / 8) * 8 * t.K);
-    if (record_op(OP_DENSITY, 0, grid, 256, a)) return;
-    hipLaunchKernelGGL(k_density, grid, dim3(256), 0, s, a);
+    issue(OP_DENSITY, 0, k_density, dim3(density_blocks(npad, t.K)), 256, a, s);
 }
-
-static int density_blocks(int npad, int K) { return ((npad / 256 + 7) / 8) * 8 * K; }
 
 // compute units of the current device (asked once per device)
 static int compute_units()
@@ -2599,9 +2564,13 @@ static size_t ff_row_bytes(const FusedDensityArgs& a)
 void launch_density_fused(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
                           int* zero_flags, int n_zero_flags, hipStream_t s)
 {
+    // (not recordable: in a lock-step batch the update runs once per class, k_finish_b, and the blocks of k_density_b load it)
+    if (current_recorder() != nullptr) {
+        fprintf(stderr, "launch_density_fused: not recordable\n");
+        abort();
+    }
     const FusedDensityArgs a = fused_density_args(t, xw, n, npad, pkfki, logpkfki, zero_flags, n_zero_flags);
-    const dim3 grid(((npad / 256 + 7) / 8) * 8 * t.K);
-    if (record_op(OP_DENSITY_FUSED, 0, grid, 256, a)) return;
+    const dim3 grid(density_blocks(npad, t.K));
     if (a.use_ff == FF_BATCHED) hipLaunchKernelGGL(k_density_fused, grid, dim3(256), ff_row_bytes(a), s, a);
     else hipLaunchKernelGGL(k_density_fused_word, grid, dim3(256), 0, s, a);
 }
@@ -2613,7 +2582,7 @@ void launch_density_start(const FinishArgs& t, const uint32_t* xw, int n, int np
     StartArgs st;
     st.prop0 = t.reset_prop; st.center0 = t.reset_center; st.disp0 = t.reset_disp;
     st.ctrl = t.reset_ctrl; st.ctrl_words = t.reset_ctrl_words; st.sweep_next = t.reset_sweep_next;
-    const dim3 grid(((npad / 256 + 7) / 8) * 8 * t.K);
+    const dim3 grid(density_blocks(npad, t.K));
     if (a.use_ff == FF_BATCHED) hipLaunchKernelGGL(k_density_start, grid, dim3(256), ff_row_bytes(a), s, a, st);
     else hipLaunchKernelGGL(k_density_start_word, grid, dim3(256), 0, s, a, st);
 }
@@ -2627,12 +2596,12 @@ void launch_density_verify(const FinishArgs& t, const uint32_t* xw, int n, int n
                            int* zero_flags, int n_zero_flags, const SweepArgs& sw, hipStream_t s)
 {
     const FusedDensityArgs a = fused_density_args(t, xw, n, npad, pkfki, logpkfki, zero_flags, n_zero_flags);
-    const int nd = ((npad / 256 + 7) / 8) * 8 * t.K;
+    const int nd = density_blocks(npad, t.K);
     const int ns = (sw.n_local + 255) / 256;
     const dim3 grid(nd + ns);
-#define NEM_DV(KT_) case KT_: hipLaunchKernelGGL((k_density_verify<KT_>), grid, dim3(256), ff_row_bytes(a), s, a, sw, nd); break;
-    switch (sw.K) { NEM_DV(1) NEM_DV(2) NEM_DV(3) NEM_DV(4) NEM_DV(5) NEM_DV(6) NEM_DV(7) NEM_DV(8) NEM_DV(9) NEM_DV(10) default: break; }
-#undef NEM_DV
+    dispatch_k<1, 10>(sw.K, [&](auto kt) {
+        hipLaunchKernelGGL((k_density_verify<decltype(kt)::value>), grid, dim3(256), ff_row_bytes(a), s, a, sw, nd);
+    });
 }
 
 // an NCEM relaxation round and M-step counts in one launch (k_sweep_counts); false: not for this shape (the caller
@@ -2645,13 +2614,10 @@ bool launch_sweep_counts(const SweepArgs& sw, int K, int D, int nw64, const uint
     const int nsweep = (sw.n_local + 255) / 256;
     const bool wide = D + 1 >= 1024;
     const dim3 grid(nsweep + (wide ? (D + 1 + 3) / 4 : D + 1));
-#define NEM_SC(KT_) case KT_:                                                                                        \
-        if (wide) hipLaunchKernelGGL((k_sweep_counts<KT_, 4>), grid, dim3(256), 0, s, sw, c, nsweep);                \
-        else hipLaunchKernelGGL((k_sweep_counts<KT_, 1>), grid, dim3(256), 0, s, sw, c, nsweep);                     \
-        break;
-    switch (K) { NEM_SC(2) NEM_SC(3) NEM_SC(4) NEM_SC(5) default: return false; }
-#undef NEM_SC
-    return true;
+    return dispatch_k<2, 5>(K, [&](auto kt) {
+        if (wide) hipLaunchKernelGGL((k_sweep_counts<decltype(kt)::value, 4>), grid, dim3(256), 0, s, sw, c, nsweep);
+        else hipLaunchKernelGGL((k_sweep_counts<decltype(kt)::value, 1>), grid, dim3(256), 0, s, sw, c, nsweep);
+    });
 }
 
 void launch_labels_post(int n_local, int lo, int K, int nw64, const uint8_t* lab_new, const uint8_t* lab_old,
@@ -2659,9 +2625,7 @@ void launch_labels_post(int n_local, int lo, int K, int nw64, const uint8_t* lab
 {
     LabelsPostArgs a{n_local, lo, K, nw64, lab_new, lab_old, mask, flags, stop, CtrlArgs{}};
     if (ctrl != nullptr) a.ca = *ctrl;
-    const dim3 grid(std::min((nw64 * 64 + 255) / 256, 128));
-    if (record_op(OP_LABELS_POST, 0, grid, 256, a)) return;
-    hipLaunchKernelGGL(k_labels_post, grid, dim3(256), 0, s, a);
+    issue(OP_LABELS_POST, 0, k_labels_post, dim3(std::min((nw64 * 64 + 255) / 256, 128)), 256, a, s);
 }
 
 void launch_mstep_counts(int K, int D, int nw64, const uint64_t* xt, const uint64_t* mask, int* stats,
@@ -2674,9 +2638,8 @@ void launch_mstep_counts(int K, int D, int nw64, const uint64_t* xt, const uint6
     const int extra = a.prev_ctrl.ctrl != nullptr ? 1 : 0;
     const bool wide = D + 1 >= 1024;
     const dim3 grid(wide ? (D + 1 + 3) / 4 + extra : D + 1 + extra);
-    if (record_op(OP_COUNTS, wide ? 4 : 1, grid, 256, a)) return;
-    if (wide) hipLaunchKernelGGL(k_mstep_counts<4>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_mstep_counts<1>, grid, dim3(256), 0, s, a);
+    if (wide) issue(OP_COUNTS, 4, k_mstep_counts<4>, grid, 256, a, s);
+    else issue(OP_COUNTS, 1, k_mstep_counts<1>, grid, 256, a, s);
 }
 
 void launch_mstep_fuzzy(int n, int npad, int K, int D, const uint32_t* xw, const uint64_t* xt, int nw64, const float* c,
@@ -2687,12 +2650,9 @@ void launch_mstep_fuzzy(int n, int npad, int K, int D, const uint32_t* xw, const
     const int ctpad = (n + kWin - 1) / kWin * kWin;
     FuzzyArgs a{n, npad, K, D, xw, xt, nw64, c, nbobs_k, in0, in1, inh_k, lastz, any1, center, iner, stop, ct, ctpad, chk, fault, inject};
     // one lane per chain at the chain's own speed: producer waves make the addends (see mstep_fuzzy_pc_body)
-    if (!record_op(OP_FUZZY_T, 0, dim3(ctpad / 256), 256, a))
-        hipLaunchKernelGGL(k_transpose_c, dim3(ctpad / 256), dim3(256), 0, s, a);
-    if (!record_op(OP_FUZZY_PC, 0, dim3(2 * DB + 2, K), 64 * kPcWaves, a))
-        hipLaunchKernelGGL(k_mstep_fuzzy_pc, dim3(2 * DB + 2, K), dim3(64 * kPcWaves), 0, s, a);
-    if (!record_op(OP_FUZZY_MED2, 0, dim3(DB, K), 64, a))
-        hipLaunchKernelGGL(k_mstep_fuzzy_med2, dim3(DB, K), dim3(64), 0, s, a);
+    issue(OP_FUZZY_T, 0, k_transpose_c, dim3(ctpad / 256), 256, a, s);
+    issue(OP_FUZZY_PC, 0, k_mstep_fuzzy_pc, dim3(2 * DB + 2, K), 64 * kPcWaves, a, s);
+    issue(OP_FUZZY_MED2, 0, k_mstep_fuzzy_med2, dim3(DB, K), 64, a, s);
 }
 
 void launch_conv_fuzzy(size_t m, const float* c, const float* cold, float thres, int* flags, const int* stop,
@@ -2700,18 +2660,13 @@ void launch_conv_fuzzy(size_t m, const float* c, const float* cold, float thres,
 {
     ConvFuzzyArgs a{m, c, cold, thres, flags, stop, CtrlArgs{}};
     if (ctrl != nullptr) a.ca = *ctrl;
-    const dim3 grid((unsigned)((m + 255) / 256));
-    if (record_op(OP_CONV_FUZZY, 0, grid, 256, a)) return;
-    hipLaunchKernelGGL(k_conv_fuzzy, grid, dim3(256), 0, s, a);
+    issue(OP_CONV_FUZZY, 0, k_conv_fuzzy, dim3((unsigned)((m + 255) / 256)), 256, a, s);
 }
 
 void launch_onehot(int n, int K, const uint8_t* lab, float* c, hipStream_t s)
 {
     const size_t m = (size_t)n * K;
-    OnehotArgs a{n, K, lab, c};
-    const dim3 grid((unsigned)((m + 255) / 256));
-    if (record_op(OP_ONEHOT, 0, grid, 256, a)) return;
-    hipLaunchKernelGGL(k_onehot, grid, dim3(256), 0, s, a);
+    issue(OP_ONEHOT, 0, k_onehot, dim3((unsigned)((m + 255) / 256)), 256, OnehotArgs{n, K, lab, c}, s);
 }
 
 void launch_criteria(int n, int K, int npad, const int* nei_ptr, const int* nei_idx, const float* nei_w, int use_nei,
@@ -2719,12 +2674,9 @@ void launch_criteria(int n, int K, int npad, const int* nei_ptr, const int* nei_
                      double* lfi, double* lzi, float* crit6, int hard, hipStream_t s)
 {
     CritArgs a{n, K, npad, nei_ptr, nei_idx, nei_w, use_nei, beta, c, pkfki, logpkfki, dik, gik, lfi, lzi, crit6, hard};
-    if (!record_op(OP_CRIT_TERMS, 0, dim3((n + 255) / 256), 256, a))
-        hipLaunchKernelGGL(k_crit_terms, dim3((n + 255) / 256), dim3(256), 0, s, a);
-    if (!record_op(OP_CRIT_REDUCE, 0, dim3(4), CH_T, a))
-        hipLaunchKernelGGL(k_crit_reduce, dim3(4), dim3(CH_T), 0, s, a);
-    if (!record_op(OP_CRIT_FINAL, 0, dim3(1), 1, a))
-        hipLaunchKernelGGL(k_crit_final, dim3(1), dim3(1), 0, s, a);
+    issue(OP_CRIT_TERMS, 0, k_crit_terms, dim3((n + 255) / 256), 256, a, s);
+    issue(OP_CRIT_REDUCE, 0, k_crit_reduce, dim3(4), CH_T, a, s);   // (a block per chain)
+    issue(OP_CRIT_FINAL, 0, k_crit_final, dim3(1), 1, a, s);
 }
 
 void launch_zipped(int kind, int variant, int B, const void* arr, int stride, const int* gx, unsigned max_gx, unsigned gy,
@@ -2732,28 +2684,14 @@ void launch_zipped(int kind, int variant, int B, const void* arr, int stride, co
 {
     const dim3 grid(max_gx, gy, (unsigned)B), blk(block);
     switch (kind) {
-    case OP_FINISH: hipLaunchKernelGGL(k_finish_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_DENSITY: hipLaunchKernelGGL(k_density_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_DENSITY_FUSED: hipLaunchKernelGGL(k_density_fused_b, grid, blk, 0, s, arr, stride, gx); break;
+#define NEM_OP_CASE(ID, KERNEL, BOUNDS, ARGS, BODY) case OP_##ID: hipLaunchKernelGGL(KERNEL##_b, grid, blk, 0, s, arr, stride, gx); break;
+    NEM_OPS(NEM_OP_CASE)
+#undef NEM_OP_CASE
     case OP_SWEEP: sweep_dispatch_batched(variant, grid, block, s, arr, stride, gx); break;
     case OP_COUNTS:
         if (variant == 4) hipLaunchKernelGGL(k_mstep_counts_b<4>, grid, blk, 0, s, arr, stride, gx);
         else hipLaunchKernelGGL(k_mstep_counts_b<1>, grid, blk, 0, s, arr, stride, gx);
         break;
-    case OP_LABELS_POST: hipLaunchKernelGGL(k_labels_post_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_CTRL: hipLaunchKernelGGL(k_ctrl_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_FUZZY_T: hipLaunchKernelGGL(k_transpose_c_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_FUZZY_PC: hipLaunchKernelGGL(k_mstep_fuzzy_pc_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_FUZZY_MED2: hipLaunchKernelGGL(k_mstep_fuzzy_med2_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_CONV_FUZZY: hipLaunchKernelGGL(k_conv_fuzzy_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_ONEHOT: hipLaunchKernelGGL(k_onehot_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_CRIT_TERMS: hipLaunchKernelGGL(k_crit_terms_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_CRIT_REDUCE: hipLaunchKernelGGL(k_crit_reduce_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_CRIT_FINAL: hipLaunchKernelGGL(k_crit_final_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_FILL: hipLaunchKernelGGL(k_fill_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_COPY: hipLaunchKernelGGL(k_copy_words_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_LAYOUT_WORDS: hipLaunchKernelGGL(k_layout_words_b, grid, blk, 0, s, arr, stride, gx); break;
-    case OP_LAYOUT_BITS: hipLaunchKernelGGL(k_layout_bits_b, grid, blk, 0, s, arr, stride, gx); break;
     default: break;
     }
 }

@@ -129,13 +129,15 @@ void launch_copy_segments(const CopySegsArgs& a, hipStream_t s);
 struct LayoutArgs { const uint32_t* xf; const int* perm; int n, wf, W, npad, d, nw64; uint32_t* xw; uint32_t* xws; uint64_t* xt; };
 
 // ---- batched launches: B independent problems per launch ---------------------------------------------------------
-// Every loop kernel has a twin that takes an ARRAY of argument blocks in device memory and runs problem blockIdx.z
-// of it.  A host thread that sets a Recorder gets the launches of the code it then runs RECORDED instead of issued
-// (same argument blocks, same grids); the batch driver (nem_engine.hip) records one sequence per problem, checks that
-// the sequences agree launch for launch, and issues each position once for all problems with launch_zipped.
-enum OpKind { OP_FINISH = 1, OP_DENSITY, OP_DENSITY_FUSED, OP_SWEEP, OP_COUNTS, OP_LABELS_POST, OP_CTRL,
-              OP_CONV_FUZZY, OP_ONEHOT, OP_CRIT_TERMS, OP_CRIT_REDUCE, OP_CRIT_FINAL, OP_FILL, OP_COPY, OP_FUZZY_T,
-              OP_FUZZY_PC, OP_FUZZY_MED2, OP_LAYOUT_WORDS, OP_LAYOUT_BITS };
+// A host thread that sets a Recorder gets the launches of the code it then runs RECORDED instead of issued (same
+// argument blocks, same grids); the batch driver (nem_engine.hip) records one sequence per problem, checks that the
+// sequences agree launch for launch (same_launch), and issues each position once for all problems with launch_zipped:
+// through the kernel's batched twin k_X_b, which takes an ARRAY of argument blocks in device memory and runs problem
+// blockIdx.z of it.  What is recordable is ONE list, NEM_OPS in nem_kernels.hip: an entry there makes the kernel, its
+// twin, the op's kind and its case in launch_zipped; the launch wrapper hands the kind and the kernel to issue().
+// The two template kernels (the sweep round, nem_sweep.hip; the M-step counts) have hand-written pairs and the first two
+// kinds; the list's kinds follow them.
+enum OpKind { OP_SWEEP = 1, OP_COUNTS, OP_LISTED };
 constexpr int kOpArgBytes = 512;
 struct OpRecord {
     int kind, variant;             // variant: template instance / block size, part of what must agree across problems
@@ -143,6 +145,11 @@ struct OpRecord {
     int nbytes;
     alignas(16) unsigned char args[kOpArgBytes];
 };
+// may the two launches go out as one?  (Everything but the argument blocks and the grid widths, which are per problem.)
+inline bool same_launch(const OpRecord& a, const OpRecord& b)
+{
+    return a.kind == b.kind && a.variant == b.variant && a.block == b.block && a.gy == b.gy && a.nbytes == b.nbytes;
+}
 struct Recorder { std::vector<OpRecord> ops; };
 void set_recorder(Recorder* r);    // thread-local; nullptr: launches are issued
 Recorder* current_recorder();
@@ -182,7 +189,7 @@ struct FinishArgs {
 void launch_finish(const FinishArgs& a, hipStream_t s);
 void launch_density(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
                     int* zero_flags, int n_zero_flags, hipStream_t s);
-// NCEM, sk_/skd, D <= kFusedMaxD: parameter update from t.stats folded into the density kernel (no k_finish)
+// NCEM, sk_/skd, D <= kFusedMaxD: parameter update from t.stats folded into the density kernel (no k_finish); not recordable
 constexpr int kFusedMaxD = 1024;   // beyond this the per-block parameter derivation costs more than a k_finish launch
 // FinishArgs::use_ff.  FF_BATCHED: the fused density kernels (33 .. kFusedMaxD organisms, a grid the device holds at
 // once) let every lane walk its own row and cross binades in batches (chain_ff_batched); every other kernel and shape
@@ -220,7 +227,6 @@ bool launch_map_margin_debug(const double* pkf, const float* ctx, int n, int K, 
 bool launch_halfsum_debug(const float* x, int n, int waves, float* out, hipStream_t s, long long* stamps = nullptr);   // n <= 8192, waves 1 | 16; out[2], stamps[6] when timing
 void launch_calib_read(const uint32_t* buf, size_t words, uint32_t* sink, hipStream_t s);
 void launch_onehot(int n, int K, const uint8_t* lab, float* c, hipStream_t s);
-constexpr int kCritReduceThreads = 1024;   // block size of k_crit_reduce (CH_T in nem_kernels.hip)
 void launch_criteria(int n, int K, int npad, const int* nei_ptr, const int* nei_idx, const float* nei_w, int use_nei,
                      float beta, const float* c, const double* pkfki, const float* logpkfki, float* dik, float* gik,
                      double* lfi, double* lzi, float* crit6, int hard, hipStream_t s);   // hard: one-hot rows (NCEM)
@@ -246,7 +252,25 @@ inline bool record_op(int kind, int variant, dim3 grid, unsigned block, const Ar
     memcpy(o.args, &a, sizeof(Args));
     return true;
 }
+// ... and the whole of most: the launch of a recordable op, stored or issued (no dynamic shared memory: a record has none)
+template <typename Args>
+inline void issue(int kind, int variant, void (*kernel)(Args), dim3 grid, unsigned block, const Args& a, hipStream_t s)
+{
+    if (record_op(kind, variant, grid, block, a)) return;
+    hipLaunchKernelGGL(kernel, grid, dim3(block), 0, s, a);
+}
 // the batched twin of a recorded k_sweep position (nem_sweep.hip)
 void sweep_dispatch_batched(int variant, dim3 grid, unsigned bdim, hipStream_t s, const void* arr, int stride, const int* gx);
+
+// A run-time K as a compile-time constant: f(std::integral_constant<int, K>{}) for LO <= K <= HI; false: no instance
+template <int LO, int HI, typename F>
+inline bool dispatch_k(int K, F&& f)
+{
+    if constexpr (LO > HI) return false;
+    else {
+        if (K == LO) { f(std::integral_constant<int, LO>{}); return true; }
+        return dispatch_k<LO + 1, HI>(K, f);
+    }
+}
 
 }  // namespace nemk

@@ -24,23 +24,20 @@ static void sweep_dispatch(int variant, dim3 grid, unsigned bdim, hipStream_t s,
 {
     const int kt = variant & 15; const bool ncem = (variant & 16) != 0, big = (variant & 32) != 0, libc = (variant & 64) != 0;
     dim3 block(bdim);                                    // (256; the large-shard instances: SweepArgs::spb rounded up to whole waves, at most 1024)
-#define NEM_SW2(KT_, NC_, BS_, LC_)                                                                                \
-    do {                                                                                                           \
-        if (BATCHED) hipLaunchKernelGGL((k_sweep_b<KT_, NC_, BS_, LC_>), grid, block, 0, s, arr, stride, gx);     \
-        else hipLaunchKernelGGL((k_sweep<KT_, NC_, BS_, LC_>), grid, block, 0, s, *a);                             \
-    } while (0)
-#define NEM_SW(KT_)                                                                                                \
-    case KT_:                                                                                                      \
-        if (big) { if (!ncem) NEM_SW2(KT_, false, 1024, false); else if (libc) NEM_SW2(KT_, true, 1024, true); else NEM_SW2(KT_, true, 1024, false); } \
-        else { if (!ncem) NEM_SW2(KT_, false, 256, false); else if (libc) NEM_SW2(KT_, true, 256, true); else NEM_SW2(KT_, true, 256, false); }       \
-        break;
-    switch (kt) {
-        NEM_SW(1) NEM_SW(2) NEM_SW(3) NEM_SW(4) NEM_SW(5) NEM_SW(6) NEM_SW(7) NEM_SW(8) NEM_SW(9) NEM_SW(10)
-    default:
-        if (!ncem) NEM_SW2(0, false, 256, false); else if (libc) NEM_SW2(0, true, 256, true); else NEM_SW2(0, true, 256, false);
-    }
-#undef NEM_SW
-#undef NEM_SW2
+    // the instance <KT, NCEM, BS, LIBC>, each a std::integral_constant
+    auto launch = [&](auto KT, auto NC, auto BS, auto LC) {
+        if (BATCHED) hipLaunchKernelGGL((k_sweep_b<decltype(KT)::value, decltype(NC)::value, decltype(BS)::value, decltype(LC)::value>), grid, block, 0, s, arr, stride, gx);
+        else hipLaunchKernelGGL((k_sweep<decltype(KT)::value, decltype(NC)::value, decltype(BS)::value, decltype(LC)::value>), grid, block, 0, s, *a);
+    };
+    // fuzzy NEM, NCEM, NCEM with the reference's tie stream
+    auto modes = [&](auto KT, auto BS) {
+        if (!ncem) launch(KT, std::false_type{}, BS, std::false_type{});
+        else if (libc) launch(KT, std::true_type{}, BS, std::true_type{});
+        else launch(KT, std::true_type{}, BS, std::false_type{});
+    };
+    const std::integral_constant<int, 256> bs256; const std::integral_constant<int, 1024> bs1024;
+    // (the generic K: a 256-site instance only, see sweep_block_sites)
+    if (!dispatch_k<1, 10>(kt, [&](auto KT) { if (big) modes(KT, bs1024); else modes(KT, bs256); })) modes(std::integral_constant<int, 0>{}, bs256);
 }
 
 // the launch geometry of a round: block size (= sites per block) for n_local sites
@@ -78,9 +75,9 @@ void launch_sweep(const SweepArgs& a0, bool ncem, hipStream_t s)
             fprintf(stderr, "launch_sweep: no counting round for this shape\n");
             abort();
         }
-#define NEM_SWC(KT_) case KT_: hipLaunchKernelGGL((k_sweep<KT_, true, 256, false, true>), grid, dim3(256), 0, s, a); break;
-        switch (a.K) { NEM_SWC(1) NEM_SWC(2) NEM_SWC(3) NEM_SWC(4) NEM_SWC(5) NEM_SWC(6) NEM_SWC(7) NEM_SWC(8) NEM_SWC(9) NEM_SWC(10) default: break; }
-#undef NEM_SWC
+        dispatch_k<1, 10>(a.K, [&](auto KT) {
+            hipLaunchKernelGGL((k_sweep<decltype(KT)::value, true, 256, false, true>), grid, dim3(256), 0, s, a);
+        });
         return;
     }
     if (record_op(OP_SWEEP, variant, grid, (unsigned)bs, a)) return;

@@ -16,8 +16,8 @@ TOL = 1e-6                        # the project's bar (BASELINE.json), TOL of te
 SOLO_KEYS = ("c", "center", "disp", "prop", "nbobs_k", "crit")
 
 # ---- the library's arithmetic, restated ---------------------------------------------------------------------------
-K_TEMPLATE_MAX = 10               # nem_sweep.hip:20   K >= 1 && K <= 10 ? K : 0 (the generic instance)
-BIG_SITES = 65536                 # nem_sweep.hip:50   big = n_local >= 65536 && !generic
+K_TEMPLATE_MAX = 10               # nem_sweep.hip, sweep_variant   K >= 1 && K <= 10 ? K : 0 (the generic instance)
+BIG_SITES = 65536                 # nem_sweep.hip, sweep_block_sites   big = n_local >= 65536 && !generic
 FUSED_MAX_D = 1024                # nem_kernels.hpp    kFusedMaxD
 FF_MIN_D = 256                    # nem_engine.hip     use_ff(): ff_mode < 0 ? d >= 256
 WIDE_COUNTS_D = 1023              # nem_kernels.hip    launch_mstep_counts: wide = D + 1 >= 1024
@@ -25,12 +25,12 @@ SWEEP_MODES = ("nem", "ncem", "ncem_libc")
 
 
 def sweep_template_k(k):
-    """nem_sweep.hip:20, sweep_variant: the K a round's kernel is compiled for, 0 = the generic instance"""
+    """nem_sweep.hip, sweep_variant: the K a round's kernel is compiled for, 0 = the generic instance"""
     return k if 1 <= k <= K_TEMPLATE_MAX else 0
 
 
 def sweep_block_sites(n, k):
-    """nem_sweep.hip:47-59, sweep_block_sites: (big, sites per block = threads per block)"""
+    """nem_sweep.hip, sweep_block_sites: (big, sites per block = threads per block)"""
     generic = not (1 <= k <= K_TEMPLATE_MAX)
     big = n >= BIG_SITES and not generic
     bs = 256
@@ -42,7 +42,7 @@ def sweep_block_sites(n, k):
 
 
 def sweep_mode(cfg):
-    """nem_sweep.hip:20: ncem, and libc only with ncem (the fuzzy round draws nothing)"""
+    """nem_sweep.hip, sweep_variant: ncem, and libc only with ncem (the fuzzy round draws nothing)"""
     if cfg["algo"] != "ncem":
         return "nem"
     return "ncem_libc" if cfg["tie"] == "libc" else "ncem"
@@ -50,13 +50,13 @@ def sweep_mode(cfg):
 
 def sweep_instance(n, k, cfg):
     """(template K, mode, block class) of the k_sweep_b instance a member's rounds run: block class 1024 is the
-    __launch_bounds__(1024) instance `big` selects (nem_sweep.hip:34), launched with sweep_block_sites' threads"""
+    __launch_bounds__(1024) instance `big` selects (nem_sweep.hip, sweep_dispatch), launched with sweep_block_sites' threads"""
     big, _ = sweep_block_sites(n, k)
     return sweep_template_k(k), sweep_mode(cfg), 1024 if big else 256
 
 
 def all_sweep_instances():
-    """the instantiations of k_sweep_b that sweep_dispatch launches (nem_sweep.hip:33-41): K 0..10 x three modes at 256,
+    """the instantiations of k_sweep_b that sweep_dispatch launches (nem_sweep.hip): K 0..10 x three modes at 256,
     K 1..10 x three at 1024 -- 63, the generic instance has no large-block form"""
     out = {(kt, m, 256) for kt in range(0, K_TEMPLATE_MAX + 1) for m in SWEEP_MODES}
     out |= {(kt, m, 1024) for kt in range(1, K_TEMPLATE_MAX + 1) for m in SWEEP_MODES}

@@ -2,9 +2,9 @@
 quietly shrink them.  (a) from the problems and the oracle's results; (b) to (d) from the members' sizes and
 configurations with the arithmetic the library uses, restated in tests/lockstep_members.py:
 
-  * nem_sweep.hip:20 (sweep_variant): template K = K when 1 <= K <= 10, else the generic instance; the mode is fuzzy,
+  * nem_sweep.hip, sweep_variant: template K = K when 1 <= K <= 10, else the generic instance; the mode is fuzzy,
     NCEM, or NCEM under the reference's tie stream;
-  * nem_sweep.hip:47-59 (sweep_block_sites): big = n >= 65 536 and K <= 10 selects the __launch_bounds__(1024)
+  * nem_sweep.hip, sweep_block_sites: big = n >= 65 536 and K <= 10 selects the __launch_bounds__(1024)
     instances (the generic one has none), launched with ceil(n / 256 blocks) sites per block rounded up to whole waves, 256 to 1024;
   * nem_engine.hip, nemgpu_engine::fused_update(): d <= kFusedMaxD = 1024 and dispersion sk_ or skd;
     nemgpu_engine::use_ff(): d >= 256;
@@ -12,10 +12,11 @@ configurations with the arithmetic the library uses, restated in tests/lockstep_
     launch_mstep_counts: four organism rows per block when d + 1 >= 1024.
 
 One thing the arithmetic says about (d) that its issue did not expect: enqueue_iteration (nem_engine.hip) takes the
-fused density launch only when nothing records (current_recorder() == nullptr), so a lock-step step never holds
-OP_DENSITY_FUSED: every member of a step updates in k_finish_b and takes k_density_b, and the three classes of
-fused_update() x use_ff() differ in what the members' SOLO runs take, which the lock-step results must equal bit for
-bit.  Within the step the classes still differ by fast-forward, by k_finish_b's variant and by the counts kernel."""
+fused density launch only when nothing records (current_recorder() == nullptr), so a lock-step step never holds one
+(launch_density_fused refuses a recorder): every member of a step updates in k_finish_b and takes k_density_b, and the
+three classes of fused_update() x use_ff() differ in what the members' SOLO runs take, which the lock-step results must
+equal bit for bit.  Within the step the classes still differ by fast-forward, by k_finish_b's variant and by the counts
+kernel."""
 import numpy as np
 
 from tests import lockstep_members as M
@@ -73,7 +74,7 @@ def test_every_sweep_instance_is_reached():
         assert all(s["d"] == 12 and s["cfg"]["it_max"] == 2 for s in specs)
         reached |= {M.sweep_instance(s["n"], s["k"], s["cfg"]) for s in specs}
     # K 0..10 x three modes x two block classes would be 66; the generic instance has no large-block form (big needs
-    # K <= 10, nem_sweep.hip:50, and sweep_dispatch's default branch launches 256-site blocks only), which leaves 63
+    # K <= 10, nem_sweep.hip, sweep_block_sites, and sweep_dispatch's default branch launches 256-site blocks only), which leaves 63
     assert len(M.all_sweep_instances()) == 63
     assert M.all_sweep_instances() == reached
 

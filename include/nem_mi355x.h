@@ -863,6 +863,45 @@ int nemgpu_random_start_counters(const nemgpu_engine* e, int out[4]);
 /* Re-target the engine to another HIP stream (e.g. the capturing stream of a torch.cuda.graph). */
 int nemgpu_set_stream(nemgpu_engine* e, void* hip_stream);
 
+/* The organisms' GFF files and the families table (PPanGGOLiN("file", ...), ppanggolin.py:180-315; csrc/nem_gff.hpp;
+   loader.py's _batch_host and families_table_host state every array).
+   _create: the families table's text (HOST, bytes < 2 GiB): tokens split at ASCII whitespace (str.isspace() below 0x80),
+     the first of a line the family, every later one a gene; a gene named twice keeps the later line's family.  The
+     distinct family names are numbered by their first line (*n_families of them; _family_spans: their (offset, length)
+     in the text, HOST int32 [n_families][2]).  hash_bits: 0 for the full 64-bit string hash, else how many of its bits
+     to keep (every table compares the bytes in full; tests make the probes collide with it).
+   _batch: the bytes of n_files whole files joined by one '\n' (HOST, < 2 GiB), file f at [file_start[f], file_end[f]).
+     The CDS lines before each file's ##FASTA become genes, ordered by (file, contig by first appearance, START, line);
+     *n_genes, *n_contigs; *error = the least ((file << 40) | (line << 8) | code) of a refused line (line 0-based within
+     its file; codes: 1 fewer than 3 fields, 2 a CDS with fewer than 9, 3 an attribute that is not key=value, 4 no ID,
+     5 an ID the table does not have and infer_singletons == 0, 6 START, 7 END not an int32 in ASCII digits, 8 an ID
+     twice in one file), all ones if none.  Nothing of a batch goes through the host between its upload and its result
+     but the counts that size its arrays.
+   _fetch: the last batch's genes (HOST, any may be NULL): file, start, end, fam (the family's number, -1 for an ID
+     the table does not have), contig (dense over the batch) int32 [n_genes]; span_off, span_len int32 [5][n_genes]: ID,
+     NAME (else GENE), PRODUCT, strand, contig name, stripped (an absent one: the empty span at the ID);
+     fasta_off int32 [n_files]: where the file's ##FASTA line starts, its end if it has none.
+   _number: after all the batches, the families' ids and the repeated ones.  name[g], org[g] (HOST): every gene's family
+     name (a number in 0 .. n_names - 1: the table's families, then the inferred singletons' names as the caller numbered
+     them) and organism, in the walk's order.  genes[g] = the ids dense by first occurrence in the walk, order[id] =
+     the name of id (*n_used of them; room for n_names), repeated[id] = 1 where the family occurs more than
+     lim_occurence > 0 times in ONE organism (room for max(n_names, 1)).
+   _stage_ms: the last batch's device time by stage, float [6]: upload, lines, parse, contigs and IDs, sort, gather.
+   _info: the byte kernels' tile in bytes and the contig sizes at which the sort changes its path (*n_thresholds of
+     them, at most 8 written): one radix sort serves every size, so there are none.  Host only; any may be NULL. */
+typedef struct nemgpu_gff nemgpu_gff;
+int nemgpu_gff_info(int* tile_bytes, int* n_thresholds, int* thresholds);
+int nemgpu_gff_create(nemgpu_gff** out, int device, const char* families_text, long long bytes, int hash_bits, int* n_families);
+int nemgpu_gff_family_spans(const nemgpu_gff* h, int32_t* spans);
+int nemgpu_gff_batch(nemgpu_gff* h, const char* text, long long bytes, const int32_t* file_start, const int32_t* file_end, int n_files,
+                     int infer_singletons, int* n_genes, int* n_contigs, unsigned long long* error);
+int nemgpu_gff_fetch(const nemgpu_gff* h, int32_t* file, int32_t* start, int32_t* end, int32_t* span_off, int32_t* span_len, int32_t* fam,
+                     int32_t* contig, int32_t* fasta_off);
+int nemgpu_gff_number(nemgpu_gff* h, const int32_t* name, const int32_t* org, int g, int n_names, int n_orgs, int lim_occurence, int32_t* genes,
+                      int32_t* order, uint8_t* repeated, int* n_used);
+int nemgpu_gff_stage_ms(const nemgpu_gff* h, float* ms);
+void nemgpu_gff_destroy(nemgpu_gff* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -513,6 +513,23 @@ class Master:
         m.repeated_by_organism = {org: frozenset(repeated) for org in o["organisms"]}     # (family_table: a node keeps the genes it got)
         return m
 
+    @classmethod
+    def from_files(cls, organisms_file, families_file, lim_occurence=0, infer_singletons=False, directed=False, device=0, **load_options):
+        """PPanGGOLiN("file", organisms_file, families_tsv, lim_occurence, infer_singletons, directed): the GFFs and the
+        families table loaded on the device (loader.load_files), then Master.from_orders of everything with the union of
+        the repeated families -- the reference too loads every organism before it builds the graph.  Carries the names as
+        a from_annotations master does; .loaded is the loader's result (orders, spans, annotations())."""
+        from .loader import load_files
+        ld = load_files(organisms_file, families_file, lim_occurence, infer_singletons, device=device, **load_options)
+        o = ld.orders
+        m = cls.from_orders(o["genes"], o["contig_ptr"], o["contig_org"], o["contig_circular"], o["d"], repeated=o["repeated"],
+                            directed=directed, device=device)
+        m.names, m.organism_names = [o["families"][i] for i in m.order], list(o["organisms"])
+        m.id_names = list(o["families"])
+        m.repeated_by_organism = {org: frozenset(ld.families_repeted) for org in o["organisms"]}
+        m.loaded = ld
+        return m
+
     def add_orders(self, genes, contig_ptr, contig_org, contig_circular, d_new, repeated=None, f=None):
         """A NEW master = this one + the gene orders of d_new new organisms (nemgpu_master_append_orders;
         master_arrays_append_orders states what it computes): contig_org holds their absolute columns d .. d + d_new - 1,

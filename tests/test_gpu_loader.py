@@ -42,6 +42,8 @@ def test_recorded_errors(gpu_lib, path):
 
 
 def test_info(gpu_lib):
+    """The thresholds list is empty (one radix sort for every contig size), so its line asserts nothing: the sizes at
+    which the sort and the scans do change their path are run by tests/test_gpu_loader_shapes.py."""
     info = loader.gff_info()
     assert info["tile"] >= 64 and info["tile"] % 16 == 0
     assert info["sort_thresholds"] == sorted(info["sort_thresholds"]) and all(t > 1 for t in info["sort_thresholds"])
@@ -59,7 +61,8 @@ def sized(lines, size):
 def shapes(tmp_path_factory):
     """One set around the kernels' tile and the sort's sizes, with its statement: files of tile - 1, 0, tile and
     tile + 1 bytes; a line longer than a tile after a line that ends exactly at a tile's edge; contigs of 1, 63, 64, 65
-    genes (and of every sort threshold and its neighbours), their starts shuffled with ties; 1 000 contigs of one gene."""
+    genes (and of every sort threshold and its neighbours), their starts shuffled with ties; 1 000 contigs of one gene.
+    The thresholds list is empty; rocPRIM's switches by total gene count are run by tests/test_gpu_loader_shapes.py."""
     info = loader.gff_info()
     tile = info["tile"]
     genes, gffs = [], []

@@ -2239,6 +2239,45 @@ static void result_unpack(const nemgpu_engine* e, const char* st, size_t b_part,
     if (nbobs_k) memcpy(nbobs_k, par + sizeof(float) * e->par_o_nb, sizeof(float) * k);
 }
 
+// What a run of zero iterations still owes before its criteria, nem_alg.c:1845-1851.  (nemgpu_run reads a fuzzy M-step's
+// fault flag between these calls: another sequence, stated there.)
+int finish_unstepped(nemgpu_engine* e)
+{
+    int r;
+    if ((r = do_mstep(e)) || (r = do_tables(e))) return r;
+    return do_density(e);
+}
+
+// The six criteria of every member of a lock-step group (all on E[0]'s stream) into crit[m]: the members' criteria
+// launches zipped, behind each member's its six words to the group's staging area, ONE copy to the host, ONE wait -- a
+// copy per member into pageable memory cost ~20 us each (16 problems: 0.3 ms of a 2 ms batch), and is what remains
+// where the group has no staging area of that size.  with_member(m) is recorded behind member m's criteria in the same
+// pass; behind_pass() enqueues, behind the pass, what the same wait is to cover.
+int criteria_many(std::vector<nemgpu_engine*>& E, float (*crit)[6], const std::function<void(int)>& with_member = nullptr,
+                  const std::function<int()>& behind_pass = nullptr)
+{
+    int r;
+    const int B = (int)E.size();
+    nemgpu_engine* lead = E[0];
+    std::vector<Recorder> recs((size_t)B);
+    std::vector<int> all((size_t)B);
+    for (int m = 0; m < B; m++) all[m] = m;
+    nemgpu_engine::ZipContext* z = zip_context(lead);
+    const bool staged = z != nullptr && z->zip_flags_dev != nullptr && z->zip_flags_host != nullptr && z->zip_flags_cap >= (size_t)8 * B;
+    if ((r = lockstep(E, all, recs, [&](int m) {
+            const int rr = criteria_enqueue(E[m], -1);
+            if (rr == NEMGPU_OK && staged) launch_copy_words(reinterpret_cast<const int*>(E[m]->crit6_dev), z->zip_flags_dev + (size_t)8 * m, 6, lead->stream);
+            if (rr == NEMGPU_OK && with_member) with_member(m);
+            return rr;
+        }, false))) return r;
+    if (behind_pass && (r = behind_pass())) return r;
+    if (staged) HIPCHK(hipMemcpyAsync(z->zip_flags_host, z->zip_flags_dev, (size_t)8 * B * sizeof(int), hipMemcpyDeviceToHost, lead->stream));
+    else for (int m = 0; m < B; m++) HIPCHK(hipMemcpyAsync(crit[m], E[m]->crit6_dev, 6 * sizeof(float), hipMemcpyDeviceToHost, lead->stream));
+    HIPCHK(hipStreamSynchronize(lead->stream));
+    if (staged) for (int m = 0; m < B; m++) memcpy(crit[m], z->zip_flags_host + (size_t)8 * m, 6 * sizeof(float));
+    return NEMGPU_OK;
+}
+
 int run_many(std::vector<nemgpu_engine*>& E, nemgpu_result* results, GroupFetch* gf = nullptr)
 {
     int r;
@@ -2294,53 +2333,32 @@ int run_many(std::vector<nemgpu_engine*>& E, nemgpu_result* results, GroupFetch*
     for (int i = 0; i < B; i++) pending_layout(E[i]);             // (it_max 0: no step has carried them)
     lap(2);
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    for (int i = 0; i < B && r == NEMGPU_OK; i++) {
-        if (E[i]->iters == 0) {                                    // nem_alg.c:1845-1851
-            if ((r = do_mstep(E[i])) || (r = do_tables(E[i])) || (r = do_density(E[i]))) break;
-        }
-    }
+    for (int i = 0; i < B && r == NEMGPU_OK; i++)
+        if (E[i]->iters == 0) r = finish_unstepped(E[i]);
     lap(3);
     if (r == NEMGPU_OK && results != nullptr) {
-        std::vector<Recorder> recs((size_t)B);
-        std::vector<int> all((size_t)B);
-        for (int i = 0; i < B; i++) all[i] = i;
-        // every member's six criteria go to the batch's staging area (zipped copies behind the zipped criteria launches)
-        // and reach the host in ONE copy: a copy per member into the caller's pageable result blocks cost ~20 us each
-        // (16 problems: 0.3 ms of a 2 ms batch)
-        nemgpu_engine::ZipContext* z = zip_context(lead);
-        const bool staged = z != nullptr && z->zip_flags_dev != nullptr && z->zip_flags_host != nullptr && z->zip_flags_cap >= (size_t)8 * B;
-        r = lockstep(E, all, recs, [&](int m) {
-            const int rr = criteria_enqueue(E[m], -1);
-            if (rr == NEMGPU_OK && staged) launch_copy_words(reinterpret_cast<const int*>(E[m]->crit6_dev), z->zip_flags_dev + (size_t)8 * m, 6, lead->stream);
-            if (rr == NEMGPU_OK && gf != nullptr) {
-                nemgpu_engine* e = E[m];
-                char* dst = gf->dev + gf->stride * (size_t)m;
-                const size_t b_part = result_part_bytes(e);
-                const void* part = e->ncem() ? (const void*)(e->lab[e->cur] + e->lo) : (const void*)(e->cbuf[e->cur] + (size_t)e->lo * e->k);
-                launch_copy_words(reinterpret_cast<const int*>(part), reinterpret_cast<int*>(dst), (int)(b_part / 4), lead->stream);
-                launch_copy_words(reinterpret_cast<const int*>(e->prop), reinterpret_cast<int*>(dst + b_part), (int)e->par_words, lead->stream);
-            }
-            return rr;
-        }, false);
-        if (r == NEMGPU_OK && gf != nullptr) {
-            if (hipMemcpyAsync(gf->host, gf->dev, gf->stride * (size_t)B, hipMemcpyDeviceToHost, lead->stream) != hipSuccess) {
-                set_error("results copy failed"); r = NEMGPU_E_DEVICE;
-            } else gf->filled = true;                              // (once the wait below is over)
-        }
-        if (r == NEMGPU_OK && staged &&
-            hipMemcpyAsync(z->zip_flags_host, z->zip_flags_dev, (size_t)8 * B * sizeof(int), hipMemcpyDeviceToHost, lead->stream) != hipSuccess) {
-            set_error("criteria copy failed"); r = NEMGPU_E_DEVICE;
-        }
+        // with the criteria, in the same pass and under the same wait: every member's results to the group's block
+        std::vector<float> crits((size_t)B * 6);
+        float (*crit)[6] = reinterpret_cast<float (*)[6]>(crits.data());
+        r = criteria_many(E, crit, [&](int m) {
+            if (gf == nullptr) return;
+            nemgpu_engine* e = E[m];
+            char* dst = gf->dev + gf->stride * (size_t)m;
+            const size_t b_part = result_part_bytes(e);
+            const void* part = e->ncem() ? (const void*)(e->lab[e->cur] + e->lo) : (const void*)(e->cbuf[e->cur] + (size_t)e->lo * e->k);
+            launch_copy_words(reinterpret_cast<const int*>(part), reinterpret_cast<int*>(dst), (int)(b_part / 4), lead->stream);
+            launch_copy_words(reinterpret_cast<const int*>(e->prop), reinterpret_cast<int*>(dst + b_part), (int)e->par_words, lead->stream);
+        }, [&]() -> int {
+            if (gf == nullptr) return NEMGPU_OK;
+            HIPCHK(hipMemcpyAsync(gf->host, gf->dev, gf->stride * (size_t)B, hipMemcpyDeviceToHost, lead->stream));
+            gf->filled = true;                                     // (once criteria_many's wait is over)
+            return NEMGPU_OK;
+        });
         for (int i = 0; i < B && r == NEMGPU_OK; i++) {
             fill_result(E[i], &results[i]);
             results[i].loop_seconds = secs;
-            if (!staged && hipMemcpyAsync(results[i].crit, E[i]->crit6_dev, 6 * sizeof(float), hipMemcpyDeviceToHost, lead->stream) != hipSuccess) {
-                set_error("criteria copy failed"); r = NEMGPU_E_DEVICE;
-            }
+            memcpy(results[i].crit, crit[i], sizeof crit[i]);
         }
-        if (r == NEMGPU_OK && hipStreamSynchronize(lead->stream) != hipSuccess) { set_error("synchronisation failed"); r = NEMGPU_E_DEVICE; }
-        if (r == NEMGPU_OK && staged)
-            for (int i = 0; i < B; i++) memcpy(results[i].crit, z->zip_flags_host + (size_t)8 * i, 6 * sizeof(float));
     }
     lap(4);
     restore();
@@ -3307,13 +3325,6 @@ int nemgpu_run_many(nemgpu_engine** engines, int count, nemgpu_result* results)
     return run_many(E, results);
 }
 
-// INIT_RANDOM: RandNemAlgo (nem_alg.c:1574-1742).  InitPara's whole-sample dispersion (:1200-1281) is one M-step
-// with every family in class 0; every start draws its centres from the data (MakeRandomPara, :1381-1473), runs the
-// INIT_PARAM_FILE pipeline on them and is ranked by criterion M (DEFAULT_CRIT, nem_typ.h:80); the best partition is
-// restored and EstimPara run on it (:1703-1713).
-constexpr int kStartsNotInLockStep = -7001;   // run_random_lockstep, logged: a start drew behind its initial sweeps -- nothing was handed to the writer, the caller runs the starts one after the other
-static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu_result* res, int* best_start, nemgpu_log_fn fn = nullptr, void* user = nullptr);
-
 // Many whole problems, from host arrays to host arrays, in one call: `workers` threads of the library build the
 // engines (bit packing, uploads out of pinned blocks -- nothing waits for the device), the calling thread runs every
 // `group` of them in lock step as soon as it is complete (nemgpu_run_many), the workers fetch the results and recycle
@@ -4199,185 +4210,6 @@ int nemgpu_solve_many_devices(nemgpu_problem* P, int count, const nemgpu_config*
     return rc;
 }
 
-static int run_random_impl(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu_result* res, int* best_start,
-                           nemgpu_log_fn fn, void* user);
-
-int nemgpu_run_random(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu_result* res, int* best_start)
-{
-    return run_random_impl(e, n_starts, seed, res, best_start, nullptr, nullptr);
-}
-
-int nemgpu_run_random_logged(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu_result* res, int* best_start,
-                             nemgpu_log_fn fn, void* user)
-{
-    if (!fn) return NEMGPU_E_FUNCARG;
-    return run_random_impl(e, n_starts, seed, res, best_start, fn, user);
-}
-
-// fn != nullptr: the starts one after the other, one logged step per host round trip (nemgpu_iterate_logged's form)
-static int run_random_impl(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu_result* res, int* best_start,
-                           nemgpu_log_fn fn, void* user)
-{
-    if (!e || n_starts <= 0) return NEMGPU_E_FUNCARG;
-    if (e->lo != 0 || e->hi != e->n_total) { set_error("random starts need the whole problem on one engine"); return NEMGPU_E_FUNCARG; }
-    if (!e->have_matrix || e->host_bits_words == 0) { set_error("the matrix must be set first"); return NEMGPU_E_FUNCARG; }
-    HIPCHK(hipSetDevice(e->device));
-    { const int fr = flush_reset(e); if (fr) return fr; }
-    int voided = 0;                                                // starts of a logged lock-step round that was thrown away whole
-    {
-        // the starts are independent EM runs on ONE matrix: by default they run in lock step, every launch serving all
-        // of them (NEM_MI355X_BATCH_STARTS=0: one after the other on this engine)
-        const char* g = getenv("NEM_MI355X_BATCH_STARTS");
-        const bool lock_ok = n_starts > 1 && !(g && g[0] == '0') && !crit_test(e);
-        if (!fn && lock_ok) return run_random_lockstep(e, n_starts, seed, res, best_start);
-        // With the per-iteration log (fn): one iteration per lock-step step, the criteria of all starts side by side, the
-        // lines handed over start by start afterwards (NEM_MI355X_BATCH_STARTS_LOGGED=0: one start after the other).  One
-        // round only -- under TIE_LIBC a start that draws behind its initial sweeps sends the call to the sequential form
-        // below before a line has been handed over.
-        const char* gl = getenv("NEM_MI355X_BATCH_STARTS_LOGGED");
-        if (fn && lock_ok && n_starts <= 64 && !(gl && gl[0] == '0')) {
-            const int rr = run_random_lockstep(e, n_starts, seed, res, best_start, fn, user);
-            if (rr != kStartsNotInLockStep) return rr;
-            voided = n_starts;
-        }
-    }
-    int r;
-    const int n = e->n, d = e->d, k = e->k, wf = e->wf;
-    const size_t kd = (size_t)k * d;
-    if ((r = ensure_state_buffers(e))) return r;
-    // ---- InitPara: dispersion of the whole sample
-    e->have_params = true;                                         // (the slots are (re)written below)
-    if ((r = reset_state(e))) return r;
-    if (e->ncem()) {
-        HIPCHK(hipMemsetAsync(e->lab[0], 0, (size_t)e->n_total, e->stream));
-    } else {
-        std::vector<float> c1((size_t)n * k, 0.0f);
-        for (int i = 0; i < n; i++) c1[(size_t)i * k] = 1.0f;
-        HIPCHK(copy_sync(e, e->cbuf[0], c1.data(), c1.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    e->cur = 0; e->masks_valid = false;
-    if ((r = do_mstep(e))) return r;
-    if (!e->ncem() && (r = read_iter_flags(e))) return r;         // (a fuzzy M-step can report a fault)
-    std::vector<float> dispsam((size_t)d);
-    HIPCHK(copy_sync(e, dispsam.data(), e->disp, sizeof(float) * d, hipMemcpyDeviceToHost));
-
-    GlibcRandom rng(seed);
-    if (e->libc() && e->cfg.tie_seed != seed) { e->cfg.tie_seed = seed; e->draw_valid = false; }   // one stream (nem_exe.c:621)
-    // RandomInteger (nem_rnd.c:40-63); with TIE_LIBC the starts' draws and the sweeps' tie draws are ONE stream
-    auto draw_integer = [&](int mini, int maxi, int* out) -> int {
-        if (mini >= maxi) { *out = maxi; return NEMGPU_OK; }
-        if (!e->libc()) { *out = rng.integer(mini, maxi); return NEMGPU_OK; }
-        uint32_t v = 0;
-        int rr = host_draw(e, &v);
-        *out = (int)(v % (uint32_t)(maxi - mini + 1)) + mini;
-        return rr;
-    };
-    std::vector<float> prop((size_t)k), center(kd), disp(kd);
-    auto bit = [&](int i, int j) { return (float)((e->host_bits[(size_t)i * wf + (j >> 5)] >> (j & 31)) & 1u); };
-    alloc_for(e);
-    if (e->ncem()) { if (!e->best_lab && (r = dev_alloc(&e->best_lab, (size_t)e->n_total))) return r; }
-    else { if (!e->best_c && (r = dev_alloc(&e->best_c, (size_t)e->n_total * k))) return r; }
-    uint8_t* best_lab = e->best_lab; float* best_c = e->best_c;
-    auto cleanup = [&]() { (void)hipStreamSynchronize(e->stream); };
-    int nbsucc = 0, best = -1, last_status = NEMGPU_OK;
-    float best_crit[6] = {0, 0, 0, 0, 0, 0};
-    nemgpu_result best_res{};
-    e->rs_rounds = e->rs_lockstep = e->rs_two_waits = 0; e->rs_alone = n_starts;   // (one after the other)
-    e->rs_redone = voided;                                         // (... after a round that lost its bet: the counters must tell)
-    for (int s = 0; s < n_starts; s++) {
-        // MakeRandomPara
-        for (int h = 0; h < k; h++) for (int j = 0; j < d; j++) disp[(size_t)h * d + j] = dispsam[j] / k;      // :1400
-        for (int h = 0; h < k; h++) prop[h] = (float)(1.0 / k);                                              // :1405
-        for (int h = 0; h < k; h++) {
-            int ipt = 0;
-            bool again = true;
-            for (int ndraw = 0; again && ndraw < 100; ndraw++) {                                             // :1419
-                if ((r = draw_integer(0, n - 1, &ipt))) { cleanup(); return r; }
-                again = false;
-                for (int g = 0; g < h && !again; g++) {
-                    bool different = false;
-                    for (int j = 0; j < d && !different; j++) different = center[(size_t)g * d + j] != bit(ipt, j);
-                    if (!different) again = true;
-                }
-            }
-            for (int j = 0; j < d; j++) center[(size_t)h * d + j] = bit(ipt, j);                             // :1457
-        }
-        HIPCHK(copy_sync(e, e->prop0, prop.data(), sizeof(float) * k, hipMemcpyHostToDevice));
-        HIPCHK(copy_sync(e, e->center0, center.data(), sizeof(float) * kd, hipMemcpyHostToDevice));
-        HIPCHK(copy_sync(e, e->disp0, disp.data(), sizeof(float) * kd, hipMemcpyHostToDevice));
-        // ComputePartitionFromPara + NemAlgo + criteria, as nemgpu_run does
-        float crit[6];
-        bool have_crit = false;
-        if (!fn) {
-            if ((r = iterate(e, e->cfg.it_max, true))) { cleanup(); return r; }
-        } else {
-            nemgpu_log_event ev{};
-            ev.kind = NEMGPU_LOG_START; ev.start = s;
-            fn(&ev, user);
-            float cb[6], ca[6];
-            std::vector<float> nb((size_t)k);
-            nemgpu_result r1{};
-            if ((r = iterate_logged_impl(e, 1, true, &r1, cb, ca, prop.data(), center.data(), disp.data(), nullptr))) { cleanup(); return r; }
-            ev.kind = NEMGPU_LOG_LINE; ev.iter = 0; ev.crit_before = cb; ev.crit_after = ca;
-            ev.prop = prop.data(); ev.center = center.data(); ev.disp = disp.data(); ev.nbobs_k = nullptr;
-            fn(&ev, user);
-            for (int iter = 1; iter <= e->cfg.it_max && !e->converged && e->status == NEMGPU_OK; iter++) {
-                if ((r = iterate_logged_impl(e, 0, true, &r1, cb, ca, prop.data(), center.data(), disp.data(), nb.data()))) { cleanup(); return r; }
-                ev.iter = iter; ev.nbobs_k = nb.data();
-                if (e->status == NEMGPU_W_EMPTYCLASS) {
-                    // EstimSizes (nem_mod.c:1275-1317) ran before the empty class was found: i-ordered float sums per class
-                    std::vector<float> part((size_t)n * k);
-                    if ((r = nemgpu_get_partition(e, part.data()))) { cleanup(); return r; }
-                    for (int h = 0; h < k; h++) {
-                        float acc = 0.0f;
-                        for (int i = 0; i < n; i++) acc += part[(size_t)i * k + h];
-                        nb[(size_t)h] = acc;
-                    }
-                    ev.kind = NEMGPU_LOG_EMPTY; ev.emptyk = e->emptyk;
-                    fn(&ev, user);
-                    break;
-                }
-                ev.kind = NEMGPU_LOG_LINE;
-                fn(&ev, user);
-                memcpy(crit, ca, sizeof crit);                     // (of the final partition, on the final densities, if the run ends here)
-                have_crit = true;
-            }
-            if (e->status == NEMGPU_W_EMPTYCLASS) have_crit = false;
-        }
-        if (e->iters == 0) {
-            if ((r = do_mstep(e)) || (r = do_tables(e)) || (r = do_density(e))) { cleanup(); return r; }
-            have_crit = false;
-        }
-        if (!have_crit && (r = criteria(e, crit))) { cleanup(); return r; }
-        last_status = e->status;
-        if (e->status == NEMGPU_OK) {
-            nbsucc++;
-            if (nbsucc == 1 || crit[3] > best_crit[3]) {                                                     // :1676-1697
-                if (e->ncem()) HIPCHK(hipMemcpyAsync(best_lab, e->lab[e->cur], (size_t)e->n_total, hipMemcpyDeviceToDevice, e->stream));
-                else HIPCHK(hipMemcpyAsync(best_c, e->cbuf[e->cur], sizeof(float) * (size_t)e->n_total * k, hipMemcpyDeviceToDevice, e->stream));
-                for (int t = 0; t < 6; t++) best_crit[t] = crit[t];
-                best = s;
-                fill_result(e, &best_res);
-            }
-        }
-    }
-    if (nbsucc > 0) {
-        if (e->ncem()) HIPCHK(hipMemcpyAsync(e->lab[e->cur], best_lab, (size_t)e->n_total, hipMemcpyDeviceToDevice, e->stream));
-        else HIPCHK(hipMemcpyAsync(e->cbuf[e->cur], best_c, sizeof(float) * (size_t)e->n_total * k, hipMemcpyDeviceToDevice, e->stream));
-        e->masks_valid = false; e->tables_fresh = false; e->density_fresh = false;
-        if ((r = do_mstep(e)) || (!e->ncem() && (r = read_iter_flags(e)))) { cleanup(); return r; }             // :1711
-        e->status = NEMGPU_OK; e->emptyk = 0;
-        e->iters = best_res.iters; e->converged = best_res.converged;
-        if (res) { *res = best_res; res->status = NEMGPU_OK; res->tie_draws = e->draws; for (int t = 0; t < 6; t++) res->crit[t] = best_crit[t]; }
-    } else if (res) {
-        fill_result(e, res);
-        res->status = last_status;
-    }
-    if (best_start) *best_start = best;
-    cleanup();
-    return NEMGPU_OK;
-}
-
 // ---- random starts in lock step -------------------------------------------------------------------------------
 // A state-only twin of `p`: matrix layouts, graph and draw table are p's, everything else is carved from `slab`.
 static int make_clone(nemgpu_engine* p, nemgpu_engine** out, char* slab, size_t slab_bytes, int* flags_host, float* par0)
@@ -4445,6 +4277,142 @@ static int ensure_clones(nemgpu_engine* e, int count)
     return NEMGPU_OK;
 }
 
+// INIT_RANDOM: RandNemAlgo (nem_alg.c:1574-1742).  InitPara's whole-sample dispersion (:1200-1281) is one M-step
+// with every family in class 0; every start draws its centres from the data (MakeRandomPara, :1381-1473), runs the
+// INIT_PARAM_FILE pipeline on them and is ranked by criterion M (DEFAULT_CRIT, nem_typ.h:80); the best partition is
+// restored and EstimPara run on it (:1703-1713).
+// What of it does not depend on how the starts are run -- one after the other or in lock step:
+struct RandomStarts {
+    nemgpu_engine* e = nullptr;
+    std::vector<float> dispsam;                                    // InitPara: the whole sample's dispersion
+    GlibcRandom rng{1};
+    int nbsucc = 0, best = -1, last_status = NEMGPU_OK;
+    float best_crit[6] = {0, 0, 0, 0, 0, 0};
+    nemgpu_result best_res{};
+
+    int begin(nemgpu_engine* engine, uint32_t seed)
+    {
+        e = engine;
+        int r;
+        const int n = e->n, k = e->k, d = e->d;
+        if ((r = ensure_state_buffers(e))) return r;
+        // ---- InitPara: dispersion of the whole sample
+        e->have_params = true;                                     // (the slots are (re)written by every start)
+        if ((r = reset_state(e))) return r;
+        if (e->ncem()) {
+            HIPCHK(hipMemsetAsync(e->lab[0], 0, (size_t)e->n_total, e->stream));
+        } else {
+            std::vector<float> c1((size_t)n * k, 0.0f);
+            for (int i = 0; i < n; i++) c1[(size_t)i * k] = 1.0f;
+            HIPCHK(copy_sync(e, e->cbuf[0], c1.data(), c1.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        e->cur = 0; e->masks_valid = false;
+        if ((r = do_mstep(e))) return r;
+        if (!e->ncem() && (r = read_iter_flags(e))) return r;     // (a fuzzy M-step can report a fault)
+        dispsam.resize((size_t)d);
+        HIPCHK(copy_sync(e, dispsam.data(), e->disp, sizeof(float) * d, hipMemcpyDeviceToHost));
+        rng.seed(seed);
+        if (e->libc() && e->cfg.tie_seed != seed) { e->cfg.tie_seed = seed; e->draw_valid = false; }   // one stream (nem_exe.c:621)
+        alloc_for(e);
+        if (e->ncem()) { if (!e->best_lab && (r = dev_alloc(&e->best_lab, (size_t)e->n_total))) return r; }
+        else { if (!e->best_c && (r = dev_alloc(&e->best_c, (size_t)e->n_total * k))) return r; }
+        return NEMGPU_OK;
+    }
+
+    // RandomInteger (nem_rnd.c:40-63); with TIE_LIBC the starts' draws and the sweeps' tie draws are ONE stream
+    int draw_integer(int mini, int maxi, int* out)
+    {
+        if (mini >= maxi) { *out = maxi; return NEMGPU_OK; }
+        if (!e->libc()) { *out = rng.integer(mini, maxi); return NEMGPU_OK; }
+        uint32_t v = 0;
+        const int r = host_draw(e, &v);
+        *out = (int)(v % (uint32_t)(maxi - mini + 1)) + mini;
+        return r;
+    }
+
+    // MakeRandomPara, nem_alg.c:1381-1473, into the caller's arrays (TIE_LIBC: from where the stream stands)
+    int make_random_para(float* prop, float* center, float* disp)
+    {
+        const int n = e->n, k = e->k, d = e->d, wf = e->wf;
+        auto bit = [&](int i, int j) { return (float)((e->host_bits[(size_t)i * wf + (j >> 5)] >> (j & 31)) & 1u); };
+        for (int h = 0; h < k; h++) for (int j = 0; j < d; j++) disp[(size_t)h * d + j] = dispsam[j] / k;      // :1400
+        for (int h = 0; h < k; h++) prop[h] = (float)(1.0 / k);                                              // :1405
+        for (int h = 0; h < k; h++) {
+            int ipt = 0;
+            bool again = true;
+            for (int ndraw = 0; again && ndraw < 100; ndraw++) {                                             // :1419
+                const int r = draw_integer(0, n - 1, &ipt);
+                if (r) return r;
+                again = false;
+                for (int g = 0; g < h && !again; g++) {
+                    bool different = false;
+                    for (int j = 0; j < d && !different; j++) different = center[(size_t)g * d + j] != bit(ipt, j);
+                    if (!different) again = true;
+                }
+            }
+            for (int j = 0; j < d; j++) center[(size_t)h * d + j] = bit(ipt, j);                             // :1457
+        }
+        return NEMGPU_OK;
+    }
+
+    // a start's parameters into the engine's initial slots
+    int upload(const float* prop, const float* center, const float* disp)
+    {
+        const size_t k = (size_t)e->k, kd = k * e->d;
+        HIPCHK(copy_sync(e, e->prop0, prop, sizeof(float) * k, hipMemcpyHostToDevice));
+        HIPCHK(copy_sync(e, e->center0, center, sizeof(float) * kd, hipMemcpyHostToDevice));
+        HIPCHK(copy_sync(e, e->disp0, disp, sizeof(float) * kd, hipMemcpyHostToDevice));
+        return NEMGPU_OK;
+    }
+
+    // one start alone on the engine itself: ComputePartitionFromPara + NemAlgo + criteria, as nemgpu_run does
+    int run_alone(const float* prop, const float* center, const float* disp, float crit[6])
+    {
+        int r;
+        if ((r = upload(prop, center, disp)) || (r = iterate(e, e->cfg.it_max, true))) return r;
+        if (e->iters == 0 && (r = finish_unstepped(e))) return r;
+        return criteria(e, crit);
+    }
+
+    // A start that `src` (the engine or a twin of it) has run: the first that succeeds, or one with a strictly greater
+    // criterion M, is the best so far -- its partition is set aside on the engine's stream
+    int offer(nemgpu_engine* src, const float* crit, int start)
+    {
+        last_status = src->status;
+        if (src->status != NEMGPU_OK) return NEMGPU_OK;
+        nbsucc++;
+        if (nbsucc == 1 || crit[3] > best_crit[3]) {                                                         // :1676-1697
+            if (e->ncem()) HIPCHK(hipMemcpyAsync(e->best_lab, src->lab[src->cur], (size_t)e->n_total, hipMemcpyDeviceToDevice, e->stream));
+            else HIPCHK(hipMemcpyAsync(e->best_c, src->cbuf[src->cur], sizeof(float) * (size_t)e->n_total * e->k, hipMemcpyDeviceToDevice, e->stream));
+            for (int t = 0; t < 6; t++) best_crit[t] = crit[t];
+            best = start;
+            fill_result(src, &best_res);
+        }
+        return NEMGPU_OK;
+    }
+
+    // the best partition back in place and EstimPara on it; without a successful start, the last one's status
+    int finish(nemgpu_result* res, int* best_start)
+    {
+        int r;
+        if (nbsucc > 0) {
+            if (e->ncem()) HIPCHK(hipMemcpyAsync(e->lab[e->cur], e->best_lab, (size_t)e->n_total, hipMemcpyDeviceToDevice, e->stream));
+            else HIPCHK(hipMemcpyAsync(e->cbuf[e->cur], e->best_c, sizeof(float) * (size_t)e->n_total * e->k, hipMemcpyDeviceToDevice, e->stream));
+            e->masks_valid = false; e->tables_fresh = false; e->density_fresh = false;
+            if ((r = do_mstep(e)) || (!e->ncem() && (r = read_iter_flags(e)))) return r;                          // :1711
+            e->status = NEMGPU_OK; e->emptyk = 0;
+            e->iters = best_res.iters; e->converged = best_res.converged;
+            if (res) { *res = best_res; res->status = NEMGPU_OK; res->tie_draws = e->draws; for (int t = 0; t < 6; t++) res->crit[t] = best_crit[t]; }
+        } else if (res) {
+            fill_result(e, res);
+            res->status = last_status;
+        }
+        if (best_start) *best_start = best;
+        HIPCHK(hipStreamSynchronize(e->stream));
+        return NEMGPU_OK;
+    }
+};
+
 // RandNemAlgo (nem_alg.c:1574-1742) with the starts in lock step.  TIE_LIBC: the starts' centre draws and the sweeps'
 // tie draws are one stream, so where start s begins depends on the ties of the starts before it.  Where the ties ARE
 // is what makes lock step possible: a random start gives every class the same dispersion (the whole sample's over K,
@@ -4457,42 +4425,16 @@ static int ensure_clones(nemgpu_engine* e, int count)
 // own initial partition, on the assumption that none of them draws.  The assumption is checked: the first start whose
 // iterations did draw is still right (its draws came from where they should) and everything behind it is redone from
 // the position it left the stream at.
-static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu_result* res, int* best_start, nemgpu_log_fn fn, void* user)
+// Logged (fn), a start that drew behind its initial sweeps ends the call with kStartsNotInLockStep: nothing was handed to
+// the writer, the caller runs the starts one after the other.
+constexpr int kStartsNotInLockStep = -7001;
+static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu_result* res, int* best_start, nemgpu_log_fn fn = nullptr, void* user = nullptr)
 {
     int r;
-    const int n = e->n, d = e->d, k = e->k, wf = e->wf;
-    const size_t kd = (size_t)k * d, par = (size_t)k + 2 * kd;
-    if ((r = ensure_state_buffers(e))) return r;
-    // ---- InitPara: dispersion of the whole sample
-    e->have_params = true;
-    if ((r = reset_state(e))) return r;
-    if (e->ncem()) {
-        HIPCHK(hipMemsetAsync(e->lab[0], 0, (size_t)e->n_total, e->stream));
-    } else {
-        std::vector<float> c1((size_t)n * k, 0.0f);
-        for (int i = 0; i < n; i++) c1[(size_t)i * k] = 1.0f;
-        HIPCHK(copy_sync(e, e->cbuf[0], c1.data(), c1.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    e->cur = 0; e->masks_valid = false;
-    if ((r = do_mstep(e))) return r;
-    if (!e->ncem() && (r = read_iter_flags(e))) return r;         // (a fuzzy M-step can report a fault)
-    std::vector<float> dispsam((size_t)d);
-    HIPCHK(copy_sync(e, dispsam.data(), e->disp, sizeof(float) * d, hipMemcpyDeviceToHost));
-
-    GlibcRandom rng(seed);
-    if (e->libc() && e->cfg.tie_seed != seed) { e->cfg.tie_seed = seed; e->draw_valid = false; }
-    auto draw_integer = [&](int mini, int maxi, int* out) -> int {
-        if (mini >= maxi) { *out = maxi; return NEMGPU_OK; }
-        if (!e->libc()) { *out = rng.integer(mini, maxi); return NEMGPU_OK; }
-        uint32_t v = 0;
-        int rr = host_draw(e, &v);
-        *out = (int)(v % (uint32_t)(maxi - mini + 1)) + mini;
-        return rr;
-    };
-    auto bit = [&](int i, int j) { return (float)((e->host_bits[(size_t)i * wf + (j >> 5)] >> (j & 31)) & 1u); };
-    alloc_for(e);
-    if (e->ncem()) { if (!e->best_lab && (r = dev_alloc(&e->best_lab, (size_t)e->n_total))) return r; }
-    else { if (!e->best_c && (r = dev_alloc(&e->best_c, (size_t)e->n_total * k))) return r; }
+    const int k = e->k;
+    const size_t kd = (size_t)k * e->d, par = (size_t)k + 2 * kd;
+    RandomStarts rs;
+    if ((r = rs.begin(e, seed))) return r;
     const int group = std::min(n_starts, 64);
     // Starts per round.  TIE_LIBC: phase B bets that no start draws behind its initial sweeps.  Whether these data keep
     // the bet is not known ahead: start 0 runs ALONE, on this engine's own pipelined path (what the sequential form
@@ -4510,12 +4452,8 @@ static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, ne
     // (random starts tie by the hundreds in their initial sweeps: the draw window is sized for that from the first start on,
     //  instead of growing -- and sliding away from the earlier starts' positions -- when the first heavy start is met)
     if (e->libc()) e->tie_heavy = true;
-    int nbsucc = 0, best = -1, last_status = NEMGPU_OK;
-    float best_crit[6] = {0, 0, 0, 0, 0, 0};
-    nemgpu_result best_res{};
     std::vector<float> host_par;
     std::vector<int> start_pos;
-    std::vector<GlibcRandom> rng_after;                           // (hash / first tie rules: the generator after each start's draws)
     int next = 0;
     static const bool prof = getenv("NEM_MI355X_BATCH_PROF") != nullptr;
     while (next < n_starts) {
@@ -4523,52 +4461,21 @@ static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, ne
         std::vector<nemgpu_engine*> E(e->clones.begin(), e->clones.begin() + M);
         host_par.assign((size_t)M * par, 0.0f);
         start_pos.assign((size_t)M, 0);
-        // MakeRandomPara, nem_alg.c:1381-1473, for start j of the round (TIE_LIBC: from where the stream stands)
+        // start j of the round
         auto make_random_para = [&](int j) -> int {
-            float* prop = host_par.data() + (size_t)j * par; float* center = prop + k; float* disp = center + kd;
-            for (int h = 0; h < k; h++) for (int t = 0; t < d; t++) disp[(size_t)h * d + t] = dispsam[t] / k;     // :1400
-            for (int h = 0; h < k; h++) prop[h] = (float)(1.0 / k);                                              // :1405
-            for (int h = 0; h < k; h++) {
-                int ipt = 0;
-                bool again = true;
-                for (int ndraw = 0; again && ndraw < 100; ndraw++) {                                             // :1419
-                    int rr = draw_integer(0, n - 1, &ipt);
-                    if (rr) return rr;
-                    again = false;
-                    for (int g = 0; g < h && !again; g++) {
-                        bool different = false;
-                        for (int t = 0; t < d && !different; t++) different = center[(size_t)g * d + t] != bit(ipt, t);
-                        if (!different) again = true;
-                    }
-                }
-                for (int t = 0; t < d; t++) center[(size_t)h * d + t] = bit(ipt, t);                             // :1457
-            }
+            float* prop = host_par.data() + (size_t)j * par;
+            const int rr = rs.make_random_para(prop, prop + k, prop + k + kd);
             start_pos[j] = e->draws;                                 // where this start's sweeps begin to draw
-            return NEMGPU_OK;
+            return rr;
         };
         if (e->libc() && M == 1) {
-            // ---- one start alone: this engine's own run (nemgpu_run_random's sequential body)
+            // ---- one start alone: this engine's own run, as one after the other
             if ((r = make_random_para(0))) return r;
-            const float* prop = host_par.data(); const float* center = prop + k; const float* disp = center + kd;
-            HIPCHK(copy_sync(e, e->prop0, prop, sizeof(float) * k, hipMemcpyHostToDevice));
-            HIPCHK(copy_sync(e, e->center0, center, sizeof(float) * kd, hipMemcpyHostToDevice));
-            HIPCHK(copy_sync(e, e->disp0, disp, sizeof(float) * kd, hipMemcpyHostToDevice));
-            e->draws_after_init = e->draws;
-            if ((r = iterate(e, e->cfg.it_max, true))) return r;
-            if (e->iters == 0) { if ((r = do_mstep(e)) || (r = do_tables(e)) || (r = do_density(e))) return r; }
             float crit[6];
-            if ((r = criteria(e, crit))) return r;
+            e->draws_after_init = e->draws;
+            if ((r = rs.run_alone(host_par.data(), host_par.data() + k, host_par.data() + k + kd, crit))) return r;
             const bool drew_late = e->draws != e->draws_after_init;  // (its iterations drew: phase B's bet would have been lost)
-            last_status = e->status;
-            if (e->status == NEMGPU_OK) {
-                nbsucc++;
-                if (nbsucc == 1 || crit[3] > best_crit[3]) {                                                     // :1676-1697
-                    HIPCHK(hipMemcpyAsync(e->best_lab, e->lab[e->cur], (size_t)e->n_total, hipMemcpyDeviceToDevice, e->stream));
-                    for (int t = 0; t < 6; t++) best_crit[t] = crit[t];
-                    best = next;
-                    fill_result(e, &best_res);
-                }
-            }
+            if ((r = rs.offer(e, crit, next))) return r;
             next += 1; e->rs_alone++;
             clean_run = drew_late ? 0 : clean_run + 1;
             width = (alone_for_good || clean_run == 0) ? 1 : (voided_in_a_row == 0 ? group : std::min(group, 4 * clean_run));
@@ -4660,33 +4567,10 @@ static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, ne
             if ((r = iterate_many_logged(E, L, host_par.data(), par, logs))) return r;
         } else if ((r = iterate_many(E, L))) return r;
         for (int j = 0; j < M; j++)
-            if (E[j]->iters == 0) { if ((r = do_mstep(E[j])) || (r = do_tables(E[j])) || (r = do_density(E[j]))) return r; }
+            if (E[j]->iters == 0 && (r = finish_unstepped(E[j]))) return r;
         std::vector<float> crits((size_t)M * 6);
-        bool staged = false;
-        {
-            std::vector<Recorder> recs((size_t)M);
-            std::vector<int> all((size_t)M);
-            for (int j = 0; j < M; j++) all[j] = j;
-            // (the starts' criteria to the batch's staging area behind the zipped criteria launches, ONE copy to the host:
-            //  see run_many)
-            nemgpu_engine::ZipContext* z = zip_context(E[0]);
-            staged = z != nullptr && z->zip_flags_dev != nullptr && z->zip_flags_host != nullptr && z->zip_flags_cap >= (size_t)8 * M;
-            if ((r = lockstep(E, all, recs, [&](int m) {
-                    const int rr = criteria_enqueue(E[m], -1);
-                    if (rr == NEMGPU_OK && staged) launch_copy_words(reinterpret_cast<const int*>(E[m]->crit6_dev), z->zip_flags_dev + (size_t)8 * m, 6, E[0]->stream);
-                    return rr;
-                }, false))) return r;
-            if (staged) {
-                HIPCHK(hipMemcpyAsync(z->zip_flags_host, z->zip_flags_dev, (size_t)8 * M * sizeof(int), hipMemcpyDeviceToHost, E[0]->stream));
-                HIPCHK(hipStreamSynchronize(E[0]->stream));
-                for (int j = 0; j < M; j++) memcpy(crits.data() + (size_t)j * 6, z->zip_flags_host + (size_t)8 * j, 6 * sizeof(float));
-            }
-        }
-        if (!staged) {
-            for (int j = 0; j < M; j++)
-                HIPCHK(hipMemcpyAsync(crits.data() + (size_t)j * 6, E[j]->crit6_dev, 6 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-        }
-        HIPCHK(hipStreamSynchronize(e->stream));
+        float (*crit)[6] = reinterpret_cast<float (*)[6]>(crits.data());
+        if ((r = criteria_many(E, crit))) return r;                 // (waits for the twins' stream, which is e's)
         // the starts of this round that stand: all of them, or (TIE_LIBC) up to the first one whose iterations drew
         int valid = M;
         if (e->libc())
@@ -4708,21 +4592,8 @@ static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, ne
                 }
             }
         }
-        for (int j = 0; j < valid; j++) {
-            nemgpu_engine* c = E[j];
-            const float* crit = crits.data() + (size_t)j * 6;
-            last_status = c->status;
-            if (c->status == NEMGPU_OK) {
-                nbsucc++;
-                if (nbsucc == 1 || crit[3] > best_crit[3]) {                                                     // :1676-1697
-                    if (e->ncem()) HIPCHK(hipMemcpyAsync(e->best_lab, c->lab[c->cur], (size_t)e->n_total, hipMemcpyDeviceToDevice, e->stream));
-                    else HIPCHK(hipMemcpyAsync(e->best_c, c->cbuf[c->cur], sizeof(float) * (size_t)e->n_total * k, hipMemcpyDeviceToDevice, e->stream));
-                    for (int t = 0; t < 6; t++) best_crit[t] = crit[t];
-                    best = next + j;
-                    fill_result(c, &best_res);
-                }
-            }
-        }
+        for (int j = 0; j < valid; j++)
+            if ((r = rs.offer(E[j], crit[j], next + j))) return r;
         if (e->libc()) {
             e->draws = E[valid - 1]->draws;                        // the stream as start `valid - 1` left it
             e->tie_heavy = e->tie_heavy || E[valid - 1]->tie_heavy;
@@ -4736,21 +4607,108 @@ static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, ne
         }
     }
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (nbsucc > 0) {
-        if (e->ncem()) HIPCHK(hipMemcpyAsync(e->lab[e->cur], e->best_lab, (size_t)e->n_total, hipMemcpyDeviceToDevice, e->stream));
-        else HIPCHK(hipMemcpyAsync(e->cbuf[e->cur], e->best_c, sizeof(float) * (size_t)e->n_total * k, hipMemcpyDeviceToDevice, e->stream));
-        e->masks_valid = false; e->tables_fresh = false; e->density_fresh = false;
-        if ((r = do_mstep(e)) || (!e->ncem() && (r = read_iter_flags(e)))) return r;                              // :1711
-        e->status = NEMGPU_OK; e->emptyk = 0;
-        e->iters = best_res.iters; e->converged = best_res.converged;
-        if (res) { *res = best_res; res->status = NEMGPU_OK; res->tie_draws = e->draws; for (int t = 0; t < 6; t++) res->crit[t] = best_crit[t]; }
-    } else if (res) {
-        fill_result(e, res);
-        res->status = last_status;
+    return rs.finish(res, best_start);
+}
+
+// fn != nullptr: the starts one after the other, one logged step per host round trip (nemgpu_iterate_logged's form)
+static int run_random_impl(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu_result* res, int* best_start,
+                           nemgpu_log_fn fn, void* user)
+{
+    if (!e || n_starts <= 0) return NEMGPU_E_FUNCARG;
+    if (e->lo != 0 || e->hi != e->n_total) { set_error("random starts need the whole problem on one engine"); return NEMGPU_E_FUNCARG; }
+    if (!e->have_matrix || e->host_bits_words == 0) { set_error("the matrix must be set first"); return NEMGPU_E_FUNCARG; }
+    HIPCHK(hipSetDevice(e->device));
+    // whichever way the call is left, in either form: nothing of it is still queued on the engine's stream
+    struct Drained { hipStream_t s; ~Drained() { (void)hipStreamSynchronize(s); } } drained{e->stream};
+    { const int fr = flush_reset(e); if (fr) return fr; }
+    int voided = 0;                                                // starts of a logged lock-step round that was thrown away whole
+    {
+        // the starts are independent EM runs on ONE matrix: by default they run in lock step, every launch serving all
+        // of them (NEM_MI355X_BATCH_STARTS=0: one after the other on this engine)
+        const char* g = getenv("NEM_MI355X_BATCH_STARTS");
+        const bool lock_ok = n_starts > 1 && !(g && g[0] == '0') && !crit_test(e);
+        if (!fn && lock_ok) return run_random_lockstep(e, n_starts, seed, res, best_start);
+        // With the per-iteration log (fn): one iteration per lock-step step, the criteria of all starts side by side, the
+        // lines handed over start by start afterwards (NEM_MI355X_BATCH_STARTS_LOGGED=0: one start after the other).  One
+        // round only -- under TIE_LIBC a start that draws behind its initial sweeps sends the call to the sequential form
+        // below before a line has been handed over.
+        const char* gl = getenv("NEM_MI355X_BATCH_STARTS_LOGGED");
+        if (fn && lock_ok && n_starts <= 64 && !(gl && gl[0] == '0')) {
+            const int rr = run_random_lockstep(e, n_starts, seed, res, best_start, fn, user);
+            if (rr != kStartsNotInLockStep) return rr;
+            voided = n_starts;
+        }
     }
-    if (best_start) *best_start = best;
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return NEMGPU_OK;
+    int r;
+    const int n = e->n, k = e->k;
+    const size_t kd = (size_t)k * e->d;
+    RandomStarts rs;
+    if ((r = rs.begin(e, seed))) return r;
+    std::vector<float> prop((size_t)k), center(kd), disp(kd);
+    e->rs_rounds = e->rs_lockstep = e->rs_two_waits = 0; e->rs_alone = n_starts;   // (one after the other)
+    e->rs_redone = voided;                                         // (... after a round that lost its bet: the counters must tell)
+    for (int s = 0; s < n_starts; s++) {
+        if ((r = rs.make_random_para(prop.data(), center.data(), disp.data()))) return r;
+        float crit[6];
+        if (!fn) {
+            if ((r = rs.run_alone(prop.data(), center.data(), disp.data(), crit))) return r;
+        } else {
+            // the same, step by step: a line per iteration
+            if ((r = rs.upload(prop.data(), center.data(), disp.data()))) return r;
+            bool have_crit = false;
+            nemgpu_log_event ev{};
+            ev.kind = NEMGPU_LOG_START; ev.start = s;
+            fn(&ev, user);
+            float cb[6], ca[6];
+            std::vector<float> nb((size_t)k);
+            nemgpu_result r1{};
+            if ((r = iterate_logged_impl(e, 1, true, &r1, cb, ca, prop.data(), center.data(), disp.data(), nullptr))) return r;
+            ev.kind = NEMGPU_LOG_LINE; ev.iter = 0; ev.crit_before = cb; ev.crit_after = ca;
+            ev.prop = prop.data(); ev.center = center.data(); ev.disp = disp.data(); ev.nbobs_k = nullptr;
+            fn(&ev, user);
+            for (int iter = 1; iter <= e->cfg.it_max && !e->converged && e->status == NEMGPU_OK; iter++) {
+                if ((r = iterate_logged_impl(e, 0, true, &r1, cb, ca, prop.data(), center.data(), disp.data(), nb.data()))) return r;
+                ev.iter = iter; ev.nbobs_k = nb.data();
+                if (e->status == NEMGPU_W_EMPTYCLASS) {
+                    // EstimSizes (nem_mod.c:1275-1317) ran before the empty class was found: i-ordered float sums per class
+                    std::vector<float> part((size_t)n * k);
+                    if ((r = nemgpu_get_partition(e, part.data()))) return r;
+                    for (int h = 0; h < k; h++) {
+                        float acc = 0.0f;
+                        for (int i = 0; i < n; i++) acc += part[(size_t)i * k + h];
+                        nb[(size_t)h] = acc;
+                    }
+                    ev.kind = NEMGPU_LOG_EMPTY; ev.emptyk = e->emptyk;
+                    fn(&ev, user);
+                    break;
+                }
+                ev.kind = NEMGPU_LOG_LINE;
+                fn(&ev, user);
+                memcpy(crit, ca, sizeof crit);                     // (of the final partition, on the final densities, if the run ends here)
+                have_crit = true;
+            }
+            if (e->status == NEMGPU_W_EMPTYCLASS) have_crit = false;
+            if (e->iters == 0) {
+                if ((r = finish_unstepped(e))) return r;
+                have_crit = false;
+            }
+            if (!have_crit && (r = criteria(e, crit))) return r;
+        }
+        if ((r = rs.offer(e, crit, s))) return r;
+    }
+    return rs.finish(res, best_start);
+}
+
+int nemgpu_run_random(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu_result* res, int* best_start)
+{
+    return run_random_impl(e, n_starts, seed, res, best_start, nullptr, nullptr);
+}
+
+int nemgpu_run_random_logged(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu_result* res, int* best_start,
+                             nemgpu_log_fn fn, void* user)
+{
+    if (!fn) return NEMGPU_E_FUNCARG;
+    return run_random_impl(e, n_starts, seed, res, best_start, fn, user);
 }
 
 int nemgpu_glibc_random(uint32_t seed, int count, int32_t* out)

@@ -333,6 +333,62 @@ def test_lockstep_random_starts_equal_sequential_ones(gpu_lib, monkeypatch, algo
             assert np.array_equal(other[key], ref[key], equal_nan=True), key
 
 
+def tiny_random_starts(oracle, monkeypatch, n, d, k, seed, algo, tie):
+    """The oracle's five random starts on a tiny problem, and the engine's with the starts one after the other ("0") and
+    in lock step ("1")."""
+    from pangenomenem_amd.engine import NemEngine
+    x, _ = synth.bernoulli_pa_matrix(n, d, seed)
+    nei = synth.contiguity_graph(n, seed)
+    want = oracle.run_random(x, nei, k, n_starts=5, rng_seed=seed, algo=algo, disper="sk_", beta=0.5, it_max=20, tie=tie,
+                             seed=seed)
+    got = {}
+    for mode in ("0", "1"):
+        monkeypatch.setenv("NEM_MI355X_BATCH_STARTS", mode)
+        eng = NemEngine(n, d, k)
+        eng.set_matrix(x)
+        eng.set_graph(nei)
+        eng.configure(algo=algo, beta=0.5, disper="sk_", propor="pk", it_max=20, tie=tie, seed=seed)
+        got[mode] = eng.run_random(n_starts=5, rng_seed=seed)
+        eng.close()
+    return want, got
+
+
+@pytest.mark.parametrize("n,d,k,seed,algo,tie", [(6, 3, 3, 2, "ncem", "libc"), (6, 3, 3, 2, "ncem", "hash"),
+                                                 (12, 4, 5, 3, "nem", "hash"), (20, 3, 6, 3, "ncem", "libc")])
+def test_random_starts_that_all_empty_a_class(gpu_lib, oracle, monkeypatch, n, d, k, seed, algo, tie):
+    """More classes than the few families can fill: every one of the five starts ends with an empty class, no start is
+    kept (RandNemAlgo's nbsucc == 0, nem_alg.c:1699-1701) and the call reports the last start's status."""
+    want, got = tiny_random_starts(oracle, monkeypatch, n, d, k, seed, algo, tie)
+    assert want["status"] == 2 and want["best_start"] == -1
+    for mode in ("0", "1"):
+        assert got[mode]["status"] == want["status"], mode
+        assert got[mode]["best_start"] == want["best_start"], mode
+    # (nothing else: what the engine's parameter buffers hold after a call without a successful start differs between
+    #  the two forms -- one after the other leaves the last start's state, lock step leaves InitPara's)
+
+
+@pytest.mark.parametrize("n,d,k,seed,algo,tie", [(6, 3, 3, 1, "ncem", "libc"), (6, 3, 3, 1, "ncem", "hash"),
+                                                 (12, 4, 5, 4, "nem", "hash"), (20, 3, 6, 2, "nem", "hash")])
+def test_random_starts_whose_winner_comes_after_failed_ones(gpu_lib, oracle, monkeypatch, n, d, k, seed, algo, tie):
+    """Most of the five starts empty a class (in the cases' order: 0, 1, 4 -- the same -- 1, 2, 3 -- 0, 1, 2, 4): the
+    first success is kept whatever its criterion, failed starts before and after it change nothing, and the result is
+    the oracle's as in test_random_starts_match_oracle."""
+    want, got = tiny_random_starts(oracle, monkeypatch, n, d, k, seed, algo, tie)
+    assert want["status"] == 0 and want["best_start"] >= 0
+    for mode in ("0", "1"):
+        g = got[mode]
+        assert g["status"] == want["status"], mode
+        assert g["best_start"] == want["best_start"], mode
+        assert g["iters"] == want["iters"] and g["converged"] == want["converged"], mode
+        assert np.array_equal(g["c"].argmax(1), want["c"].argmax(1)), mode
+        if algo == "ncem":
+            assert np.array_equal(g["c"], want["c"]), mode
+        assert np.array_equal(g["center"], want["center"]), mode
+        for key in ("disp", "prop"):
+            assert maxdiff(g[key], want[key]) <= TOL, (mode, key)
+        assert_crit_close(g["crit"], want["crit"], 1e-6)
+
+
 def test_the_starts_beta_sweep_gets_two_rounds_once_that_was_enough_and_three_again_when_it_is_not(gpu_lib, oracle):
     """NCEM under a stateless tie rule: a pipelined start enqueues three relaxation rounds for its beta sweep until three
     starts in a row were through in two, then two (the third launch only found out that it had nothing to do).  A start

@@ -409,6 +409,7 @@ hipError_t pool_get(int device, bool pinned, size_t bytes, char** out, size_t* g
         nemgpu_release_cached();
         err = pinned ? hipHostMalloc((void**)out, want) : hipMalloc((void**)out, want);
     }
+    if (err != hipSuccess) *out = nullptr;
     return err;
 }
 void pool_put(int device, bool pinned, char* ptr, size_t size)
@@ -2096,115 +2097,162 @@ int iterate_many(std::vector<nemgpu_engine*>& E, std::vector<LoopCursor>& L)
 // 75-100 us at configs[1] size): one start after the other they are most of a logged iteration; with the starts in lock
 // step the blocks of all starts run side by side.  The lines are kept per start and handed to the caller's writer in the
 // reference's order afterwards.
-struct StartLogLine {
+//
+// What every logged path shares.  A line on its way to the writer is a LogLine: a view of numbers someone else holds -- a
+// staging slot on the host, the caller's arrays, a StartLogLine -- that emit() turns into the caller's event.
+struct LogLine {
     int kind = NEMGPU_LOG_LINE, iter = 0, emptyk = 0;
-    float cb[6] = {0, 0, 0, 0, 0, 0}, ca[6] = {0, 0, 0, 0, 0, 0};
-    std::vector<float> prop, center, disp, nb;
-    bool has_nb = false;
+    const float *cb = nullptr, *ca = nullptr, *prop = nullptr, *center = nullptr, *disp = nullptr, *nb = nullptr;   // (nb: not in line 0; all an emptied class has)
+    static LogLine empty(int iter, int emptyk, const float* sizes) { return {NEMGPU_LOG_EMPTY, iter, emptyk, nullptr, nullptr, nullptr, nullptr, nullptr, sizes}; }
 };
-struct StartLog { std::vector<StartLogLine> lines; };
+static void emit(nemgpu_log_fn fn, void* user, int start, const LogLine& ln)
+{
+    const nemgpu_log_event ev{ln.kind, start, ln.iter, ln.emptyk, ln.cb, ln.ca, ln.prop, ln.center, ln.disp, ln.nb};   // (the header's order)
+    fn(&ev, user);
+}
+// the owning copy of a line (the starts in lock step keep theirs until the round is through): a view into its own numbers
+struct StartLogLine {
+    LogLine v; std::vector<float> buf;
+    StartLogLine(const LogLine& src, size_t k, size_t kd) : v(src)
+    {
+        buf.reserve(2 * (6 + k + kd));                             // (no growth below: the pointers stay good, also when the line is moved)
+        auto own = [&](const float*& p, size_t count) { if (p) { buf.insert(buf.end(), p, p + count); p = buf.data() + buf.size() - count; } };
+        own(v.cb, 6); own(v.ca, 6); own(v.prop, k); own(v.center, kd); own(v.disp, kd); own(v.nb, k);
+    }
+    StartLogLine(StartLogLine&&) = default;                        // (and no copies: theirs would point into the original)
+};
 
-int criteria(nemgpu_engine* e, float crit6[6], int buf);
+// a device and a pinned block from the pool (either may be left out) for the length of a scope: whichever way the scope is
+// left, the stream that may still be copying into them is waited for before they go back
+struct PooledPair {
+    int device; hipStream_t stream;
+    char* dev = nullptr; char* host = nullptr; size_t dev_size = 0, host_size = 0;
+    PooledPair(int device_, hipStream_t s) : device(device_), stream(s) {}
+    PooledPair(const PooledPair&) = delete;
+    hipError_t get(bool pinned, size_t bytes) { return pool_get(device, pinned, bytes, pinned ? &host : &dev, pinned ? &host_size : &dev_size); }
+    int get_both(size_t bytes, const char* no_pinned)
+    {
+        HIPCHK(get(false, bytes));
+        if (get(true, bytes) != hipSuccess) { set_error(no_pinned); return NEMGPU_E_DEVICE; }
+        return NEMGPU_OK;
+    }
+    void put() { pool_put(device, false, dev, dev_size); pool_put(device, true, host, host_size); dev = host = nullptr; }   // (nothing queued targets them any more)
+    ~PooledPair() { if (dev || host) { (void)hipStreamSynchronize(stream); put(); } }
+};
+
+// The lines' staging slots, each [6 criteria before | 6 criteria after | the engine's parameter block].  With a device block
+// the words go there by recordable copy kernels and fetch() brings the slots to the pinned block; without, by copy commands.
+struct LogSlot {
+    enum Side : size_t { kBefore = 0, kAfter = 6, kPar = 12 };
+    const nemgpu_engine* e;                                        // (its parameter block's shape, its stream: a group's lead)
+    PooledPair st{e->device, e->stream};
+    size_t bytes(int slots) const { return (size_t)slots * (kPar + e->par_words) * sizeof(float); }
+    float* at(char* block, int m, size_t side) const { return reinterpret_cast<float*>(block) + (size_t)m * (kPar + e->par_words) + side; }
+    float* par_dev(int m) const { return at(st.dev, m, kPar); }
+    hipError_t put(int m, Side side, const float* src) const       // the six criteria at `src`, or the parameter block
+    {
+        const size_t count = side == kPar ? e->par_words : 6;
+        if (!st.dev) return hipMemcpyAsync(at(st.host, m, side), src, count * sizeof(float), hipMemcpyDeviceToHost, st.stream);
+        launch_copy_words(reinterpret_cast<const int*>(src), reinterpret_cast<int*>(at(st.dev, m, side)), (int)count, st.stream);
+        return hipSuccess;
+    }
+    hipError_t fetch(int slots) const                              // the first `slots` to the host, and the wait for them
+    {
+        const hipError_t err = hipMemcpyAsync(st.host, st.dev, bytes(slots), hipMemcpyDeviceToHost, st.stream);
+        return err != hipSuccess ? err : hipStreamSynchronize(st.stream);
+    }
+    LogLine line(int m, int iter) const                            // (host slot m, once the stream has been waited for)
+    {
+        const float *f = at(st.host, m, 0), *p = f + kPar;
+        return {NEMGPU_LOG_LINE, iter, 0, f + kBefore, f + kAfter, p, p + e->par_o_center, p + e->par_o_disp, p + e->par_o_nb};
+    }
+};
+
+// the line of an iteration whose sweep the host had to finish: the plain sequence of calls
+static int plain_line(nemgpu_engine* e, float cb[6], float ca[6], float* prop, float* center, float* disp, float* nb)
+{
+    int r;
+    if ((r = criteria(e, cb, (e->cur + 2) % 3)) || (r = criteria(e, ca, -1))) return r;
+    return nemgpu_get_results(e, prop, center, disp, nb, nullptr);
+}
+// EstimSizes (nem_mod.c:1275-1317) ran before the empty class was found: i-ordered float sums per class
+static int estim_sizes_host(nemgpu_engine* e, float* nb)
+{
+    std::vector<float> part((size_t)e->n * e->k);
+    const int r = nemgpu_get_partition(e, part.data());
+    for (int h = 0; h < e->k && r == NEMGPU_OK; h++) {
+        nb[h] = 0.0f;
+        for (int i = 0; i < e->n; i++) nb[h] += part[(size_t)i * e->k + h];
+    }
+    return r;
+}
 
 // E: the starts' engines behind their initial partitions (cur = 2; blind partition in buffer 1); L: their cursors with
 // first = false; host_par: the starts' own parameters, `par` floats apart (prop | center | disp)
 static int iterate_many_logged(std::vector<nemgpu_engine*>& E, std::vector<LoopCursor>& L, const float* host_par, size_t par,
-                               std::vector<StartLog>& logs)
+                               std::vector<std::vector<StartLogLine>>& logs)
 {
     int r;
     const int B = (int)E.size();
     nemgpu_engine* lead = E[0];
     const int k = lead->k, d = lead->d;
-    const size_t kd = (size_t)k * d, W = 12 + lead->par_words;
+    const size_t kd = (size_t)k * d;
     std::vector<Recorder> recs((size_t)B);
-    std::vector<int> members((size_t)B), left((size_t)B), it_no((size_t)B, 0), oldbuf((size_t)B, 0), newbuf((size_t)B, 0);
+    std::vector<int> members((size_t)B), left((size_t)B), it_no((size_t)B, 0);
     for (int i = 0; i < B; i++) { members[i] = i; left[i] = L[i].remaining; }
-    char* st_dev = nullptr; char* st_host = nullptr; size_t dev_size = 0, host_size = 0;
-    HIPCHK(pool_get(lead->device, false, (size_t)B * W * sizeof(float), &st_dev, &dev_size));
-    if (pool_get(lead->device, true, (size_t)B * W * sizeof(float), &st_host, &host_size) != hipSuccess) {
-        pool_put(lead->device, false, st_dev, dev_size);
-        set_error("no pinned memory for the starts' log lines"); return NEMGPU_E_DEVICE;
-    }
-    struct Back { int dev; char* a; size_t as; char* b; size_t bs; hipStream_t s; ~Back() { (void)hipStreamSynchronize(s); pool_put(dev, false, a, as); pool_put(dev, true, b, bs); } }
-        back{lead->device, st_dev, dev_size, st_host, host_size, lead->stream};
-    auto slot_dev = [&](int m) { return reinterpret_cast<int*>(st_dev) + (size_t)m * W; };
-    auto slot_host = [&](int m) { return reinterpret_cast<const float*>(st_host) + (size_t)m * W; };
-    auto fetch = [&]() -> int {
-        HIPCHK(hipMemcpyAsync(st_host, st_dev, (size_t)B * W * sizeof(float), hipMemcpyDeviceToHost, lead->stream));
-        HIPCHK(hipStreamSynchronize(lead->stream));
-        return NEMGPU_OK;
-    };
+    LogSlot slot{lead};
+    if ((r = slot.st.get_both(slot.bytes(B), "no pinned memory for the starts' log lines"))) return r;
     auto two_criteria = [&](int m, int before, int after) -> int {   // (recorded: zipped over the members)
         nemgpu_engine* c = E[m];
         int rr = criteria_enqueue(c, before);
-        if (rr == NEMGPU_OK) launch_copy_words(reinterpret_cast<const int*>(c->crit6_dev), slot_dev(m), 6, lead->stream);
+        if (rr == NEMGPU_OK) HIPCHK(slot.put(m, LogSlot::kBefore, c->crit6_dev));
         if (rr == NEMGPU_OK) rr = criteria_enqueue(c, after);
-        if (rr == NEMGPU_OK) launch_copy_words(reinterpret_cast<const int*>(c->crit6_dev), slot_dev(m) + 6, 6, lead->stream);
+        if (rr == NEMGPU_OK) HIPCHK(slot.put(m, LogSlot::kAfter, c->crit6_dev));
         return rr;
     };
     // ---- line 0: the initial partition (before: the blind sweep's, buffer 1; after: the beta sweep's, buffer 2)
     if ((r = lockstep(E, members, recs, [&](int m) { return two_criteria(m, 1, 2); }, false))) return r;
-    if ((r = fetch())) return r;
+    HIPCHK(slot.fetch(B));
     for (int m = 0; m < B; m++) {
-        StartLogLine ln;
-        ln.iter = 0;
-        memcpy(ln.cb, slot_host(m), sizeof ln.cb); memcpy(ln.ca, slot_host(m) + 6, sizeof ln.ca);
-        const float* p0 = host_par + (size_t)m * par;
-        ln.prop.assign(p0, p0 + k); ln.center.assign(p0 + k, p0 + k + kd); ln.disp.assign(p0 + k + kd, p0 + k + 2 * kd);
-        logs[(size_t)m].lines.push_back(std::move(ln));
+        LogLine ln = slot.line(m, 0);                              // (its criteria; the parameters are the start's own, no sizes yet)
+        ln.prop = host_par + (size_t)m * par; ln.center = ln.prop + k; ln.disp = ln.center + kd; ln.nb = nullptr;
+        logs[(size_t)m].emplace_back(ln, (size_t)k, kd);
     }
     // ---- one iteration per step for every start that still runs
+    float cb[6], ca[6];
+    std::vector<float> own((size_t)2 * k + 2 * kd);                // (a line the host puts together: prop | center | disp | sizes)
+    float* const own_nb = own.data() + k + 2 * kd;
     for (;;) {
         members.clear();
         for (int i = 0; i < B; i++) if (left[i] > 0 && !E[i]->converged && E[i]->status == NEMGPU_OK) members.push_back(i);
         if (members.empty()) break;
-        r = lockstep(E, members, recs, [&](int m) {
+        r = lockstep(E, members, recs, [&](int m) -> int {
             nemgpu_engine* c = E[m];
             L[m].remaining = 1;
             int rr = batch_plan(c, L[m]);
-            oldbuf[m] = L[m].base; newbuf[m] = (L[m].base + 1) % 3;
+            const int oldbuf = L[m].base, newbuf = (L[m].base + 1) % 3;
             if (rr == NEMGPU_OK) rr = batch_enqueue(c, L[m], false);
-            if (rr == NEMGPU_OK) rr = two_criteria(m, oldbuf[m], newbuf[m]);     // (speculated: void if the sweep was not through)
-            if (rr == NEMGPU_OK) launch_copy_words(reinterpret_cast<const int*>(c->prop), slot_dev(m) + 12, (int)c->par_words, lead->stream);
+            if (rr == NEMGPU_OK) rr = two_criteria(m, oldbuf, newbuf);           // (speculated: void if the sweep was not through)
+            if (rr == NEMGPU_OK) HIPCHK(slot.put(m, LogSlot::kPar, c->prop));
             return rr;
         }, true);
         if (r) return r;
-        if ((r = fetch())) return r;
+        HIPCHK(slot.fetch(B));
         for (int m : members) {
             nemgpu_engine* c = E[m];
             const bool clean = c->h_ctrl()[C_NEED_ROUNDS] == 0 && c->h_ctrl()[C_STATUS] != NEMGPU_W_EMPTYCLASS;
             c->n_plain++;
             if ((r = batch_finish(c, L[m]))) return r;
             left[m] -= 1; it_no[m] += 1;
-            StartLogLine ln;
-            ln.iter = it_no[m];
+            LogLine ln = slot.line(m, it_no[m]);
             if (c->status == NEMGPU_W_EMPTYCLASS) {
-                // EstimSizes (nem_mod.c:1275-1317) ran before the empty class was found: i-ordered float sums per class
-                std::vector<float> part((size_t)c->n * k);
-                if ((r = nemgpu_get_partition(c, part.data()))) return r;
-                ln.kind = NEMGPU_LOG_EMPTY; ln.emptyk = c->emptyk; ln.nb.assign((size_t)k, 0.0f); ln.has_nb = true;
-                for (int h = 0; h < k; h++) {
-                    float acc = 0.0f;
-                    for (int i = 0; i < c->n; i++) acc += part[(size_t)i * k + h];
-                    ln.nb[(size_t)h] = acc;
-                }
-                logs[(size_t)m].lines.push_back(std::move(ln));
-                continue;
+                if ((r = estim_sizes_host(c, own_nb))) return r;
+                ln = LogLine::empty(it_no[m], c->emptyk, own_nb);
+            } else if (!clean) {                                   // (the sweep was finished from the host, this start alone)
+                ln.cb = cb; ln.ca = ca; ln.prop = own.data(); ln.center = ln.prop + k; ln.disp = ln.center + kd; ln.nb = own_nb;
+                if ((r = plain_line(c, cb, ca, own.data(), own.data() + k, own.data() + k + kd, own_nb))) return r;
             }
-            ln.prop.resize((size_t)k); ln.center.resize(kd); ln.disp.resize(kd); ln.nb.resize((size_t)k); ln.has_nb = true;
-            if (clean) {
-                const float* f = slot_host(m);
-                memcpy(ln.cb, f, sizeof ln.cb); memcpy(ln.ca, f + 6, sizeof ln.ca);
-                memcpy(ln.prop.data(), f + 12, sizeof(float) * k);
-                memcpy(ln.center.data(), f + 12 + c->par_o_center, sizeof(float) * kd);
-                memcpy(ln.disp.data(), f + 12 + c->par_o_disp, sizeof(float) * kd);
-                memcpy(ln.nb.data(), f + 12 + c->par_o_nb, sizeof(float) * k);
-            } else {
-                // (the sweep was finished from the host: the plain sequence of calls, this start alone)
-                if ((r = criteria(c, ln.cb, (c->cur + 2) % 3)) || (r = criteria(c, ln.ca, -1))) return r;
-                if ((r = nemgpu_get_results(c, ln.prop.data(), ln.center.data(), ln.disp.data(), ln.nb.data(), nullptr))) return r;
-            }
-            logs[(size_t)m].lines.push_back(std::move(ln));
+            logs[(size_t)m].emplace_back(ln, (size_t)k, kd);
         }
     }
     for (int i = 0; i < B; i++) L[i].remaining = 0;
@@ -3045,15 +3093,8 @@ static int iterate_logged_impl(nemgpu_engine* e, int with_init, bool keep_draws,
     HIPCHK(hipStreamSynchronize(e->stream));
     const auto t0 = std::chrono::steady_clock::now();
     int r;
-    auto plain_tail = [&]() -> int {
-        if (e->status == NEMGPU_W_EMPTYCLASS) return NEMGPU_OK;          // (the E-step did not run: nothing to log)
-        int rr;
-        if ((rr = criteria(e, crit_before, (e->cur + 2) % 3))) return rr;
-        if ((rr = criteria(e, crit_after, -1))) return rr;
-        return nemgpu_get_results(e, prop, center, disp, nbobs_k, nullptr);
-    };
     bool speculated = false;
-    char* st = nullptr; size_t got = 0;
+    LogSlot slot{e};                                               // (the pinned side alone: the line comes by copy commands)
     if (with_init && (crit_test(e) || e->libc() || !(e->lo == 0 && e->hi == e->n_total))) {
         // (the start whose two sweeps the host completes one after the other: the plain sequence of calls)
         const int draws = e->draws;
@@ -3074,38 +3115,35 @@ static int iterate_logged_impl(nemgpu_engine* e, int with_init, bool keep_draws,
             if ((r = batch_plan(e, lc))) return r;
             // (a start: the blind sweep's partition is in buffer 1, the beta sweep's in 2)
             const int oldbuf = with_init ? 1 : lc.base, newbuf = with_init ? 2 : (lc.base + 1) % 3;
-            const size_t words = 12 + e->par_words;
-            if (pool_get(e->device, true, words * sizeof(float), &st, &got) != hipSuccess) { (void)hipGetLastError(); st = nullptr; }
+            if (slot.st.get(true, slot.bytes(1)) != hipSuccess) (void)hipGetLastError();   // (without it: the plain sequence below)
             e->n_plain++;
-            if ((r = batch_enqueue(e, lc, true))) { if (st) pool_put(e->device, true, st, got); return r; }
-            if (st) {
-                float* f = reinterpret_cast<float*>(st);
-                r = criteria_pair_enqueue(e, newbuf, oldbuf);                  // both partitions in the same launches
-                if (r == NEMGPU_OK) HIPCHK(hipMemcpyAsync(f, e->crit2_6, 6 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-                if (r == NEMGPU_OK) HIPCHK(hipMemcpyAsync(f + 6, e->crit6_dev, 6 * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-                if (r == NEMGPU_OK) HIPCHK(hipMemcpyAsync(f + 12, e->prop, e->par_words * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-                if (r) { (void)hipStreamSynchronize(e->stream); pool_put(e->device, true, st, got); return r; }
+            if ((r = batch_enqueue(e, lc, true))) return r;
+            if (slot.st.host) {
+                if ((r = criteria_pair_enqueue(e, newbuf, oldbuf))) return r;   // both partitions in the same launches
+                HIPCHK(slot.put(0, LogSlot::kBefore, e->crit2_6));
+                HIPCHK(slot.put(0, LogSlot::kAfter, e->crit6_dev));
+                HIPCHK(slot.put(0, LogSlot::kPar, e->prop));
             }
             HIPCHK(hipStreamSynchronize(e->stream));
             const bool clean = e->h_ctrl()[C_NEED_ROUNDS] == 0 && e->h_ctrl()[C_STATUS] != NEMGPU_W_EMPTYCLASS;
-            if ((r = batch_finish(e, lc))) { if (st) pool_put(e->device, true, st, got); return r; }
-            speculated = st != nullptr && clean;
+            if ((r = batch_finish(e, lc))) return r;
+            speculated = slot.st.host != nullptr && clean;
         }
     } else {
         if ((r = iterate(e, 1))) return r;
     }
     if (speculated) {
-        const float* f = reinterpret_cast<const float*>(st);
-        memcpy(crit_before, f, 6 * sizeof(float));
-        memcpy(crit_after, f + 6, 6 * sizeof(float));
+        const LogLine ln = slot.line(0, 0);
         const size_t kd = (size_t)e->k * e->d;
-        if (prop) memcpy(prop, f + 12, sizeof(float) * e->k);
-        if (center) memcpy(center, f + 12 + e->par_o_center, sizeof(float) * kd);
-        if (disp) memcpy(disp, f + 12 + e->par_o_disp, sizeof(float) * kd);
-        if (nbobs_k) memcpy(nbobs_k, f + 12 + e->par_o_nb, sizeof(float) * e->k);
+        memcpy(crit_before, ln.cb, 6 * sizeof(float)); memcpy(crit_after, ln.ca, 6 * sizeof(float));
+        if (prop) memcpy(prop, ln.prop, sizeof(float) * e->k);
+        if (center) memcpy(center, ln.center, sizeof(float) * kd);
+        if (disp) memcpy(disp, ln.disp, sizeof(float) * kd);
+        if (nbobs_k) memcpy(nbobs_k, ln.nb, sizeof(float) * e->k);
     }
-    if (st) pool_put(e->device, true, st, got);
-    if (!speculated && (r = plain_tail())) return r;
+    slot.st.put();
+    if (!speculated && e->status != NEMGPU_W_EMPTYCLASS &&           // (an emptied class: the E-step did not run, nothing to log)
+        (r = plain_line(e, crit_before, crit_after, prop, center, disp, nbobs_k))) return r;
     HIPCHK(hipStreamSynchronize(e->stream));
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     fill_result(e, res);
@@ -3138,19 +3176,14 @@ int nemgpu_run_logged(nemgpu_engine* e, nemgpu_result* res, nemgpu_log_fn fn, vo
     std::vector<float> prop((size_t)k), center(kd), disp(kd), nb((size_t)k);
     float cb[6], ca[6];
     nemgpu_result r1{};
-    auto emit_line = [&](int iter, const float* b, const float* a, const float* p, const float* c, const float* s, const float* sizes) {
-        nemgpu_log_event ev{};
-        ev.kind = NEMGPU_LOG_LINE; ev.start = 0; ev.iter = iter; ev.crit_before = b; ev.crit_after = a;
-        ev.prop = p; ev.center = c; ev.disp = s; ev.nbobs_k = sizes;
-        fn(&ev, user);
-    };
+    auto emit_own = [&](int iter, const float* sizes) { emit(fn, user, 0, LogLine{NEMGPU_LOG_LINE, iter, 0, cb, ca, prop.data(), center.data(), disp.data(), sizes}); };
     const auto t0 = std::chrono::steady_clock::now();
     static const bool prof = getenv("NEM_MI355X_BATCH_PROF") != nullptr;
     auto lapt = t0;
     auto lap = [&](const char* what) { if (prof) { const auto now = std::chrono::steady_clock::now(); fprintf(stderr, "[logged run] %s: %.0f us\n", what, std::chrono::duration<double, std::micro>(now - lapt).count()); lapt = now; } };
     // ---- line 0: the start (reset, the two initial sweeps), both criteria, the parameters
     if ((r = iterate_logged_impl(e, 1, false, &r1, cb, ca, prop.data(), center.data(), disp.data(), nb.data()))) return r;
-    emit_line(0, cb, ca, prop.data(), center.data(), disp.data(), nullptr);   // (no EstimPara yet: no sizes, as the header says)
+    emit_own(0, nullptr);                                          // (no EstimPara yet: no sizes, as the header says)
     lap("line 0 (start, two criteria)");
     static const bool batched_on = !(getenv("NEM_MI355X_LOG_BATCHED") && getenv("NEM_MI355X_LOG_BATCHED")[0] == '0');
     const bool batched = batched_on && e->ncem() && !crit_test(e) && e->lo == 0 && e->hi == e->n_total && e->parent == nullptr;
@@ -3160,11 +3193,11 @@ int nemgpu_run_logged(nemgpu_engine* e, nemgpu_result* res, nemgpu_log_fn fn, vo
         for (int iter = 1; iter <= e->cfg.it_max && !e->converged && e->status == NEMGPU_OK; iter++) {
             if ((r = iterate_logged_impl(e, 0, false, &r1, cb, ca, prop.data(), center.data(), disp.data(), nb.data()))) return r;
             if (e->status == NEMGPU_W_EMPTYCLASS) {
-                nemgpu_log_event ev{}; ev.kind = NEMGPU_LOG_EMPTY; ev.iter = iter; ev.emptyk = e->emptyk; fn(&ev, user);
+                emit(fn, user, 0, LogLine::empty(iter, e->emptyk, nullptr));   // (no sizes: only a random start hands them on)
                 last_logged = false;
                 break;
             }
-            emit_line(iter, cb, ca, prop.data(), center.data(), disp.data(), nb.data());
+            emit_own(iter, nb.data());
             last_logged = true;
         }
     } else {
@@ -3173,15 +3206,8 @@ int nemgpu_run_logged(nemgpu_engine* e, nemgpu_result* res, nemgpu_log_fn fn, vo
         if ((r = ensure_clones(e, 2 * kPipeDepth))) return r;
         for (nemgpu_engine* c : e->clones) { c->cfg = e->cfg; c->stream = e->stream; }
         std::vector<nemgpu_engine*> T(e->clones.begin(), e->clones.begin() + 2 * kPipeDepth);
-        const size_t W = 12 + e->par_words;
-        char* st_dev = nullptr; char* st_host = nullptr; size_t dev_size = 0, host_size = 0;
-        HIPCHK(pool_get(e->device, false, (size_t)kPipeDepth * W * sizeof(float), &st_dev, &dev_size));
-        if (pool_get(e->device, true, (size_t)kPipeDepth * W * sizeof(float), &st_host, &host_size) != hipSuccess) {
-            pool_put(e->device, false, st_dev, dev_size);
-            set_error("no pinned memory for the log lines"); return NEMGPU_E_DEVICE;
-        }
-        struct Back { int dev; char* a; size_t as; char* b; size_t bs; hipStream_t s; ~Back() { (void)hipStreamSynchronize(s); pool_put(dev, false, a, as); pool_put(dev, true, b, bs); } }
-            back{e->device, st_dev, dev_size, st_host, host_size, e->stream};
+        LogSlot slot{e};
+        if ((r = slot.st.get_both(slot.bytes(kPipeDepth), "no pinned memory for the log lines"))) return r;
         std::vector<Recorder> recs((size_t)2 * kPipeDepth);
         lap("twins and staging");
         int iter = 0;
@@ -3207,7 +3233,7 @@ int nemgpu_run_logged(nemgpu_engine* e, nemgpu_result* res, nemgpu_log_fn fn, vo
                     seg(e->pkfki, c->pkfki, sizeof(double) * (size_t)k * e->npad);
                     seg(e->logpkfki, c->logpkfki, sizeof(float) * (size_t)k * e->npad);
                 }
-                seg(e->prop, reinterpret_cast<float*>(st_dev) + (size_t)j * W + 12, sizeof(float) * e->par_words);
+                seg(e->prop, slot.par_dev(j), sizeof(float) * e->par_words);
                 cs.n = q;
                 launch_copy_segments(cs, e->stream);                // (one launch: seven copy commands were 28 us of issue time per iteration)
                 HIPCHK(hipGetLastError());
@@ -3228,20 +3254,15 @@ int nemgpu_run_logged(nemgpu_engine* e, nemgpu_result* res, nemgpu_log_fn fn, vo
                 std::vector<nemgpu_engine*> TT(T.begin(), T.begin() + 2 * whole);
                 std::vector<int> all((size_t)2 * whole);
                 for (int m = 0; m < 2 * whole; m++) all[(size_t)m] = m;
-                if ((r = lockstep(TT, all, recs, [&](int m) {
+                if ((r = lockstep(TT, all, recs, [&](int m) -> int {   // (twin m: iteration m / 2, before or after)
                         nemgpu_engine* c = TT[(size_t)m];
-                        int* slot = reinterpret_cast<int*>(st_dev) + (size_t)(m / 2) * W + (m % 2) * 6;
                         const int rr = criteria_enqueue(c, 0);
-                        if (rr == NEMGPU_OK) launch_copy_words(reinterpret_cast<const int*>(c->crit6_dev), slot, 6, e->stream);
+                        if (rr == NEMGPU_OK) HIPCHK(slot.put(m / 2, m % 2 ? LogSlot::kAfter : LogSlot::kBefore, c->crit6_dev));
                         return rr;
                     }, false))) return r;
-                HIPCHK(hipMemcpyAsync(st_host, st_dev, (size_t)whole * W * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-                HIPCHK(hipStreamSynchronize(e->stream));
-                for (int m = 0; m < whole; m++) {
-                    const float* f = reinterpret_cast<const float*>(st_host) + (size_t)m * W;
-                    emit_line(iter + m + 1, f, f + 6, f + 12, f + 12 + e->par_o_center, f + 12 + e->par_o_disp, f + 12 + e->par_o_nb);
-                    if (m == whole - 1) memcpy(ca, f + 6, sizeof ca);
-                }
+                HIPCHK(slot.fetch(whole));
+                for (int m = 0; m < whole; m++) emit(fn, user, 0, slot.line(m, iter + m + 1));
+                memcpy(ca, slot.line(whole - 1, 0).ca, sizeof ca);
                 last_logged = true;
                 lap("its criteria and lines");
             }
@@ -3249,14 +3270,12 @@ int nemgpu_run_logged(nemgpu_engine* e, nemgpu_result* res, nemgpu_log_fn fn, vo
             if (tail_open && done > 0) {
                 iter += 1;
                 if (e->status == NEMGPU_W_EMPTYCLASS) {
-                    nemgpu_log_event ev{}; ev.kind = NEMGPU_LOG_EMPTY; ev.iter = iter; ev.emptyk = e->emptyk; fn(&ev, user);
+                    emit(fn, user, 0, LogLine::empty(iter, e->emptyk, nullptr));
                     last_logged = false;
                     break;
                 }
-                // (its sweep was finished from the host: the plain sequence of calls)
-                if ((r = criteria(e, cb, (e->cur + 2) % 3)) || (r = criteria(e, ca, -1))) return r;
-                if ((r = nemgpu_get_results(e, prop.data(), center.data(), disp.data(), nb.data(), nullptr))) return r;
-                emit_line(iter, cb, ca, prop.data(), center.data(), disp.data(), nb.data());
+                if ((r = plain_line(e, cb, ca, prop.data(), center.data(), disp.data(), nb.data()))) return r;   // (its sweep was finished from the host)
+                emit_own(iter, nb.data());
                 last_logged = true;
             }
             if (done == 0) break;                                  // (nothing ran: the loop tests above end it)
@@ -4557,7 +4576,7 @@ static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, ne
             for (int j = 0; j < M; j++) if ((r = loop_begin(E[j], L[j], e->cfg.it_max, true))) return r;
         }
         // ---- the EM iterations in lock step (TIE_LIBC: phase B)
-        std::vector<StartLog> logs((size_t)(fn ? M : 0));
+        std::vector<std::vector<StartLogLine>> logs((size_t)(fn ? M : 0));
         if (fn) {
             if (!e->libc()) {                                       // (the initial partitions first: a batch of no iterations)
                 for (int j = 0; j < M; j++) L[j].remaining = 0;
@@ -4579,17 +4598,8 @@ static int run_random_lockstep(nemgpu_engine* e, int n_starts, uint32_t seed, ne
         if (fn) {
             // the round's lines to the caller's writer, start by start in the reference's order
             for (int j = 0; j < M; j++) {
-                nemgpu_log_event ev{};
-                ev.kind = NEMGPU_LOG_START; ev.start = next + j;
-                fn(&ev, user);
-                for (const StartLogLine& ln : logs[(size_t)j].lines) {
-                    ev = nemgpu_log_event{};
-                    ev.kind = ln.kind; ev.start = next + j; ev.iter = ln.iter; ev.emptyk = ln.emptyk;
-                    ev.crit_before = ln.cb; ev.crit_after = ln.ca;
-                    ev.prop = ln.prop.data(); ev.center = ln.center.data(); ev.disp = ln.disp.data();
-                    ev.nbobs_k = ln.has_nb ? ln.nb.data() : nullptr;
-                    fn(&ev, user);
-                }
+                emit(fn, user, next + j, LogLine{NEMGPU_LOG_START});
+                for (const StartLogLine& ln : logs[(size_t)j]) emit(fn, user, next + j, ln.v);
             }
         }
         for (int j = 0; j < valid; j++)
@@ -4640,7 +4650,7 @@ static int run_random_impl(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu
         }
     }
     int r;
-    const int n = e->n, k = e->k;
+    const int k = e->k;
     const size_t kd = (size_t)k * e->d;
     RandomStarts rs;
     if ((r = rs.begin(e, seed))) return r;
@@ -4656,34 +4666,21 @@ static int run_random_impl(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu
             // the same, step by step: a line per iteration
             if ((r = rs.upload(prop.data(), center.data(), disp.data()))) return r;
             bool have_crit = false;
-            nemgpu_log_event ev{};
-            ev.kind = NEMGPU_LOG_START; ev.start = s;
-            fn(&ev, user);
+            emit(fn, user, s, LogLine{NEMGPU_LOG_START});
             float cb[6], ca[6];
             std::vector<float> nb((size_t)k);
             nemgpu_result r1{};
+            auto own = [&](int iter, const float* sizes) { return LogLine{NEMGPU_LOG_LINE, iter, 0, cb, ca, prop.data(), center.data(), disp.data(), sizes}; };
             if ((r = iterate_logged_impl(e, 1, true, &r1, cb, ca, prop.data(), center.data(), disp.data(), nullptr))) return r;
-            ev.kind = NEMGPU_LOG_LINE; ev.iter = 0; ev.crit_before = cb; ev.crit_after = ca;
-            ev.prop = prop.data(); ev.center = center.data(); ev.disp = disp.data(); ev.nbobs_k = nullptr;
-            fn(&ev, user);
+            emit(fn, user, s, own(0, nullptr));
             for (int iter = 1; iter <= e->cfg.it_max && !e->converged && e->status == NEMGPU_OK; iter++) {
                 if ((r = iterate_logged_impl(e, 0, true, &r1, cb, ca, prop.data(), center.data(), disp.data(), nb.data()))) return r;
-                ev.iter = iter; ev.nbobs_k = nb.data();
                 if (e->status == NEMGPU_W_EMPTYCLASS) {
-                    // EstimSizes (nem_mod.c:1275-1317) ran before the empty class was found: i-ordered float sums per class
-                    std::vector<float> part((size_t)n * k);
-                    if ((r = nemgpu_get_partition(e, part.data()))) return r;
-                    for (int h = 0; h < k; h++) {
-                        float acc = 0.0f;
-                        for (int i = 0; i < n; i++) acc += part[(size_t)i * k + h];
-                        nb[(size_t)h] = acc;
-                    }
-                    ev.kind = NEMGPU_LOG_EMPTY; ev.emptyk = e->emptyk;
-                    fn(&ev, user);
+                    if ((r = estim_sizes_host(e, nb.data()))) return r;
+                    emit(fn, user, s, LogLine::empty(iter, e->emptyk, nb.data()));
                     break;
                 }
-                ev.kind = NEMGPU_LOG_LINE;
-                fn(&ev, user);
+                emit(fn, user, s, own(iter, nb.data()));
                 memcpy(crit, ca, sizeof crit);                     // (of the final partition, on the final densities, if the run ends here)
                 have_crit = true;
             }

@@ -271,6 +271,30 @@ int nemgpu_master_create_orders(nemgpu_master** out, int device, int d, int f, i
 int nemgpu_master_append_orders(nemgpu_master** out, const nemgpu_master* m, int d_new, int f, const int32_t* genes, int g,
                                 const int32_t* contig_ptr, const int32_t* contig_org, const uint8_t* contig_circular, int c,
                                 const uint8_t* repeated);
+/* Two masters MERGED on the device: PPanGGOLiN's `+=` (__iadd__, ppanggolin.py:368-391, "add a pangenome to this
+   pangenome"), which throws the graph away and walks every annotation of both pangenomes again.  *out is a new master on
+   a's device (its own allocation and stream) = the union of the two graphs as nx.Graph would hold it had b's organisms
+   been walked after a's; a and b are only read and stay valid (a nemgpu_votes made for them or a nemgpu_solve_chunks
+   running on them is not disturbed; the caller destroys them).  Neither master's arrays cross PCIe: b's family ids and
+   a's numbering go up, the new sizes and the new families' ids come back.
+     ids_b[b's n]         HOST: the id of b's family j in a's id space, distinct, in [0, f); NULL: b's own numbering
+                          (nemgpu_master_fetch's `order`), that is, one id space shared by both;
+     f                    the id space of the merged master (>= the f a was made with, above every id of b).
+   Organisms: a's columns, then b's as d_a .. d_a + d_b - 1.  Families: a's keep their numbers, b's whose id a lacks are
+   numbered n_a, n_a + 1, ... in b's order.  Rows: an entry of a keeps its place; an entry of b that a lacks goes behind
+   the row's entries of a, in the order b's row lists them; a self-loop stays one entry.  Per entry: edge_bits (stride
+   ceil((d_a + d_b) / 32)) = a's words, the bits above organism d_a - 1 dropped, OR b's bits shifted up by d_a bits; the
+   extras a's, then b's with organism + d_a; counts unchanged.  Presence: a's rows re-strided, b's with their family bits
+   permuted.  chunks.master_arrays_merge states it in numpy.  With the same `repeated` for both parts, merging the master
+   of B into the master of A is nemgpu_master_create_orders of A + B, array for array; a family repeated in one part
+   alone keeps the node and the edges the other part gave it (nemgpu_master_append_orders' rule).
+   Refused on the host before any HIP call (NEMGPU_E_ARG, nemgpu_last_error says why): f <= 0, a master built with
+   directed = 1 or a bits-only master on either side, masters on different devices, f below a's id space or not above
+   every id of b, an id of b out of range or used twice, more than 131 072 organisms in all.  After the numbering:
+   2 bits(n) + bits(d) <= 63 (the merged master stays one that nemgpu_master_append_orders accepts); after the plan: at
+   most 2^31 - 1 entries and extras; an entry's count in a + its count in b may not exceed 2^24 (checked on the device,
+   reported as create reports it).  out, a or b NULL: NEMGPU_E_FUNCARG. */
+int nemgpu_master_merge(nemgpu_master** out, const nemgpu_master* a, const nemgpu_master* b, const int32_t* ids_b, int f);
 /* A partition PROJECTED onto the organisms from the master: what PPanGGOLiN.projection (ppanggolin.py:1698-1755; the
    CLI's -pr; the first step of partition_shell(Q = "auto"), :1190-1192) counts and writes, as arrays, with no graph and
    no per-gene loop on the host.  HOST arrays; m is only read and stays valid and unchanged; the work runs on m's stream

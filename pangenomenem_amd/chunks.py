@@ -21,7 +21,9 @@ twice in an organism (tandem duplicates, repeated operons and every edge of a di
 (``nemgpu_master_create_orders``, csrc/nem_orders.hip): no graph, no networkx; ``master_arrays_from_orders`` is that build
 in numpy.  ``Master.add_orders`` / ``Master.add_annotations`` grow a master by new organisms
 (PPanGGOLiN.add_organism, ppanggolin.py:342-358) from their gene orders alone (``nemgpu_master_append_orders``);
-``master_arrays_append_orders`` is that append in numpy.
+``master_arrays_append_orders`` is that append in numpy.  ``Master.merge`` / ``Master.merge_named`` join two resident masters
+(PPanGGOLiN.__iadd__, ppanggolin.py:368-391) from the masters alone (``nemgpu_master_merge``, csrc/nem_merge.hip);
+``master_arrays_merge`` is that merge in numpy.
 
 ``Master`` puts that one pangenome on the device (``nemgpu_master_create[_counts]``); ``solve_chunks`` solves any number of
 samples in ONE library call (``nemgpu_solve_chunks``): the device forms every sample's problem straight into its engine's
@@ -66,6 +68,7 @@ def _bind_master(lib):
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.nemgpu_master_append_orders.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.nemgpu_master_merge.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.nemgpu_master_project.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
     lib.nemgpu_master_shape.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
     lib.nemgpu_master_fetch.argtypes = [C.c_void_p] * 9
@@ -425,6 +428,92 @@ def master_arrays_append_orders(master_arrays, order, f_old, genes, contig_ptr, 
     return x, (ptr.astype(np.int32), idx), edge_bits, edge_counts, grown_order, list(range(d))
 
 
+def master_arrays_merge(a_arrays, order_a, b_arrays, ids_b):
+    """The master that master_arrays_from_graph makes of the union of two nx.Graphs, had B's organisms been walked after
+    A's (PPanGGOLiN.__iadd__, ppanggolin.py:368-391, which rebuilds the graph from both pangenomes' annotations), from the
+    two masters' arrays alone, in numpy: the statement of what nemgpu_master_merge computes.  a_arrays, b_arrays:
+    (x uint8 [n][d], (ptr, idx), edge_bits, edge_counts, ...) of undirected masters with known counts; order_a int [n_a]:
+    A's family i is caller id order_a[i]; ids_b int [n_b]: the id of B's family j in A's id space (distinct).
+      * organisms: A's columns 0 .. d_a - 1, then B's in B's order as d_a .. d_a + d_b - 1;
+      * families: A's keep their numbers; B's whose id A lacks are numbered n_a, n_a + 1, ... in B's order;
+      * an entry (row, neighbour) of A keeps its place; an entry of B whose (mapped row, mapped neighbour) A lacks goes
+        behind the row's A entries, in the order B's row lists them; a row new in B is B's row, mapped;
+      * edge_bits (stride ceil((d_a + d_b) / 32)): A's bits below d_a, B's bits d_a further up; the extras A's, then B's
+        with organism + d_a, counts unchanged; an entry's total count (A's + B's) may not exceed 2^24;
+      * presence: A's rows, B's with their families mapped; absent elsewhere.
+    It equals master_arrays_from_orders of A's orders followed by B's only when both were built with the same repeated
+    families: a family repeated in one part alone keeps the node and the edges the other part gave it.
+    Returns what master_arrays_from_orders returns: x, (ptr, idx), edge_bits, edge_counts, order (grown), range(d_a + d_b)."""
+    def parts(m):
+        x = np.asarray(m[0], np.uint8)
+        ptr, idx = (np.asarray(v, np.int64) for v in m[1])
+        n, d = x.shape
+        eb = np.ascontiguousarray(m[2], np.uint32).reshape(len(idx), (d + 31) // 32)
+        xptr, xorg, xcnt = (np.asarray(v, np.int64) for v in m[3])
+        if ptr.shape != (n + 1,) or xptr.shape != (len(idx) + 1,) or len(xorg) != len(xcnt):
+            raise ValueError("merge: a master's arrays")
+        bits = np.unpackbits(eb.view(np.uint8), axis=1, bitorder="little")[:, :d] if len(idx) else np.zeros((0, d), np.uint8)
+        return x, ptr, idx, bits, xptr, xorg, xcnt, np.repeat(np.arange(n, dtype=np.int64), np.diff(ptr))
+
+    xa, ptr_a, idx_a, bits_a, xptr_a, xorg_a, xcnt_a, row_a = parts(a_arrays)
+    xb, ptr_b, idx_b, bits_b, xptr_b, xorg_b, xcnt_b, row_b = parts(b_arrays)
+    (n_a, d_a), (n_b, d_b) = xa.shape, xb.shape
+    nnz_a, nnz_b = len(idx_a), len(idx_b)
+    order_a, ids_b = np.asarray(order_a, np.int64), np.asarray(ids_b, np.int64)
+    if order_a.shape != (n_a,) or ids_b.shape != (n_b,):
+        raise ValueError("merge: order_a [n_a] and ids_b [n_b]")
+    if (len(ids_b) and ids_b.min() < 0) or len(np.unique(ids_b)) != n_b or len(np.unique(order_a)) != n_a:
+        raise ValueError("merge: distinct family ids, none negative")
+    # the numbering
+    table = np.full(int(max(order_a.max(initial=-1), ids_b.max(initial=-1))) + 1, -1, np.int64)
+    table[order_a] = np.arange(n_a)
+    new = table[ids_b] < 0
+    mapb = np.where(new, n_a + np.cumsum(new) - 1, table[ids_b])
+    n, d = n_a + int(new.sum()), d_a + d_b
+    order = np.concatenate([order_a, ids_b[new]]).astype(np.int32)
+    x = np.zeros((n, d), np.uint8)
+    x[:n_a, :d_a] = xa
+    x[mapb, d_a:] = xb
+    # every entry of B in A's row, or new
+    r, c = mapb[row_b], mapb[idx_b]
+    akey = row_a * n + idx_a
+    by = np.argsort(akey, kind="stable")
+    at = np.searchsorted(akey[by], r * n + c)
+    found = np.zeros(nnz_b, bool)
+    inside = at < nnz_a
+    found[inside] = akey[by][at[inside]] == (r * n + c)[inside]
+    deg_a = np.zeros(n, np.int64)
+    deg_a[:n_a] = np.diff(ptr_a)
+    ptr = np.zeros(n + 1, np.int64)
+    ptr[1:] = np.cumsum(deg_a + np.bincount(r[~found], minlength=n))
+    nnz = int(ptr[-1])
+    fwd_a = ptr[row_a] + (np.arange(nnz_a) - ptr_a[row_a])    # A's entry t -> its entry now
+    before = np.concatenate([[0], np.cumsum(~found)])         # the new entries before B's entry t
+    fwd_b = np.empty(nnz_b, np.int64)
+    fwd_b[found] = fwd_a[by[at[found]]]
+    fwd_b[~found] = (ptr[r] + deg_a[r] + before[:-1] - before[ptr_b[row_b]])[~found]
+    idx = np.empty(nnz, np.int32)
+    idx[fwd_a] = idx_a
+    idx[fwd_b[~found]] = c[~found]
+    wf = (d + 31) // 32
+    bits = np.zeros((nnz, wf * 32), np.uint8)
+    bits[fwd_a, :d_a] = bits_a
+    bits[fwd_b, d_a:d] = bits_b
+    edge_bits = np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little")).view(np.uint32).reshape(nnz, wf)
+    # the extras: an entry's A ones, then its B ones (every column of B lies behind every column of A)
+    xe = np.concatenate([fwd_a[np.repeat(np.arange(nnz_a), np.diff(xptr_a))], fwd_b[np.repeat(np.arange(nnz_b), np.diff(xptr_b))]])
+    xo = np.concatenate([xorg_a, xorg_b + d_a])
+    xc = np.concatenate([xcnt_a, xcnt_b])
+    total = bits.sum(axis=1, dtype=np.int64) + np.bincount(xe, weights=xc - 1, minlength=nnz).astype(np.int64)
+    if nnz and total.max() > 1 << 24:
+        raise ValueError("merge: an edge's total count above 2^24 (a float weight would not be exact)")
+    xs = np.lexsort((xo, xe))
+    xptr = np.zeros(nnz + 1, np.int32)
+    xptr[1:] = np.cumsum(np.bincount(xe, minlength=nnz))
+    edge_counts = (xptr, xo[xs].astype(np.int32), xc[xs].astype(np.int32))
+    return x, (ptr.astype(np.int32), idx), edge_bits, edge_counts, order, list(range(d))
+
+
 class Master:
     """One pangenome on the device: presence/absence matrix, neighbourhood graph, per directed edge its organisms."""
 
@@ -487,11 +576,18 @@ class Master:
     def _of_orders(cls, lib, what, head, genes, contig_ptr, contig_org, contig_circular, repeated, directed, f):
         """the master that the entry point `what` makes of checked gene orders (head: its arguments between the handle
         and the orders), with its numbering read back"""
+        return cls._of_call(lib, what, head + (genes.ctypes.data, len(genes), contig_ptr.ctypes.data, contig_org.ctypes.data,
+                                               contig_circular.ctypes.data, len(contig_org), repeated.ctypes.data if repeated is not None else None),
+                            directed, f)
+
+    @classmethod
+    def _of_call(cls, lib, what, args, directed, f):
+        """the master that the entry point `what` makes on the device (args: its arguments behind the handle), with its
+        numbering read back"""
         m = cls.__new__(cls)
         m.lib = lib
         m._h = C.c_void_p()
-        rc = getattr(lib, what)(C.byref(m._h), *head, genes.ctypes.data, len(genes), contig_ptr.ctypes.data, contig_org.ctypes.data,
-                                contig_circular.ctypes.data, len(contig_org), repeated.ctypes.data if repeated is not None else None)
+        rc = getattr(lib, what)(C.byref(m._h), *args)
         if rc != 0:
             raise NemGpuError("%s failed (status %d): %s" % (what, rc, lib.nemgpu_last_error().decode()))
         m.n, m.d, _, _ = m.shape()
@@ -561,6 +657,46 @@ class Master:
         m.names, m.organism_names = [m.id_names[i] for i in m.order], list(o["organisms"])
         if getattr(self, "repeated_by_organism", None) is not None:
             m.repeated_by_organism = dict(self.repeated_by_organism, **{org: frozenset(repeated) for org in new_organisms})
+        return m
+
+    def merge(self, other, ids=None, f=None):
+        """A NEW master = this one + another resident master (PPanGGOLiN's `+=`, __iadd__, ppanggolin.py:368-391;
+        nemgpu_master_merge; master_arrays_merge states what it computes): the union of the two graphs as built, other's
+        organisms behind this master's.  ids int [other.n]: the id of other's family j in this master's id space
+        (default: other.order, one id space shared by both); f: the merged id space (default: the smallest that holds
+        both).  Both masters are only read and stay usable; neither's arrays leave the device.  Not for a directed
+        master, nor for a bits-only one, on either side.  It equals from_orders of everything only when both masters were
+        built with the same repeated families."""
+        if not isinstance(other, Master):
+            raise TypeError("merge: a Master")
+        if self.directed or other.directed:                   # (the library knows it of a master built from orders; from_graph's is known here)
+            raise NemGpuError("merge: a master was built directed (a row's order cannot be recovered); rebuild it")
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, np.int32)
+            if ids.shape != (other.n,):
+                raise ValueError("merge: ids [other.n]")
+        if f is None:
+            f = max(self.f, other.f) if ids is None else max(self.f, int(ids.max()) + 1 if len(ids) else 1)
+        return Master._of_call(self.lib, "nemgpu_master_merge", (self._h, other._h, ids.ctypes.data if ids is not None else None, int(f)),
+                               False, int(f))
+
+    def merge_named(self, other):
+        """merge() of two masters that carry names (from_annotations, from_files, from_graph or add_annotations): other's
+        families are joined to this master's id_names by name, new names extend them; an organism name that both
+        masters carry raises ValueError.  Returns the new master with .names, .organism_names, .id_names and the union
+        of repeated_by_organism."""
+        if getattr(self, "id_names", None) is None or getattr(other, "id_names", None) is None:
+            raise ValueError("merge_named: both masters must carry names (use merge)")
+        if set(self.organism_names) & set(other.organism_names):
+            raise ValueError("merge_named: an organism that both masters have")
+        fam_id = {name: i for i, name in enumerate(self.id_names)}
+        ids = np.asarray([fam_id.setdefault(name, len(fam_id)) for name in other.names], np.int32)
+        m = self.merge(other, ids=ids, f=max(len(fam_id), self.f))
+        m.id_names = list(fam_id)
+        m.names, m.organism_names = [m.id_names[i] for i in m.order], list(self.organism_names) + list(other.organism_names)
+        mine, theirs = getattr(self, "repeated_by_organism", None), getattr(other, "repeated_by_organism", None)
+        if mine is not None and theirs is not None:
+            m.repeated_by_organism = dict(mine, **theirs)
         return m
 
     def project_orders(self, part, genes, contig_ptr, contig_org, repeated=None, f=None):

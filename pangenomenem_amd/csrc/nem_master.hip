@@ -1,6 +1,6 @@
 // nem_master.hip -- the resident master pangenome's host side: made from arrays (nemgpu_master_create,
 // _create_counts) or on the device from the gene orders (_create_orders, nem_orders.hpp), appended to (_append_orders),
-// projected from (_project, nem_project.hpp), read back (_shape, _fetch) and destroyed.  Everything refused is refused
+// merged with another (_merge, nem_merge.hpp), projected from (_project, nem_project.hpp), read back (_shape, _fetch) and destroyed.  Everything refused is refused
 // on the host before the first HIP call, so the refusals can be tested without a device.
 #include <hip/hip_runtime.h>
 
@@ -10,6 +10,7 @@
 
 #include "nem_internal.hpp"
 #include "nem_master.hpp"
+#include "nem_merge.hpp"
 #include "nem_orders.hpp"
 #include "nem_project.hpp"
 
@@ -257,6 +258,70 @@ int nemgpu_master_append_orders(nemgpu_master** out, const nemgpu_master* old, i
     if (f < old->f_old) { set_error("nemgpu_master_append_orders: f is below the master's " + std::to_string(old->f_old) + " family ids"); return NEMGPU_E_ARG; }
     return master_from_orders(out, old, old->device, "nemgpu_master_append_orders",
                               OrdersIn{d, f, 0, g, c, genes, contig_ptr, contig_org, contig_circular, repeated});
+}
+
+// Two masters merged on the device (nem_merge.hpp): everything that does not need the numbering or the plan is refused on
+// the host before any HIP call
+int nemgpu_master_merge(nemgpu_master** out, const nemgpu_master* a, const nemgpu_master* b, const int32_t* ids_b, int f)
+{
+    if (!out) return NEMGPU_E_FUNCARG;
+    *out = nullptr;
+    const std::string who = "nemgpu_master_merge";
+    if (f <= 0) { set_error(who + ": f must lie above every family id"); return NEMGPU_E_ARG; }
+    if (!a || !b) { set_error(who + ": two masters are needed"); return NEMGPU_E_FUNCARG; }
+    for (const nemgpu_master* m : {a, b}) {
+        const char* side = m == a ? "the first" : "the second";
+        if (m->directed) {
+            set_error(who + ": " + side + " master was built directed (a row's predecessor / successor order cannot be recovered from "
+                      "its summed counts); rebuild it from all the orders");
+            return NEMGPU_E_ARG;
+        }
+        if (m->bits_only) { set_error(who + ": " + side + " master is a bits-only master (nemgpu_master_create): its counts are not known"); return NEMGPU_E_ARG; }
+    }
+    if (a->device != b->device) { set_error(who + ": the masters are on different devices"); return NEMGPU_E_ARG; }
+    if (f < a->f_old) { set_error(who + ": f is below the first master's " + std::to_string(a->f_old) + " family ids"); return NEMGPU_E_ARG; }
+    std::vector<int32_t> ids((size_t)b->n);                   // B's ids in A's id space (ids_b null: its own numbering's)
+    for (int j = 0; j < b->n; j++) ids[(size_t)j] = ids_b ? ids_b[j] : b->order.empty() ? j : b->order[(size_t)j];
+    std::vector<uint8_t> seen((size_t)f, 0);
+    for (int j = 0; j < b->n; j++) {
+        const int id = ids[(size_t)j];
+        if (id < 0 || id >= f) {
+            set_error(ids_b ? who + ": ids_b[" + std::to_string(j) + "]: family id out of range" : who + ": f is not above the second master's family ids");
+            return NEMGPU_E_ARG;
+        }
+        if (seen[(size_t)id]) { set_error(who + ": ids_b[" + std::to_string(j) + "]: family id " + std::to_string(id) + " used twice"); return NEMGPU_E_ARG; }
+        seen[(size_t)id] = 1;
+    }
+    const long long d_ll = (long long)a->d + b->d;
+    if ((d_ll + 31) / 32 > chunk_mask_words_max()) { set_error(who + ": more than 131 072 organisms"); return NEMGPU_E_ARG; }
+    const int d = (int)d_ll;
+    nemgpu_master* m = nullptr;
+    { const int r = master_open(&m, a->device, nullptr); if (r != NEMGPU_OK) return r; }
+    MergeBuild* build = nullptr;
+    auto fail = [&](int rc, const std::string& what) { merge_free(build); return master_abandon(m, nullptr, rc, what); };
+    int n = 0;
+    std::vector<int32_t> fresh((size_t)b->n);                 // the ids of the families the first master lacks
+    hipError_t err = merge_number(a->dev, a->order.empty() ? nullptr : a->order.data(), b->dev, ids.data(), f, m->stream, &build, &n, fresh.data());
+    if (err != hipSuccess) return fail(NEMGPU_E_DEVICE, who + ": " + hipGetErrorString(err));
+    if (!orders_key_fits(n, d)) return fail(NEMGPU_E_ARG, who + ": too many families for this many organisms (2 bits(n) + bits(d) > 63)");
+    long long nnz = 0;
+    if ((err = merge_plan(build, m->stream, &nnz)) != hipSuccess) return fail(NEMGPU_E_DEVICE, who + ": " + hipGetErrorString(err));
+    if (nnz > 0x7fffffff) return fail(NEMGPU_E_ARG, who + ": more than 2^31 - 1 CSR entries");
+    if ((long long)a->nx + b->nx > 0x7fffffff) return fail(NEMGPU_E_ARG, who + ": more than 2^31 - 1 multi-copy pairs");
+    MasterLayout L(n, d, (int)nnz, a->nx + b->nx);
+    if (!L.alloc(m)) return fail(NEMGPU_E_DEVICE, who + ": device memory");
+    int over = 0;
+    err = merge_fill(build, a->nx, b->nx, (int)nnz, L.xt, L.nw64, L.ptr, L.idx, L.eb, L.wf, L.xptr, L.xorg, L.xadd, &over, m->stream);
+    if (err != hipSuccess) return fail(NEMGPU_E_DEVICE, who + ": " + hipGetErrorString(err));
+    if (over) return fail(NEMGPU_E_ARG, "edge counts: an edge's total count above 2^24 (a float weight would not be exact)");
+    merge_free(build);
+    m->order.resize((size_t)n);
+    if (a->order.empty()) for (int i = 0; i < a->n; i++) m->order[(size_t)i] = i;
+    else std::copy(a->order.begin(), a->order.end(), m->order.begin());
+    std::copy(fresh.begin(), fresh.begin() + (n - a->n), m->order.begin() + a->n);
+    m->f_old = f;
+    *out = m;
+    return NEMGPU_OK;
 }
 
 // A partition projected onto the organisms (nem_project.hpp): everything refused is refused on the host, before any launch

@@ -1,7 +1,10 @@
 """Merging two masters, on the host: chunks.master_arrays_merge (the numpy statement of nemgpu_master_merge) against
 master_arrays_from_orders of the concatenated orders and against master_arrays_append_orders, where both parts are built
 with the same repeated families -- on the recorded add_organism fixtures split into base and update and on random
-annotation sets cut at a random organism; its associativity; and what the library refuses before it looks at a master."""
+annotation sets cut at a random organism; a part numbered apart, in a larger id space, with the ids that lead back
+(either part); parts built with different repeated families, where the merge is by construction not the single build:
+a hand-written case with every row spelled out and a random one; the 2^24 bound on the summed count; its associativity;
+and what the library refuses before it looks at a master."""
 import ctypes as C
 
 import numpy as np
@@ -9,8 +12,10 @@ import pytest
 
 from pangenomenem_amd.chunks import master_arrays_merge
 from tests import master_shapes as ms
-from tests.append_util import build_host
-from tests.merge_util import fixture_cases, host_expectations, host_merge, random_cases, same_with_order, triple_alone
+from tests.append_util import build_host, slice_orders
+from tests.merge_util import (different_repeated_parts, fixture_cases, host_expectations, host_merge, random_cases,
+                              random_different_repeated_parts, relabelled, same_with_order, scattered_ids, triple_alone, two_parts)
+from tests.orders_util import synthetic_orders
 
 
 def test_fixtures_equal_one_build_and_the_append():
@@ -53,6 +58,66 @@ def test_ids_in_another_id_space():
         master_arrays_merge(ma, ma[4], mb, [7, 1, 7])
     with pytest.raises(ValueError):
         master_arrays_merge(ma, ma[4], mb, [7, 1])
+
+
+def test_b_numbered_apart_in_a_larger_id_space():
+    """B built from its own orders with every id i written sigma[i] (scattered over 3 f ids), merged with the ids that
+    lead back (sigma^-1 of B's order): the single build of everything, order included -- at 40 + 10 families x 33 + 31
+    organisms (an organism word crossed on either side) and on the fixtures"""
+    base = synthetic_orders(40, 33, 533, density=0.5, p_repeat=0.05)
+    upd = slice_orders(synthetic_orders(50, 64, 1533, density=0.5, p_repeat=0.0), 33, 64)
+    upd["repeated"] = np.r_[base["repeated"], np.zeros(10, np.uint8)]
+    cases = [("40 + 10 x 33 + 31", two_parts(base, upd, 33, 31))] + list(fixture_cases())
+    for seed, (name, (a, b, u, whole)) in enumerate(cases):
+        f = len(b["repeated"])
+        sigma, inverse = scattered_ids(f, 3 * f, 90 + seed)
+        ma, mb = build_host(a), build_host(relabelled(b, sigma, 3 * f))
+        assert np.array_equal(inverse[mb[4]], build_host(b)[4]) and (f < 3 or not np.array_equal(np.argsort(sigma), np.arange(f)))
+        got = master_arrays_merge(ma, ma[4], mb, inverse[mb[4]])
+        same_with_order(got, build_host(whole), name + ": one build")
+        # and the other way round: A numbered apart, B's ids led into A's space; the merged order is sigma of the build's
+        ma = build_host(relabelled(a, sigma, 3 * f))
+        mb = build_host(b)
+        got = master_arrays_merge(ma, ma[4], mb, sigma[mb[4]])
+        want = build_host(whole)
+        same_with_order(got, tuple(want[:4]) + (sigma[want[4]],), name + ": A numbered apart")
+    assert len(cases) >= 5
+
+
+def test_parts_built_with_different_repeated_families():
+    """A was built with family 3 repeated, B with family 1.  The statement keeps what each part gave: family 1 has A's
+    node, row and bits and gains nothing from B's genes of it; family 3 has B's node and row, mapped, and is absent from
+    A's organisms though A walked genes of it.  The single build with either repeated vector, or their union, is
+    another master."""
+    a, b = different_repeated_parts()
+    ma, mb = build_host(a), build_host(b)
+    rows = lambda m: [m[1][1][p:q].tolist() for p, q in zip(m[1][0][:-1], m[1][0][1:])]
+    assert ma[4].tolist() == [0, 1, 2, 4] and rows(ma) == [[1, 2], [0, 2], [1, 3, 0], [2]]
+    assert mb[4].tolist() == [3, 0, 4] and rows(mb) == [[1, 2], [0], [0]] and mb[3][2].tolist() == [2, 2]
+    got = host_merge(ma, mb)
+    assert got[4].tolist() == [0, 1, 2, 4, 3]
+    assert got[0].tolist() == [[1, 1, 1], [1, 1, 0], [1, 1, 0], [1, 0, 1], [0, 0, 1]]
+    assert rows(got) == [[1, 2, 4], [0, 2], [1, 3, 0], [2, 4], [0, 3]]
+    assert got[2].ravel().tolist() == [3, 2, 4, 3, 1, 1, 1, 2, 1, 4, 4, 4]
+    assert got[3][0].tolist() == [0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2] and got[3][1].tolist() == [2, 2] and got[3][2].tolist() == [2, 2]
+    # family 1 (row 1): as in A
+    assert rows(got)[1] == rows(ma)[1] and got[2].ravel()[3:5].tolist() == ma[2].ravel()[2:4].tolist() and got[0][1].tolist() == ma[0][1].tolist() + [0]
+    whole = ms.concat_orders([a, dict(b, contig_org=b["contig_org"] + 2)], 3)
+    for rep in ([3], [1], [1, 3]):
+        one = build_host(dict(whole, repeated=np.isin(np.arange(5), rep).astype(np.uint8)))
+        assert one[4].tolist() != got[4].tolist()
+    # at random: no repeated family in A, some in B -- those keep A's rows among A's families
+    ra, rb = random_different_repeated_parts()
+    ma, mb = build_host(ra), build_host(rb)
+    got = host_merge(ma, mb)
+    rep = np.flatnonzero(rb["repeated"])
+    at = np.flatnonzero(np.isin(ma[4], rep))
+    assert len(at) >= 3 and not np.isin(mb[4], rep).any() and not got[0][at, ra["d"]:].any()
+    assert np.array_equal(got[0][:len(ma[4]), :ra["d"]], ma[0])
+    for r in at:                                              # (its row: A's, entry for entry -- B has no node of it to hang an edge on)
+        mine = got[1][1][got[1][0][r]:got[1][0][r + 1]]
+        assert np.array_equal(mine[:ma[1][0][r + 1] - ma[1][0][r]], ma[1][1][ma[1][0][r]:ma[1][0][r + 1]])
+        assert len(mine) == ma[1][0][r + 1] - ma[1][0][r]
 
 
 def test_the_count_bound_is_on_the_sum():

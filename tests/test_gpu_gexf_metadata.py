@@ -13,6 +13,7 @@ import pytest
 from pangenomenem_amd.chunks import Master
 from pangenomenem_amd.engine import NemGpuError
 from pangenomenem_amd.gexf import attvalues_host, edge_metadata_arrays, metavalues_host, write_gexf
+from tests.gexf_bounds_util import EDGES, attributes, shape_orders
 from tests.gexf_metadata_util import METADATA_FIXTURES, metadata_of, read_text
 from tests.gexf_util import contigs_orders, path_contigs, same_gexf_text, sizes_of
 from tests.orders_util import load, same_master
@@ -21,7 +22,6 @@ from tests.projection_util import annotations_of
 pytestmark = pytest.mark.gpu
 
 E_ARG = 3
-EDGES = 300                                                   # the path's edges: 75 blocks of 4 waves, an edge a wave
 
 
 def from_orders(o):
@@ -31,39 +31,6 @@ def from_orders(o):
 def table_of(m, o):
     return m.edge_table(orders=(o["genes"], o["contig_ptr"], o["contig_org"], o["repeated"]), starts=o["starts"], ends=o["ends"],
                         contig_sizes=o["contig_sizes"])
-
-
-def shape_orders(rng, d):
-    """the path of EDGES edges (organism 0 all of it, the others a stretch), then an edge carried by every organism next
-    to edges carried by one, a tandem pair and a circular contig of one gene"""
-    n = EDGES + 1
-    contigs = path_contigs(rng, EDGES, d)
-    contigs += [(o, [n, n + 1], -1) for o in range(d)] + [(0, [n + 2, n + 3], -1), (d - 1, [n + 3, n + 4], -1)]
-    contigs += [(d // 2, [n + 5, n + 5], -1), (d - 1, [n + 6], 40)]
-    return contigs_orders(contigs, d, rng)
-
-
-def attributes(rng, d, counts, ids):
-    """the arrays of len(counts) attributes: every value of an attribute of at most d values is some organism's (of d
-    values: every organism another one); the values' bytes differ in length, an empty one, one of a single byte and one
-    of 150 bytes among them"""
-    rank = np.zeros((len(counts), d), np.int32)
-    texts = []
-    for a, nv in enumerate(counts):
-        if nv <= d:
-            rank[a] = rng.permutation(np.concatenate([np.arange(nv), rng.integers(0, nv, d - nv)]))
-        else:
-            rank[a] = rng.choice(nv, d, replace=False)
-        mine = [("v%d" % k).encode() * int(rng.integers(1, 9)) for k in range(nv)]
-        mine[0] = b""
-        if nv > 1:
-            mine[nv - 1] = b"x"
-        if nv > 2:
-            mine[nv // 2] = ("long|&amp;%d " % a).encode() * 13 + "Å".encode()
-            assert len(mine[nv // 2]) > 128
-        texts += mine
-    ptr = np.concatenate([[0], np.cumsum([len(t) for t in texts])]).astype(np.int64)
-    return np.asarray(ids, np.int32), rank, np.asarray(counts, np.int32), ptr, np.frombuffer(b"".join(texts), np.uint8).copy()
 
 
 def held_to_statement(m, t, meta, what, batches=()):

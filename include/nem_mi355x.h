@@ -878,6 +878,9 @@ int nemgpu_set_graph_policy(nemgpu_engine* e, int capture_on_first);
 /* out[0] batches sent as plain launches, out[1] batches captured + instantiated, out[2] graph replays,
    out[3] sweeps the host had to finish round by round */
 int nemgpu_graph_counters(const nemgpu_engine* e, int out[4]);
+/* debug: starts of this engine that went out without a blind launch -- the first round of the start's beta sweep
+   labelled the blind partition itself (NEM_MI355X_BLIND_FOLD, default on) --, graph replays included; -1: no engine */
+int nemgpu_debug_blind_folds(const nemgpu_engine* e);
 /* how the last nemgpu_run_random went (RandNemAlgo, nem_alg.c:1574-1742, starts in lock step): out = {lock-step rounds,
    starts that stood in them, starts run alone on the engine's own path, starts thrown away and redone because a start
    before them drew tie-breaks behind its initial sweeps (TIE_LIBC: one random() stream for all starts)}.  A logged

@@ -212,6 +212,12 @@ struct nemgpu_engine {
     // ... and (NEM_MI355X_START_FUSED, default on; see enqueue_init) a start's restart head runs inside its density launch
     // (k_density_start) instead of as a k_finish launch ahead of k_density.
     bool start_fused = true;
+    // ... and (NEM_MI355X_BLIND_FOLD, default on; see blind_fold_on) the start has no blind launch: round 0 of its beta
+    // sweep computes the blind labels it needs (sweep_body's BLIND instances).  n_blind_folds: starts that went out so.
+    bool blind_fold = true;
+    int n_blind_folds = 0;
+    int blind_slot_once = -1; uint32_t blind_id_once = 0;   // the next sweep_enqueue's round 0 is such a round: the blind sweep's flag slot and number
+
     int* stats_slot[2] = {};
     int* stats_last = nullptr;
     float* par_copy[3] = {}; double* pkfki_copy[3] = {}; float* logpkfki_copy[3] = {};
@@ -759,6 +765,9 @@ struct SweepCtx {
     SweepArgs* hold = nullptr;
     // ... and the round that makes the masks adds the M-step counts of its labels into this (zeroed) slot (nullptr: no)
     int* count_into = nullptr;
+    // a start's beta sweep without a blind launch ahead of it (blind_fold_on): round 0 computes the blind labels it
+    // needs, stores its own sites' into the sweep's old buffer and tallies into the blind sweep's flag slot (-1: no)
+    int blind_slot = -1; uint32_t blind_id = 0;
 };
 
 int clear_sweep_flags(nemgpu_engine* e)
@@ -858,6 +867,9 @@ int sweep_launch_rounds(nemgpu_engine* e, SweepCtx& c, int count)
         c.a.stop = e->stop_ptr;
         c.a.post_on = 0;
         c.a.post_stats = nullptr;
+        const bool blind = ncem && c.blind_slot >= 0 && r == 0;    // (round 0 only: every later round reads the labels it wrote)
+        c.a.blind_off = blind ? (int)(e->round_flags(c.blind_slot) - c.a.flags) : 0;   // (its guess and its old buffer are both P)
+        c.a.blind_sweep_id = blind ? c.blind_id : 0u;
         if (c.hold != nullptr && c.post && ncem && r0 == 0 && count >= 2 && b >= count - 2) {
             c.a.post_on = 1; c.a.post_skip_guess = (r % 2 == 1) ? 1 : 0;
             c.a.post_nw64 = e->nw64; c.a.post_mask = e->mask; c.a.post_flags = e->iter_flags();
@@ -908,6 +920,7 @@ int sweep_enqueue(nemgpu_engine* e, float beta, SweepCtx& c, bool id_by_value = 
 {
     c = SweepCtx();
     c.slot_base = slot_base;
+    c.blind_slot = e->blind_slot_once; c.blind_id = e->blind_id_once; e->blind_slot_once = -1;
     if (post_ctrl != nullptr && e->ncem()) {
         c.post = true; c.post_moved = post_moved; c.post_ctrl = *post_ctrl; c.hold = hold;
         c.count_into = hold != nullptr ? count_into : nullptr;
@@ -1185,6 +1198,19 @@ static int init_beta_rounds(const nemgpu_engine* e)
 
 bool shadow_engine(const nemgpu_engine* e);
 
+// Does a start of this engine go out without its blind launch (round 0 of the beta sweep labels the blind partition
+// itself, sweep_body's BLIND instances)?  The fused start of a shadow-verify engine, K = 2 .. 7 (the instances there
+// are), NEM_MI355X_BLIND_FOLD not 0 -- and a round of at most kBlindFoldMaxBlocks blocks of 256 sites.  128, not more:
+// the sharded driver keeps its three launches, and tests/test_gpu_distributed.py holds it within 1.3 times the single
+// engine at 50 000 x 1 000 (196 blocks), where the ratio stands at 1.25-1.29 -- no room for a gain on one side alone.
+// Raising it belongs with a change that gives the sharded start as much.
+constexpr int kBlindFoldMaxBlocks = 128;
+static bool blind_fold_on(const nemgpu_engine* e)
+{
+    return e->blind_fold && e->start_fused && shadow_engine(e) && e->k >= 2 && e->k <= 7 &&
+           (e->n + 255) / 256 <= kBlindFoldMaxBlocks;
+}
+
 // hold (shadow-verify schedule, NCEM): the beta sweep's last round and the loop control are left in *hold for the first
 // iteration's density launch (defer_ctrl is then ignored); count_into (with hold): the round before it adds the first
 // iteration's M-step counts into these statistics, which this launch's restart head zeroes
@@ -1218,7 +1244,13 @@ int enqueue_init(nemgpu_engine* e, bool defer_ctrl, SweepArgs* hold = nullptr, i
     // behind a fixed point carry it along), the loop control checks both sweeps and books their draws (ctrl_logic).
     const bool libc = e->libc();
     const int ra = libc ? e->libc_ra : 1;
-    if ((r = sweep_enqueue(e, 0.0f, c0, true, nullptr, false, kRoundCap - ra, libc ? ra : 0))) return r;
+    const bool fold = blind_fold_on(e);
+    if (fold) {
+        // no blind launch: round 0 of the beta sweep below computes the blind labels, stores them in buffer 1 and
+        // tallies into the blind sweep's slot.  The host state as it would be behind the blind sweep (number 0).
+        e->blind_slot_once = kRoundCap - ra; e->blind_id_once = e->sweep_counter++;
+        e->n_blind_folds++;
+    } else if ((r = sweep_enqueue(e, 0.0f, c0, true, nullptr, false, kRoundCap - ra, libc ? ra : 0))) return r;
     e->flags_clean = true;
     e->cur = 1;
     CtrlArgs ca{};
@@ -1818,10 +1850,13 @@ int iterate_pipelined(nemgpu_engine* e, int n_iters, bool with_init)
         // it saves unless the batch is replayed, and a nem() call's engine enqueues most shapes once.  (A batch's
         // enqueue changes cur and sweep_counter besides the freshness flags; a capture counts as a replay too.)
         const int cur0 = e->cur; const uint32_t sweep_counter0 = e->sweep_counter;
+        const int folds0 = e->n_blind_folds;
         Graphed how;
         r = run_graphed(e, lc.g < 8 ? &e->batch_graphs : nullptr, {(uint64_t)lc.batch_first, (uint64_t)lc.base, (uint64_t)lc.g, (uint64_t)lc.deep},
                         2, e->stream, [&]() { return batch_enqueue(e, lc, true); },
-                        [&]() { e->cur = cur0; e->sweep_counter = sweep_counter0; }, &how);
+                        [&]() { e->cur = cur0; e->sweep_counter = sweep_counter0; e->n_blind_folds = folds0; }, &how);
+        // (a replayed start was captured by this engine with the switch and the shape it has now)
+        if (how == Graphed::replayed && lc.batch_first && blind_fold_on(e)) e->n_blind_folds++;
         e->n_plain += how == Graphed::plain;
         e->n_captured += how == Graphed::captured;
         e->n_replayed += how == Graphed::replayed || (how == Graphed::captured && r == NEMGPU_OK);
@@ -2666,6 +2701,7 @@ int nemgpu_create(nemgpu_engine** out, int n_total, int d, int k, int site_lo, i
     e->flag_sets = e->shadow_verify ? 3 : 1;
     if (const char* g = getenv("NEM_MI355X_ROUND_COUNTS")) e->round_counts = (g[0] != '0');   // 0: a counts launch per iteration
     if (const char* g = getenv("NEM_MI355X_START_FUSED")) e->start_fused = (g[0] != '0');     // 0: k_finish + k_density start a run
+    if (const char* g = getenv("NEM_MI355X_BLIND_FOLD")) e->blind_fold = (g[0] != '0');       // 0: the blind sweep as a launch of its own
     if (const char* g = getenv("NEM_MI355X_ROUNDS")) e->round_batch = std::max(2, std::min(kRoundBatchMax, atoi(g)));
     if (const char* g = getenv("NEM_MI355X_ROUNDS_ITER")) e->rounds_iter = std::max(2, std::min(e->round_batch, atoi(g)));
     e->rounds_iter = std::min(e->rounds_iter, e->round_batch);
@@ -5793,6 +5829,12 @@ int nemgpu_graph_counters(const nemgpu_engine* e, int out[4])
     if (!e || !out) return NEMGPU_E_FUNCARG;
     out[0] = e->n_plain; out[1] = e->n_captured; out[2] = e->n_replayed; out[3] = e->n_host_rounds;
     return NEMGPU_OK;
+}
+
+// starts that went out without a blind launch (blind_fold_on), replays of such a start's graph included; -1: no engine
+int nemgpu_debug_blind_folds(const nemgpu_engine* e)
+{
+    return e ? e->n_blind_folds : -1;
 }
 
 int nemgpu_random_start_counters(const nemgpu_engine* e, int out[4])

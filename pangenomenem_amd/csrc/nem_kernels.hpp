@@ -61,7 +61,8 @@ struct SweepArgs {
     // fuzzy state: float rows [n_total][K], GLOBAL family indexing
     const float* c_old; const float* c_guess; float* c_out;
     int tie_rule; uint32_t tie_seed; uint32_t sweep_id;
-    const int* sweep_id_ptr;                   // when set, the sweep number is read from the device instead
+    uint32_t blind_sweep_id;                   // a BLIND round (blind_off below): the blind sweep's number, which keys ITS ties
+    const int* sweep_id_ptr;                  // when set, the sweep number is read from the device instead
     int* flags;                                // this round's slot
     const int* prev_changed;                   // previous round's FLAG_CHANGED (nullptr for round 0)
     const int* stop;                           // loop-control stop word (nullptr outside the pipelined loop)
@@ -98,6 +99,12 @@ struct SweepArgs {
     const uint8_t* rank_tot_in; int rank_index; uint8_t* rank_tot_out;
     // sites per block of the large-shard kernel instances (set by launch_sweep; 0: the kernel's block size)
     int spb;
+    // A start's first beta round with the blind sweep inside it (sweep_body's BLIND instances; 0: an ordinary round).
+    // Such a round computes every blind label it needs from the densities and reads no labels buffer: its blocks STORE
+    // their own sites' blind labels to lab_guess (= lab_old: the buffer the blind sweep would have written) and tally
+    // the blind sweep's zero-density sites into that sweep's flag slot, flags + blind_off.  (This word and
+    // blind_sweep_id sit where the struct had padding: no other argument moved.)
+    int blind_off;
     // shadow-verify schedule, the round that makes the class masks of a held sweep: the M-step counts of those masks
     // (k_mstep_counts' {N_k, S1[k][d]}) added into post_stats, zeroed by an earlier launch -- every block its 256
     // families' share, from the organism-major bit rows post_xt ([post_D][post_nw64]).  nullptr: no counting.

@@ -14,6 +14,9 @@ namespace nemk {
 
 template <int KT, bool NCEM, int BS, bool LIBC = false, bool COUNT = false>
 __global__ __launch_bounds__(BS) void k_sweep(SweepArgs a) { sweep_body<KT, NCEM, BS, LIBC, COUNT>(a, blockIdx.x, gridDim.x); }
+// round 0 of a start's beta sweep with the blind sweep inside it (sweep_body's BLIND; a name of its own in a trace)
+template <int KT, bool COUNT>
+__global__ __launch_bounds__(256) void k_sweep_blind(SweepArgs a) { sweep_body<KT, true, 256, false, COUNT, true>(a, blockIdx.x, gridDim.x); }
 template <int KT, bool NCEM, int BS, bool LIBC = false>
 __global__ __launch_bounds__(BS) void k_sweep_b(const void* arr, int stride, const int* gx) { NEM_B_HEAD(SweepArgs) sweep_body<KT, NCEM, BS, LIBC>(a, blockIdx.x, nblk); }
 
@@ -67,6 +70,23 @@ void launch_sweep(const SweepArgs& a0, bool ncem, hipStream_t s)
     a.spb = big ? bs : 0;
     dim3 grid((a.n_local + bs - 1) / bs);
     const int variant = sweep_variant(a.K, ncem, big, a.tie_rule == NEMGPU_TIE_LIBC);
+    if (a.blind_off != 0) {
+        // a start's first beta round with the blind sweep inside it (SweepArgs::blind_off): instances of its own, plain
+        // and counting (not recordable: the batched twins have none); the engine asks for it where there is one only
+        const bool count = a.post_stats != nullptr;
+        if (!(current_recorder() == nullptr && ncem && !big && a.K >= 2 && a.K <= 7 && a.tie_rule != NEMGPU_TIE_LIBC && a.use_nei &&
+              a.lo == 0 && a.slot_stride == 0 && a.flags_in == nullptr && a.prev_changed == nullptr &&
+              a.lab_guess != nullptr && a.lab_guess == a.lab_old && a.lab_out != a.lab_guess &&
+              (!count || (a.post_on && !a.post_no_masks && a.post_D >= 1 && a.post_D <= kFusedMaxD)))) {
+            fprintf(stderr, "launch_sweep: no blind round for this shape\n");
+            abort();
+        }
+        dispatch_k<2, 7>(a.K, [&](auto KT) {
+            if (count) hipLaunchKernelGGL((k_sweep_blind<decltype(KT)::value, true>), grid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((k_sweep_blind<decltype(KT)::value, false>), grid, dim3(256), 0, s, a);
+        });
+        return;
+    }
     if (a.post_stats != nullptr) {
         // the counting round (SweepArgs::post_stats): an instance of its own, so that no other round carries its registers
         // (not recordable: the batched twins have no such instance)

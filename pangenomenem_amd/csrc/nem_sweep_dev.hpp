@@ -348,14 +348,62 @@ __device__ __forceinline__ int wave_sum_i32(int v)
     return __builtin_amdgcn_readlane(v, 63);
 }
 
+// A site's label in the blind sweep (beta = 0, no neighbour term) from its K densities alone -- what a round with
+// use_nei = 0 computes: local_cinum's row v = pkf[k], the clear row's maximum (nem_map.hpp) or else the normalised row
+// and ComputeMAP, the tie pick keyed by (seed, the BLIND sweep's number, the true family index `site`) under `hash`
+// and the first maximum under `first`.  One function for a block's own sites and for every neighbour it gathers from
+// another block: equal densities give equal labels in every block.  *zero: the site hit the "density = 0" branch.
+template <int KA>
+__device__ __forceinline__ int blind_label(const SweepArgs& a, int K, const double* pkf, uint32_t site, bool* zero)
+{
+    double cinum[KA];
+    double cum = 0.0;
+#pragma unroll
+    for (int k = 0; k < KA; k++) {
+        if (k < K) {
+            const double v = pkf[k];
+            cinum[k] = v;
+            cum = cum + v;
+        }
+    }
+    *zero = !(cum > 0);
+    int kmax = 0;
+    if (!a.map_full && map_clear_row<KA>(cinum, K, cum, kmax)) return kmax;
+    float cf[KA];
+    map_normalise<KA>(cinum, K, cum, cf);
+    kmax = 0; float ukmax = cf[0];                       // ComputeMAP, nem_alg.c:603-640
+#pragma unroll
+    for (int k = 1; k < KA; k++) if (k < K && cf[k] > ukmax) { ukmax = cf[k]; kmax = k; }
+    if (a.tie_rule != NEMGPU_TIE_FIRST) {
+        int nequal = 0;
+#pragma unroll
+        for (int k = 1; k < KA; k++) if (k < K && k > kmax && cf[k] == ukmax) nequal++;
+        if (nequal > 0) {
+            const int pick = (int)(mix32(a.tie_seed, a.blind_sweep_id, site) % (uint32_t)(nequal + 1));
+            int seen_eq = 0, chosen = kmax;
+#pragma unroll
+            for (int k = 1; k < KA; k++)
+                if (k < K && k > kmax && cf[k] == ukmax) { seen_eq++; if (seen_eq == pick) chosen = k; }
+            kmax = chosen;
+        }
+    }
+    return kmax;
+}
+
 // LIBC: the reference's tie stream (TIE_LIBC) -- its bookkeeping (who drew, per wave and block, at every block-local
 // step) is compiled into the instances that need it only
 // COUNT: the round also adds its block's M-step counts into SweepArgs::post_stats (the round that makes the class masks
 // of a held sweep, see the shadow-verify schedule in nem_engine.hip); NCEM, 256 sites per block, D <= kFusedMaxD only
-template <int KT, bool NCEM, int BS, bool LIBC = false, bool COUNT = false>
+// BLIND: round 0 of a start's beta sweep with the blind sweep inside it (SweepArgs::blind_off): its guess and its old
+// partition are both the blind labels, and it reads neither from memory -- a site's own label, and that of a neighbour
+// in another block, come from blind_label() on the densities; the block's own labels go to lab_guess and into two LDS
+// arrays (the running labels and the old ones).  No block reads what another block of the launch wrote.  With and
+// without COUNT; NCEM, 256 sites per block, K = 2 .. 7 (the label shortcut's instances), unsharded (lo = 0)
+template <int KT, bool NCEM, int BS, bool LIBC = false, bool COUNT = false, bool BLIND = false>
 __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, const int nblk)
 {
     static_assert(!COUNT || (NCEM && BS == 256 && !LIBC && KT > 0), "the counting round: NCEM, 256 sites per block");
+    static_assert(!BLIND || (NCEM && BS == 256 && !LIBC && KT >= 2 && KT <= 7), "the blind round: NCEM, 256 sites per block, K = 2 .. 7");
     static_assert(C_STOP == 0 && C_FOLD == 1, "one 8-byte load");
     NEM_SWEEP_PHASE_TAKE(t_entry);
     const int spb = (BS > 256 && a.spb > 0) ? a.spb : BS;   // sites of this block (large shards: fewer than the launch bound)
@@ -405,7 +453,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
         int pc = *(a.prev_changed != nullptr ? a.prev_changed : some);
         // (the two bytes last: the compiler masks my_old where it is loaded, and waits for it there -- behind the other
         //  requests that wait is for all of them at once)
-        if (active) { my_guess = a.lab_guess[gi]; my_old = a.lab_old[gi] & kLabMask; }
+        if constexpr (!BLIND) { if (active) { my_guess = a.lab_guess[gi]; my_old = a.lab_old[gi] & kLabMask; } }
         if (a.stop == nullptr) sf = make_int2(0, 0);
         if (a.prev_changed == nullptr) pc = 1;
         // (a compiler-only fence, no instruction: without it the loads above are sunk below the tests, to their uses)
@@ -459,6 +507,20 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
     bool changed = false;
     __shared__ int s_anydrew;                            // TIE_LIBC: a site of the block drew at some local step of this launch
     if (threadIdx.x == 0) { s_nzero = 0; s_first = 0; s_chg = 0; s_mov = 0; s_anydrew = 0; }
+    // BLIND: the block's old labels (the blind partition; s_lab moves on with the block-local steps), and the blind
+    // sweep's own zero-density tally.  The site's blind label: from its densities, which were asked for at entry
+    __shared__ __attribute__((aligned(16))) uint8_t s_old[BLIND ? BS : 1];
+    __shared__ int s_bnzero, s_bfirst;
+    bool blind_zero = false;
+    if constexpr (BLIND) {
+        if (threadIdx.x == 0) { s_bnzero = 0; s_bfirst = 0; }
+        bool z;
+        my_guess = blind_label<KA>(a, K, pkf, (uint32_t)gi, &z);
+        my_old = my_guess;
+        blind_zero = active && z;
+        s_old[threadIdx.x] = (uint8_t)my_guess;
+        if (active) const_cast<uint8_t*>(a.lab_guess)[gi] = (uint8_t)my_guess;   // (stored, never read in this launch)
+    }
     if (NCEM) s_lab[threadIdx.x] = (uint8_t)my_guess;
     if (NCEM && a.use_nei && !skip && threadIdx.x < kExpTab) s_exp[threadIdx.x] = exp((double)a.beta * (double)(float)threadIdx.x);
     // TIE_LIBC: draws of the blocks below this one, as the guess has them -- summed once by the block's first wave (a
@@ -510,12 +572,36 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
             jn[u] = ok ? a.nei_idx[nb + u] : gi;
             wn[u] = ok ? a.nei_w[nb + u] : 0.0f;
         }
+        if constexpr (BLIND) {
+            // a neighbour at or above the site in the block: the block's old labels; in another block: its K densities,
+            // gathered for all four at once -- they depend on nei_idx exactly as the label gather did -- and
+            // blind_label(), which the lanes of a wave that have such a neighbour branch into together
+            // (one neighbour's densities at a time instead: the same register counts, K = 2 .. 7 -- the instance's peak is
+            //  not here)
+            bool far[4];
+            double pn[4][KA];
+#pragma unroll
+            for (int u = 0; u < 4; u++) far[u] = nb + u < ne && (jn[u] < blk_lo || jn[u] >= blk_lo + BS);
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+                for (int k = 0; k < KA; k++) pn[u][k] = far[u] ? a.pkfki[(size_t)k * a.npad + (jn[u] - a.lo)] : 0.0;
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                if (nb + u < ne) {
+                    if (jn[u] < gi && jn[u] >= blk_lo) dyn[u] = jn[u] - blk_lo;
+                    else if (!far[u]) fl[u] = s_old[jn[u] - blk_lo];
+                    else { bool z; fl[u] = blind_label<KA>(a, K, pn[u], (uint32_t)jn[u], &z); }
+                }
+            }
+        } else {
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             if (nb + u < ne) {
                 if (jn[u] < gi && jn[u] >= blk_lo) dyn[u] = jn[u] - blk_lo;
                 else fl[u] = ((jn[u] < gi) ? a.lab_guess[jn[u]] : a.lab_old[jn[u]]) & kLabMask;
             }
+        }
         }
     }
     const bool long_row = ne - nb > 4;
@@ -564,6 +650,16 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
                     const float wt = a.nei_w[t];
                     int l;
                     if (j < gi && j >= blk_lo) l = s_lab[j - blk_lo] & kLabMask;
+                    else if constexpr (BLIND) {          // (the same three cases as the first four)
+                        if (j >= blk_lo && j < blk_lo + BS) l = s_old[j - blk_lo];
+                        else {
+                            double pj[KA];
+#pragma unroll
+                            for (int k = 0; k < KA; k++) pj[k] = a.pkfki[(size_t)k * a.npad + (j - a.lo)];
+                            bool z;
+                            l = blind_label<KA>(a, K, pj, (uint32_t)j, &z);
+                        }
+                    }
                     else l = ((j < gi) ? a.lab_guess[j] : a.lab_old[j]) & kLabMask;
 #pragma unroll
                     for (int k = 0; k < KA; k++)
@@ -712,8 +808,21 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const int bx, con
         atomicAdd(&s_nzero, (int)__popcll(zmask));
         atomicMax(&s_first, a.n_total - (gi + (int)__ffsll((long long)zmask) - 1));   // lanes are consecutive sites
     }
+    if constexpr (BLIND) {                               // the blind sweep's tally: the block's OWN sites' blind evaluations
+        const uint64_t bmask = __ballot(blind_zero);
+        if (bmask != 0ull && (threadIdx.x & 63) == 0) {
+            atomicAdd(&s_bnzero, (int)__popcll(bmask));
+            atomicMax(&s_bfirst, a.n_total - (gi + (int)__ffsll((long long)bmask) - 1));
+        }
+    }
     __syncthreads();
     NEM_SWEEP_PHASE(5);
+    // BLIND: into the blind sweep's flag slot, as a blind round's blocks would (its FLAG_CHANGED stays 0: nobody reads it)
+    if (BLIND && threadIdx.x == 0 && s_bnzero > 0) {
+        int* bf = a.flags + a.blind_off;
+        atomicAdd(&bf[FLAG_NZERO], s_bnzero);
+        if (bf[FLAG_FIRSTZERO] < s_bfirst) atomicMax(&bf[FLAG_FIRSTZERO], s_bfirst);
+    }
     // One same-address atomic per block is what a round costs when every site reports (all densities underflow at
     // D = 5000: 196 blocks x ~45 ns, 12 of a round's 26 us at 200 000 x 5 000).  Once the loop control has seen
     // such a sweep (ctrl[C_FOLD], set by ctrl_logic, read with the stop word) the tally rides on the last-block

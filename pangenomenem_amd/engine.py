@@ -115,6 +115,8 @@ def load_library():
     lib.nemgpu_set_fast_forward.argtypes = [vp, C.c_int]
     lib.nemgpu_set_graph_policy.argtypes = [vp, C.c_int]
     lib.nemgpu_graph_counters.argtypes = [vp, ip]
+    if hasattr(lib, "nemgpu_debug_blind_folds"):       # (NEM_MI355X_LIB may name a build from before the fold)
+        lib.nemgpu_debug_blind_folds.argtypes = [vp]
     lib.nemgpu_profile_density_many.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.nemgpu_random_start_counters.argtypes = [vp, ip]
     lib.nemgpu_rccl_ranks.argtypes = [vp]
@@ -520,6 +522,10 @@ class NemEngine:
         out = (C.c_int * 4)()
         self._chk(self.lib.nemgpu_graph_counters(self._h, out))
         return dict(plain=out[0], captured=out[1], replayed=out[2], host_finished_sweeps=out[3])
+
+    def blind_folds(self):
+        """starts that went out without a blind launch (NEM_MI355X_BLIND_FOLD), graph replays included"""
+        return int(self.lib.nemgpu_debug_blind_folds(self._h)) if hasattr(self.lib, "nemgpu_debug_blind_folds") else 0
 
     def random_start_counters(self):
         out = (C.c_int * 4)()

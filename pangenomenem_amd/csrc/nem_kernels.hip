@@ -34,6 +34,10 @@ __device__ unsigned long long g_phase[32];
 // (a stamp taken ahead of a test that may end the block, stored once the block is past it)
 #define NEM_PHASE_TAKE(t) const unsigned long long t = wall_clock64()
 #define NEM_PHASE_PUT(i, t) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_phase[i] = t; } while (0)
+// (a stamp that waits for the value v: arithmetic carries no order against the clock, an empty asm that reads v does)
+#define NEM_PHASE_AFTER(i, v) do { asm volatile("" :: "v"(v)); NEM_PHASE(i); } while (0)
+// (a stamp once every load the thread has asked for so far has arrived)
+#define NEM_PHASE_LOADS_IN(i) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); NEM_PHASE(i); } while (0)
 // the fast-forwarded chain of block 0, per wave (4 each): the clock at the end of the last launch's chain, then -- summed
 // over the launches -- the trips of chain_ff_batched and the crossing passes of either chain (nemgpu_debug_ff_waves)
 __device__ unsigned long long g_ff_wave[12];
@@ -46,6 +50,8 @@ __device__ unsigned long long g_ff_wave[12];
 #define NEM_PHASE(i) do { } while (0)
 #define NEM_PHASE_TAKE(t) do { } while (0)
 #define NEM_PHASE_PUT(i, t) do { } while (0)
+#define NEM_PHASE_AFTER(i, v) do { } while (0)
+#define NEM_PHASE_LOADS_IN(i) do { } while (0)
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -526,6 +532,7 @@ __device__ __forceinline__ float chain_ff_batched(const XwHead& h, int npad, int
 #pragma unroll
         for (int b = 0; b < 32; b++) dk0 = bern_step(dk0, m, b, l1h, l0);
         bits = __float_as_uint(dk0);
+        NEM_PHASE_AFTER(28, bits);
         ff_load(sQ0, sDQ, bits, q0, dq, end);
     }
     put(0, h.x0);
@@ -727,6 +734,7 @@ __device__ __forceinline__ void density_body(const DensityArgs& a)
 // ------------------------------------------------------------------------------------------
 constexpr int FD_MAXD = kFusedMaxD; // organisms the fused kernel supports (iner/eps staged in LDS as floats)
 constexpr int FD_CH = 256;        // organisms per general-path table chunk
+constexpr int kCentreIntMax = 1 << 24;                   // class sizes below it: the centres' rule in integers (density_fused_body)
 
 struct FusedDensityArgs {
     const uint4* xw; int n, npad, dpad, D, K, n_total, disper, propor;
@@ -816,7 +824,9 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
     const float propk = START ? st->prop0[k] : (a.propor == NEMGPU_PROP_K) ? nkf / (float)a.n_total : (float)(1.0 / K);
     if (writer && tid == 0) { a.prop[k] = propk; a.nbobs_k[k] = nkf; }
     const double pkd = (double)propk;
+    NEM_PHASE(13);
     const float logpk = (pkd > kEpsilonD) ? (float)log(pkd) : -INFINITY;
+    NEM_PHASE_AFTER(14, logpk);
     if (tile == 0 && k == 0) {
         for (int t = tid; t < a.n_zero_flags; t += 256) a.zero_flags[t] = 0;
         for (int t = tid; t < a.n_zero_stats; t += 256) a.zero_stats[t] = 0;
@@ -831,10 +841,20 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
         }
     }
     NEM_PHASE(18);
+    NEM_PHASE_LOADS_IN(15);
 
     // ---- centres + inertia of class k from the counts (k_finish's centers_ncem_entry, per block)
     long long acc2 = 0;
+    int acc1 = 0;                                        // (centre_int) the thread's rows' inertia, not doubled
     int general = 0;
+    // A non-empty class below 2^24 families: N_k - S1, N_k and N_k / 2 are exact as floats, so ComputeMedian's
+    // three-way float comparison of the zero count S0 with N_k / 2 is S0 against S1 in integers, the inertia -- S1,
+    // N_k / 2 = S0 or S0 -- is min(S0, S1), and the centre 0, 1/2 or 1 as S0 is above, at or below S1.  The mismatch
+    // masks are abs((int)(x - mu)): set for x = 0 where the centre is 1, for x = 1 where it is 0, neither at 1/2.
+    // Branch-free; twice the inertia is added up as an integer (a thread's kRows rows and the wave's 64 lanes of at
+    // most N_k / 2 each stay below 2^31) instead of through a float-to-int64 conversion per row.
+    const bool centre_int = !START && nonempty && nkI < kCentreIntMax;      // (block-uniform)
+    static_assert((long long)kRows * 64 * (kCentreIntMax / 2) <= (1ll << 31), "the wave's inertia sum is 32 bits");
     int differ = 0;                                      // START: a dispersion that is not the class's first, or not above EPSILON
     auto centre_of = [&](const int d, const int s1_d) {  // organism d (dpad % 64 == 0: whole waves reach the ballots)
         float mu = 0.0f, in = 0.0f;
@@ -845,6 +865,15 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
                 in = st->disp0[k * D + d];               // (sVal holds the given dispersions from here on)
                 if (writer) a.disp[k * D + d] = in;
                 differ |= (__float_as_uint(in) != __float_as_uint(st->disp0[k * D])) || !((double)in > kEpsilonD);
+            } else if (centre_int) {
+                const int s1 = s1_d, s0 = nkI - s1;
+                const int inI = min(s0, s1);
+                a0 = (s0 < s1); a1 = (s0 > s1);
+                mu = a1 ? 0.0f : a0 ? 1.0f : 0.5f;
+                in = (float)inI;
+                acc1 += inI;
+                if (writer) a.center[k * D + d] = mu;
+                sVal[d] = in;
             } else if (nonempty) {
                 const float half = nkf / 2;
                 const int s1 = s1_d;
@@ -855,12 +884,14 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
             } else {
                 mu = a.center_in[k * D + d];             // empty class keeps its centre (nem_mod.c:1405)
             }
-            if (writer) a.center[k * D + d] = mu;
-            const int ad0 = abs((int)(0.0f - mu)), ad1 = abs((int)(1.0f - mu));
-            a0 = (ad0 != 0); a1 = (ad1 != 0);
-            if (ad0 > 1 || ad1 > 1) general = 1;
-            sVal[d] = in;
-            if constexpr (!START) acc2 += (long long)(2.0f * in);
+            if (START || !centre_int) {
+                if (writer) a.center[k * D + d] = mu;
+                const int ad0 = abs((int)(0.0f - mu)), ad1 = abs((int)(1.0f - mu));
+                a0 = (ad0 != 0); a1 = (ad1 != 0);
+                if (ad0 > 1 || ad1 > 1) general = 1;
+                sVal[d] = in;
+                if constexpr (!START) acc2 += (long long)(2.0f * in);
+            }
         }
         const uint64_t b0 = __ballot(a0), b1 = __ballot(a1);
         if (lane == 0) {
@@ -878,7 +909,10 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
     }
     // the waves' partial sums go to a slot each and every thread adds the four up: no LDS atomic, no barrier ahead of
     // the loop to initialise its target
-    if constexpr (!START) acc2 = wave_reduce_add_ll(acc2);
+    if constexpr (!START) {
+        if (centre_int) acc2 = 2ll * (long long)(uint32_t)wave_reduce_add(acc1);
+        else acc2 = wave_reduce_add_ll(acc2);
+    }
     const int gen_w = __any(general);
     if (lane == 0) { sTot2w[tid >> 6] = (unsigned long long)acc2; sGenW[tid >> 6] = gen_w; }
     bool eps_per_d = false;                              // epsilon differs between organisms -> general chain
@@ -951,14 +985,22 @@ __device__ __forceinline__ int density_fused_body(const FusedDensityArgs& a, con
     bool uniform = !eps_per_d && !any_general && ((double)eps_u > kEpsilonD);
     double l1 = 0.0, l0 = 0.0;
     if (uniform) {
-        l1 = log((double)((1.0f - eps_u) / eps_u));
-        l0 = log((double)(1.0f - eps_u));
+        // the class's two logs in ONE call: odd lanes take 1 - eps, even lanes (1 - eps) / eps -- for a lone wave two
+        // inlined log sequences one behind the other cost twice one.  The same function on the same arguments in lanes 1
+        // and 0 (active in every wave: the control flow is block-uniform here), read back into scalar registers.
+        const float om = 1.0f - eps_u;
+        const double lg = log((lane & 1) ? (double)om : (double)(om / eps_u));
+        NEM_PHASE_AFTER(25, lg);
+        l1 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(lg), 0), __builtin_amdgcn_readlane(__double2loint(lg), 0));
+        l0 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(lg), 1), __builtin_amdgcn_readlane(__double2loint(lg), 1));
+        NEM_PHASE_AFTER(26, l0);
         if (!isfinite(l1) || !isfinite(l0)) uniform = false;
     }
     if (uniform) {
         const double l1h = 0.5 * l1;                     // l1 is 0 or a normal double: halving is exact
         if (a.use_ff && l1 >= 0.0 && l0 <= 0.0) {        // block-uniform
             ff_build(sQ0, sQ1, l1, l0, tid);
+            NEM_PHASE(27);
             __syncthreads();
             NEM_PHASE(21);
             if constexpr (START) xh = xw_head(a.xw, npad, i, D);

@@ -704,42 +704,133 @@ int clear_fault(nemgpu_engine* e)
     return NEMGPU_OK;
 }
 
+// ---- the kernels' argument blocks: each is made HERE, once, from the engine, and a caller adds only what is its own.
+// FinishArgs: finish_args, restart_head, shard_stats.  SweepArgs: sweep_args (buffers, flag slot, post / hold / blind,
+// shard and draw fields are the callers').  CtrlArgs: ctrl_args.  The density launchers: density_io; density_launch and
+// finish_launch also set the host flags that go with their launch.
+// The smaller kernels: counts_args, fuzzy_args, labels_post_args, conv_fuzzy_args, crit_args, layout_args.
 FinishArgs finish_args(nemgpu_engine* e, int mode, const int* stats)
 {
     FinishArgs t;
-    t.mode = mode;
-    t.K = e->k; t.D = e->d; t.dpad = e->dpad; t.n_total = e->n_true; t.disper = e->cfg.disper; t.propor = e->cfg.propor;
+    t.mode = mode; t.K = e->k; t.D = e->d; t.dpad = e->dpad; t.n_total = e->n_true; t.disper = e->cfg.disper; t.propor = e->cfg.propor;
     t.stats = stats; t.stats_ranks = 1; t.stats_rank_stride = 0;
     t.prop = e->prop; t.center = e->center; t.disp = e->disp; t.nbobs_k = e->nbobs_k; t.iner = e->iner;
     t.tabT = e->tabT; t.tabL0 = e->tabL0; t.nz0 = e->nz0; t.nz1 = e->nz1;
     t.am0 = e->am0; t.am1 = e->am1; t.uni = e->uni; t.nonuni = e->nonuni;
-    t.pk = e->pk; t.logpk = e->logpk; t.flags = e->iter_flags();
-    t.stop = e->stop_ptr;
-    t.reset_prop = nullptr; t.reset_center = nullptr; t.reset_disp = nullptr;
-    t.reset_ctrl = nullptr; t.reset_ctrl_words = 0; t.reset_sweep_next = nullptr;
-    t.prev_center = nullptr; t.prev_disp = nullptr;
-    t.zero_stats = nullptr; t.n_zero_stats = 0;
-    t.use_ff = !e->use_ff() ? FF_OFF : e->ff_batch ? FF_BATCHED : FF_WORD;
-    t.perm = e->perm;
-    t.ffq = e->ffq;
+    t.pk = e->pk; t.logpk = e->logpk; t.flags = e->iter_flags(); t.stop = e->stop_ptr;
+    t.reset_prop = nullptr; t.reset_center = nullptr; t.reset_disp = nullptr; t.reset_ctrl = nullptr; t.reset_ctrl_words = 0; t.reset_sweep_next = nullptr;
+    t.prev_center = nullptr; t.prev_disp = nullptr; t.zero_stats = nullptr; t.n_zero_stats = 0;
+    t.use_ff = !e->use_ff() ? FF_OFF : e->ff_batch ? FF_BATCHED : FF_WORD; t.perm = e->perm; t.ffq = e->ffq;
     return t;
+}
+// the head of a restart: the initial parameters back in place, loop control and sweep counter cleared
+void restart_head(nemgpu_engine* e, FinishArgs& t)
+{
+    t.reset_prop = e->prop0; t.reset_center = e->center0; t.reset_disp = e->disp0;
+    t.reset_ctrl = e->ctrl(); t.reset_ctrl_words = C_WORDS; t.reset_sweep_next = e->sweep_next;
+}
+// sharded: the statistics are every rank's partial counts, in the tails of the gathered label blocks
+void shard_stats(const nemgpu_engine* e, FinishArgs& t) { t.stats_ranks = e->sh_world; t.stats_rank_stride = e->sh_stride / 4; }
+// what every round of a sweep shares, made in place (a recorder's member makes one per sweep: no copy of the block).
+// on_device: the sweep's number is read from e->sweep_next (pipelined loop), not `id`
+void sweep_args(const nemgpu_engine* e, SweepArgs& a, float beta, uint32_t id, bool on_device = false)
+{
+    a = SweepArgs{};
+    a.n_local = e->n; a.lo = e->lo; a.n_total = e->n_total; a.K = e->k; a.npad = e->npad;
+    a.use_nei = (e->has_graph && beta != 0.0f) ? 1 : 0; a.nei_ptr = e->nei_ptr; a.nei_idx = e->nei_idx; a.nei_w = e->nei_w;
+    a.beta = beta; a.pkfki = e->pkfki;
+    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.map_full = e->map_margin ? 0 : 1;
+    a.sweep_id = id; a.sweep_id_ptr = on_device ? e->sweep_next : nullptr;
+}
+// the loop control behind a sweep of n_rounds enqueued rounds.  A sweep is verified (use_nei) when its sites are coupled:
+// through the graph, or through the reference's tie stream
+CtrlArgs ctrl_args(nemgpu_engine* e, int n_rounds, float beta)
+{
+    CtrlArgs ca{};
+    ca.ctrl = e->ctrl(); ca.iter_flags = e->iter_flags(); ca.round0 = e->round_flags(0); ca.n_rounds = n_rounds;
+    ca.param_fix = e->cfg.param_fix; ca.use_nei = ((e->has_graph && beta != 0.0f) || e->libc()) ? 1 : 0; ca.cvtest = e->cfg.cvtest;
+    ca.ncem = e->ncem() ? 1 : 0; ca.cvthres = e->cfg.cvthres; ca.sweep_next = e->sweep_next; ca.ticket = e->sweep_next + 32;
+    ca.draw_ctl = e->libc() ? e->draw_ctl : nullptr;
+    return ca;
+}
+CountsArgs counts_args(const nemgpu_engine* e, int* stats, const CtrlArgs* prev_ctrl)
+{
+    CountsArgs a{};
+    a.K = e->k; a.D = e->d; a.nw64 = e->nw64; a.xt = e->xt; a.mask = e->mask; a.stats = stats; a.stop = e->stop_ptr;
+    if (prev_ctrl != nullptr) a.prev_ctrl = *prev_ctrl;
+    return a;
+}
+// c: memberships [n_total][K] (this engine's rows are read); ctpad is the launch wrapper's
+FuzzyArgs fuzzy_args(nemgpu_engine* e, const float* c, const int* stop)
+{
+    FuzzyArgs a{};
+    a.n = e->n; a.npad = e->npad; a.K = e->k; a.D = e->d; a.xw = e->xw; a.xt = e->xt; a.nw64 = e->nw64;
+    a.c = c + (size_t)e->lo * e->k; a.nbobs_k = e->nbobs_k; a.center = e->center; a.iner = e->iner; a.stop = stop;
+    a.in0 = e->fz_in0; a.in1 = e->fz_in1; a.inh_k = e->fz_inh; a.lastz = e->fz_lastz; a.any1 = e->fz_any1;
+    a.ct = e->fz_ct; a.chk = e->fz_chk; a.fault = e->iter_flags() + FLAG_FAULT; a.inject = e->fault_inject;
+    return a;
+}
+LabelsPostArgs labels_post_args(nemgpu_engine* e, const uint8_t* lab_new, const uint8_t* lab_old, const CtrlArgs* ctrl)
+{
+    LabelsPostArgs a{};
+    a.lo = e->lo; a.n_local = e->n; a.K = e->k; a.nw64 = e->nw64; a.lab_new = lab_new; a.lab_old = lab_old;
+    a.mask = e->mask; a.flags = e->iter_flags(); a.stop = e->stop_ptr;
+    if (ctrl != nullptr) a.ca = *ctrl;
+    return a;
+}
+// c_new, c_old: memberships [n_total][K] (this engine's rows are compared)
+ConvFuzzyArgs conv_fuzzy_args(nemgpu_engine* e, const float* c_new, const float* c_old, const int* stop, const CtrlArgs* ctrl)
+{
+    ConvFuzzyArgs a{};
+    a.m = (size_t)e->n * e->k; a.c = c_new + (size_t)e->lo * e->k; a.cold = c_old + (size_t)e->lo * e->k;
+    a.thres = e->cfg.cvthres; a.flags = e->iter_flags(); a.stop = stop;
+    if (ctrl != nullptr) a.ca = *ctrl;
+    return a;
+}
+// c: memberships or one-hot rows [n][K]; second: the evaluation writes the crit2_* set of buffers
+CritArgs crit_args(const nemgpu_engine* e, const float* c, bool second)
+{
+    CritArgs a{};
+    a.n = e->n; a.K = e->k; a.npad = e->npad; a.nei_ptr = e->nei_ptr; a.nei_idx = e->nei_idx; a.nei_w = e->nei_w;
+    a.use_nei = e->has_graph ? 1 : 0; a.beta = e->cfg.beta; a.c = c; a.pkfki = e->pkfki; a.logpkfki = e->logpkfki;
+    a.dik = second ? e->crit2_dik : e->crit_dik; a.gik = second ? e->crit2_gik : e->crit_gik;
+    a.lfi = second ? e->crit2_lfi : e->crit_lfi; a.lzi = second ? e->crit2_lzi : e->crit_lzi;
+    a.crit6 = second ? e->crit2_6 : e->crit6_dev; a.hard = e->ncem() ? 1 : 0;
+    return a;
+}
+// xf: the uploaded family-major bit matrix
+LayoutArgs layout_args(const nemgpu_engine* e, const uint32_t* xf)
+{
+    return LayoutArgs{xf, e->perm, e->n, e->wf, e->W, e->npad, e->d, e->nw64, e->xw, e->xws, e->xt};
+}
+DensityIO density_io(nemgpu_engine* e)
+{
+    return DensityIO{e->xws, e->n, e->npad, e->pkfki, e->logpkfki, e->iter_flags() + FLAG_MOVED, kSweepFlagWords};
+}
+// k_finish and the host flags behind it: the tables are those of the parameters now in place, the densities are not
+void finish_launch(nemgpu_engine* e, const FinishArgs& t) { launch_finish(t, e->stream); e->tables_fresh = true; e->density_fresh = false; }
+// A density launch that derives the parameters itself: with a held sweep round beside it (held), as the start of a run (t
+// carries the restart head), else fused.  None rebuilds the table buffers.  flags = false: the host flags stay (the probes)
+void density_launch(nemgpu_engine* e, const FinishArgs& t, const SweepArgs* held = nullptr, bool flags = true)
+{
+    if (held != nullptr) launch_density_verify(t, density_io(e), *held, e->stream);
+    else if (t.reset_prop != nullptr) launch_density_start(t, density_io(e), e->stream);
+    else launch_density_fused(t, density_io(e), e->stream);
+    if (flags) { e->flags_clean = true; e->tables_fresh = false; e->density_fresh = true; }
 }
 
 // density tables from the current parameters (k_finish mode 0); a no-op when they are up to date
 int do_tables(nemgpu_engine* e)
 {
     if (e->tables_fresh) return NEMGPU_OK;
-    launch_finish(finish_args(e, 0, nullptr), e->stream);
+    finish_launch(e, finish_args(e, 0, nullptr));
     HIPCHK(hipGetLastError());
-    e->tables_fresh = true;
-    e->density_fresh = false;
     return NEMGPU_OK;
 }
 
 int do_density(nemgpu_engine* e)
 {
-    launch_density(finish_args(e, 0, nullptr), e->xws, e->n, e->npad, e->pkfki, e->logpkfki, e->iter_flags() + FLAG_MOVED,
-                   kSweepFlagWords, e->stream);
+    launch_density(finish_args(e, 0, nullptr), density_io(e), e->stream);
     HIPCHK(hipGetLastError());
     e->flags_clean = true;
     e->density_fresh = true;
@@ -753,7 +844,6 @@ int do_density(nemgpu_engine* e)
 // is NOT advanced (the caller commits).
 struct SweepCtx {
     SweepArgs a{};
-    bool use_nei = false;
     bool multi = false;  // the sweep needs verified relaxation rounds: it reads neighbours, or its ties share a draw stream
     int r = 0;           // rounds launched so far
     int checked = 0;     // rounds whose flags the host has examined
@@ -898,37 +988,35 @@ int sweep_launch_rounds(nemgpu_engine* e, SweepCtx& c, int count)
 // the arguments every round of one sweep shares (takes the sweep's number)
 int sweep_setup(nemgpu_engine* e, float beta, SweepCtx& c, bool id_by_value)
 {
-    c.use_nei = e->has_graph && beta != 0.0f;
-    c.multi = c.use_nei || e->libc();
-    SweepArgs& a = c.a;
-    a.n_local = e->n; a.lo = e->lo; a.n_total = e->n_total; a.K = e->k; a.npad = e->npad;
-    a.use_nei = c.use_nei ? 1 : 0;
-    a.nei_ptr = e->nei_ptr; a.nei_idx = e->nei_idx; a.nei_w = e->nei_w;
-    a.beta = beta;
-    a.pkfki = e->pkfki;
-    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.map_full = e->map_margin ? 0 : 1; a.sweep_id = e->sweep_counter++;
-    a.sweep_id_ptr = (e->stop_ptr != nullptr && !id_by_value) ? e->sweep_next : nullptr;   // pipelined loop: the device keeps count
+    sweep_args(e, c.a, beta, e->sweep_counter++, e->stop_ptr != nullptr && !id_by_value);   // pipelined loop: the device keeps count
+    c.multi = c.a.use_nei || e->libc();
     if (e->libc()) {
         if (e->stop_ptr == nullptr) { int r = ensure_draw_window(e, e->draws, draw_need(e)); if (r) return r; }
-        sweep_draw_args(e, a, e->stop_ptr == nullptr);
+        sweep_draw_args(e, c.a, e->stop_ptr == nullptr);
     }
     return NEMGPU_OK;
 }
 
-int sweep_enqueue(nemgpu_engine* e, float beta, SweepCtx& c, bool id_by_value = false, const CtrlArgs* post_ctrl = nullptr,
-                  bool post_moved = false, int slot_base = 0, int rounds = 0, SweepArgs* hold = nullptr, int* count_into = nullptr)
+// what a sweep_enqueue may ask for beyond the plain sweep (post_ctrl .. count_into: NCEM, as SweepCtx explains them)
+struct SweepOpts {
+    bool id_by_value = false;             // the sweep's number as an argument even inside the pipelined loop
+    int slot_base = 0, rounds = 0;        // first flag slot of the round window; rounds to enqueue (0: round_batch)
+    const CtrlArgs* post_ctrl = nullptr; bool post_moved = false; SweepArgs* hold = nullptr; int* count_into = nullptr;
+};
+
+int sweep_enqueue(nemgpu_engine* e, float beta, SweepCtx& c, const SweepOpts& o = SweepOpts())
 {
     c = SweepCtx();
-    c.slot_base = slot_base;
+    c.slot_base = o.slot_base;
     c.blind_slot = e->blind_slot_once; c.blind_id = e->blind_id_once; e->blind_slot_once = -1;
-    if (post_ctrl != nullptr && e->ncem()) {
-        c.post = true; c.post_moved = post_moved; c.post_ctrl = *post_ctrl; c.hold = hold;
-        c.count_into = hold != nullptr ? count_into : nullptr;
+    if (o.post_ctrl != nullptr && e->ncem()) {
+        c.post = true; c.post_moved = o.post_moved; c.post_ctrl = *o.post_ctrl; c.hold = o.hold;
+        c.count_into = o.hold != nullptr ? o.count_into : nullptr;
     }
-    { int r = sweep_setup(e, beta, c, id_by_value); if (r) return r; }
+    { int r = sweep_setup(e, beta, c, o.id_by_value); if (r) return r; }
     if (!e->flags_clean) { int r = clear_sweep_flags(e); if (r) return r; }
     e->flags_clean = false;
-    return sweep_launch_rounds(e, c, c.multi ? (rounds > 0 ? rounds : e->round_batch) : 1);
+    return sweep_launch_rounds(e, c, c.multi ? (o.rounds > 0 ? o.rounds : e->round_batch) : 1);
 }
 
 // `extra` is set when rounds beyond the first batch were needed (work enqueued after the first
@@ -998,8 +1086,7 @@ int do_sweep(nemgpu_engine* e, float beta, int* rounds_out)
 
 int do_labels_post(nemgpu_engine* e, int newbuf, int oldbuf, const CtrlArgs* ctrl = nullptr)
 {
-    launch_labels_post(e->n, e->lo, e->k, e->nw64, e->lab[newbuf], oldbuf >= 0 ? e->lab[oldbuf] : nullptr, e->mask,
-                       e->iter_flags(), e->stop_ptr, ctrl, e->stream);
+    launch_labels_post(labels_post_args(e, e->lab[newbuf], oldbuf >= 0 ? e->lab[oldbuf] : nullptr, ctrl), e->stream);
     HIPCHK(hipGetLastError());
     e->masks_valid = true;
     return NEMGPU_OK;
@@ -1010,19 +1097,14 @@ int do_mstep(nemgpu_engine* e, const CtrlArgs* prev_ctrl = nullptr)
 {
     if (e->ncem()) {
         if (!e->masks_valid) { int r = do_labels_post(e, e->cur, -1); if (r) return r; }
-        launch_mstep_counts(e->k, e->d, e->nw64, e->xt, e->mask, e->stats, e->stop_ptr, prev_ctrl, e->stream);
-        launch_finish(finish_args(e, 1, e->stats), e->stream);
+        launch_mstep_counts(counts_args(e, e->stats, prev_ctrl), e->stream);
+        finish_launch(e, finish_args(e, 1, e->stats));
         e->stats_last = e->stats;
     } else {
-        launch_mstep_fuzzy(e->n, e->npad, e->k, e->d, e->xw, e->xt, e->nw64, e->cbuf[e->cur] + (size_t)e->lo * e->k,
-                           e->fz_ct, e->nbobs_k,
-                           e->fz_in0, e->fz_in1, e->fz_inh, e->fz_lastz, e->fz_any1, e->center, e->iner, e->stop_ptr, e->stream,
-                           e->fz_chk, e->iter_flags() + FLAG_FAULT, e->fault_inject);
-        launch_finish(finish_args(e, 2, nullptr), e->stream);
+        launch_mstep_fuzzy(fuzzy_args(e, e->cbuf[e->cur], e->stop_ptr), e->stream);
+        finish_launch(e, finish_args(e, 2, nullptr));
     }
     HIPCHK(hipGetLastError());
-    e->tables_fresh = true;                                        // k_finish rebuilt them from the new parameters
-    e->density_fresh = false;
     return NEMGPU_OK;
 }
 
@@ -1072,9 +1154,7 @@ int post_sweep(nemgpu_engine* e, int newbuf, int oldbuf, const CtrlArgs* ctrl = 
 {
     if (e->ncem()) return do_labels_post(e, newbuf, oldbuf, ctrl);
     if (e->cfg.cvtest == NEMGPU_CV_CLAS) {
-        launch_conv_fuzzy((size_t)e->n * e->k, e->cbuf[newbuf] + (size_t)e->lo * e->k,
-                          e->cbuf[oldbuf] + (size_t)e->lo * e->k, e->cfg.cvthres, e->iter_flags(), e->stop_ptr, ctrl,
-                          e->stream);
+        launch_conv_fuzzy(conv_fuzzy_args(e, e->cbuf[newbuf], e->cbuf[oldbuf], e->stop_ptr, ctrl), e->stream);
         HIPCHK(hipGetLastError());
     } else if (ctrl != nullptr) {
         launch_ctrl(*ctrl, e->stream);
@@ -1090,21 +1170,20 @@ constexpr int kPipeDepth = 7;       // (the graph table holds batches of up to 7
 int host_rounds_ctx(nemgpu_engine* e, SweepCtx& sc, uint32_t sweep_id, int launched)
 {
     sc = SweepCtx();
-    sc.use_nei = e->has_graph && e->cfg.beta != 0.0f;
     sc.multi = true;
-    SweepArgs& a = sc.a;
-    a.n_local = e->n; a.lo = e->lo; a.n_total = e->n_total; a.K = e->k; a.npad = e->npad; a.use_nei = sc.use_nei ? 1 : 0;
-    a.nei_ptr = e->nei_ptr; a.nei_idx = e->nei_idx; a.nei_w = e->nei_w; a.beta = e->cfg.beta; a.pkfki = e->pkfki;
-    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.map_full = e->map_margin ? 0 : 1; a.sweep_id = sweep_id; a.sweep_id_ptr = nullptr;
+    sweep_args(e, sc.a, e->cfg.beta, sweep_id);
     sc.r = launched; sc.checked = launched;               // (the enqueued rounds all changed something)
     if (e->libc()) {
         for (int q = 0; q < launched; q++) if (e->h_round(q)[FLAG_NTIES] & (1 << 30)) e->tie_heavy = true;
         int r = ensure_draw_window(e, e->draws, draw_need(e));
         if (r) return r;
-        sweep_draw_args(e, a, true);
+        sweep_draw_args(e, sc.a, true);
     }
     return NEMGPU_OK;
 }
+
+// puts e->cur back when an enqueue step that set it for its own launches leaves, by whichever exit
+struct CurGuard { nemgpu_engine* e; int saved; ~CurGuard() { e->cur = saved; } };
 
 // enqueue one whole iteration whose current partition is buffer `cur`.  defer_ctrl: another iteration follows in
 // the same batch -- an NCEM iteration's loop control then runs in that iteration's counts launch (k_mstep_counts)
@@ -1122,7 +1201,7 @@ int iteration_rounds(const nemgpu_engine* e, int pos, bool deep)
 int enqueue_iteration(nemgpu_engine* e, int cur, uint32_t sweep_id, bool defer_ctrl, bool deep, int pos = -1)
 {
     int r;
-    const int saved = e->cur;
+    const CurGuard restore{e, e->cur};
     e->cur = cur;
     // one engine alone: the parameter update rides in the density launch (a launch boundary costs more than the
     // redundant per-block derivation).  In a lock-step batch the launch is shared by all members and the kernels are
@@ -1135,44 +1214,34 @@ int enqueue_iteration(nemgpu_engine* e, int cur, uint32_t sweep_id, bool defer_c
     }
     if (fused) {
         // M-step counts, then ONE kernel: parameter update (per block, from the counts) + density
-        if (!e->masks_valid) { if ((r = do_labels_post(e, e->cur, -1))) { e->cur = saved; return r; } }
-        launch_mstep_counts(e->k, e->d, e->nw64, e->xt, e->mask, e->stats, e->stop_ptr,
-                            e->ctrl_pending ? &e->ctrl_deferred : nullptr, e->stream);
+        if (!e->masks_valid) { if ((r = do_labels_post(e, e->cur, -1))) return r; }
+        launch_mstep_counts(counts_args(e, e->stats, e->ctrl_pending ? &e->ctrl_deferred : nullptr), e->stream);
         e->ctrl_pending = false;
-        launch_density_fused(finish_args(e, 1, e->stats), e->xws, e->n, e->npad, e->pkfki, e->logpkfki,
-                             e->iter_flags() + FLAG_MOVED, kSweepFlagWords, e->stream);
-        hipError_t le = hipGetLastError();
-        if (le != hipSuccess) { e->cur = saved; set_error(std::string("launch failed: ") + hipGetErrorString(le)); return NEMGPU_E_DEVICE; }
-        e->flags_clean = true;
-        e->tables_fresh = false;                                   // the table buffers were not rebuilt
-        e->density_fresh = true;
+        density_launch(e, finish_args(e, 1, e->stats));
+        HIPCHK(hipGetLastError());
     } else {
         if (!e->cfg.param_fix) {                                   // nem_alg.c:1806
-            if ((r = do_mstep(e, e->ctrl_pending ? &e->ctrl_deferred : nullptr))) { e->cur = saved; return r; }
+            if ((r = do_mstep(e, e->ctrl_pending ? &e->ctrl_deferred : nullptr))) return r;
             e->ctrl_pending = false;
-            if ((r = do_tables(e))) { e->cur = saved; return r; }
+            if ((r = do_tables(e))) return r;
         }
-        if ((r = do_density(e))) { e->cur = saved; return r; }
+        if ((r = do_density(e))) return r;
     }
     SweepCtx c;
     e->sweep_counter = sweep_id;
-    CtrlArgs ca{};
     // (members of a lock-step batch all take the same number of rounds: a member with a sequence of its own would
     //  need launches of its own)
     const int it_rounds = iteration_rounds(e, pos, deep);
-    ca.ctrl = e->ctrl(); ca.iter_flags = e->iter_flags(); ca.round0 = e->round_flags(0); ca.n_rounds = it_rounds;
-    ca.param_fix = e->cfg.param_fix; ca.use_nei = ((e->has_graph && e->cfg.beta != 0.0f) || e->libc()) ? 1 : 0; ca.cvtest = e->cfg.cvtest;
-    ca.ncem = e->ncem() ? 1 : 0; ca.cvthres = e->cfg.cvthres; ca.sweep_next = e->sweep_next; ca.ticket = e->sweep_next + 32;
-    ca.draw_ctl = e->libc() ? e->draw_ctl : nullptr;
+    const CtrlArgs ca = ctrl_args(e, it_rounds, e->cfg.beta);
     // NCEM: the bookkeeping (masks, "moved", loop tests) rides in the last relaxation round's launch -- the loop
     // tests in the next iteration's counts launch when there is one
     const bool defer = defer_ctrl && counts_first;
-    CtrlArgs none{};
-    if ((r = sweep_enqueue(e, e->cfg.beta, c, false, e->ncem() ? (defer ? &none : &ca) : nullptr, true, 0, it_rounds))) { e->cur = saved; return r; }
+    const CtrlArgs none{};
+    SweepOpts o; o.post_ctrl = e->ncem() ? (defer ? &none : &ca) : nullptr; o.post_moved = true; o.rounds = it_rounds;
+    if ((r = sweep_enqueue(e, e->cfg.beta, c, o))) return r;
     if (defer) { e->ctrl_deferred = ca; e->ctrl_pending = true; }
-    if (!e->ncem()) { if ((r = post_sweep(e, (cur + 1) % 3, cur, &ca))) { e->cur = saved; return r; } }
+    if (!e->ncem()) { if ((r = post_sweep(e, (cur + 1) % 3, cur, &ca))) return r; }
     else e->masks_valid = true;
-    e->cur = saved;
     return NEMGPU_OK;
 }
 
@@ -1218,22 +1287,18 @@ int enqueue_init(nemgpu_engine* e, bool defer_ctrl, SweepArgs* hold = nullptr, i
 {
     int r;
     FinishArgs t = finish_args(e, 0, nullptr);
-    t.reset_prop = e->prop0; t.reset_center = e->center0; t.reset_disp = e->disp0;
-    t.reset_ctrl = e->ctrl(); t.reset_ctrl_words = C_WORDS; t.reset_sweep_next = e->sweep_next;
+    restart_head(e, t);
     if (hold != nullptr && count_into != nullptr) { t.zero_stats = count_into; t.n_zero_stats = e->k + e->k * e->d; }
     e->cur = 0;
     if (e->start_fused && shadow_engine(e)) {
         // one launch: initial parameters back in place, loop control and sweep flag slots cleared, and the density, every
         // block deriving its class constants from the given parameters (k_density_start)
-        launch_density_start(t, e->xws, e->n, e->npad, e->pkfki, e->logpkfki, e->iter_flags() + FLAG_MOVED, kSweepFlagWords, e->stream);
+        density_launch(e, t);
         HIPCHK(hipGetLastError());
-        e->tables_fresh = false;                                   // the table buffers were not rebuilt
-        e->flags_clean = true; e->density_fresh = true;
     } else {
         // one launch: initial parameters back in place, loop control cleared, density tables built
-        launch_finish(t, e->stream);
+        finish_launch(e, t);
         HIPCHK(hipGetLastError());
-        e->tables_fresh = true; e->density_fresh = false;
         if ((r = do_density(e))) return r;                         // (also clears every sweep flag slot)
     }
     SweepCtx c0, c1;
@@ -1250,22 +1315,22 @@ int enqueue_init(nemgpu_engine* e, bool defer_ctrl, SweepArgs* hold = nullptr, i
         // tallies into the blind sweep's slot.  The host state as it would be behind the blind sweep (number 0).
         e->blind_slot_once = kRoundCap - ra; e->blind_id_once = e->sweep_counter++;
         e->n_blind_folds++;
-    } else if ((r = sweep_enqueue(e, 0.0f, c0, true, nullptr, false, kRoundCap - ra, libc ? ra : 0))) return r;
+    } else {
+        SweepOpts o; o.id_by_value = true; o.slot_base = kRoundCap - ra; o.rounds = libc ? ra : 0;
+        if ((r = sweep_enqueue(e, 0.0f, c0, o))) return r;
+    }
     e->flags_clean = true;
     e->cur = 1;
-    CtrlArgs ca{};
-    ca.ctrl = e->ctrl(); ca.iter_flags = e->iter_flags(); ca.round0 = e->round_flags(0); ca.n_rounds = init_beta_rounds(e);
-    ca.param_fix = e->cfg.param_fix; ca.use_nei = ((e->has_graph && e->cfg.beta != 0.0f) || e->libc()) ? 1 : 0; ca.cvtest = e->cfg.cvtest;
-    ca.ncem = e->ncem() ? 1 : 0; ca.cvthres = e->cfg.cvthres; ca.sweep_next = e->sweep_next; ca.ticket = e->sweep_next + 32;
-    ca.draw_ctl = e->libc() ? e->draw_ctl : nullptr;
+    CtrlArgs ca = ctrl_args(e, init_beta_rounds(e), e->cfg.beta);
     ca.is_init = 1;
     ca.blind = e->round_flags(kRoundCap - ra);
     ca.blind_rounds = libc ? ra : 0;
     const bool defer = defer_ctrl && e->ncem() && !e->cfg.param_fix && hold == nullptr;
-    CtrlArgs none{};
+    const CtrlArgs none{};
     if (libc) e->draw_extra_once = e->round_flags(kRoundCap - 1) + FLAG_NTIES;
-    if ((r = sweep_enqueue(e, e->cfg.beta, c1, true, e->ncem() ? (defer ? &none : &ca) : nullptr, false, 0, ca.n_rounds, hold,
-                           count_into))) return r;   // 1 -> 2 (and 0 as the pong buffer)
+    SweepOpts o; o.id_by_value = true; o.post_ctrl = e->ncem() ? (defer ? &none : &ca) : nullptr; o.rounds = ca.n_rounds;
+    o.hold = hold; o.count_into = count_into;
+    if ((r = sweep_enqueue(e, e->cfg.beta, c1, o))) return r;   // 1 -> 2 (and 0 as the pong buffer)
     e->draw_extra_once = nullptr;
     if (defer) { e->ctrl_deferred = ca; e->ctrl_pending = true; }
     if (e->ncem()) e->masks_valid = true;
@@ -1281,18 +1346,18 @@ int libc_init_a(nemgpu_engine* e, SweepCtx& c, int rounds = 0)
 {
     int r;
     FinishArgs t = finish_args(e, 0, nullptr);                 // initial parameters back in place, loop control cleared, tables
-    t.reset_prop = e->prop0; t.reset_center = e->center0; t.reset_disp = e->disp0;
-    t.reset_ctrl = e->ctrl(); t.reset_ctrl_words = C_WORDS; t.reset_sweep_next = e->sweep_next;
-    launch_finish(t, e->stream);
-    e->tables_fresh = true; e->density_fresh = false;
+    restart_head(e, t);
+    finish_launch(e, t);
     e->cur = 0; e->sweep_counter = 0;
     if ((r = do_density(e))) return r;
-    return sweep_enqueue(e, 0.0f, c, false, nullptr, false, 0, rounds);          // blind sweep 0 -> 1
+    SweepOpts o; o.rounds = rounds;
+    return sweep_enqueue(e, 0.0f, c, o);                       // blind sweep 0 -> 1
 }
 int libc_init_b(nemgpu_engine* e, SweepCtx& c, int rounds = 0)
 {
     e->cur = 1;
-    return sweep_enqueue(e, e->cfg.beta, c, false, nullptr, false, 0, rounds);   // 1 -> 2
+    SweepOpts o; o.rounds = rounds;
+    return sweep_enqueue(e, e->cfg.beta, c, o);                // 1 -> 2
 }
 int libc_init_c(nemgpu_engine* e)
 {
@@ -1316,19 +1381,18 @@ int libc_init_one_wait(nemgpu_engine* e, int ra, int rb, bool* redo, int rounds[
     *redo = false;
     ra = std::max(1, std::min(ra, kRoundCap / 4)); rb = std::max(1, std::min(rb, kRoundCap / 2));
     FinishArgs t = finish_args(e, 0, nullptr);
-    t.reset_prop = e->prop0; t.reset_center = e->center0; t.reset_disp = e->disp0;
-    t.reset_ctrl = e->ctrl(); t.reset_ctrl_words = C_WORDS; t.reset_sweep_next = e->sweep_next;
-    launch_finish(t, e->stream);
-    e->tables_fresh = true; e->density_fresh = false;
+    restart_head(e, t);
+    finish_launch(e, t);
     e->cur = 0; e->sweep_counter = 0;
     if ((r = do_density(e))) return r;                             // (also clears every sweep flag slot)
     SweepCtx ca, cb;
     const int base_a = kRoundCap - ra;
-    if ((r = sweep_enqueue(e, 0.0f, ca, false, nullptr, false, base_a, ra))) return r;          // blind sweep 0 -> 1
+    SweepOpts oa, ob; oa.slot_base = base_a; oa.rounds = ra; ob.rounds = rb;
+    if ((r = sweep_enqueue(e, 0.0f, ca, oa))) return r;            // blind sweep 0 -> 1
     e->flags_clean = true;                                         // (the beta sweep's slots have not been touched)
     e->cur = 1;
     e->draw_extra_once = e->round_flags(kRoundCap - 1) + FLAG_NTIES;
-    if ((r = sweep_enqueue(e, e->cfg.beta, cb, false, nullptr, false, 0, rb))) return r;         // 1 -> 2
+    if ((r = sweep_enqueue(e, e->cfg.beta, cb, ob))) return r;     // 1 -> 2
     e->draw_extra_once = nullptr;
     // the flags leave as soon as the rounds are through (an event marks the copy); the class masks and the sweep counter
     // run while the host wakes up and draws the next start's centres
@@ -1558,39 +1622,32 @@ int enqueue_iteration_shadow(nemgpu_engine* e, int cur, uint32_t sweep_id, bool 
                              SweepArgs* held, bool* pending, int* stats, int* count_into, bool* counted)
 {
     int r;
-    const int saved = e->cur;
+    const CurGuard restore{e, e->cur};
     e->cur = cur;
     if (!(*pending && *counted)) {
-        if (!e->masks_valid) { if ((r = do_labels_post(e, e->cur, -1))) { e->cur = saved; return r; } }
-        launch_mstep_counts(e->k, e->d, e->nw64, e->xt, e->mask, stats, e->stop_ptr, nullptr, e->stream);
+        if (!e->masks_valid) { if ((r = do_labels_post(e, e->cur, -1))) return r; }
+        launch_mstep_counts(counts_args(e, stats, nullptr), e->stream);
     }
     if (!hold) count_into = nullptr;
     use_copy(e, copy);
     FinishArgs t = finish_args(e, 1, stats);
     if (count_into != nullptr) { t.zero_stats = count_into; t.n_zero_stats = e->k + e->k * e->d; }
     t.prev_center = e->par_copy[prev] + e->par_o_center; t.prev_disp = e->par_copy[prev] + e->par_o_disp;
-    if (*pending) launch_density_verify(t, e->xws, e->n, e->npad, e->pkfki, e->logpkfki, e->iter_flags() + FLAG_MOVED,
-                                        kSweepFlagWords, *held, e->stream);
-    else launch_density_fused(t, e->xws, e->n, e->npad, e->pkfki, e->logpkfki, e->iter_flags() + FLAG_MOVED, kSweepFlagWords, e->stream);
+    density_launch(e, t, *pending ? held : nullptr);
     *pending = false;
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) { e->cur = saved; set_error(std::string("launch failed: ") + hipGetErrorString(le)); return NEMGPU_E_DEVICE; }
-    e->flags_clean = true;
-    e->tables_fresh = false;
-    e->density_fresh = true;
+    HIPCHK(hipGetLastError());
     SweepCtx c;
     e->sweep_counter = sweep_id;
-    CtrlArgs ca{};
     const int it_rounds = iteration_rounds(e, pos, deep);
-    ca.ctrl = e->ctrl(); ca.iter_flags = e->iter_flags(); ca.round0 = e->round_flags(0); ca.n_rounds = it_rounds;
-    ca.param_fix = 0; ca.use_nei = 1; ca.cvtest = e->cfg.cvtest;
-    ca.ncem = 1; ca.cvthres = e->cfg.cvthres; ca.sweep_next = e->sweep_next; ca.ticket = e->sweep_next + 32;
+    // (what the rule gives under shadow_engine(e): use_nei = 1, ncem = 1, param_fix = 0, and no draw words -- the schedule
+    //  has no TIE_LIBC)
+    const CtrlArgs ca = ctrl_args(e, it_rounds, e->cfg.beta);
     if (hold) *held = SweepArgs{};
-    if ((r = sweep_enqueue(e, e->cfg.beta, c, false, &ca, true, 0, it_rounds, hold ? held : nullptr, count_into))) { e->cur = saved; return r; }
+    SweepOpts o; o.post_ctrl = &ca; o.post_moved = true; o.rounds = it_rounds; o.hold = hold ? held : nullptr; o.count_into = count_into;
+    if ((r = sweep_enqueue(e, e->cfg.beta, c, o))) return r;
     *pending = hold && held->post_ctrl.ctrl != nullptr;    // (a sweep of one round has nothing to hold back)
     *counted = *pending && count_into != nullptr;
     e->masks_valid = true;
-    e->cur = saved;
     return NEMGPU_OK;
 }
 
@@ -2087,7 +2144,7 @@ int lockstep(std::vector<nemgpu_engine*>& E, const std::vector<int>& members, st
 static void pending_layout(nemgpu_engine* e)
 {
     if (!e->layout_pending) return;
-    launch_layout(e->xf_stage, e->n, e->wf, e->W, e->npad, e->d, e->nw64, e->xw, e->xt, e->perm, e->xws, e->stream);
+    launch_layout(layout_args(e, e->xf_stage), e->stream);
     e->layout_pending = false;
 }
 
@@ -2478,13 +2535,10 @@ int criteria_enqueue(nemgpu_engine* e, int buf = -1, bool second)
     const float* c = e->cbuf[buf];
     if (e->ncem()) {
         float* onehot = second ? e->c_onehot2 : e->c_onehot;
-        launch_onehot(e->n_total, e->k, e->lab[buf], onehot, e->stream);
+        launch_onehot(OnehotArgs{e->n_total, e->k, e->lab[buf], onehot}, e->stream);
         c = onehot;
     }
-    launch_criteria(e->n, e->k, e->npad, e->nei_ptr, e->nei_idx, e->nei_w, e->has_graph ? 1 : 0, e->cfg.beta, c,
-                    e->pkfki, e->logpkfki, second ? e->crit2_dik : e->crit_dik, second ? e->crit2_gik : e->crit_gik,
-                    second ? e->crit2_lfi : e->crit_lfi, second ? e->crit2_lzi : e->crit_lzi, second ? e->crit2_6 : e->crit6_dev,
-                    e->ncem() ? 1 : 0, e->stream);
+    launch_criteria(crit_args(e, c, second), e->stream);
     if (!current_recorder()) HIPCHK(hipGetLastError());
     return NEMGPU_OK;
 }
@@ -2913,7 +2967,7 @@ static int upload_bits(nemgpu_engine* e, const int* pc_in)
     e->layout_pending = false;
     if (err == hipSuccess && e->defer_layout && async && staged_in_chunk) e->layout_pending = true;   // (run_many: pending_layout)
     else if (err == hipSuccess) {
-        launch_layout(xf, e->n, e->wf, e->W, e->npad, e->d, e->nw64, e->xw, e->xt, e->perm, e->xws, e->stream);
+        launch_layout(layout_args(e, xf), e->stream);
         err = hipGetLastError();
     }
     if (err == hipSuccess && !(async && staged_in_chunk)) err = hipStreamSynchronize(e->stream);
@@ -3668,7 +3722,7 @@ static int adopt_chunk(nemgpu_engine* e, const nemgpu_master* M, const nemk::Chu
     e->nnz = nnz; e->has_graph = nnz > 0;
     e->host_bits = nullptr; e->host_bits_words = 0;              // (no host copy of the rows: random starts are not for chunk engines)
     if (e->defer_layout) e->layout_pending = true;               // (the group's first step carries the layouts, zipped)
-    else { launch_layout(e->xf_stage, e->n, e->wf, e->W, e->npad, e->d, e->nw64, e->xw, e->xt, e->perm, e->xws, e->stream); HIPCHK(hipGetLastError()); }
+    else { launch_layout(layout_args(e, e->xf_stage), e->stream); HIPCHK(hipGetLastError()); }
     e->have_matrix = true;
     return NEMGPU_OK;
 }
@@ -4820,14 +4874,7 @@ int nemgpu_shard_layout(nemgpu_engine* e, int world, int rank, int blk, int stri
 namespace {
 void shard_sweep_args(nemgpu_engine* e, SweepArgs& a, float beta, int sweep_id)
 {
-    a = SweepArgs{};
-    a.n_local = e->n; a.lo = e->lo; a.n_total = e->n_total; a.K = e->k; a.npad = e->npad;
-    a.use_nei = (e->has_graph && beta != 0.0f) ? 1 : 0;
-    a.nei_ptr = e->nei_ptr; a.nei_idx = e->nei_idx; a.nei_w = e->nei_w;
-    a.beta = beta; a.pkfki = e->pkfki;
-    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.map_full = e->map_margin ? 0 : 1;
-    a.sweep_id = sweep_id >= 0 ? (uint32_t)sweep_id : 0u;
-    a.sweep_id_ptr = sweep_id >= 0 ? nullptr : e->sweep_next;     // -1: the device keeps count (pipelined loop)
+    sweep_args(e, a, beta, sweep_id >= 0 ? (uint32_t)sweep_id : 0u, sweep_id < 0);   // -1: the device keeps count (pipelined loop)
     a.stop = e->stop_ptr;
     a.n_ranks = e->sh_world; a.slot_stride = e->sh_stride; a.slot_pad = e->sh_stride - e->sh_blk;
     a.fold_ticket = e->sweep_next + 32;
@@ -4909,11 +4956,9 @@ int nemgpu_shard_begin_restart(nemgpu_engine* e)
     e->reset_pending = false;
     if ((r = clear_fault(e))) return r;
     FinishArgs t = finish_args(e, 0, nullptr);
-    t.reset_prop = e->prop0; t.reset_center = e->center0; t.reset_disp = e->disp0;
-    t.reset_ctrl = e->ctrl(); t.reset_ctrl_words = C_WORDS; t.reset_sweep_next = e->sweep_next;
-    launch_finish(t, e->stream);
+    restart_head(e, t);
+    finish_launch(e, t);
     HIPCHK(hipGetLastError());
-    e->tables_fresh = true; e->density_fresh = false;
     if (e->libc()) {                                               // (srandom(seed): the stream starts over)
         if ((r = ensure_draw_window(e, e->draws, draw_need(e)))) return r;
         if ((r = publish_draw_ctl(e))) return r;
@@ -4929,7 +4974,7 @@ int nemgpu_shard_counts(nemgpu_engine* e, int32_t* stats_dev)
     if (!e || !stats_dev) return NEMGPU_E_FUNCARG;
     HIPCHK(hipSetDevice(e->device));
     { const int fr = flush_reset(e); if (fr) return fr; }
-    launch_mstep_counts(e->k, e->d, e->nw64, e->xt, e->mask, stats_dev, e->stop_ptr, nullptr, e->stream);
+    launch_mstep_counts(counts_args(e, stats_dev, nullptr), e->stream);
     HIPCHK(hipGetLastError());
     return NEMGPU_OK;
 }
@@ -4940,9 +4985,8 @@ int nemgpu_shard_mstep_partial(nemgpu_engine* e, const uint8_t* labels_cur_dev, 
     if (!e || !labels_cur_dev || !stats_dev) return NEMGPU_E_FUNCARG;
     HIPCHK(hipSetDevice(e->device));
     { const int fr = flush_reset(e); if (fr) return fr; }
-    launch_labels_post(e->n, e->lo, e->k, e->nw64, labels_cur_dev, nullptr, e->mask, e->iter_flags(), e->stop_ptr,
-                       nullptr, e->stream);
-    launch_mstep_counts(e->k, e->d, e->nw64, e->xt, e->mask, stats_dev, e->stop_ptr, nullptr, e->stream);
+    launch_labels_post(labels_post_args(e, labels_cur_dev, nullptr, nullptr), e->stream);
+    launch_mstep_counts(counts_args(e, stats_dev, nullptr), e->stream);
     HIPCHK(hipGetLastError());
     e->masks_valid = false;
     return NEMGPU_OK;
@@ -4961,21 +5005,15 @@ int nemgpu_shard_estep_round0(nemgpu_engine* e, const int32_t* stats_dev, float 
     if (fused) {
         // parameter update (per block, from the summed counts) + density in one launch
         FinishArgs t = finish_args(e, 1, stats_dev);
-        t.stats_ranks = e->sh_world; t.stats_rank_stride = e->sh_stride / 4;
-        launch_density_fused(t, e->xws, e->n, e->npad, e->pkfki, e->logpkfki,
-                             e->iter_flags() + FLAG_MOVED, kSweepFlagWords, e->stream);
+        shard_stats(e, t);
+        density_launch(e, t);
         HIPCHK(hipGetLastError());
-        e->tables_fresh = false;
-        e->density_fresh = true;
-        e->flags_clean = true;
     } else {
         if (stats_dev != nullptr) {
             FinishArgs t = finish_args(e, 1, stats_dev);
-            t.stats_ranks = e->sh_world; t.stats_rank_stride = e->sh_stride / 4;
-            launch_finish(t, e->stream);
+            shard_stats(e, t);
+            finish_launch(e, t);
             HIPCHK(hipGetLastError());
-            e->tables_fresh = true;
-            e->density_fresh = false;
         } else if ((r = do_tables(e))) return r;
         if (e->density_fresh) { if (!e->flags_clean && (r = clear_sweep_flags(e))) return r; }   // same parameters as the last E1: keep pkfki
         else if ((r = do_density(e))) return r;                    // also clears MOVED + the round flag window
@@ -5024,9 +5062,10 @@ int nemgpu_shard_estep_round1_counts(nemgpu_engine* e, float beta, int sweep_id,
     shard_round1_args(e, a, beta, sweep_id, labels_old_dev, labels_guess_dev, labels_out_dev);
     { const int tr = shard_tie_args(e, a, labels_guess_dev, labels_out_dev); if (tr) return tr; }
     static const bool merge = !(getenv("NEM_DIST_MERGE") && getenv("NEM_DIST_MERGE")[0] == '0');
-    if (!merge || !launch_sweep_counts(a, e->k, e->d, e->nw64, e->xt, e->mask, stats_dev, e->stop_ptr, e->stream)) {
+    const CountsArgs ca = counts_args(e, stats_dev, nullptr);
+    if (!merge || !launch_sweep_counts(a, ca, e->stream)) {
         launch_sweep(a, true, e->stream);
-        launch_mstep_counts(e->k, e->d, e->nw64, e->xt, e->mask, stats_dev, e->stop_ptr, nullptr, e->stream);
+        launch_mstep_counts(ca, e->stream);
     }
     HIPCHK(hipGetLastError());
     return NEMGPU_OK;
@@ -5064,12 +5103,8 @@ int nemgpu_shard_fuzzy_round(nemgpu_engine* e, float beta, int sweep_id, int rou
     if ((r = ensure_state_buffers(e))) return r;
     const int slot = round % kRoundCap;
     HIPCHK(hipMemsetAsync(e->round_flags(slot), 0, FLAG_ROUND_STRIDE * sizeof(int), e->stream));
-    SweepArgs a{};
-    a.n_local = e->n; a.lo = e->lo; a.n_total = e->n_total; a.K = e->k; a.npad = e->npad;
-    a.use_nei = (e->has_graph && beta != 0.0f) ? 1 : 0;
-    a.nei_ptr = e->nei_ptr; a.nei_idx = e->nei_idx; a.nei_w = e->nei_w;
-    a.beta = beta; a.pkfki = e->pkfki;
-    a.tie_rule = e->cfg.tie_rule; a.tie_seed = e->cfg.tie_seed; a.map_full = e->map_margin ? 0 : 1; a.sweep_id = (uint32_t)sweep_id;
+    SweepArgs a;
+    sweep_args(e, a, beta, (uint32_t)sweep_id);                    // (host-driven: no stop word)
     a.c_old = c_old_dev; a.c_guess = c_guess_dev; a.c_out = c_out_dev;
     a.flags = e->round_flags(slot);
     a.fold_ticket = e->sweep_next + 32;
@@ -5098,10 +5133,7 @@ int nemgpu_shard_fuzzy_mstep_cols(nemgpu_engine* e, const float* c_dev, float* n
     { const int fr = flush_reset(e); if (fr) return fr; }
     int r;
     if ((r = ensure_state_buffers(e))) return r;
-    launch_mstep_fuzzy(e->n, e->npad, e->k, e->d, e->xw, e->xt, e->nw64, c_dev + (size_t)e->lo * e->k,
-                       e->fz_ct, e->nbobs_k,
-                       e->fz_in0, e->fz_in1, e->fz_inh, e->fz_lastz, e->fz_any1, e->center, e->iner, nullptr, e->stream,
-                       e->fz_chk, e->iter_flags() + FLAG_FAULT, e->fault_inject);
+    launch_mstep_fuzzy(fuzzy_args(e, c_dev, nullptr), e->stream);
     HIPCHK(hipGetLastError());
     const size_t kd = (size_t)e->k * e->d;
     HIPCHK(hipMemcpyAsync(nbobs_out_dev, e->nbobs_k, sizeof(float) * e->k, hipMemcpyDeviceToDevice, e->stream));
@@ -5126,9 +5158,8 @@ int nemgpu_shard_fuzzy_finish(nemgpu_engine* e, const float* nbobs_dev, const fl
     HIPCHK(hipMemcpyAsync(e->nbobs_k, nbobs_dev, sizeof(float) * e->k, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->center, center_dev, sizeof(float) * kd, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->iner, iner_dev, sizeof(float) * kd, hipMemcpyDeviceToDevice, e->stream));
-    launch_finish(finish_args(e, 2, nullptr), e->stream);
+    finish_launch(e, finish_args(e, 2, nullptr));
     HIPCHK(hipGetLastError());
-    e->tables_fresh = true; e->density_fresh = false;
     if ((r = read_iter_flags(e))) return r;
     const int ek = e->h_iter()[FLAG_EMPTYK];
     if (emptyk) *emptyk = ek;
@@ -5143,8 +5174,7 @@ int nemgpu_shard_fuzzy_moved(nemgpu_engine* e, const float* c_new_dev, const flo
     if (!e || !c_new_dev || !c_old_dev || !moved) return NEMGPU_E_FUNCARG;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemsetAsync(e->iter_flags() + FLAG_MOVED, 0, sizeof(int), e->stream));
-    launch_conv_fuzzy((size_t)e->n * e->k, c_new_dev + (size_t)e->lo * e->k, c_old_dev + (size_t)e->lo * e->k, e->cfg.cvthres,
-                      e->iter_flags(), nullptr, nullptr, e->stream);
+    launch_conv_fuzzy(conv_fuzzy_args(e, c_new_dev, c_old_dev, nullptr, nullptr), e->stream);
     HIPCHK(hipGetLastError());
     int r;
     if ((r = read_iter_flags(e))) return r;
@@ -5158,19 +5188,17 @@ int nemgpu_shard_finish_iteration(nemgpu_engine* e, float beta, int is_init, con
 {
     if (!e || !labels_old_dev || !labels_q_dev || !labels_r_dev) return NEMGPU_E_FUNCARG;
     HIPCHK(hipSetDevice(e->device));
-    CtrlArgs ca{};
-    ca.ctrl = e->ctrl(); ca.iter_flags = e->iter_flags(); ca.round0 = e->round_flags(0); ca.n_rounds = 2;
-    ca.param_fix = e->cfg.param_fix; ca.use_nei = beta != 0.0f ? 1 : 0; ca.cvtest = e->cfg.cvtest; ca.ncem = 1;
-    ca.cvthres = e->cfg.cvthres; ca.sweep_next = e->sweep_next; ca.ticket = e->sweep_next + 32;
+    CtrlArgs ca = ctrl_args(e, 2, beta);                           // (the path is NCEM-only, shard_check)
     ca.q_flags = labels_q_dev + e->sh_blk; ca.r_flags = labels_r_dev + e->sh_blk;
     ca.n_ranks = e->sh_world; ca.flag_stride = e->sh_stride; ca.is_init = is_init;
     if (is_init) ca.blind = e->round_flags(kRoundCap - 1);         // (the blind sweep's zero-density tally)
     // every rank's "one of my labels moved" byte came with the gather of the sweep's last round: round 1's, or -- no
     // neighbours to verify against (beta = 0) -- round 0's
+    // (the driver runs the verifying round whenever beta != 0, graph or no graph: here the rule is its own)
     const bool two_rounds = beta != 0.0f || e->libc();             // (the reference's tie stream couples the sites of a sweep without neighbours too)
     ca.use_nei = two_rounds ? 1 : 0;
     ca.moved_bytes = is_init ? 0 : (two_rounds ? 1 : 2);
-    if (e->libc()) { ca.draw_ctl = e->draw_ctl; ca.q_tot = labels_q_dev + e->sh_tot_off(); }
+    if (e->libc()) ca.q_tot = labels_q_dev + e->sh_tot_off();
     launch_ctrl(ca, e->stream);
     HIPCHK(hipGetLastError());
     return NEMGPU_OK;
@@ -5622,8 +5650,7 @@ int nemgpu_profile_density(nemgpu_engine* e, int reps, double* avg_ms, double* a
     for (int i = 0; i < reps; i++) {
         HIPCHK(hipEventRecord(e->ev0, e->stream));
         if (fused) {
-            launch_density_fused(finish_args(e, 1, e->stats_last), e->xws, e->n, e->npad, e->pkfki, e->logpkfki,
-                                 e->iter_flags() + FLAG_MOVED, kSweepFlagWords, e->stream);
+            density_launch(e, finish_args(e, 1, e->stats_last), nullptr, false);
             HIPCHK(hipGetLastError());
         } else if ((r = do_density(e))) return r;
         HIPCHK(hipEventRecord(e->ev1, e->stream));
@@ -5721,13 +5748,13 @@ int nemgpu_profile_kernels(nemgpu_engine* e, int reps, double avg_ms[3], double 
         return NEMGPU_OK;
     };
     // M-step counts first: they leave the statistics the fused E1 derives its parameters from
-    if ((r = timed([&] { launch_mstep_counts(e->k, e->d, e->nw64, e->xt, e->mask, e->stats, nullptr, nullptr, e->stream); }, &avg_ms[2]))) return r;
+    CountsArgs ca = counts_args(e, e->stats, nullptr);
+    ca.stop = nullptr;                                             // (the timed launches read no stop word)
+    if ((r = timed([&] { launch_mstep_counts(ca, e->stream); }, &avg_ms[2]))) return r;
     e->stats_last = e->stats;
     if ((r = timed([&] {
-            if (fused) launch_density_fused(finish_args(e, 1, e->stats), e->xws, e->n, e->npad, e->pkfki, e->logpkfki,
-                                            e->iter_flags() + FLAG_MOVED, kSweepFlagWords, e->stream);
-            else launch_density(finish_args(e, 0, nullptr), e->xws, e->n, e->npad, e->pkfki, e->logpkfki, e->iter_flags() + FLAG_MOVED,
-                                kSweepFlagWords, e->stream);
+            if (fused) density_launch(e, finish_args(e, 1, e->stats), nullptr, false);
+            else launch_density(finish_args(e, 0, nullptr), density_io(e), e->stream);
         }, &avg_ms[0]))) return r;
     e->density_fresh = true; e->flags_clean = true;
     if (fused) e->tables_fresh = false;

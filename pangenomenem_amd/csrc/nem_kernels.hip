@@ -2531,11 +2531,9 @@ void launch_copy_words(const int* src, int* dst, int words, hipStream_t s)
 
 // the device layouts of an uploaded matrix (recordable: nemgpu_solve_many leaves them to the group's run, one launch each
 // for all members instead of three small launches per engine next to the running group)
-void launch_layout(const uint32_t* xf, int n, int wf, int W, int npad, int d, int nw64, uint32_t* xw, uint64_t* xt,
-                   const int* perm, uint32_t* xws, hipStream_t s)
+void launch_layout(const LayoutArgs& a, hipStream_t s)
 {
-    const LayoutArgs a{xf, perm, n, wf, W, npad, d, nw64, xw, xws, xt};
-    const dim3 gw((npad + 255) / 256, ((W + 3) / 4) * 4), gb((nw64 * 64 + 255) / 256, W);
+    const dim3 gw((a.npad + 255) / 256, ((a.W + 3) / 4) * 4), gb((a.nw64 * 64 + 255) / 256, a.W);
     issue(OP_LAYOUT_WORDS, 0, k_layout_words, gw, 256, a, s);
     issue(OP_LAYOUT_BITS, 0, k_layout_bits, gb, 256, a, s);
 }
@@ -2549,16 +2547,15 @@ void launch_finish(const FinishArgs& a, hipStream_t s)
 
 static int density_blocks(int npad, int K) { return ((npad / 256 + 7) / 8) * 8 * K; }
 
-void launch_density(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
-                    int* zero_flags, int n_zero_flags, hipStream_t s)
+void launch_density(const FinishArgs& t, const DensityIO& io, hipStream_t s)
 {
     DensityArgs a;
-    a.xw = (const uint4*)xw; a.n = n; a.npad = npad; a.dpad = t.dpad; a.D = t.D; a.K = t.K;
+    a.xw = (const uint4*)io.xw; a.n = io.n; a.npad = io.npad; a.dpad = t.dpad; a.D = t.D; a.K = t.K;
     a.tabT = t.tabT; a.tabL0 = t.tabL0; a.nz0 = t.nz0; a.nz1 = t.nz1; a.am0 = t.am0; a.am1 = t.am1;
     a.uni = t.uni; a.nonuni = t.nonuni; a.pk = t.pk; a.logpk = t.logpk;
-    a.pkfki = pkfki; a.logpkfki = logpkfki; a.zero_flags = zero_flags; a.n_zero_flags = n_zero_flags;
+    a.pkfki = io.pkfki; a.logpkfki = io.logpkfki; a.zero_flags = io.zero_flags; a.n_zero_flags = io.n_zero_flags;
     a.stop = t.stop; a.use_ff = t.use_ff; a.perm = t.perm; a.ffq = t.ffq;
-    issue(OP_DENSITY, 0, k_density, dim3(density_blocks(npad, t.K)), 256, a, s);
+    issue(OP_DENSITY, 0, k_density, dim3(density_blocks(io.npad, t.K)), 256, a, s);
 }
 
 // compute units of the current device (asked once per device)
@@ -2575,17 +2572,16 @@ static int compute_units()
     return cus[dev];
 }
 
-static FusedDensityArgs fused_density_args(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki,
-                                           float* logpkfki, int* zero_flags, int n_zero_flags)
+static FusedDensityArgs fused_density_args(const FinishArgs& t, const DensityIO& io)
 {
     FusedDensityArgs a;
-    a.xw = (const uint4*)xw; a.n = n; a.npad = npad; a.dpad = t.dpad; a.D = t.D; a.K = t.K; a.n_total = t.n_total;
+    a.xw = (const uint4*)io.xw; a.n = io.n; a.npad = io.npad; a.dpad = t.dpad; a.D = t.D; a.K = t.K; a.n_total = t.n_total;
     a.disper = t.disper; a.propor = t.propor; a.stats = t.stats;
     a.stats_ranks = t.stats_ranks; a.stats_rank_stride = t.stats_rank_stride;
     a.center = t.center; a.disp = t.disp; a.prop = t.prop; a.nbobs_k = t.nbobs_k; a.iter_flags = t.flags;
     a.center_in = t.prev_center != nullptr ? t.prev_center : t.center;
     a.disp_in = t.prev_disp != nullptr ? t.prev_disp : t.disp;
-    a.pkfki = pkfki; a.logpkfki = logpkfki; a.zero_flags = zero_flags; a.n_zero_flags = n_zero_flags; a.stop = t.stop;
+    a.pkfki = io.pkfki; a.logpkfki = io.logpkfki; a.zero_flags = io.zero_flags; a.n_zero_flags = io.n_zero_flags; a.stop = t.stop;
     a.zero_stats = t.zero_stats; a.n_zero_stats = t.zero_stats != nullptr ? t.n_zero_stats : 0;
     a.use_ff = t.use_ff; a.perm = t.perm;
     // the lane-by-lane walk where it pays: more than one word, and a grid that is resident at once with the walk's LDS
@@ -2593,7 +2589,7 @@ static FusedDensityArgs fused_density_args(const FinishArgs& t, const uint32_t* 
     // blocks per compute unit waits for; a grid that fills the device several times over is bound by the sum of its
     // waves' work and by how many of them are resident, and there the rows cost more than the passes save
     // (200 000 x 1 000: 5 % slower with the walk, 400 000 x 300: 13 %).
-    if (a.use_ff == FF_BATCHED && !(t.D > 32 && density_blocks(npad, t.K) <= 3 * compute_units())) a.use_ff = FF_WORD;
+    if (a.use_ff == FF_BATCHED && !(t.D > 32 && density_blocks(io.npad, t.K) <= 3 * compute_units())) a.use_ff = FF_WORD;
     return a;
 }
 
@@ -2603,28 +2599,26 @@ static size_t ff_row_bytes(const FusedDensityArgs& a)
     return a.use_ff == FF_BATCHED ? sizeof(uint32_t) * kFFRowWords * 256 : 0;
 }
 
-void launch_density_fused(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
-                          int* zero_flags, int n_zero_flags, hipStream_t s)
+void launch_density_fused(const FinishArgs& t, const DensityIO& io, hipStream_t s)
 {
     // (not recordable: in a lock-step batch the update runs once per class, k_finish_b, and the blocks of k_density_b load it)
     if (current_recorder() != nullptr) {
         fprintf(stderr, "launch_density_fused: not recordable\n");
         abort();
     }
-    const FusedDensityArgs a = fused_density_args(t, xw, n, npad, pkfki, logpkfki, zero_flags, n_zero_flags);
-    const dim3 grid(density_blocks(npad, t.K));
+    const FusedDensityArgs a = fused_density_args(t, io);
+    const dim3 grid(density_blocks(io.npad, t.K));
     if (a.use_ff == FF_BATCHED) hipLaunchKernelGGL(k_density_fused, grid, dim3(256), ff_row_bytes(a), s, a);
     else hipLaunchKernelGGL(k_density_fused_word, grid, dim3(256), 0, s, a);
 }
 
-void launch_density_start(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
-                          int* zero_flags, int n_zero_flags, hipStream_t s)
+void launch_density_start(const FinishArgs& t, const DensityIO& io, hipStream_t s)
 {
-    const FusedDensityArgs a = fused_density_args(t, xw, n, npad, pkfki, logpkfki, zero_flags, n_zero_flags);
+    const FusedDensityArgs a = fused_density_args(t, io);
     StartArgs st;
     st.prop0 = t.reset_prop; st.center0 = t.reset_center; st.disp0 = t.reset_disp;
     st.ctrl = t.reset_ctrl; st.ctrl_words = t.reset_ctrl_words; st.sweep_next = t.reset_sweep_next;
-    const dim3 grid(density_blocks(npad, t.K));
+    const dim3 grid(density_blocks(io.npad, t.K));
     if (a.use_ff == FF_BATCHED) hipLaunchKernelGGL(k_density_start, grid, dim3(256), ff_row_bytes(a), s, a, st);
     else hipLaunchKernelGGL(k_density_start_word, grid, dim3(256), 0, s, a, st);
 }
@@ -2634,11 +2628,10 @@ bool density_verify_supported(int n_local, int K, int tie_rule)
     return n_local < 65536 && K >= 1 && K <= 10 && tie_rule != NEMGPU_TIE_LIBC;
 }
 
-void launch_density_verify(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
-                           int* zero_flags, int n_zero_flags, const SweepArgs& sw, hipStream_t s)
+void launch_density_verify(const FinishArgs& t, const DensityIO& io, const SweepArgs& sw, hipStream_t s)
 {
-    const FusedDensityArgs a = fused_density_args(t, xw, n, npad, pkfki, logpkfki, zero_flags, n_zero_flags);
-    const int nd = density_blocks(npad, t.K);
+    const FusedDensityArgs a = fused_density_args(t, io);
+    const int nd = density_blocks(io.npad, t.K);
     const int ns = (sw.n_local + 255) / 256;
     const dim3 grid(nd + ns);
     dispatch_k<1, 10>(sw.K, [&](auto kt) {
@@ -2648,75 +2641,58 @@ void launch_density_verify(const FinishArgs& t, const uint32_t* xw, int n, int n
 
 // an NCEM relaxation round and M-step counts in one launch (k_sweep_counts); false: not for this shape (the caller
 // launches the two separately)
-bool launch_sweep_counts(const SweepArgs& sw, int K, int D, int nw64, const uint64_t* xt, const uint64_t* mask, int* stats,
-                         const int* stop, hipStream_t s)
+bool launch_sweep_counts(const SweepArgs& sw, const CountsArgs& c, hipStream_t s)
 {
-    if (current_recorder() != nullptr || sw.n_local >= 65536 || K < 2 || K > 5 || sw.tie_rule == NEMGPU_TIE_LIBC) return false;
-    CountsArgs c{K, D, nw64, xt, mask, stats, stop, CtrlArgs{}};
+    if (current_recorder() != nullptr || sw.n_local >= 65536 || c.K < 2 || c.K > 5 || sw.tie_rule == NEMGPU_TIE_LIBC) return false;
     const int nsweep = (sw.n_local + 255) / 256;
-    const bool wide = D + 1 >= 1024;
-    const dim3 grid(nsweep + (wide ? (D + 1 + 3) / 4 : D + 1));
-    return dispatch_k<2, 5>(K, [&](auto kt) {
+    const bool wide = c.D + 1 >= 1024;
+    const dim3 grid(nsweep + (wide ? (c.D + 1 + 3) / 4 : c.D + 1));
+    return dispatch_k<2, 5>(c.K, [&](auto kt) {
         if (wide) hipLaunchKernelGGL((k_sweep_counts<decltype(kt)::value, 4>), grid, dim3(256), 0, s, sw, c, nsweep);
         else hipLaunchKernelGGL((k_sweep_counts<decltype(kt)::value, 1>), grid, dim3(256), 0, s, sw, c, nsweep);
     });
 }
 
-void launch_labels_post(int n_local, int lo, int K, int nw64, const uint8_t* lab_new, const uint8_t* lab_old,
-                        uint64_t* mask, int* flags, const int* stop, const CtrlArgs* ctrl, hipStream_t s)
+void launch_labels_post(const LabelsPostArgs& a, hipStream_t s)
 {
-    LabelsPostArgs a{n_local, lo, K, nw64, lab_new, lab_old, mask, flags, stop, CtrlArgs{}};
-    if (ctrl != nullptr) a.ca = *ctrl;
-    issue(OP_LABELS_POST, 0, k_labels_post, dim3(std::min((nw64 * 64 + 255) / 256, 128)), 256, a, s);
+    issue(OP_LABELS_POST, 0, k_labels_post, dim3(std::min((a.nw64 * 64 + 255) / 256, 128)), 256, a, s);
 }
 
-void launch_mstep_counts(int K, int D, int nw64, const uint64_t* xt, const uint64_t* mask, int* stats,
-                         const int* stop, const CtrlArgs* prev_ctrl, hipStream_t s)
+void launch_mstep_counts(const CountsArgs& a, hipStream_t s)
 {
     // wide matrices: 4 organism rows per block (fewer re-reads of the class masks); narrow ones keep one row per
     // block so that the launch still spreads over the CUs
-    CountsArgs a{K, D, nw64, xt, mask, stats, stop, CtrlArgs{}};
-    if (prev_ctrl != nullptr) a.prev_ctrl = *prev_ctrl;
     const int extra = a.prev_ctrl.ctrl != nullptr ? 1 : 0;
-    const bool wide = D + 1 >= 1024;
-    const dim3 grid(wide ? (D + 1 + 3) / 4 + extra : D + 1 + extra);
+    const bool wide = a.D + 1 >= 1024;
+    const dim3 grid(wide ? (a.D + 1 + 3) / 4 + extra : a.D + 1 + extra);
     if (wide) issue(OP_COUNTS, 4, k_mstep_counts<4>, grid, 256, a, s);
     else issue(OP_COUNTS, 1, k_mstep_counts<1>, grid, 256, a, s);
 }
 
-void launch_mstep_fuzzy(int n, int npad, int K, int D, const uint32_t* xw, const uint64_t* xt, int nw64, const float* c,
-                        float* ct, float* nbobs_k, float* in0, float* in1, float* inh_k, int* lastz, int* any1, float* center,
-                        float* iner, const int* stop, hipStream_t s, float* chk, int* fault, int inject)
+void launch_mstep_fuzzy(const FuzzyArgs& args, hipStream_t s)
 {
-    const int DB = (D + 63) / 64;
-    const int ctpad = (n + kWin - 1) / kWin * kWin;
-    FuzzyArgs a{n, npad, K, D, xw, xt, nw64, c, nbobs_k, in0, in1, inh_k, lastz, any1, center, iner, stop, ct, ctpad, chk, fault, inject};
+    FuzzyArgs a = args;
+    const int DB = (a.D + 63) / 64;
+    a.ctpad = (a.n + kWin - 1) / kWin * kWin;
     // one lane per chain at the chain's own speed: producer waves make the addends (see mstep_fuzzy_pc_body)
-    issue(OP_FUZZY_T, 0, k_transpose_c, dim3(ctpad / 256), 256, a, s);
-    issue(OP_FUZZY_PC, 0, k_mstep_fuzzy_pc, dim3(2 * DB + 2, K), 64 * kPcWaves, a, s);
-    issue(OP_FUZZY_MED2, 0, k_mstep_fuzzy_med2, dim3(DB, K), 64, a, s);
+    issue(OP_FUZZY_T, 0, k_transpose_c, dim3(a.ctpad / 256), 256, a, s);
+    issue(OP_FUZZY_PC, 0, k_mstep_fuzzy_pc, dim3(2 * DB + 2, a.K), 64 * kPcWaves, a, s);
+    issue(OP_FUZZY_MED2, 0, k_mstep_fuzzy_med2, dim3(DB, a.K), 64, a, s);
 }
 
-void launch_conv_fuzzy(size_t m, const float* c, const float* cold, float thres, int* flags, const int* stop,
-                       const CtrlArgs* ctrl, hipStream_t s)
+void launch_conv_fuzzy(const ConvFuzzyArgs& a, hipStream_t s)
 {
-    ConvFuzzyArgs a{m, c, cold, thres, flags, stop, CtrlArgs{}};
-    if (ctrl != nullptr) a.ca = *ctrl;
-    issue(OP_CONV_FUZZY, 0, k_conv_fuzzy, dim3((unsigned)((m + 255) / 256)), 256, a, s);
+    issue(OP_CONV_FUZZY, 0, k_conv_fuzzy, dim3((unsigned)((a.m + 255) / 256)), 256, a, s);
 }
 
-void launch_onehot(int n, int K, const uint8_t* lab, float* c, hipStream_t s)
+void launch_onehot(const OnehotArgs& a, hipStream_t s)
 {
-    const size_t m = (size_t)n * K;
-    issue(OP_ONEHOT, 0, k_onehot, dim3((unsigned)((m + 255) / 256)), 256, OnehotArgs{n, K, lab, c}, s);
+    issue(OP_ONEHOT, 0, k_onehot, dim3((unsigned)(((size_t)a.n * a.K + 255) / 256)), 256, a, s);
 }
 
-void launch_criteria(int n, int K, int npad, const int* nei_ptr, const int* nei_idx, const float* nei_w, int use_nei,
-                     float beta, const float* c, const double* pkfki, const float* logpkfki, float* dik, float* gik,
-                     double* lfi, double* lzi, float* crit6, int hard, hipStream_t s)
+void launch_criteria(const CritArgs& a, hipStream_t s)
 {
-    CritArgs a{n, K, npad, nei_ptr, nei_idx, nei_w, use_nei, beta, c, pkfki, logpkfki, dik, gik, lfi, lzi, crit6, hard};
-    issue(OP_CRIT_TERMS, 0, k_crit_terms, dim3((n + 255) / 256), 256, a, s);
+    issue(OP_CRIT_TERMS, 0, k_crit_terms, dim3((a.n + 255) / 256), 256, a, s);
     issue(OP_CRIT_REDUCE, 0, k_crit_reduce, dim3(4), CH_T, a, s);   // (a block per chain)
     issue(OP_CRIT_FINAL, 0, k_crit_final, dim3(1), 1, a, s);
 }

@@ -113,7 +113,8 @@ struct SweepArgs {
     // is normalised, as the reference does (NEM_MI355X_MAP_MARGIN=0)
     int map_full;
 };
-// argument blocks of the kernels whose launch wrappers take scalars (the batched launches need them as structs)
+// argument blocks of the smaller kernels; the engine makes each in one place (nem_engine.hip, next to finish_args) and
+// the launch wrappers below take them whole
 struct LabelsPostArgs { int n_local, lo, K, nw64; const uint8_t* lab_new; const uint8_t* lab_old; uint64_t* mask; int* flags;
                         const int* stop; CtrlArgs ca; };
 struct CountsArgs { int K, D, nw64; const uint64_t* xt; const uint64_t* mask; int* stats; const int* stop; CtrlArgs prev_ctrl; };
@@ -168,8 +169,7 @@ void launch_fill(int* ptr, int words, int value, hipStream_t s);   // recordable
 void launch_copy_words(const int* src, int* dst, int words, hipStream_t s);   // recordable device-to-device copy
 
 
-void launch_layout(const uint32_t* xf, int n, int wf, int W, int npad, int d, int nw64, uint32_t* xw, uint64_t* xt,
-                   const int* perm, uint32_t* xws, hipStream_t s);
+void launch_layout(const LayoutArgs& a, hipStream_t s);
 // parameter update + density tables (k_finish); also carries the table pointers k_density reads
 struct FinishArgs {
     int mode;                      // 0: tables only; 1: NCEM centres from counts + dispersion + tables; 2: dispersion + tables
@@ -194,49 +194,39 @@ struct FinishArgs {
     int* zero_stats; int n_zero_stats;
 };
 void launch_finish(const FinishArgs& a, hipStream_t s);
-void launch_density(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
-                    int* zero_flags, int n_zero_flags, hipStream_t s);
+// what a density launch takes besides the FinishArgs (host side only: the launchers copy it into the kernels' blocks)
+struct DensityIO { const uint32_t* xw; int n, npad; double* pkfki; float* logpkfki; int* zero_flags; int n_zero_flags; };
+void launch_density(const FinishArgs& t, const DensityIO& io, hipStream_t s);
 // NCEM, sk_/skd, D <= kFusedMaxD: parameter update from t.stats folded into the density kernel (no k_finish); not recordable
 constexpr int kFusedMaxD = 1024;   // beyond this the per-block parameter derivation costs more than a k_finish launch
 // FinishArgs::use_ff.  FF_BATCHED: the fused density kernels (33 .. kFusedMaxD organisms, a grid the device holds at
 // once) let every lane walk its own row and cross binades in batches (chain_ff_batched); every other kernel and shape
 // reads it as FF_WORD.
 enum FFMode { FF_OFF = 0, FF_WORD = 1, FF_BATCHED = 2 };
-void launch_density_fused(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
-                          int* zero_flags, int n_zero_flags, hipStream_t s);
+void launch_density_fused(const FinishArgs& t, const DensityIO& io, hipStream_t s);
 // the start of a run in ONE launch (k_density_start): the restart head (t.reset_*: initial parameters into t.prop / center /
 // disp, class sizes zeroed, loop control and sweep counter cleared, t.zero_stats cleared) and the density of the given
 // parameters, every block deriving its class constants from them.  The table buffers are not rebuilt.  Same shapes as
 // launch_density_fused; not recordable.
-void launch_density_start(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
-                          int* zero_flags, int n_zero_flags, hipStream_t s);
+void launch_density_start(const FinishArgs& t, const DensityIO& io, hipStream_t s);
 // ... and the same density beside the last relaxation round of the previous iteration's sweep, in ONE launch
 // (k_density_verify); the round's arguments are complete, its last-block ticket included.  Not recordable.
 bool density_verify_supported(int n_local, int K, int tie_rule);
-void launch_density_verify(const FinishArgs& t, const uint32_t* xw, int n, int npad, double* pkfki, float* logpkfki,
-                           int* zero_flags, int n_zero_flags, const SweepArgs& sw, hipStream_t s);
+void launch_density_verify(const FinishArgs& t, const DensityIO& io, const SweepArgs& sw, hipStream_t s);
 void launch_sweep(const SweepArgs& a, bool ncem, hipStream_t s);
 // one NCEM relaxation round and the M-step counts (of the partition whose class masks exist already) in ONE launch;
 // returns false when the shape has no such kernel (2 <= K <= 5, fewer than 65 536 families, not recordable)
-bool launch_sweep_counts(const SweepArgs& sw, int K, int D, int nw64, const uint64_t* xt, const uint64_t* mask, int* stats,
-                         const int* stop, hipStream_t s);
-void launch_labels_post(int n_local, int lo, int K, int nw64, const uint8_t* lab_new, const uint8_t* lab_old,
-                        uint64_t* mask, int* flags, const int* stop, const CtrlArgs* ctrl, hipStream_t s);
-void launch_mstep_counts(int K, int D, int nw64, const uint64_t* xt, const uint64_t* mask, int* stats,
-                         const int* stop, const CtrlArgs* prev_ctrl, hipStream_t s);
-void launch_mstep_fuzzy(int n, int npad, int K, int D, const uint32_t* xw, const uint64_t* xt, int nw64, const float* c,
-                        float* ct, float* nbobs_k, float* in0, float* in1, float* inh_k, int* lastz, int* any1, float* center,
-                        float* iner, const int* stop, hipStream_t s, float* chk, int* fault, int inject);
-void launch_conv_fuzzy(size_t m, const float* c, const float* cold, float thres, int* flags, const int* stop,
-                       const CtrlArgs* ctrl, hipStream_t s);
+bool launch_sweep_counts(const SweepArgs& sw, const CountsArgs& c, hipStream_t s);   // (c.prev_ctrl is not read)
+void launch_labels_post(const LabelsPostArgs& a, hipStream_t s);
+void launch_mstep_counts(const CountsArgs& a, hipStream_t s);
+void launch_mstep_fuzzy(const FuzzyArgs& a, hipStream_t s);   // (sets ctpad itself)
+void launch_conv_fuzzy(const ConvFuzzyArgs& a, hipStream_t s);
 void launch_chain_debug(const double* x, long long n, float init, float* out, hipStream_t s);
 bool launch_map_margin_debug(const double* pkf, const float* ctx, int n, int K, float beta, int use_nei, int* out, hipStream_t s);   // K <= 8; out[n][4]
 bool launch_halfsum_debug(const float* x, int n, int waves, float* out, hipStream_t s, long long* stamps = nullptr);   // n <= 8192, waves 1 | 16; out[2], stamps[6] when timing
 void launch_calib_read(const uint32_t* buf, size_t words, uint32_t* sink, hipStream_t s);
-void launch_onehot(int n, int K, const uint8_t* lab, float* c, hipStream_t s);
-void launch_criteria(int n, int K, int npad, const int* nei_ptr, const int* nei_idx, const float* nei_w, int use_nei,
-                     float beta, const float* c, const double* pkfki, const float* logpkfki, float* dik, float* gik,
-                     double* lfi, double* lzi, float* crit6, int hard, hipStream_t s);   // hard: one-hot rows (NCEM)
+void launch_onehot(const OnehotArgs& a, hipStream_t s);
+void launch_criteria(const CritArgs& a, hipStream_t s);   // a.hard: one-hot rows (NCEM)
 
 // the head of every batched kernel twin: problem = blockIdx.z, its own grid width, its argument block
 #define NEM_B_HEAD(Args)                                                   \

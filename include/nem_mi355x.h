@@ -31,6 +31,10 @@ extern "C" {
  * 1. Drop-in entry (reference: nem_exe.h:23-35).
  *
  *   Fname          base path; inputs <Fname>.str .dat .nei .m, outputs <Fname>.uf|.cf .mf .stderr .log
+ *                  .dat: N*D values 0 or 1; a token strtof reads as NaN (nan, NaN, nan(...)) is a cell that was not
+ *                  observed, as in the reference (nem_exe.c:477-490, nem_mod.c:654).  Files with such cells run under
+ *                  algo "ncem" with init_mode 2 (nemgpu_set_observed_bits below); "nem" and init_mode 1 on them return
+ *                  2 and say why in <Fname>.stderr.  Any other value is refused as a file error.
  *   nk             number of classes K (> 0)
  *   algo           "nem" | "ncem"            ("gem" is not reachable from PPanGGOLiN; rejected)
  *   beta           MRF weight of the neighbourhood term
@@ -144,6 +148,19 @@ int nemgpu_set_matrix_bytes(nemgpu_engine* e, const uint8_t* x_host);
    organism 32w+b), ceil(d/32) words per row, HOST memory.  Bits above organism d-1 in a row's last word are
    padding: the library clears them in its own copy (the caller's buffer is not written), whatever they hold. */
 int nemgpu_set_matrix_bits(nemgpu_engine* e, const uint32_t* xbits_host);
+/* Missing cells (a `nan` in the .dat, which the reference's NEM treats as not observed: DensBernoulli nem_mod.c:654,
+   EstimSizes :1310, ComputeMedian :1455, EstimLaplaceIner :1682, InerToDisp* in their MISSING_IGNORE branches).
+   obits_host: the layout of nemgpu_set_matrix_bits, bit j of row i = 1 when organism j of family i was observed; bits
+   above organism d-1 are ignored.  NULL removes the mask.  The matrix bit of an unobserved cell is don't-care (the
+   masked kernels read every matrix word through the mask).  The mask stays with the engine when another matrix is
+   uploaded (nemgpu_set_matrix_*): only NULL here removes it.  (An engine holds at most 2^24 families, nemgpu_create:
+   the observed counts are exact as floats, as the reference's sums are.)  An engine with a mask -- even one of all ones -- runs
+   NCEM on the masked path: k_density_masked, k_mstep_counts_masked and k_finish_masked (nem_missing.hip), one host
+   round trip per EM iteration, no graphs, no pipelining.  nemgpu_run, nemgpu_iterate, nemgpu_run_logged,
+   nemgpu_iterate_logged, nemgpu_init_partition and the single steps (nemgpu_density, _sweep, _mstep, _criteria) work on it; the fuzzy algorithm,
+   nemgpu_run_many, nemgpu_run_random*, nemgpu_restart_iterate, every nemgpu_shard_* and the nemgpu_profile_* calls
+   refuse it with NEMGPU_E_ARG before any launch.  An engine without a mask runs exactly what it ran before. */
+int nemgpu_set_observed_bits(nemgpu_engine* e, const uint32_t* obits_host);
 /* Neighbourhood graph of the owned shard in CSR, .nei file order inside a row; neighbour
    indices are GLOBAL family indices (0-based).  ptr has (site_hi-site_lo)+1 entries.  HOST memory. */
 int nemgpu_set_graph(nemgpu_engine* e, const int32_t* ptr, const int32_t* idx, const float* w);
@@ -781,6 +798,9 @@ int nemgpu_get_partition(nemgpu_engine* e, float* c_nk);
 int nemgpu_get_labels(nemgpu_engine* e, uint8_t* labels);
 int nemgpu_get_params(nemgpu_engine* e, float* prop, float* center, float* disp, float* nbobs_k);
 int nemgpu_get_density(nemgpu_engine* e, double* pkfki_nk, float* logpkfki_nk);
+/* An engine with an observed mask: NbObs_KD [k*d] of its last M-step, the class's observed families per organism
+   (EstimSizes, nem_mod.c:1310; what the reference's log prints behind the dispersions).  NEMGPU_E_ARG without a mask. */
+int nemgpu_get_observed_counts(nemgpu_engine* e, float* nbobs_kd);
 /* ------------------------------------------------------------------------------------------
  * 3. File layer (host only; what nem() uses on either side of the engine).  Readers follow
  *    ReadStrFile / ReadMatrixFile / ReadPtsNeighs / ReadParamFile (nem_exe.c:739-1091, 1278-1478),
@@ -795,6 +815,9 @@ int nemio_sizes(const nemio_inputs* in, int* n, int* d, int* nnz, int* max_neigh
 /* copy out: xbits [n * ceil(d/32)], nei_ptr [n+1], nei_idx/nei_w [nnz], prop [k], center/disp [k*d]; NULL skips */
 int nemio_copy(const nemio_inputs* in, uint32_t* xbits, int32_t* nei_ptr, int32_t* nei_idx, float* nei_w,
                float* prop, float* center, float* disp);
+/* the .dat file's observed mask: obits [n * ceil(d/32)] (bit = 1: the cell held a number, 0: a `nan` token; padding
+   bits 0), n_missing = the number of nan cells (nem_exe.c:477-490); NULL skips */
+int nemio_observed(const nemio_inputs* in, uint32_t* obits, int* n_missing);
 int nemio_write_uf(const char* path, const float* c_nk, int n, int k);
 /* Test hook: " %<width>.<dec>f" (dec <= 3) of a float exactly as printf prints it -- the formatter behind the
    per-iteration <Fname>.log lines (WriteLogClasses' " %5.3f", " %7.3f", " %7.1f").  out: at least 64 bytes;

@@ -143,7 +143,7 @@ static inline void put_fixed(std::string& out, float v, int width, int dec)
     }
 }
 
-struct LogParams { std::vector<float> prop, center, disp, nk; };
+struct LogParams { std::vector<float> prop, center, disp, nk; std::vector<float> nkd; };   // nkd: NbObs_KD itself (missing cells), else empty
 
 void log_classes(std::string& line, const LogParams& P, float beta, int k, int d, bool sizes_known)
 {
@@ -160,7 +160,9 @@ void log_classes(std::string& line, const LogParams& P, float beta, int k, int d
     for (size_t t = 0; t < (size_t)k * d; t++) put_fixed(line, disp[t], 7, 3);
     line += " ";
     // NbObs_KD: zero until the first EstimPara (calloc, nem_exe.c:320), then N_K for every organism (no missing data)
-    for (int h = 0; h < k; h++) for (int j = 0; j < d; j++) put_fixed(line, sizes_known ? nk[h] : 0.0f, 7, 1);
+    // (a matrix with missing cells: the observed counts per class and organism, EstimSizes nem_mod.c:1310)
+    if (sizes_known && !P.nkd.empty()) for (size_t t = 0; t < (size_t)k * d; t++) put_fixed(line, P.nkd[t], 7, 1);
+    else for (int h = 0; h < k; h++) for (int j = 0; j < d; j++) put_fixed(line, sizes_known ? nk[h] : 0.0f, 7, 1);
     line += "\n";
 }
 
@@ -290,7 +292,7 @@ void random_log_event(const nemgpu_log_event* ev, void* user)
 
 // The INIT_PARAM_FILE run with the reference's log through nemgpu_run_logged: the iterations pipelined, the criteria of a
 // batch's iterations evaluated together, the lines formatted by the writer's threads.
-struct RunLog { LogWriter* w; int k, d; bool sizes; };
+struct RunLog { LogWriter* w; int k, d; bool sizes; nemgpu_engine* masked = nullptr; };   // masked: the engine, when it has an observed mask
 
 void run_log_event(const nemgpu_log_event* ev, void* user)
 {
@@ -310,6 +312,10 @@ void run_log_event(const nemgpu_log_event* ev, void* user)
     j.P = LogParams{std::vector<float>(ev->prop, ev->prop + L.k), std::vector<float>(ev->center, ev->center + kd),
                     std::vector<float>(ev->disp, ev->disp + kd),
                     sizes ? std::vector<float>(ev->nbobs_k, ev->nbobs_k + L.k) : std::vector<float>((size_t)L.k, 0.0f)};
+    if (sizes && L.masked != nullptr) {                                      // (the line is emitted behind its iteration: the M-step's counts are in place)
+        j.P.nkd.resize(kd);
+        if (nemgpu_get_observed_counts(L.masked, j.P.nkd.data()) != NEMGPU_OK) j.P.nkd.clear();
+    }
     memcpy(j.cb, ev->crit_before, sizeof j.cb); memcpy(j.ca, ev->crit_after, sizeof j.ca);
     snprintf(t, sizeof t, "%4d ", ev->iter);
     j.text = t;
@@ -318,7 +324,7 @@ void run_log_event(const nemgpu_log_event* ev, void* user)
     if (ev->iter == 0) { LogJob h; h.kind = LogJob::HEADER; L.w->push(std::move(h)); }   // NemAlgo's header, :1783
 }
 
-int run_logged_pipelined(nemgpu_engine* e, const nemgpu_config& cfg, int n, int d, int k, FILE* fl, nemgpu_result* res)
+int run_logged_pipelined(nemgpu_engine* e, const nemgpu_config& cfg, int n, int d, int k, FILE* fl, nemgpu_result* res, bool masked = false)
 {
     const float mult = log_mult(n);
     fprintf(fl, "NEM log file  -  %s\n", date_line().c_str());
@@ -328,7 +334,7 @@ int run_logged_pipelined(nemgpu_engine* e, const nemgpu_config& cfg, int n, int 
     int rc;
     {
         LogWriter w(fl, mult, cfg.beta, k, d, 2);
-        RunLog L{&w, k, d, !cfg.param_fix};
+        RunLog L{&w, k, d, !cfg.param_fix, masked ? e : nullptr};
         rc = nemgpu_run_logged(e, res, run_log_event, &L);
         w.finish();
     }
@@ -492,6 +498,8 @@ extern "C" int nem(const char* Fname, const int nk, const char* algo, const floa
     if (!in.str_comment.empty()) lg.pr("%s\n", in.str_comment.c_str()); else lg.pr("\n");
     lg.pr("  file names =  %10s   |   nb points   = %10d\n", Fname, in.n);
     lg.pr("  type       =  %10s   |   dim         = %10d\n", in.type == 'N' ? "NoSpatial" : "Spatial", in.d);
+    const bool missing = !in.obits.empty();
+    if (missing) lg.pr("  %d missing values / %d\n", (int)in.n_missing, in.n * in.d);   // nem_exe.c:589-593
     if (in.type != 'N') {
         lg.pr("Neighborhood system :\n  max neighb =  %10d\n", in.max_neighs);
         lg.pr("%s\n", in.nei_comment.c_str());
@@ -508,6 +516,18 @@ extern "C" int nem(const char* Fname, const int nk, const char* algo, const floa
         lg.close();
         return EXIT_E_BUG_;
     }
+    // Missing cells (nan in the .dat): NCEM from a parameter file runs on the engine's masked path.  The fuzzy
+    // algorithm's M-step (i-ordered float sums per class and organism) has no masked form here, and MakeRandomPara has a
+    // missing-data rule of its own (nem_alg.c:1436-1458) that the random starts do not state.
+    if (missing && (cfg.algo != NEMGPU_ALGO_NCEM || random_init)) {
+        if (cfg.algo != NEMGPU_ALGO_NCEM)
+            lg.pr(" Missing values (nan) in %s.dat : only algorithm ncem is supported with missing data by this engine\n", base.c_str());
+        if (random_init)
+            lg.pr(" Missing values (nan) in %s.dat : random starts (init_mode 1) are not supported with missing data by this engine\n", base.c_str());
+        lg.pr("*** NEM error status : bad arguments\n");
+        lg.close();
+        return EXIT_E_ARGS_;
+    }
 
     // ---- the EM run on the GPU (ClassifyByNem, :624)
     const clk::time_point t_read = clk::now();
@@ -522,6 +542,7 @@ extern "C" int nem(const char* Fname, const int nk, const char* algo, const floa
     int rc = nemgpu_default_device(&device);
     if (rc == NEMGPU_OK) rc = nemgpu_create(&e, in.n, in.d, nk, 0, in.n, device, nullptr);
     if (rc == NEMGPU_OK) rc = nemgpu_set_matrix_bits(e, in.xbits.data());
+    if (rc == NEMGPU_OK && missing) rc = nemgpu_set_observed_bits(e, in.obits.data());
     if (rc == NEMGPU_OK) rc = nemgpu_set_graph(e, in.nei_ptr.data(), in.nei_idx.data(), in.nei_w.data());
     if (rc == NEMGPU_OK && !random_init) rc = nemgpu_set_params(e, in.prop.data(), in.center.data(), in.disp.data());
     if (rc == NEMGPU_OK) rc = nemgpu_configure(e, &cfg);
@@ -545,7 +566,7 @@ extern "C" int nem(const char* Fname, const int nk, const char* algo, const floa
             // trip per iteration); NEM_MI355X_LOG=0 keeps the pipelined run and writes a header-only log
             const char* lenv = getenv("NEM_MI355X_LOG");
             FILE* fl = (dolog && !(lenv && lenv[0] == '0')) ? fopen((base + ".log").c_str(), "w") : nullptr;
-            if (fl) { rc = run_logged_pipelined(e, cfg, in.n, in.d, nk, fl, &res); fclose(fl); full_log = true; }
+            if (fl) { rc = run_logged_pipelined(e, cfg, in.n, in.d, nk, fl, &res, missing); fclose(fl); full_log = true; }
             else rc = nemgpu_run(e, &res);
         }
     }
@@ -657,6 +678,22 @@ int nemio_copy(const nemio_inputs* h, uint32_t* xbits, int32_t* nei_ptr, int32_t
     if (prop) memcpy(prop, in.prop.data(), in.prop.size() * sizeof(float));
     if (center) memcpy(center, in.center.data(), in.center.size() * sizeof(float));
     if (disp) memcpy(disp, in.disp.data(), in.disp.size() * sizeof(float));
+    return NEMGPU_OK;
+}
+
+int nemio_observed(const nemio_inputs* h, uint32_t* obits, int* n_missing)
+{
+    if (!h) return NEMGPU_E_FUNCARG;
+    const NemInputs& in = h->in;
+    if (n_missing) *n_missing = (int)in.n_missing;
+    if (obits) {
+        if (!in.obits.empty()) memcpy(obits, in.obits.data(), in.obits.size() * sizeof(uint32_t));
+        else {                                                     // nothing missing: every cell observed, padding bits 0
+            const int wf = (in.d + 31) / 32;
+            for (size_t t = 0; t < (size_t)in.n * wf; t++) obits[t] = 0xFFFFFFFFu;
+            if (in.d & 31) for (int i = 0; i < in.n; i++) obits[(size_t)i * wf + (wf - 1)] = (1u << (in.d & 31)) - 1u;
+        }
+    }
     return NEMGPU_OK;
 }
 

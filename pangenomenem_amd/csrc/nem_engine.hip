@@ -304,6 +304,16 @@ struct nemgpu_engine {
     // captured the second time a shape is enqueued (nemgpu_shard_enqueue_batch)
     GraphCache shard_graphs{64, true, false};
 
+    // Missing cells (nemgpu_set_observed_bits): the observed mask in the matrix's three layouts, the observed counts per
+    // (class, organism) as the masked M-step takes them (ints) and as the reference keeps them (NbObs_KD, floats), and the
+    // upload staging.  has_obs sends do_density / do_mstep to the kernels of nem_missing.hip and iterate() to
+    // iterate_stepwise; without it nothing below is touched.
+    bool has_obs = false;
+    uint32_t *ow = nullptr, *ows = nullptr, *obs_stage = nullptr;
+    uint64_t* ot = nullptr;
+    int* obs_stats = nullptr;
+    float* nbobs_kd = nullptr;
+
     bool ncem() const { return cfg.algo == NEMGPU_ALGO_NCEM; }
     int* ctrl() const { return flags_dev; }
     int* iter_flags() const { return flags_dev + C_WORDS + (size_t)fset * kFlagSetWords; }
@@ -828,9 +838,25 @@ int do_tables(nemgpu_engine* e)
     return NEMGPU_OK;
 }
 
+// an engine with an observed mask: what cannot run on it says so before any launch
+int masked_refuse(const nemgpu_engine* e, const char* who)
+{
+    if (!e->has_obs) return NEMGPU_OK;
+    set_error(std::string(who) + ": the engine has an observed mask (missing cells); masked data runs NCEM through nemgpu_run, "
+              "nemgpu_iterate, the logged runs and the single steps only");
+    return NEMGPU_E_ARG;
+}
+int masked_algo_check(const nemgpu_engine* e)
+{
+    if (!e->has_obs || e->ncem()) return NEMGPU_OK;
+    set_error("missing cells: only algo = ncem runs on an engine with an observed mask (the fuzzy M-step has no masked form)");
+    return NEMGPU_E_ARG;
+}
+
 int do_density(nemgpu_engine* e)
 {
-    launch_density(finish_args(e, 0, nullptr), density_io(e), e->stream);
+    if (e->has_obs) launch_density_masked(finish_args(e, 0, nullptr), density_io(e), e->xw, e->ow, e->stream);
+    else launch_density(finish_args(e, 0, nullptr), density_io(e), e->stream);
     HIPCHK(hipGetLastError());
     e->flags_clean = true;
     e->density_fresh = true;
@@ -1095,6 +1121,18 @@ int do_labels_post(nemgpu_engine* e, int newbuf, int oldbuf, const CtrlArgs* ctr
 // EstimPara (nem_mod.c:415-469) on the current partition; leaves FLAG_EMPTYK in the iteration flags.
 int do_mstep(nemgpu_engine* e, const CtrlArgs* prev_ctrl = nullptr)
 {
+    if (e->has_obs) {
+        // masked counts, the update with NbObs_KD = observed counts, then the tables of the new parameters (k_finish mode 0)
+        { const int r = masked_algo_check(e); if (r) return r; }
+        if (!e->masks_valid) { int r = do_labels_post(e, e->cur, -1); if (r) return r; }
+        launch_mstep_counts_masked(CountsMaskedArgs{e->k, e->d, e->nw64, e->xt, e->ot, e->mask, e->stats, e->obs_stats}, e->stream);
+        launch_finish_masked(FinishMaskedArgs{e->k, e->d, e->n_true, e->cfg.disper, e->cfg.propor, e->stats, e->obs_stats, e->prop,
+                                              e->center, e->disp, e->nbobs_k, e->iner, e->nbobs_kd, e->iter_flags()}, e->stream);
+        finish_launch(e, finish_args(e, 0, nullptr));
+        e->stats_last = e->stats;
+        HIPCHK(hipGetLastError());
+        return NEMGPU_OK;
+    }
     if (e->ncem()) {
         if (!e->masks_valid) { int r = do_labels_post(e, e->cur, -1); if (r) return r; }
         launch_mstep_counts(counts_args(e, e->stats, prev_ctrl), e->stream);
@@ -1127,6 +1165,7 @@ int init_partition(nemgpu_engine* e)
 {
     int r;
     if (!e->have_matrix || !e->have_params) { set_error("matrix and parameters must be set first"); return NEMGPU_E_FUNCARG; }
+    if ((r = masked_algo_check(e))) return r;
     if ((r = flush_reset(e))) return r;
     if ((r = ensure_state_buffers(e))) return r;
     if ((r = do_tables(e))) return r;
@@ -1926,6 +1965,51 @@ int iterate_pipelined(nemgpu_engine* e, int n_iters, bool with_init)
 
 int criteria(nemgpu_engine* e, float crit6[6], int buf);
 
+// An engine with an observed mask (missing cells): NemAlgo's loop body (nem_alg.c:1789-1840) one launch group at a time,
+// from the steps init_partition uses -- M-step, tables, density, sweep, bookkeeping -- with do_mstep and do_density on the
+// masked kernels.  No graph, no pipelining: the host reads the iteration's flags (empty class, "a label moved") once per
+// iteration, besides the sweep's own round trip.
+int iterate_stepwise(nemgpu_engine* e, int n_iters, bool with_init)
+{
+    int r;
+    if ((r = masked_algo_check(e))) return r;
+    if (with_init) {
+        const int draws = e->draws;                                // (the caller's: one srandom per nem() call)
+        if ((r = reset_state(e))) return r;
+        e->draws = draws;
+        if ((r = init_partition(e))) return r;
+    } else if ((r = flush_reset(e))) return r;
+    for (int it = 0; it < n_iters && !e->converged && e->status == NEMGPU_OK; it++) {
+        if (!e->cfg.param_fix) { if ((r = do_mstep(e))) return r; }
+        if ((r = do_tables(e))) return r;
+        e->iters++;
+        if (!e->cfg.param_fix) {
+            if ((r = read_iter_flags(e))) return r;
+            const int ek = e->h_iter()[FLAG_EMPTYK];
+            if (ek != 0) {                                         // nem_alg.c:1831-1838: the E-step does not run
+                e->status = NEMGPU_W_EMPTYCLASS; e->emptyk = ek;
+                break;
+            }
+        }
+        if ((r = do_density(e))) return r;
+        const int oldbuf = e->cur, newbuf = (e->cur + 1) % 3;
+        if ((r = do_sweep(e, e->cfg.beta, nullptr))) return r;
+        if ((r = do_labels_post(e, newbuf, oldbuf))) return r;     // (FLAG_MOVED was cleared by the density launch)
+        if ((r = read_iter_flags(e))) return r;
+        e->cur = newbuf;
+        if (e->cfg.cvtest == NEMGPU_CV_CLAS) {                     // HasConverged, nem_alg.c:2075-2089
+            const int moved = e->h_iter()[FLAG_MOVED];
+            e->converged = moved ? (1.0f < e->cfg.cvthres) : (0.0f < e->cfg.cvthres);
+        }
+    }
+    return NEMGPU_OK;
+}
+// one or more iterations, no criterion test: pipelined, or step by step for an engine with an observed mask
+int iterate_plain(nemgpu_engine* e, int n_iters, bool with_init)
+{
+    return e->has_obs ? iterate_stepwise(e, n_iters, with_init) : iterate_pipelined(e, n_iters, with_init);
+}
+
 // CVTEST_CRIT (HasConverged, nem_alg.c:2090-2105): iterate until the chosen criterion (M, DEFAULT_CRIT nem_typ.h:80)
 // moves by less than the threshold, relatively.  The criterion is an i-ordered float sum over all families that the
 // loop does not otherwise need, so this test runs one iteration per host round trip: iteration, criteria, decision.
@@ -1935,7 +2019,7 @@ int iterate_crit(nemgpu_engine* e, int n_iters, bool with_init)
 {
     int r;
     if (with_init) {
-        if ((r = iterate_pipelined(e, 0, true))) return r;
+        if ((r = iterate_plain(e, 0, true))) return r;
         e->crit_ref = 0.0f;
         if (e->cfg.cvtest == NEMGPU_CV_CRIT_LOGGED) {
             float c6[6];
@@ -1945,7 +2029,7 @@ int iterate_crit(nemgpu_engine* e, int n_iters, bool with_init)
     }
     for (int it = 0; it < n_iters && !e->converged && e->status == NEMGPU_OK; it++) {
         const float oldcrit = e->crit_ref;
-        if ((r = iterate_pipelined(e, 1, false))) return r;
+        if ((r = iterate_plain(e, 1, false))) return r;
         if (e->status != NEMGPU_OK) break;
         float c6[6];
         if ((r = criteria(e, c6, -1))) return r;
@@ -1963,7 +2047,7 @@ bool crit_test(const nemgpu_engine* e) { return e->cfg.cvtest == NEMGPU_CV_CRIT 
 
 int iterate(nemgpu_engine* e, int n_iters, bool with_init = false)
 {
-    return crit_test(e) ? iterate_crit(e, n_iters, with_init) : iterate_pipelined(e, n_iters, with_init);
+    return crit_test(e) ? iterate_crit(e, n_iters, with_init) : iterate_plain(e, n_iters, with_init);
 }
 
 // ============================================================================================
@@ -2993,6 +3077,48 @@ int nemgpu_set_matrix_bits(nemgpu_engine* e, const uint32_t* xbits_host)
     return upload_bits(e, nullptr);
 }
 
+int nemgpu_set_observed_bits(nemgpu_engine* e, const uint32_t* obits_host)
+{
+    if (!e) return NEMGPU_E_FUNCARG;
+    HIPCHK(hipSetDevice(e->device));
+    if (e->parent != nullptr || !(e->lo == 0 && e->hi == e->n_total)) {
+        set_error("nemgpu_set_observed_bits: a whole single-GPU engine only (no shard, no lock-step twin)");
+        return NEMGPU_E_ARG;
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    // the freshness flags are the unmasked kernels' or the masked ones': either way what they left is void now
+    e->density_fresh = false; e->tables_fresh = false;
+    if (obits_host == nullptr) { e->has_obs = false; return NEMGPU_OK; }
+    const size_t words = (size_t)e->n * e->wf;
+    if (!e->ow) {
+        alloc_for(e);
+        int r = NEMGPU_OK;
+        auto A = [&](int rr) { if (r == NEMGPU_OK) r = rr; };
+        A(dev_alloc(&e->obs_stage, words));
+        A(dev_alloc(&e->ow, (size_t)e->W * e->npad));
+        A(dev_alloc(&e->ows, (size_t)((e->W + 3) / 4) * 4 * e->npad));
+        A(dev_alloc(&e->ot, (size_t)e->d * e->nw64));
+        A(dev_alloc(&e->obs_stats, (size_t)e->k * e->d));
+        A(dev_alloc(&e->nbobs_kd, (size_t)e->k * e->d));
+        if (r) { e->obs_stage = e->ow = e->ows = nullptr; e->ot = nullptr; e->obs_stats = nullptr; e->nbobs_kd = nullptr; return r; }
+    }
+    // bits above organism d-1 are not cells: cleared in the library's copy, as the matrix's padding bits are
+    std::vector<uint32_t> bits(obits_host, obits_host + words);
+    if (e->d & 31) {
+        const uint32_t keep = (1u << (e->d & 31)) - 1u;
+        for (size_t i = 0; i < (size_t)e->n; i++) bits[i * e->wf + (e->wf - 1)] &= keep;
+    }
+    HIPCHK(copy_sync(e, e->obs_stage, bits.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    // the matrix's layout kernels on the mask (the copy in E1's lane order, ows, is made with it and not read)
+    LayoutArgs la = layout_args(e, e->obs_stage);
+    la.xw = e->ow; la.xws = e->ows; la.xt = e->ot;
+    launch_layout(la, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->has_obs = true;
+    return NEMGPU_OK;
+}
+
 // engines packing a byte matrix right now, in all threads of the process: a lone caller takes helper threads, callers
 // that already run side by side (pangenomenem_amd.batch) pack their own rows
 static std::atomic<int> g_packers{0};
@@ -3185,7 +3311,7 @@ static int iterate_logged_impl(nemgpu_engine* e, int with_init, bool keep_draws,
     int r;
     bool speculated = false;
     LogSlot slot{e};                                               // (the pinned side alone: the line comes by copy commands)
-    if (with_init && (crit_test(e) || e->libc() || !(e->lo == 0 && e->hi == e->n_total))) {
+    if (with_init && (crit_test(e) || e->libc() || e->has_obs || !(e->lo == 0 && e->hi == e->n_total))) {
         // (the start whose two sweeps the host completes one after the other: the plain sequence of calls)
         const int draws = e->draws;
         if ((r = reset_state(e))) return r;
@@ -3197,7 +3323,7 @@ static int iterate_logged_impl(nemgpu_engine* e, int with_init, bool keep_draws,
             if ((r = criteria(e, c6))) return r;
             e->crit_ref = c6[3];
         }
-    } else if (!crit_test(e) && e->lo == 0 && e->hi == e->n_total) {
+    } else if (!crit_test(e) && !e->has_obs && e->lo == 0 && e->hi == e->n_total) {
         LoopCursor lc;
         if (with_init && !keep_draws) e->draws = 0;
         if ((r = loop_begin(e, lc, with_init ? 0 : 1, with_init != 0))) return r;
@@ -3276,7 +3402,9 @@ int nemgpu_run_logged(nemgpu_engine* e, nemgpu_result* res, nemgpu_log_fn fn, vo
     emit_own(0, nullptr);                                          // (no EstimPara yet: no sizes, as the header says)
     lap("line 0 (start, two criteria)");
     static const bool batched_on = !(getenv("NEM_MI355X_LOG_BATCHED") && getenv("NEM_MI355X_LOG_BATCHED")[0] == '0');
-    const bool batched = batched_on && e->ncem() && !crit_test(e) && e->lo == 0 && e->hi == e->n_total && e->parent == nullptr;
+    // (a masked engine: one logged iteration per call, each line emitted behind its iteration -- the drop-in's log callback
+    //  reads that iteration's observed counts from the engine, nemgpu_get_observed_counts)
+    const bool batched = batched_on && e->ncem() && !crit_test(e) && !e->has_obs && e->lo == 0 && e->hi == e->n_total && e->parent == nullptr;
     bool last_logged = false;
     if (!batched) {
         // (the fuzzy algorithm, the `crit` test, a sharded engine: one logged iteration per call, as nemgpu_iterate_logged)
@@ -3387,6 +3515,7 @@ int nemgpu_restart_iterate(nemgpu_engine* e, int n_iters, nemgpu_result* res)
 {
     // reset + ComputePartitionFromPara(Needinit=1) + up to n_iters EM iterations as ONE pipelined batch sequence
     if (!e) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_restart_iterate"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     e->draws = 0;
     int r = iterate(e, n_iters, true);
@@ -3430,6 +3559,7 @@ int nemgpu_run_many(nemgpu_engine** engines, int count, nemgpu_result* results)
         for (int j = 0; j < i; j++) if (engines[j] == engines[i]) { set_error("nemgpu_run_many: the same engine twice"); return NEMGPU_E_ARG; }
         E[i] = engines[i];
     }
+    for (int i = 0; i < count; i++) { const int mr = masked_refuse(E[i], "nemgpu_run_many"); if (mr) return mr; }
     HIPCHK(hipSetDevice(E[0]->device));
     return run_many(E, results);
 }
@@ -4715,6 +4845,8 @@ static int run_random_impl(nemgpu_engine* e, int n_starts, uint32_t seed, nemgpu
                            nemgpu_log_fn fn, void* user)
 {
     if (!e || n_starts <= 0) return NEMGPU_E_FUNCARG;
+    // (MakeRandomPara has a missing-data rule of its own, nem_alg.c:1436-1458, that this engine does not state)
+    { const int mr = masked_refuse(e, "nemgpu_run_random"); if (mr) return mr; }
     if (e->lo != 0 || e->hi != e->n_total) { set_error("random starts need the whole problem on one engine"); return NEMGPU_E_FUNCARG; }
     if (!e->have_matrix || e->host_bits_words == 0) { set_error("the matrix must be set first"); return NEMGPU_E_FUNCARG; }
     HIPCHK(hipSetDevice(e->device));
@@ -4862,6 +4994,7 @@ int nemgpu_stats_words(const nemgpu_engine* e) { return e ? e->k + e->k * e->d :
 int nemgpu_shard_layout(nemgpu_engine* e, int world, int rank, int blk, int stride, int n_true)
 {
     if (!e || world <= 0 || rank < 0 || rank >= world || blk <= 0 || stride < blk + 1 || n_true <= 0) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_layout"); if (mr) return mr; }
     if (e->lo != rank * stride || e->n > blk || e->n_total != world * stride) {
         set_error("shard layout does not match the engine's slot range");
         return NEMGPU_E_ARG;
@@ -4931,6 +5064,7 @@ static int shard_check(nemgpu_engine* e)
 int nemgpu_shard_begin(nemgpu_engine* e)
 {
     { const int cr = shard_check(e); if (cr) return cr; }
+    { const int mr = masked_refuse(e, "nemgpu_shard_begin"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     { const int fr = flush_reset(e); if (fr) return fr; }
     HIPCHK(hipMemsetAsync(e->ctrl(), 0, C_WORDS * sizeof(int), e->stream));
@@ -4949,6 +5083,7 @@ int nemgpu_shard_begin(nemgpu_engine* e)
 int nemgpu_shard_begin_restart(nemgpu_engine* e)
 {
     { const int cr = shard_check(e); if (cr) return cr; }
+    { const int mr = masked_refuse(e, "nemgpu_shard_begin_restart"); if (mr) return mr; }
     if (!e->have_matrix || !e->have_params) { set_error("matrix and parameters must be set first"); return NEMGPU_E_FUNCARG; }
     HIPCHK(hipSetDevice(e->device));
     int r;
@@ -4972,6 +5107,7 @@ int nemgpu_shard_begin_restart(nemgpu_engine* e)
 int nemgpu_shard_counts(nemgpu_engine* e, int32_t* stats_dev)
 {
     if (!e || !stats_dev) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_counts"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     { const int fr = flush_reset(e); if (fr) return fr; }
     launch_mstep_counts(counts_args(e, stats_dev, nullptr), e->stream);
@@ -4983,6 +5119,7 @@ int nemgpu_shard_counts(nemgpu_engine* e, int32_t* stats_dev)
 int nemgpu_shard_mstep_partial(nemgpu_engine* e, const uint8_t* labels_cur_dev, int32_t* stats_dev)
 {
     if (!e || !labels_cur_dev || !stats_dev) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_mstep_partial"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     { const int fr = flush_reset(e); if (fr) return fr; }
     launch_labels_post(labels_post_args(e, labels_cur_dev, nullptr, nullptr), e->stream);
@@ -4998,6 +5135,7 @@ int nemgpu_shard_estep_round0(nemgpu_engine* e, const int32_t* stats_dev, float 
                               const uint8_t* labels_old_dev, uint8_t* labels_out_dev)
 {
     if (!e || !labels_old_dev || !labels_out_dev) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_estep_round0"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     { const int fr = flush_reset(e); if (fr) return fr; }
     int r;
@@ -5042,6 +5180,7 @@ int nemgpu_shard_estep_round1(nemgpu_engine* e, float beta, int sweep_id, const 
                               const uint8_t* labels_guess_dev, uint8_t* labels_out_dev)
 {
     if (!e || !labels_old_dev || !labels_guess_dev || !labels_out_dev) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_estep_round1"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     SweepArgs a;
     shard_round1_args(e, a, beta, sweep_id, labels_old_dev, labels_guess_dev, labels_out_dev);
@@ -5057,6 +5196,7 @@ int nemgpu_shard_estep_round1_counts(nemgpu_engine* e, float beta, int sweep_id,
                                      const uint8_t* labels_guess_dev, uint8_t* labels_out_dev, int32_t* stats_dev)
 {
     if (!e || !labels_old_dev || !labels_guess_dev || !labels_out_dev || !stats_dev) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_estep_round1_counts"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     SweepArgs a;
     shard_round1_args(e, a, beta, sweep_id, labels_old_dev, labels_guess_dev, labels_out_dev);
@@ -5083,6 +5223,7 @@ int nemgpu_shard_estep_round1_counts(nemgpu_engine* e, float beta, int sweep_id,
 int nemgpu_shard_fuzzy_layout(nemgpu_engine* e, int n_true)
 {
     if (!e || n_true <= 0 || n_true > e->n_total) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_fuzzy_layout"); if (mr) return mr; }
     if (e->ncem()) { set_error("nemgpu_shard_fuzzy_*: the engine must be configured with algo = nem"); return NEMGPU_E_ARG; }
     e->n_true = n_true;
     return NEMGPU_OK;
@@ -5096,6 +5237,7 @@ int nemgpu_shard_fuzzy_round(nemgpu_engine* e, float beta, int sweep_id, int rou
                              float* c_out_dev, int* changed, int* nzero, int* firstzero)
 {
     if (!e || !c_old_dev || !c_guess_dev || !c_out_dev || round < 0) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_fuzzy_round"); if (mr) return mr; }
     if (e->ncem()) { set_error("nemgpu_shard_fuzzy_round: the engine must be configured with algo = nem"); return NEMGPU_E_ARG; }
     HIPCHK(hipSetDevice(e->device));
     { const int fr = flush_reset(e); if (fr) return fr; }
@@ -5128,6 +5270,7 @@ int nemgpu_shard_fuzzy_round(nemgpu_engine* e, float beta, int sweep_id, int rou
 int nemgpu_shard_fuzzy_mstep_cols(nemgpu_engine* e, const float* c_dev, float* nbobs_out_dev, float* center_out_dev, float* iner_out_dev)
 {
     if (!e || !c_dev || !nbobs_out_dev || !center_out_dev || !iner_out_dev) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_fuzzy_mstep_cols"); if (mr) return mr; }
     if (e->ncem()) { set_error("nemgpu_shard_fuzzy_mstep_cols: the engine must be configured with algo = nem"); return NEMGPU_E_ARG; }
     HIPCHK(hipSetDevice(e->device));
     { const int fr = flush_reset(e); if (fr) return fr; }
@@ -5149,6 +5292,7 @@ int nemgpu_shard_fuzzy_mstep_cols(nemgpu_engine* e, const float* c_dev, float* n
 int nemgpu_shard_fuzzy_finish(nemgpu_engine* e, const float* nbobs_dev, const float* center_dev, const float* iner_dev, int* emptyk)
 {
     if (!e || !nbobs_dev || !center_dev || !iner_dev) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_fuzzy_finish"); if (mr) return mr; }
     if (e->ncem()) { set_error("nemgpu_shard_fuzzy_finish: the engine must be configured with algo = nem"); return NEMGPU_E_ARG; }
     HIPCHK(hipSetDevice(e->device));
     { const int fr = flush_reset(e); if (fr) return fr; }
@@ -5172,6 +5316,7 @@ int nemgpu_shard_fuzzy_finish(nemgpu_engine* e, const float* nbobs_dev, const fl
 int nemgpu_shard_fuzzy_moved(nemgpu_engine* e, const float* c_new_dev, const float* c_old_dev, int* moved)
 {
     if (!e || !c_new_dev || !c_old_dev || !moved) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_fuzzy_moved"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemsetAsync(e->iter_flags() + FLAG_MOVED, 0, sizeof(int), e->stream));
     launch_conv_fuzzy(conv_fuzzy_args(e, c_new_dev, c_old_dev, nullptr, nullptr), e->stream);
@@ -5187,6 +5332,7 @@ int nemgpu_shard_finish_iteration(nemgpu_engine* e, float beta, int is_init, con
                                   const uint8_t* labels_q_dev, const uint8_t* labels_r_dev)
 {
     if (!e || !labels_old_dev || !labels_q_dev || !labels_r_dev) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_finish_iteration"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     CtrlArgs ca = ctrl_args(e, 2, beta);                           // (the path is NCEM-only, shard_check)
     ca.q_flags = labels_q_dev + e->sh_blk; ca.r_flags = labels_r_dev + e->sh_blk;
@@ -5210,6 +5356,7 @@ int nemgpu_shard_round_sync(nemgpu_engine* e, float beta, int sweep_id, const ui
                             const uint8_t* labels_guess_dev, uint8_t* labels_out_dev, int* changed)
 {
     if (!e || !labels_old_dev || !labels_guess_dev || !labels_out_dev || !changed) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_round_sync"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     const int* saved = e->stop_ptr;
     e->stop_ptr = nullptr;
@@ -5244,6 +5391,7 @@ int nemgpu_shard_round_sync(nemgpu_engine* e, float beta, int sweep_id, const ui
 int nemgpu_shard_set_labels(nemgpu_engine* e, const uint8_t* lab0, const uint8_t* lab1, const uint8_t* lab2)
 {
     if (!e || !lab0 || !lab1 || !lab2) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_set_labels"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     e->shard_lab[0] = lab0; e->shard_lab[1] = lab1; e->shard_lab[2] = lab2;
     alloc_for(e);
@@ -5255,6 +5403,7 @@ int nemgpu_shard_set_labels(nemgpu_engine* e, const uint8_t* lab0, const uint8_t
 int nemgpu_shard_round_draws(nemgpu_engine* e, int* draws, int* table_short)
 {
     if (!e) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_round_draws"); if (mr) return mr; }
     const int v = e->h_round(2)[FLAG_NTIES];
     if (draws) *draws = v & ((1 << 30) - 1);
     if (table_short) *table_short = (v >> 30) & 1;
@@ -5268,6 +5417,7 @@ int nemgpu_shard_end_enqueue(nemgpu_engine* e)
 {
     // last call of a batch's enqueue phase (may be inside a graph capture): copy the control block to the host
     if (!e) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_end_enqueue"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     e->stop_ptr = nullptr;
     HIPCHK(hipMemcpyAsync(e->flags_host, e->flags_dev, e->flag_words() * sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -5278,6 +5428,7 @@ int nemgpu_shard_end(nemgpu_engine* e, nemgpu_result* res, int* commits, int* ne
 {
     // wait for the batch and report; call after nemgpu_shard_end_enqueue (or after replaying a captured batch)
     if (!e) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_end"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     e->stop_ptr = nullptr;
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -5470,6 +5621,7 @@ int nemgpu_shard_enqueue_batch(nemgpu_engine* e, int with_init, int n_iters, int
                                uint8_t* lab0, uint8_t* lab1, uint8_t* lab2, int stats_off)
 {
     if (!e || !lab0 || !lab1 || !lab2 || n_iters < 0 || base < 0 || base > 2) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_enqueue_batch"); if (mr) return mr; }
     if (!e->rccl_comm) { set_error("nemgpu_rccl_attach first"); return NEMGPU_E_FUNCARG; }
     // A rank alone has no collective inside its batches: they go out as hipGraphs of the library's own, captured the
     // second time a shape is enqueued (as the single engine's batches are).  With more ranks the batch holds RCCL
@@ -5514,6 +5666,7 @@ int nemgpu_shard_enqueue_batch(nemgpu_engine* e, int with_init, int n_iters, int
 int nemgpu_shard_set_sweep_number(nemgpu_engine* e, int next_sweep)
 {
     if (!e) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_shard_set_sweep_number"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)e->sweep_next, next_sweep, 1, e->stream));
     return NEMGPU_OK;
@@ -5611,6 +5764,15 @@ int nemgpu_get_params(nemgpu_engine* e, float* prop, float* center, float* disp,
     return nemgpu_get_results(e, prop, center, disp, nbobs_k, nullptr);
 }
 
+int nemgpu_get_observed_counts(nemgpu_engine* e, float* nbobs_kd)
+{
+    if (!e || !nbobs_kd) return NEMGPU_E_FUNCARG;
+    if (!e->has_obs) { set_error("nemgpu_get_observed_counts: the engine has no observed mask"); return NEMGPU_E_ARG; }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(copy_sync(e, nbobs_kd, e->nbobs_kd, sizeof(float) * e->k * e->d, hipMemcpyDeviceToHost));
+    return NEMGPU_OK;
+}
+
 int nemgpu_get_density(nemgpu_engine* e, double* pkfki_nk, float* logpkfki_nk)
 {
     // device layout is class-major [k][npad]; hand back the reference's row-major [n][k]
@@ -5639,6 +5801,7 @@ int nemgpu_profile_density(nemgpu_engine* e, int reps, double* avg_ms, double* a
                            int* used_fused_kernel)
 {
     if (!e || reps <= 0) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_profile_density"); if (mr) return mr; }
     HIPCHK(hipSetDevice(e->device));
     { const int fr = flush_reset(e); if (fr) return fr; }
     int r;
@@ -5679,6 +5842,7 @@ int nemgpu_profile_density_many(nemgpu_engine** engines, int count, int reps, do
     nemgpu_engine* lead = engines[0];
     HIPCHK(hipSetDevice(lead->device));
     int r;
+    for (int m = 0; m < count; m++) if (engines[m] && (r = masked_refuse(engines[m], "nemgpu_profile_density_many"))) return r;
     std::vector<Recorder> recs((size_t)count);
     double bytes = 0.0;
     for (int m = 0; m < count; m++) {
@@ -5726,6 +5890,7 @@ int nemgpu_profile_density_many(nemgpu_engine** engines, int count, int reps, do
 int nemgpu_profile_kernels(nemgpu_engine* e, int reps, double avg_ms[3], double bytes[3], int which[1])
 {
     if (!e || reps <= 0 || !avg_ms || !bytes) return NEMGPU_E_FUNCARG;
+    { const int mr = masked_refuse(e, "nemgpu_profile_kernels"); if (mr) return mr; }
     if (!e->ncem() || e->lo != 0 || e->hi != e->n_total) { set_error("the kernel probe times a whole NCEM problem on one engine"); return NEMGPU_E_FUNCARG; }
     HIPCHK(hipSetDevice(e->device));
     { const int fr = flush_reset(e); if (fr) return fr; }

@@ -42,6 +42,8 @@ struct NemInputs {
     std::string str_comment;               // opening '#' comment of .str (echoed in .stderr)
     std::string nei_comment;
     std::vector<uint32_t> xbits;           // family-major bit rows, ceil(d/32) words per family
+    std::vector<uint32_t> obits;           // same layout: 1 = observed; EMPTY when the .dat holds no nan token
+    long n_missing = 0;                    // nan cells of the .dat (nem_exe.c:477-490)
     std::vector<int32_t> nei_ptr, nei_idx; // CSR, 0-based, .nei order after ReadPtsNeighs filtering
     std::vector<float> nei_w;
     int max_neighs = 0;

@@ -242,6 +242,7 @@ int read_dat_file(const std::string& base, NemInputs& in, std::string& err)
 {
     std::vector<char> buf;
     const std::string path = base + ".dat";
+    in.obits.clear(); in.n_missing = 0;                  // (a regular file holds 0 / 1 only: nothing is missing)
     {
         const int wf0 = (in.d + 31) / 32;
         in.xbits.assign((size_t)in.n * wf0, 0u);
@@ -250,6 +251,17 @@ int read_dat_file(const std::string& base, NemInputs& in, std::string& err)
     if (!slurp(path, buf)) { err = "File matrix " + path + " does not exist"; return NEMGPU_E_FILEIN; }
     const int n = in.n, d = in.d, wf = (d + 31) / 32;
     in.xbits.assign((size_t)n * wf, 0u);
+    // A token strtof reads as NaN (nan, NaN, NAN, nan(...)) is a cell that was not observed (nem_exe.c:477-490 counts
+    // them, nem_mod.c treats them as missing).  The mask is made when the first one is met: all ones for the cells
+    // before it, then a cleared bit per nan.
+    auto mark_missing = [&](int i, int j) {
+        if (in.obits.empty()) {
+            in.obits.assign((size_t)n * wf, 0xFFFFFFFFu);
+            if (d & 31) for (int r = 0; r < n; r++) in.obits[(size_t)r * wf + (wf - 1)] = (1u << (d & 31)) - 1u;
+        }
+        in.obits[(size_t)i * wf + (j >> 5)] &= ~(1u << (j & 31));
+        in.n_missing++;
+    };
     const char* p = buf.data();
     const char* const bend = buf.data() + buf.size() - 1;        // the terminating NUL slurp() appended
     for (int i = 0; i < n; i++) {
@@ -282,6 +294,7 @@ int read_dat_file(const std::string& base, NemInputs& in, std::string& err)
             if (end == p) { err = path + " : unreadable value"; return NEMGPU_E_FILE; }
             p = end;
             if (v == 1.0f) row[j >> 5] |= 1u << (j & 31);
+            else if (std::isnan(v)) mark_missing(i, j);
             else if (v != 0.0f) {
                 err = path + " : only 0/1 presence/absence values are supported by this engine";
                 return NEMGPU_E_FILE;

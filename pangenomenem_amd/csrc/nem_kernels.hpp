@@ -228,6 +228,19 @@ void launch_calib_read(const uint32_t* buf, size_t words, uint32_t* sink, hipStr
 void launch_onehot(const OnehotArgs& a, hipStream_t s);
 void launch_criteria(const CritArgs& a, hipStream_t s);   // a.hard: one-hot rows (NCEM)
 
+// ---- matrices with missing cells (nem_missing.hip): the three kernels of a masked NCEM iteration --------------------
+// ow / ot: the observed mask in xw's and xt's layouts (launch_layout made them), read word for word beside the matrix.
+// E1, the general chain of k_density with the step taken only where the cell was observed (DensBernoulli,
+// nem_mod.c:654); t: k_finish's pk / logpk / nz0 / nz1 and the parameters; io.xw is not read (xw: the unsorted copy)
+void launch_density_masked(const FinishArgs& t, const DensityIO& io, const uint32_t* xw, const uint32_t* ow, hipStream_t s);
+// per (class, organism): stats[K + k*D + d] = observed ones, obs[k*D + d] = observed cells; stats[k] = class size
+struct CountsMaskedArgs { int K, D, nw64; const uint64_t* xt; const uint64_t* ot; const uint64_t* mask; int* stats; int* obs; };
+void launch_mstep_counts_masked(const CountsMaskedArgs& a, hipStream_t s);
+// EstimLaplaceCenters + EstimLaplaceIner + InerToDisp* (MISSING_IGNORE) + proportions with NbObs_KD = obs; one block
+struct FinishMaskedArgs { int K, D, n_total, disper, propor; const int* stats; const int* obs;
+                          float* prop; float* center; float* disp; float* nbobs_k; float* iner; float* nbobs_kd; int* flags; };
+void launch_finish_masked(const FinishMaskedArgs& a, hipStream_t s);
+
 // the head of every batched kernel twin: problem = blockIdx.z, its own grid width, its argument block
 #define NEM_B_HEAD(Args)                                                   \
     const int p__ = blockIdx.z;                                            \

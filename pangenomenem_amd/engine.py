@@ -80,6 +80,8 @@ def load_library():
     lib.nemgpu_destroy.restype = None
     lib.nemgpu_set_matrix_bytes.argtypes = [vp, vp]
     lib.nemgpu_set_matrix_bits.argtypes = [vp, vp]
+    lib.nemgpu_set_observed_bits.argtypes = [vp, vp]
+    lib.nemgpu_get_observed_counts.argtypes = [vp, vp]
     lib.nemgpu_set_graph.argtypes = [vp, vp, vp, vp]
     lib.nemgpu_set_params.argtypes = [vp, vp, vp, vp]
     lib.nemgpu_configure.argtypes = [vp, C.POINTER(Config)]
@@ -154,6 +156,7 @@ def load_library():
     lib.nemio_free.restype = None
     lib.nemio_sizes.argtypes = [vp, ip, ip, ip, ip, ip, ip]
     lib.nemio_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.nemio_observed.argtypes = [vp, vp, ip]
     lib.nemio_write_uf.argtypes = [C.c_char_p, vp, C.c_int, C.c_int]
     lib.nemio_write_cf.argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_int, C.c_uint32]
     lib.nemio_write_mf.argtypes = [C.c_char_p, fp, C.c_float, C.c_int, C.c_int, vp, vp, vp]
@@ -215,9 +218,41 @@ class NemEngine:
 
     # ---- inputs
     def set_matrix(self, x):
+        """0/1 presence/absence rows.  A float array may hold NaN for cells that were not observed (the reference's
+        missing data): its 0/1 part is uploaded and the NaN cells become the engine's observed mask (set_observed).
+        A matrix without NaN removes a mask that an earlier set_matrix made from NaN cells; a mask given through
+        set_observed stays until set_observed(None)."""
+        x = np.asarray(x)
+        miss = np.isnan(x) if x.dtype.kind == "f" else None
+        if miss is not None and miss.any():
+            x = np.where(miss, 0, x)
+        else:
+            miss = None
         x = np.ascontiguousarray(x, np.uint8)
         assert x.shape == (self.n, self.d)
         self._chk(self.lib.nemgpu_set_matrix_bytes(self._h, _vp(x)))
+        if miss is not None:
+            self.set_observed(~miss)
+            self._mask_from_matrix = True
+        elif getattr(self, "_mask_from_matrix", False):
+            self.set_observed(None)
+
+    def set_observed(self, obs):
+        """Which cells of the matrix were observed: a bool (n, d) array, or None for a complete matrix.  An engine
+        with a mask -- even one that is all True -- runs NCEM on the masked kernels, one host round trip per
+        iteration; run_many, run_random, restart_iterate, the sharded and the profiling calls refuse it."""
+        self._mask_from_matrix = False
+        if obs is None:
+            self._chk(self.lib.nemgpu_set_observed_bits(self._h, None))
+            return
+        obs = np.asarray(obs, bool)
+        assert obs.shape == (self.n, self.d)
+        wf = (self.d + 31) // 32
+        by = np.zeros((self.n, wf * 4), np.uint8)
+        pk = np.packbits(obs, axis=1, bitorder="little")
+        by[:, :pk.shape[1]] = pk
+        bits = np.ascontiguousarray(by).view("<u4")
+        self._chk(self.lib.nemgpu_set_observed_bits(self._h, _vp(bits)))
 
     def set_matrix_bits(self, bits):
         bits = np.ascontiguousarray(bits, np.uint32)
@@ -577,14 +612,17 @@ def profile_density_many(engines, reps=30):
     return ms.value, by.value
 
 
-def solve(x, nei, k, prop, center, disp, device=0, fast_forward=None, **cfg):
-    """Convenience: build an engine, run the whole EM, return full-precision results."""
+def solve(x, nei, k, prop, center, disp, device=0, fast_forward=None, observed=None, **cfg):
+    """Convenience: build an engine, run the whole EM, return full-precision results.  Missing cells: NaN in a float
+    x, or observed = a bool (n, d) array (NemEngine.set_observed)."""
     n, d = x.shape
     eng = NemEngine(n, d, k, device=device)
     try:
         if fast_forward is not None:
             eng.set_fast_forward(fast_forward)
         eng.set_matrix(x)
+        if observed is not None:
+            eng.set_observed(observed)
         eng.set_graph(nei)
         eng.set_params(prop, center, disp)
         eng.configure(**cfg)
@@ -615,8 +653,17 @@ def read_inputs(fname, nk):
         disp = np.zeros((nk, d), np.float32)
         lib.nemio_copy(h, _vp(xbits), _vp(ptr), _vp(idx), _vp(w), _vp(prop), _vp(center), _vp(disp))
         x = ((xbits[:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]) & 1).reshape(n, wf * 32)[:, :d]
+        # nan tokens of the .dat: observed = bool (n, d), or None when every cell held a number
+        obits = np.zeros((n, wf), np.uint32)
+        nmiss = C.c_int(0)
+        lib.nemio_observed(h, _vp(obits), C.byref(nmiss))
+        observed = None
+        if nmiss.value > 0:
+            observed = (((obits[:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]) & 1)
+                        .reshape(n, wf * 32)[:, :d]).astype(bool)
         return dict(n=n, d=d, x=x.astype(np.uint8), xbits=xbits, nei=(ptr, idx[:nnz], w[:nnz]), max_neighs=mx.value,
-                    param_mode=pm.value, type=chr(ty.value), prop=prop, center=center, disp=disp)
+                    param_mode=pm.value, type=chr(ty.value), prop=prop, center=center, disp=disp,
+                    observed=observed, n_missing=nmiss.value)
     finally:
         lib.nemio_free(h)
 

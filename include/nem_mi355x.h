@@ -443,6 +443,48 @@ int nemgpu_edge_table_metavalues_size(nemgpu_edge_table* t, const nemgpu_master*
 int nemgpu_edge_table_metavalues(nemgpu_edge_table* t, const nemgpu_master* m, int row0, int rows, char* text, int64_t capacity, int64_t* needed,
                                  int64_t* edge_end);
 void nemgpu_edge_table_destroy(nemgpu_edge_table* t);
+/* The NODES' <attvalue> lines of the same export, formatted on the device from the master, the flat orders of ALL its
+   organisms and every gene's ID, NAME and PRODUCT given as (offset, length) spans of the load's text (the loader's
+   SPAN_ID, SPAN_NAME, SPAN_PRODUCT; an absent NAME or PRODUCT is an empty span).  gexf.node_text_host (Python) states the
+   bytes.  HOST arrays; m is the table's master in every call, only read; the work runs on m's stream, scratch is
+   allocated for the call and freed.
+   _create: f, genes[g], contig_ptr[c + 1], contig_org[c], repeated[f] or NULL as nemgpu_edge_table_create takes them
+     (g > 0, at most (2^31 - 1) / 3; contig_org non-decreasing).  A gene is kept when its id is not flagged.  The kept
+     genes' (family, organism) cells must be exactly the master's presence bits: if not, NEMGPU_E_ARG and no table.
+     hash_bits (tests): 0, or the bits of the string hash that are kept, so that the probes collide.
+   _text: once per batch of genes gene0 .. gene1 - 1, in order from 0 to g: text[bytes] is the part of the load's text the
+     batch's spans lie in (a run of whole files), span_off[3][gene1 - gene0] offsets into it, span_len[3][gene1 - gene0]
+     (ID, NAME, PRODUCT; a length at most 2^24).  A span past the end of the text is refused before any launch.  The
+     device keeps the spans of the kept genes, escaped as ElementTree escapes an attribute, and not the text.
+   _finish: after the last batch: the distinct names and products of every family (equal bytes), each at its first
+     gene in walk order.
+   _shape, _fetch: n, d, g; nb_genes[n] the families' kept genes, org_first_node[d] the first family, in master order,
+     with a kept gene of the organism (n: none).  Either may be NULL.
+   _ids: numbers the node attributes as networkx does when `tail` titles follow a node's organisms (partition,
+     partition_exact, [the subpartition,] the four length_*): nb_genes 0, node 0's first organism, name, product, node
+     0's other organisms, the tail, then every organism first met at a later node in (node, organism) order; in the
+     light export nb_genes 0, name 1, product 2.  org_id[d] (-1: the organism has no kept gene), name_id[2] (light,
+     full; product's is one more), node_end_full[n], node_end_light[n]: every node's end offset in the text of all
+     nodes.  Any may be NULL.  The text calls format for the last numbering.
+   _lines_size, _lines: the text of nodes row0 .. row0 + rows - 1 into text[capacity] (HOST): per node one slice -- full:
+     the first organism's line, the name line, the product line, the other organisms' lines; light (full = 0): the name
+     and product lines -- each line `          <attvalue for="ID" value="A|B|..." />\n`; node_end[rows]: every node's
+     end offset in the batch; *needed (may be NULL) = the bytes the batch takes; capacity below that: NEMGPU_E_ARG,
+     *needed still set, nothing written. */
+typedef struct nemgpu_node_table nemgpu_node_table;
+int nemgpu_node_table_create(nemgpu_node_table** out, const nemgpu_master* m, int f, const int32_t* genes, int g, const int32_t* contig_ptr,
+                             const int32_t* contig_org, int c, const uint8_t* repeated, int hash_bits);
+int nemgpu_node_table_text(nemgpu_node_table* t, const nemgpu_master* m, const char* text, int64_t bytes, int gene0, int gene1,
+                           const int64_t* span_off, const int32_t* span_len);
+int nemgpu_node_table_finish(nemgpu_node_table* t, const nemgpu_master* m);
+int nemgpu_node_table_shape(const nemgpu_node_table* t, int* n, int* d, int* g);
+int nemgpu_node_table_fetch(const nemgpu_node_table* t, int32_t* nb_genes, int32_t* org_first_node);
+int nemgpu_node_table_ids(nemgpu_node_table* t, const nemgpu_master* m, int tail, int32_t* org_id, int32_t* name_id, int64_t* node_end_full,
+                          int64_t* node_end_light);
+int nemgpu_node_table_lines_size(const nemgpu_node_table* t, int full, int row0, int rows, int64_t* bytes);
+int nemgpu_node_table_lines(nemgpu_node_table* t, const nemgpu_master* m, int full, int row0, int rows, char* text, int64_t capacity,
+                            int64_t* needed, int64_t* node_end);
+void nemgpu_node_table_destroy(nemgpu_node_table* t);
 /* The pangenome graph LAID OUT on the device: PPanGGOLiN.compute_layout (ppanggolin.py:1250-1292), which hands the
    family graph to ForceAtlas2 (Jacomy et al. 2014) and puts the positions on the nodes.  The reference delegates to the
    external package fa2 (Barnes-Hut at theta 1.2); here the repulsion is the EXACT all-pairs sum, n^2 per iteration

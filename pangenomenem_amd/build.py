@@ -13,7 +13,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-UNITS = ("nem_kernels.hip", "nem_missing.hip", "nem_sweep.hip", "nem_chunks.hip", "nem_vote.hip", "nem_resample.hip", "nem_orders.hip", "nem_merge.hip", "nem_project.hip", "nem_matrix.hip", "nem_edges.hip", "nem_edge_meta.hip", "nem_layout.hip", "nem_layout_bh.hip", "nem_orgdist.hip", "nem_gff.hip", "nem_master.hip", "nem_engine.hip", "nem_io.cpp", "nem_capi.cpp")
+UNITS = ("nem_kernels.hip", "nem_missing.hip", "nem_sweep.hip", "nem_chunks.hip", "nem_vote.hip", "nem_resample.hip", "nem_orders.hip", "nem_merge.hip", "nem_project.hip", "nem_matrix.hip", "nem_edges.hip", "nem_edge_meta.hip", "nem_nodes.hip", "nem_layout.hip", "nem_layout_bh.hip", "nem_orgdist.hip", "nem_gff.hip", "nem_master.hip", "nem_engine.hip", "nem_io.cpp", "nem_capi.cpp")
 SRC = [os.path.join(HERE, "csrc", f) for f in UNITS]
 HDR = sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith(".hpp")) + \
       [os.path.join(HERE, "..", "include", "nem_mi355x.h")]

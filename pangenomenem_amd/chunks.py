@@ -821,6 +821,74 @@ class Master:
         o = gexf.gexf_orders(annotations, self.organism_names, self.id_names, by_org, circular_contig_size, family)
         return gexf.EdgeTable(self, o["genes"], o["starts"], o["ends"], o["contig_ptr"], o["contig_org"], o["contig_sizes"], o["repeated"])
 
+    def node_table(self, loaded=None, *, orders=None, text=None, spans=None, batch_bytes=256 << 20, _hash_bits=0):
+        """The nodes' <attvalue> text of the GEXF export, formatted on the device from this master, the flat orders of ALL
+        its organisms and every gene's ID, NAME and PRODUCT as (offset, length) spans of the load's text
+        (nemgpu_node_table_*; gexf.node_text_host states it): write_gexf(node_table=) then needs no annotations.
+        loaded: a loader.Loaded (default: this master's .loaded, what from_files keeps) supplies the orders, the files'
+        text and the spans; the text goes up a second time, in runs of whole files of at most batch_bytes (a file above
+        it alone), and only the escaped spans of the kept genes stay on the device.  Or orders=(genes, contig_ptr,
+        contig_org[, repeated[, f]]) with text= (bytes or uint8) and spans=(span_off int64 [3][G], span_len int32 [3][G]):
+        flat arrays; the text then goes up in runs of genes whose spans lie within batch_bytes.  A master whose repeated
+        families differ between organisms (grown by add_annotations with other sets) is refused with ValueError when the
+        orders come from a Loaded, whose flags are one global set: that case stays on write_gexf's annotations path.
+        Orders whose cells are not this master's presence bits, and a span past the end of the text, raise NemGpuError
+        before any launch.  _hash_bits (tests): keep only that many bits of the string hash.  Returns a gexf.NodeTable
+        (titles(), ids(), lines_size(), lines(), close())."""
+        from . import gexf
+        if orders is not None:
+            if loaded is not None or text is None or spans is None:
+                raise ValueError("node_table: a Loaded, or orders= with text= and spans=")
+            t = gexf.NodeTable(self, orders[0], orders[1], orders[2], orders[3] if len(orders) > 3 else None, orders[4] if len(orders) > 4 else None,
+                               _hash_bits=_hash_bits)
+            try:
+                text = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+                off, length = np.asarray(spans[0], np.int64), np.asarray(spans[1], np.int32)
+                if off.shape != (3, t.g) or length.shape != (3, t.g):
+                    raise ValueError("node_table: spans = (span_off [3][G], span_len [3][G])")
+                lo = np.where(length > 0, off, np.iinfo(np.int64).max).min(axis=0)       # (an empty span lies anywhere)
+                hi = np.where(length > 0, off + length, 0).max(axis=0)
+                gene0 = 0
+                while gene0 < t.g:
+                    a, b, gene1 = int(lo[gene0]), int(hi[gene0]), gene0 + 1
+                    while gene1 < t.g and max(b, int(hi[gene1])) - min(a, int(lo[gene1])) <= batch_bytes:
+                        a, b, gene1 = min(a, int(lo[gene1])), max(b, int(hi[gene1])), gene1 + 1
+                    a = max(min(a, b), 0)                      # (no span with a byte in the run: an empty text)
+                    part = off[:, gene0:gene1] - a             # (a span outside the text stays outside its slice: the library refuses it)
+                    t.add_text(text[a:b], gene0, gene1, np.where(length[:, gene0:gene1] > 0, part, 0), length[:, gene0:gene1])
+                    gene0 = gene1
+                return t.finish()
+            except Exception:
+                t.close()
+                raise
+        ld = getattr(self, "loaded", None) if loaded is None else loaded
+        if ld is None:
+            raise ValueError("node_table: a Loaded (a master made by from_files keeps its own), or orders= with text= and spans=")
+        by_org = getattr(self, "repeated_by_organism", None)
+        if by_org is not None and len(set(by_org.values())) > 1:
+            raise ValueError("node_table: this master's repeated families differ between organisms (it was grown by add_annotations with other "
+                             "sets); a Loaded flags one global set -- use write_gexf(annotations=)")
+        o = ld.orders
+        t = gexf.NodeTable(self, o["genes"], o["contig_ptr"], o["contig_org"], o["repeated"], _hash_bits=_hash_bits)
+        try:
+            files, base = ld._files, ld._base
+            ptr, corg = np.asarray(o["contig_ptr"], np.int64), np.asarray(o["contig_org"], np.int64)
+            # the genes of file k (organism k): the contigs of organism k are adjacent, in column order
+            gene_at = ptr[np.searchsorted(corg, np.arange(len(files) + 1))]
+            i = 0
+            while i < len(files):
+                j, total = i + 1, len(files[i]) + 1
+                while j < len(files) and total + len(files[j]) + 1 <= batch_bytes:
+                    total, j = total + len(files[j]) + 1, j + 1
+                gene0, gene1 = int(gene_at[i]), int(gene_at[j])
+                if gene1 > gene0:
+                    t.add_text(b"\n".join(files[i:j]), gene0, gene1, ld.span_off[:3, gene0:gene1] - int(base[i]), ld.span_len[:3, gene0:gene1])
+                i = j
+            return t.finish()
+        except Exception:
+            t.close()
+            raise
+
     def layout(self, iterations=500, pos=None, rng=None, repulsion="exact", theta=1.2, **params):
         """The family graph laid out on the device (PPanGGOLiN.compute_layout, ppanggolin.py:1250-1292; nemgpu_layout_*;
         layout.layout_arrays states what it computes: ForceAtlas2 with an exact all-pairs repulsion, n^2 per iteration).

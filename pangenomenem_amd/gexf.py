@@ -18,6 +18,12 @@ the values on the host, ``edge_metadata_arrays`` states the edges' present-value
 lines; ``nemgpu_edge_table_metadata`` / ``_metamasks`` / ``_metavalues`` (csrc/nem_edge_meta.hip) compute both on the
 device; ``shell_init_from_metadata`` turns the same dict into ``partition_shell``'s ``init_using_qual``.
 
+The nodes' organism, name and product lines need the genes' ids, names and products.  ``write_gexf`` reads them from
+the nested ``annotations``, or -- for a load from files, which has no nested dict -- takes them from a node table:
+``node_text_host`` states the nodes' text in plain Python on the flat orders, a text and the (offset, length) spans of
+every gene's ID, NAME and PRODUCT; ``nemgpu_node_table_*`` (csrc/nem_nodes.hip) format it on the device,
+``Master.node_table`` is their Python surface, ``NodeTable`` / ``HostNodeTable`` hold the result.
+
 Where the reference's bytes are not determined -- ``"|".join(set)`` of a node's names, products and an organism's genes
 follows string hash order; the ``<meta>`` element holds the date and networkx's version -- the values are joined in walk
 order here and ``<meta>`` names this package.
@@ -582,6 +588,260 @@ def escape(text):
     return text
 
 
+_ESCAPED = {ord("&"): b"&amp;", ord("<"): b"&lt;", ord(">"): b"&gt;", ord('"'): b"&quot;", ord("\r"): b"&#13;", ord("\n"): b"&#10;",
+            ord("\t"): b"&#09;"}
+NODE_TAIL = 6                                                 # partition, partition_exact and the four length_* behind a node's organisms
+
+
+def escape_bytes(data):
+    """escape() on bytes: the same seven replacements, every other byte (those >= 0x80 too) as it is"""
+    if not any(ch in _ESCAPED for ch in data):
+        return bytes(data)
+    return b"".join(_ESCAPED.get(ch, bytes((ch,))) for ch in data)
+
+
+def node_attribute_ids(first, n, tail=NODE_TAIL):
+    """The ids networkx gives the node attributes, a title numbered where it is first met, from first int [d]: every
+    organism's first family in master order with a kept gene of it (n: none), when `tail` titles follow a node's
+    organisms.  Full: nb_genes 0, node 0's first organism, name, product, node 0's other organisms, the tail, then every
+    organism first met at a later node in (node, organism) order; light: nb_genes 0, name 1, product 2, the tail.
+    Returns (org_id int32 [d], -1 for an organism without a kept gene; name_id (light, full), product's is one more;
+    titles (light, full): each the titles in id order -- "nb_genes", "name", "product", ("tail", j) or an organism's
+    column; both empty when n is 0)."""
+    first = np.asarray(first, np.int64)
+    org_id = np.full(len(first), -1, np.int32)
+    if n == 0:
+        return org_id, (1, 1), ([], [])
+    met = [int(o) for o in np.lexsort((np.arange(len(first)), first)) if first[o] < n]
+    here = [o for o in met if first[o] == 0]
+    full = ["nb_genes"] + here[:1] + ["name", "product"] + here[1:] + [("tail", j) for j in range(tail)] + met[len(here):]
+    for k, what in enumerate(full):
+        if isinstance(what, int):
+            org_id[what] = k
+    return org_id, (1, full.index("name")), (["nb_genes", "name", "product"] + [("tail", j) for j in range(tail)], full)
+
+
+def node_text_host(x, order, genes, contig_ptr, contig_org, repeated, text, spans, f=None, d=None, tail=NODE_TAIL):
+    """What nemgpu_node_table_* compute, in plain Python / numpy on flat arrays: the nodes' <attvalue> text of write_gexf
+    without the nested annotations.
+    x, order: the master's matrix (uint8 [n][d], or packed rows with d=) and its family order (master family i is caller
+    id order[i]); genes, contig_ptr, contig_org, repeated uint8 [f], f: the flat orders of ALL the master's organisms
+    (family_table_arrays' layout), contig_org non-decreasing; text: bytes; spans = (span_off int64 [3][g], span_len int32
+    [3][g]): every gene's ID, NAME and PRODUCT in text (the loader's SPAN_ID, SPAN_NAME, SPAN_PRODUCT; an absent NAME or
+    PRODUCT is an empty span).
+      * a gene is kept when its id is not flagged in `repeated`: one global set.  Repeated sets per organism (a dict, as a
+        master grown by add_annotations holds them) are refused with ValueError: they stay on the annotations path,
+        unless the orders already carry them gene by gene (table_orders' one flagged id);
+      * per family i in master order: the organisms with a kept gene of it in walk order (increasing column), per
+        organism its kept genes' IDs in walk order, its distinct NAME byte strings in first-occurrence order over the
+        walk (the empty string is a value like any other) and its distinct PRODUCT byte strings by the same rule;
+      * a node's text is one slice: the first organism's line, the name line, the product line, the other organisms'
+        lines, each `          <attvalue for="ID" value="A|B|..." />\\n` with the pieces escaped (escape_bytes); light:
+        the name and product lines alone;
+      * the ids: node_attribute_ids;
+      * the kept genes' (family, organism) cells must be exactly the master's presence bits, every kept gene's family a
+        family of the master, every span inside the text: ValueError otherwise.
+    Returns a dict: nb_genes int32 [n], first int32 [d], org_id int32 [d], name_id (light, full), titles (light, full),
+    text (light, full) uint8, node_end (light, full) int64 [n]."""
+    from .matrix import _presence
+    if isinstance(repeated, dict):
+        raise ValueError("node_text_host: repeated sets per organism stay on the annotations path (one global set of flagged ids is taken)")
+    present = _presence(x, d)
+    n, d = present.shape
+    order = np.asarray(order, np.int64)
+    if order.shape != (n,):
+        raise ValueError("node_text_host: order [n]")
+    if f is None:
+        f = len(repeated) if repeated is not None else max(int(order.max()) + 1 if n else 1, int(np.max(genes)) + 1 if len(genes) else 1)
+    genes, contig_ptr, contig_org, repeated = check_projection_orders(genes, contig_ptr, contig_org, repeated, d, int(f))
+    if (np.diff(contig_org) < 0).any():
+        raise ValueError("node_text_host: contig_org must be non-decreasing (the organisms walked in column order)")
+    g = len(genes)
+    off, ln = np.asarray(spans[0], np.int64), np.asarray(spans[1], np.int64)
+    blob = bytes(memoryview(np.ascontiguousarray(text, np.uint8))) if isinstance(text, np.ndarray) else bytes(text)
+    if off.shape != (3, g) or ln.shape != (3, g):
+        raise ValueError("node_text_host: spans = (span_off [3][g], span_len [3][g])")
+    if g and ((off < 0).any() or (ln < 0).any() or (off + ln > len(blob)).any()):
+        raise ValueError("node_text_host: a span is past the end of the text")
+    inv = np.full(int(f), -2, np.int64)
+    inside = order < f
+    inv[order[inside]] = np.flatnonzero(inside)
+    fam = inv[genes] if g else np.zeros(0, np.int64)
+    kept = np.ones(g, bool) if repeated is None else repeated[genes] == 0
+    if (fam[kept] < 0).any():
+        raise ValueError("these orders are not this master's: a kept gene's family is not in the master")
+    org = np.repeat(contig_org.astype(np.int64), np.diff(contig_ptr))
+    derived = np.zeros(n * d, bool)
+    derived[np.unique(fam[kept] * d + org[kept])] = True
+    if not np.array_equal(derived.reshape(n, d), present):
+        raise ValueError("these orders are not this master's: their cells are not its presence bits")
+    first = np.where(present.any(axis=0), present.argmax(axis=0), n).astype(np.int32) if n else np.full(d, 0, np.int32)
+    org_id, name_id, titles = node_attribute_ids(first, n, tail)
+    kp = np.flatnonzero(kept)
+    walk = kp[np.argsort(fam[kp], kind="stable")]             # a family's kept genes: one segment, in walk order
+    start = np.searchsorted(fam[walk], np.arange(n + 1))
+
+    def piece(k, p):
+        return escape_bytes(blob[off[k, p]:off[k, p] + ln[k, p]])
+
+    def line(k, pieces):
+        return b'          <attvalue for="%d" value="' % k + b"|".join(pieces) + b'" />\n'
+
+    parts, ends = ([], []), (np.zeros(n, np.int64), np.zeros(n, np.int64))
+    size = [0, 0]
+    for i in range(n):
+        cells, names, products = {}, {}, {}                   # (insertion-ordered sets)
+        for p in walk[start[i]:start[i + 1]]:
+            cells.setdefault(int(org[p]), []).append(piece(0, p))
+            names[piece(1, p)] = None
+            products[piece(2, p)] = None
+        organisms = [line(org_id[o], ids) for o, ids in cells.items()]
+        for full in (0, 1):
+            both = line(name_id[full], names) + line(name_id[full] + 1, products)
+            node = b"".join(organisms[:1]) + both + b"".join(organisms[1:]) if full else both
+            parts[full].append(node)
+            size[full] += len(node)
+            ends[full][i] = size[full]
+    return dict(nb_genes=np.diff(start).astype(np.int32), first=first, org_id=org_id, name_id=name_id, titles=titles,
+                text=tuple(np.frombuffer(b"".join(p), np.uint8).copy() for p in parts), node_end=ends)
+
+
+def _bind_nodes(lib):
+    lib.nemgpu_node_table_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_int]
+    lib.nemgpu_node_table_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.nemgpu_node_table_finish.argtypes = [C.c_void_p, C.c_void_p]
+    lib.nemgpu_node_table_shape.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
+    lib.nemgpu_node_table_fetch.argtypes = [C.c_void_p] * 3
+    lib.nemgpu_node_table_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    lib.nemgpu_node_table_lines_size.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    lib.nemgpu_node_table_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]
+    lib.nemgpu_node_table_destroy.argtypes = [C.c_void_p]
+    lib.nemgpu_node_table_destroy.restype = None
+    return lib
+
+
+class _Nodes:
+    """what both node tables share: NodeTable on the device, HostNodeTable in plain Python.  n, d, nb_genes int32 [n],
+    first int32 [d]; after _layout(tail): org_id, name_id, node_end (light, full), _titles (light, full)."""
+    tail = None
+
+    def titles(self, full=True, tail=NODE_TAIL):
+        """the node attributes' titles in id order, as node_attribute_ids gives them; the text calls that follow format
+        for this numbering"""
+        if tail != self.tail:
+            self._layout(int(tail))
+        return self._titles[1 if full else 0]
+
+    def ids(self, tail=NODE_TAIL):
+        """(org_id int32 [d], name_id (light, full)) of that numbering"""
+        self.titles(True, tail)
+        return self.org_id, self.name_id
+
+    def _ends(self, full):
+        if self.tail is None:
+            self._layout(NODE_TAIL)
+        return self.node_end[1 if full else 0]
+
+    def _rows(self, row0, rows):
+        rows = self.n - row0 if rows is None else rows
+        if row0 < 0 or rows <= 0 or row0 + rows > self.n:
+            raise ValueError("node table: rows outside the table")
+        return rows
+
+    def lines_size(self, row0=0, rows=None, full=True):
+        """the bytes of the text of nodes row0 .. row0 + rows - 1"""
+        rows, ends = self._rows(row0, rows), self._ends(full)
+        return int(ends[row0 + rows - 1] - (ends[row0 - 1] if row0 else 0))
+
+    def _batches(self, budget, full=True):
+        """(row0, rows) covering the nodes, each batch's text within the budget (one node where a node alone is above it)"""
+        ends, row0 = self._ends(full), 0
+        while row0 < self.n:
+            base = ends[row0 - 1] if row0 else 0
+            rows = max(1, int(np.searchsorted(ends, base + budget, side="right")) - row0)
+            yield row0, rows
+            row0 += rows
+
+
+class NodeTable(DeviceTable, _Nodes):
+    """The node text of a master on the device (nemgpu_node_table_*; node_text_host states it).  Made from the flat orders;
+    add_text() takes the load's text batch by batch, finish() closes it: Master.node_table does all three.  The master
+    must stay open as long as the table writes."""
+    KIND = "node_table"
+
+    def __init__(self, master, genes, contig_ptr, contig_org, repeated=None, f=None, _hash_bits=0):
+        self.lib = _bind_nodes(master.lib)
+        f, genes, contig_ptr, contig_org, repeated = self._orders(master, genes, contig_ptr, contig_org, repeated, f)
+        if not len(genes):
+            raise ValueError("node table: genes [G], G > 0")
+        self.master, self._h = master, C.c_void_p()
+        self._call("create", C.byref(self._h), master._h, f, genes.ctypes.data, len(genes), contig_ptr.ctypes.data, contig_org.ctypes.data,
+                   len(contig_org), repeated.ctypes.data if repeated is not None else None, int(_hash_bits))
+        v = [C.c_int() for _ in range(3)]
+        self._call("shape", self._h, *(C.byref(a) for a in v))
+        self.n, self.d, self.g = (a.value for a in v)
+        self.nb_genes, self.first = np.zeros(self.n, np.int32), np.zeros(self.d, np.int32)
+        self._call("fetch", self._h, self.nb_genes.ctypes.data if self.n else None, self.first.ctypes.data if self.d else None)
+
+    def add_text(self, text, gene0, gene1, span_off, span_len):
+        """the text of genes gene0 .. gene1 - 1 (the batches in order): text uint8 or bytes, span_off int64 [3][gene1 -
+        gene0] into it, span_len int32 of the same shape"""
+        text = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8)
+        span_off, span_len = np.ascontiguousarray(span_off, np.int64), np.ascontiguousarray(span_len, np.int32)
+        if span_off.shape != (3, gene1 - gene0) or span_len.shape != span_off.shape:
+            raise ValueError("node table: span_off, span_len [3][gene1 - gene0]")
+        self._call("text", self._h, self.master._h, text.ctypes.data if text.size else None, text.size, int(gene0), int(gene1),
+                   span_off.ctypes.data, span_len.ctypes.data)
+
+    def finish(self):
+        self._call("finish", self._h, self.master._h)
+        return self
+
+    def _layout(self, tail):
+        org_id, name_id = np.zeros(self.d, np.int32), np.zeros(2, np.int32)
+        ends = np.zeros(max(self.n, 1), np.int64), np.zeros(max(self.n, 1), np.int64)
+        self._call("ids", self._h, self.master._h, tail, org_id.ctypes.data, name_id.ctypes.data, ends[1].ctypes.data, ends[0].ctypes.data)
+        self.org_id, self.name_id = org_id, (int(name_id[0]), int(name_id[1]))
+        self.node_end = ends[0][:self.n], ends[1][:self.n]
+        self._titles = node_attribute_ids(self.first, self.n, tail)[2]
+        self.tail = tail
+
+    def lines(self, row0=0, rows=None, full=True, out=None):
+        """The text of nodes row0 .. row0 + rows - 1, formatted on the device (nemgpu_node_table_lines): (text uint8
+        [bytes], node_end int64 [rows]).  out: a uint8 buffer to write into (too small: NemGpuError that says the size
+        needed, nothing written)."""
+        rows = self._rows(row0, rows)
+        if out is None:
+            out = np.empty(max(self.lines_size(row0, rows, full), 1), np.uint8)
+        ends, needed = np.zeros(rows, np.int64), C.c_int64()
+        return self._text("lines", out, needed, self._h, self.master._h, 1 if full else 0, int(row0), int(rows), out.ctypes.data, out.size,
+                          C.byref(needed), ends.ctypes.data), ends
+
+
+class HostNodeTable(_Nodes):
+    """The same table from the host statement (node_text_host): what the device is held against, and a table for a caller
+    who has the master's matrix on the host.  x, order, d: the master's; the rest as node_text_host takes it."""
+
+    def __init__(self, x, order, genes, contig_ptr, contig_org, repeated, text, spans, f=None, d=None):
+        self._args = (x, order, genes, contig_ptr, contig_org, repeated, text, spans, f, d)
+        self._layout(NODE_TAIL)
+        self.n, self.d = len(self.nb_genes), len(self.first)
+
+    def _layout(self, tail):
+        made = node_text_host(*self._args, tail=tail)
+        self.nb_genes, self.first, self.org_id, self.name_id = made["nb_genes"], made["first"], made["org_id"], made["name_id"]
+        self._titles, self._text, self.node_end, self.tail = made["titles"], made["text"], made["node_end"], tail
+
+    def lines(self, row0=0, rows=None, full=True):
+        rows, ends, k = self._rows(row0, rows), self._ends(full), 1 if full else 0
+        base = int(ends[row0 - 1]) if row0 else 0
+        return self._text[k][base:int(ends[row0 + rows - 1])].copy(), ends[row0:row0 + rows] - base
+
+    def close(self):
+        pass
+
+
 def _median(lo, hi, count):
     """utils.median of the reference from the two middle elements: the element itself (an int) when the count is odd, their
     true division when it is even; export_to_GEXF wraps it in float()"""
@@ -593,8 +853,8 @@ def _lengths(total, count, lo, hi, low, high):
     return (str(float(int(total)) / max(int(count), 1)), str(_median(lo, hi, int(count))), str(int(low)), str(int(high)))
 
 
-def write_gexf(path, partitions, family_table, edge_table, annotations, all_node_attributes=True, all_edge_attributes=True, compressed=False,
-               budget=TEXT_BUDGET, positions=None, subpartition=None, metadata=None):
+def write_gexf(path, partitions, family_table, edge_table, annotations=None, all_node_attributes=True, all_edge_attributes=True, compressed=False,
+               budget=TEXT_BUDGET, positions=None, subpartition=None, metadata=None, node_table=None):
     """<path>.gexf (compressed: <path>.gexf.gz through gzip) as PPanGGOLiN.export_to_GEXF and networkx's write_gexf write
     it for a partitioned nx.Graph (ppanggolin.py:1294-1362), streamed: no networkx, no tree.  partitions: what
     Master.partition returned, or uint8 [n]; family_table, edge_table: Master.family_table / Master.edge_table (or their
@@ -613,8 +873,12 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
     the escaping and the values' blob are made on the host (rank_metadata), the sets and the lines on the device, a
     slice per edge.  ValueError: a missing organism; a value that is not a str; organisms whose attribute names or their
     order differ (the CLI's zip over one header row cannot produce that); an attribute named like an organism, like
-    weight or like a length_* title.  An empty metadata (or one without attributes) is none, as in the reference."""
-    ft, et = family_table, edge_table
+    weight or like a length_* title.  An empty metadata (or one without attributes) is none, as in the reference.
+    node_table: Master.node_table's (or a HostNodeTable) of the same master and orders; annotations may then be None: the
+    genes are not walked, a node's organism, name and product lines are the table's bytes, a slice per node, and the
+    host writes a node's head, its viz lines, nb_genes and the tail values around them, one write per node.  Everything
+    else is as without it, and the file is the same byte for byte."""
+    ft, et, nt = family_table, edge_table, node_table
     names, orgs = ft.names, ft.organism_names
     if names is None or orgs is None:
         raise ValueError("write_gexf: a master that carries names (from_annotations, from_graph, add_annotations)")
@@ -626,19 +890,10 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
         positions = np.asarray(positions, np.float64)
         if positions.shape != (n, 2):
             raise ValueError("write_gexf: positions float64 [n][2]")
-    index = {name: i for i, name in enumerate(names)}
-    gene_names, products, cells = [dict() for _ in names], [dict() for _ in names], [dict() for _ in names]   # (insertion-ordered sets)
-    by_org = ft.repeated_names if isinstance(ft.repeated_names, dict) else None
-    for org, contigs in annotations.items():
-        skipped = by_org[org] if by_org is not None else ft.repeated_names
-        for annot in contigs.values():
-            for gene, info in annot.items():
-                if info[FAMILY] in skipped:
-                    continue
-                i = index[info[FAMILY]]
-                gene_names[i][info[NAME]] = None
-                products[i][info[PRODUCT]] = None
-                cells[i].setdefault(org, dict())[gene] = None
+    tail = (("partition", "string"), ("partition_exact", "string"), ("length_avg", "double"), ("length_med", "double"), ("length_min", "long"),
+            ("length_max", "long"))
+    if subpartition is not None:
+        tail = tail[:2] + ((subpartition[0], "string"),) + tail[2:]
     # the attribute ids: one counter over the nodes, then the edges, a title numbered where it is first met
     node_ids, node_titles = {}, []
 
@@ -648,23 +903,45 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
             node_titles.append((title, kind))
         return node_ids[title]
 
-    tail = (("partition", "string"), ("partition_exact", "string"), ("length_avg", "double"), ("length_med", "double"), ("length_min", "long"),
-            ("length_max", "long"))
-    if subpartition is not None:
-        tail = tail[:2] + ((subpartition[0], "string"),) + tail[2:]
-    node_keys = []                                            # per family: the organisms before and after name and product
-    for i in range(n):
-        present = list(cells[i]) if all_node_attributes else []
-        node_id("nb_genes", "long")
-        for org in present[:1]:
-            node_id(org, "string")
-        node_id("name", "string")
-        node_id("product", "string")
-        for org in present[1:]:
-            node_id(org, "string")
-        for title, kind in tail:
-            node_id(title, kind)
-        node_keys.append(present)
+    if nt is not None:
+        if nt.n != n or nt.d != d or not np.array_equal(nt.nb_genes, ft.nb_genes):
+            raise ValueError("write_gexf: the node table is not of the family table's master and orders")
+        for what in nt.titles(all_node_attributes, len(tail)):
+            if isinstance(what, tuple):
+                node_id(*tail[what[1]])
+            elif isinstance(what, str):
+                node_id(what, "long" if what == "nb_genes" else "string")
+            else:
+                node_id(orgs[what], "string")
+    else:
+        if annotations is None:
+            raise ValueError("write_gexf: annotations, or a node_table")
+        index = {name: i for i, name in enumerate(names)}
+        gene_names, products, cells = [dict() for _ in names], [dict() for _ in names], [dict() for _ in names]   # (insertion-ordered sets)
+        by_org = ft.repeated_names if isinstance(ft.repeated_names, dict) else None
+        for org, contigs in annotations.items():
+            skipped = by_org[org] if by_org is not None else ft.repeated_names
+            for annot in contigs.values():
+                for gene, info in annot.items():
+                    if info[FAMILY] in skipped:
+                        continue
+                    i = index[info[FAMILY]]
+                    gene_names[i][info[NAME]] = None
+                    products[i][info[PRODUCT]] = None
+                    cells[i].setdefault(org, dict())[gene] = None
+        node_keys = []                                            # per family: the organisms before and after name and product
+        for i in range(n):
+            present = list(cells[i]) if all_node_attributes else []
+            node_id("nb_genes", "long")
+            for org in present[:1]:
+                node_id(org, "string")
+            node_id("name", "string")
+            node_id("product", "string")
+            for org in present[1:]:
+                node_id(org, "string")
+            for title, kind in tail:
+                node_id(title, kind)
+            node_keys.append(present)
     meta = rank_metadata(metadata, orgs, ("weight",) + LENGTH_TITLES) if metadata else None
     if meta is not None and not (meta["titles"] and et.n_edges):
         meta = None
@@ -692,7 +969,9 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
             w(b"    </attributes>\n")
         w(b"    <nodes>\n" if n else b"    <nodes />\n")
         att = '          <attvalue for="%d" value="%s" />\n'
-        for i in range(n):
+
+        def node(i, middle):
+            """node i: its head, viz lines and nb_genes; middle(lines) adds its organism, name and product lines; the tail"""
             nb_org = int(ft.nb_org[i])
             exact = "core_exact" if nb_org == d else "accessory"
             color = COLORS_RGB[longs[i] if longs[i] != "undefined" else exact]
@@ -705,18 +984,35 @@ def write_gexf(path, partitions, family_table, edge_table, annotations, all_node
                              % (str(float(positions[i, 0])), str(float(positions[i, 1])), {"persistent": 2, "shell": 1}.get(longs[i], 0)))
             lines += ["        <attvalues>\n",
                       att % (node_ids["nb_genes"], int(ft.nb_genes[i]))]
-            present = node_keys[i]
-            for org in present[:1]:
-                lines.append(att % (node_ids[org], escape("|".join(cells[i][org]))))
-            lines.append(att % (node_ids["name"], escape("|".join(gene_names[i]))))
-            lines.append(att % (node_ids["product"], escape("|".join(products[i]))))
-            for org in present[1:]:
-                lines.append(att % (node_ids[org], escape("|".join(cells[i][org]))))
+            head = middle(lines)
+            lines = []
             values = (longs[i], exact) + (() if subpartition is None else (escape(subpartition[1][names[i]]),)) + _lengths(ft.len_sum[i], ft.len_distinct[i], et.fam_mid_lo[i], et.fam_mid_hi[i], ft.len_min[i], ft.len_max[i])
             for (title, _), value in zip(tail, values):
                 lines.append(att % (node_ids[title], value))
             lines.append("        </attvalues>\n      </node>\n")
-            w("".join(lines).encode())
+            w(head + "".join(lines).encode())
+
+        def walked(i):
+            def middle(lines):
+                present = node_keys[i]
+                for org in present[:1]:
+                    lines.append(att % (node_ids[org], escape("|".join(cells[i][org]))))
+                lines.append(att % (node_ids["name"], escape("|".join(gene_names[i]))))
+                lines.append(att % (node_ids["product"], escape("|".join(products[i]))))
+                for org in present[1:]:
+                    lines.append(att % (node_ids[org], escape("|".join(cells[i][org]))))
+                return "".join(lines).encode()
+            return middle
+
+        if nt is not None:
+            for row0, rows in nt._batches(budget, all_node_attributes):
+                text, ends = nt.lines(row0, rows, all_node_attributes)
+                view = memoryview(text)
+                for r in range(rows):
+                    node(row0 + r, lambda lines, r=r: "".join(lines).encode() + bytes(view[int(ends[r - 1]) if r else 0:int(ends[r])]))
+        else:
+            for i in range(n):
+                node(i, walked(i))
         if n:
             w(b"    </nodes>\n")
         ne = et.n_edges

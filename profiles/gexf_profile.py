@@ -5,9 +5,11 @@ the reference tree and networkx, as the generators under tests/golden/ do) or fr
 Master.from_annotations, family_table, edge_table, write_gexf; needs the GPU).  Both label a family persistent above
 0.9 d organisms, cloud below 0.1 d, shell between.  --metadata: three metadata attributes of 2, 20 and 200 distinct
 values (export_to_GEXF's metadata=, write_gexf's metadata=) -- the exports are timed with and, on the device, also
-without them, and the device's metadata lines of all the edges on their own.  Prints one JSON line.
+without them, and the device's metadata lines of all the edges on their own.  --nodes: the export from the loader's flat
+form (needs the GPU), through Loaded.annotations() and through Master.node_table.  Prints one JSON line.
 
     python profiles/gexf_profile.py --n 2000 --d 200 --seed 11 --device --runs 3
+    python profiles/gexf_profile.py --n 2000 --d 200 --seed 11 --nodes --runs 5
 """
 import argparse
 import json
@@ -123,6 +125,82 @@ def device(ann, orgs, circular, runs, tmp, metadata=False):
     return out
 
 
+def flat_load(ann, orgs, families, circular):
+    """the annotations in the loader's flat form: a loader.Loaded with one text per organism that holds, per gene, its id,
+    name, product, strand and contig name, and the spans into it -- what Master.from_files keeps, without the GFF columns"""
+    import numpy as np
+    from pangenomenem_amd.gexf import gexf_orders
+    from pangenomenem_amd.loader import Loaded
+    o = gexf_orders(ann, orgs, families, {org: frozenset() for org in orgs}, circular)
+    files, base, off, length, coff, clen, at = [], [], [[], [], [], []], [[], [], [], []], [], [], 0
+    for contigs in ann.values():
+        parts, here = [], 0
+        for contig, annot in contigs.items():
+            coff.append(at + here)
+            clen.append(len(contig.encode()))
+            parts.append(contig.encode() + b"\t")
+            here += clen[-1] + 1
+            for gene, info in annot.items():
+                for j, piece in enumerate((gene, info[5], info[6], info[4])):
+                    piece = piece.encode()
+                    off[j].append(at + here)
+                    length[j].append(len(piece))
+                    parts.append(piece + b"\t")
+                    here += len(piece) + 1
+        files.append(b"".join(parts)[:-1] if parts else b"")
+        base.append(at)
+        at += len(files[-1]) + 1
+    o.update(families=list(families), organisms=list(orgs), d=len(orgs), lengths=(o["ends"].astype(np.int64) - o["starts"]).astype(np.int32))
+    return Loaded(list(orgs), files, np.asarray(base, np.int64), o, list(families), set(), dict(circular),
+                  (np.asarray(off, np.int64), np.asarray(length, np.int32)), (np.asarray(coff, np.int64), np.asarray(clen, np.int32)))
+
+
+def nodes(ann, orgs, circular, runs, tmp, metadata=False):
+    """write_gexf from the loader's flat form, through Loaded.annotations() (the walk that builds the nested dict is counted)
+    and through Master.node_table (the second upload and the table's creation are counted); then node_table() alone and
+    lines() over all nodes.  The family and edge tables are made from the flat orders once, for both."""
+    from pangenomenem_amd.chunks import Master
+    from pangenomenem_amd.gexf import write_gexf
+    m = Master.from_annotations(ann, orgs, list(circular))
+    ld = flat_load(ann, orgs, m.id_names, circular)
+    o = ld.orders
+    orders = (o["genes"], o["contig_ptr"], o["contig_org"], o["repeated"])
+    ft = m.family_table(orders=orders, lengths=o["lengths"])
+    et = m.edge_table(orders=orders, starts=o["starts"], ends=o["ends"], contig_sizes=o["contig_sizes"])
+    labels = {name: label(int(nb), len(orgs)) for name, nb in zip(m.names, ft.nb_org)}
+    light = dict(all_node_attributes=False, all_edge_attributes=False)
+
+    def old(path, **kw):
+        write_gexf(path, labels, ft, et, ld.annotations(), **kw)
+
+    def new(path, **kw):
+        nt = m.node_table(ld)
+        write_gexf(path, labels, ft, et, node_table=nt, **kw)
+        nt.close()
+
+    old(tmp + "/old")                                         # (warm-up of both paths, and the two files to compare)
+    new(tmp + "/new")
+    same = open(tmp + "/old.gexf", "rb").read() == open(tmp + "/new.gexf", "rb").read()
+    out = dict(who="nodes", families=m.n, edges=et.n_edges, text_bytes=sum(len(f) + 1 for f in ld._files), same_bytes=same,
+               full_bytes=os.path.getsize(tmp + "/new.gexf"))
+    for _ in range(2):                                        # (alternated)
+        for name, fn, kw in (("annotations_full_s", old, {}), ("node_table_full_s", new, {}), ("annotations_light_s", old, light),
+                             ("node_table_light_s", new, light)):
+            out.setdefault(name, []).extend(timed(lambda: fn(tmp + "/" + name, **kw), runs))
+    out["annotations_walk_s"] = timed(ld.annotations, runs)
+    tables = []
+    out["node_table_s"] = timed(lambda: tables.append(m.node_table(ld)), runs)
+    nt = tables[-1]
+    nt.titles()
+    out["node_text_bytes"] = nt.lines_size()
+    out["lines_all_nodes_s"] = timed(lambda: [nt.lines(row0, rows) for row0, rows in nt._batches(64 << 20)], runs)
+    out["lines_all_nodes_light_s"] = timed(lambda: [nt.lines(row0, rows, False) for row0, rows in nt._batches(64 << 20, False)], runs)
+    for t in tables + [ft, et]:
+        t.close()
+    m.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=2000)
@@ -132,11 +210,12 @@ def main():
     ap.add_argument("--reference", action="store_true")
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--metadata", action="store_true")
+    ap.add_argument("--nodes", action="store_true")
     args = ap.parse_args()
     ann, orgs, circular = annotated_pangenome(args.n, args.d, args.seed)
     genes = sum(len(annot) for contigs in ann.values() for annot in contigs.values())
     tmp = tempfile.mkdtemp()
-    for who, fn in (("reference", reference), ("device", device)):
+    for who, fn in (("reference", reference), ("device", device), ("nodes", nodes)):
         if getattr(args, who):
             res = fn(ann, orgs, circular, args.runs, tmp, args.metadata)
             res.update(n=args.n, d=args.d, seed=args.seed, genes=genes, date=time.strftime("%Y-%m-%d"))
